@@ -12,7 +12,8 @@ ITSELF: the parent process -- which never touches the GPU -- runs
 as a child and exits with its code.  Under a launcher (RANK / WORLD_SIZE in the
 environment) it is one rank of the job; WORLD_SIZE != --gpus is an error.
 
-Multi-GPU, both schemes in one line (`--mode both`, the default for G > 1):
+Multi-GPU, both schemes in one line (`--mode both`, the default for G > 1 under `--full`; a plain
+run times `value` alone):
   * `value`: chunk + merge -- each rank owns a contiguous shard of the sequences and
     runs the greedy on it, the reference's own `-np G` scheme (diverse_seq/records.py:
     225-245, diverse_seq/util.py:82-102) -- then the G*n winners' frequency rows are
@@ -22,6 +23,12 @@ Multi-GPU, both schemes in one line (`--mode both`, the default for G > 1):
     per greedy step (the `-np 1` answer).
 
 Prints ONE JSON line (rank 0).
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, the
+outputs of the last of them when `--dump-outputs DIR` is given, the line.  `--full` adds the rest: the
+steps timed again with the offsets cache on, the single-GPU side runs (streaming passes, histogram
+alone, the drop-in module, configs[1], the large point), the CPU baseline with its oracle check of the
+last timed step, and with G > 1 the exact scheme beside the chunk scheme.
 """
 import argparse
 import json
@@ -48,21 +55,30 @@ def parse():
                     help="multi-GPU scheme: 'chunk' = the reference's -np G (independent greedy per GPU + "
                          "one all_gather + final_nmost); 'exact' = rows sharded block-cyclically, set state "
                          "replicated, ONE all_gather per greedy step: every rank's first event + its candidate row "
-                         "(same answer as 1 GPU); 'both' (the default with --gpus > 1) = chunk as `value`, then "
-                         "exact as `value_exact` in the same line")
+                         "(same answer as 1 GPU); 'both' (the default with --gpus > 1 and --full; 'chunk' without "
+                         "--full) = chunk as `value`, then exact as `value_exact` in the same line")
     ap.add_argument("--input", choices=("bytes", "packed"), default="bytes",
                     help="form of the sequences resident in HBM: 'bytes' = one byte per base, as the reference's "
                          "boundary delivers them (src/record.rs:205-209); 'packed' = 2-bit codes + 1-bit invalid "
                          "mask (dvs_pack_sequences, done once outside the timed region)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the steps timed again with the "
+                         "offsets cache on, the single-GPU side runs, the CPU baseline with its oracle check of the "
+                         "last timed step, and with --gpus > 1 the exact scheme beside the chunk scheme (--mode both). "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float64, "
+                         "the count sample float32): the selection's members and total_jsd, every row's total and "
+                         "entropy, and a fixed, seeded sample of count rows (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
     ap.add_argument("--no-side-runs", action="store_true",
-                    help="only the timed steps: no streaming passes, no configs[1] side number (profiling runs: "
+                    help="(--full) no streaming passes, no configs[1] side number (profiling runs: "
                          "every launch of the dominant kernel is then a headline launch)")
     ap.add_argument("--no-large-point", action="store_true",
-                    help="skip the 1 000 000 x 5 kb side point (8.2 GB of 16-bit rows: the largest single-GPU "
-                         "stream, where the scan dominates the event chain)")
+                    help="(--full) skip the 1 000 000 x 5 kb side point (8.2 GB of 16-bit rows: the largest "
+                         "single-GPU stream, where the scan dominates the event chain)")
     ap.add_argument("--cpu-sample", type=int, default=100_000,
-                    help="sequences of the same workload the 1-thread CPU oracle is timed on")
+                    help="(--full) sequences of the same workload the 1-thread CPU oracle is timed on")
     return ap.parse_args()
 
 
@@ -206,9 +222,10 @@ class Bench:
                  "scan_ms_last": 0.0, "rows_scored_last": 0, "arbiter_ms": 0.0}
         timing = {}   # exact: per-step all_gather; chunk: the merge's all_gathers (device events / host clock)
         last = {}     # members and statistics of the last timed step (checked against the oracle below)
+        held = {}     # (--dump-outputs) the last timed step's matrix, closed once the clock has stopped
         merge_buffers = {}
 
-        def step(collect: bool, keep: bool = False):
+        def step(collect: bool, keep: bool = False, hold: bool = False):
             t0 = time.perf_counter()
             m = self.build(seqs, offsets, a.k, packed)
             t1 = time.perf_counter()
@@ -232,9 +249,13 @@ class Bench:
                 if keep:
                     mem = sel.members(False)
                     last.update(positions=np.asarray(mem.positions).copy(), delta_jsd=np.asarray(mem.delta_jsd).copy(),
+                                labels=np.asarray(mem.labels).copy(), entropy=np.asarray(mem.entropy).copy(),
                                 total_jsd=s.total_jsd, n_accepts=s.n_accepts, size=s.size)
             sel.close()
-            m.close()
+            if hold:
+                held["m"] = m
+            else:
+                m.close()
 
         def timed_loop(collect: bool) -> float:
             if self.dist_on:
@@ -242,7 +263,8 @@ class Bench:
             self.sync()
             t0 = time.perf_counter()
             for i in range(a.steps):
-                step(collect, keep=collect and i == a.steps - 1)
+                last_step = collect and i == a.steps - 1
+                step(collect, keep=last_step, hold=last_step and a.dump_outputs is not None and rank == 0)
             self.sync()
             if self.dist_on:
                 dist.barrier()
@@ -271,16 +293,22 @@ class Bench:
         last.clear()
         timing.clear()
         elapsed = timed_loop(True)
+        outputs = None
+        if "m" in held:
+            outputs = step_outputs(held.pop("m"), last)
         del os.environ["DVS_NO_OFFSETS_CACHE"]
         ctx.refresh_knobs()
-        step(False)
-        elapsed_cached = timed_loop(False)
+        elapsed_cached = None
+        if a.full:
+            step(False)
+            elapsed_cached = timed_loop(False)
         if self.on_gpu:
             from diverseseq_amd.parallel import collective_times
 
             collective_times(timing)  # (chunk mode: device events -> milliseconds)
         res = {"mode": mode, "elapsed": elapsed, "elapsed_cached": elapsed_cached, "stats": stats,
-               "timing": timing, "last": last, "seqs": seqs, "offsets": offsets, "packed": packed}
+               "timing": timing, "last": last, "seqs": seqs, "offsets": offsets, "packed": packed,
+               "outputs": outputs}
         if collect_side:
             self.side_runs(res)
         return res
@@ -430,6 +458,48 @@ class Bench:
                 stats["large_point"] = {"error": repr(e)}
 
 
+OUTPUT_SEED = 20260424      # the rows (and, for very wide rows, the bins) --dump-outputs samples
+OUTPUT_ROWS = 256           # count rows sampled ...
+OUTPUT_CELLS = 4 << 20      # ... at most this many counts in all (16 MB of float32)
+OUTPUT_ROW_STATS = 1 << 20  # rows whose total and entropy are written (a seeded sample beyond it)
+
+
+def step_outputs(m, last) -> dict:
+    """what the last timed step computed, as float64 / float32 arrays (--dump-outputs): the selection as its caller
+    receives it (members in set order: positions, labels, delta_jsd, entropy; total_jsd) and of the count matrix
+    every row's total and entropy and a fixed, seeded sample of count rows.  Closes m."""
+    rng = np.random.default_rng(OUTPUT_SEED)
+    try:
+        nrows, nbins = int(m.nrows), int(m.nbins)
+        stat_rows = (np.arange(nrows) if nrows <= OUTPUT_ROW_STATS else
+                     np.sort(rng.choice(nrows, size=OUTPUT_ROW_STATS, replace=False)))
+        rows = np.sort(rng.choice(nrows, size=min(OUTPUT_ROWS, nrows, max(1, OUTPUT_CELLS // nbins)), replace=False))
+        cols = None if nbins <= OUTPUT_CELLS else np.sort(rng.choice(nbins, size=OUTPUT_CELLS, replace=False))
+        sample = np.stack([m.counts(int(r), 1)[0] if cols is None else m.counts(int(r), 1)[0][cols] for r in rows])
+        out = {
+            "members_positions": np.asarray(last["positions"], dtype=np.float64),
+            "members_labels": np.asarray(last["labels"], dtype=np.float64),
+            "members_delta_jsd": np.asarray(last["delta_jsd"], dtype=np.float64),
+            "members_entropy": np.asarray(last["entropy"], dtype=np.float64),
+            "total_jsd": np.array([last["total_jsd"]], dtype=np.float64),
+            "row_totals": np.asarray(m.totals(), dtype=np.float64)[stat_rows],
+            "row_entropy": np.asarray(m.entropy(), dtype=np.float64)[stat_rows],
+            "count_sample_rows": rows.astype(np.float64),
+            "count_sample": sample.astype(np.float32),
+        }
+        if cols is not None:
+            out["count_sample_bins"] = cols.astype(np.float64)
+        return out
+    finally:
+        m.close()
+
+
+def write_outputs(path, outputs) -> None:
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+
+
 def collective_summary(timing, what):
     cm = timing.get("collective_ms") if timing else None
     if not cm:
@@ -442,7 +512,7 @@ def main():
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(self_launch(a))
     if a.mode is None:
-        a.mode = "both" if a.gpus > 1 else "chunk"
+        a.mode = "both" if a.gpus > 1 and a.full else "chunk"
     # RCCL prints a version banner on stdout when the process exits; the contract is ONE JSON
     # line on stdout, so everything C-level goes to stderr and the line is written to the real
     # stdout explicitly.
@@ -453,13 +523,15 @@ def main():
     failed = False
     single = world == 1 and not b.force_dist
     first_mode = "exact" if a.mode == "exact" else "chunk"
-    res = b.run(first_mode, collect_side=(rank == 0 and single and first_mode == "chunk" and not a.no_side_runs
-                                          and b.on_gpu))
+    res = b.run(first_mode, collect_side=(a.full and rank == 0 and single and first_mode == "chunk"
+                                          and not a.no_side_runs and b.on_gpu))
     res_exact = b.run("exact", collect_side=False) if a.mode == "both" else None
     exact = first_mode == "exact"
     stats, elapsed, elapsed_cached, last = res["stats"], res["elapsed"], res["elapsed_cached"], res["last"]
     seqs, offsets = res["seqs"], res["offsets"]
     if rank == 0:
+        if a.dump_outputs is not None:
+            write_outputs(a.dump_outputs, res["outputs"])
         total_seqs = a.nseq * world * a.steps
         scan_s = stats["scan_ms"] / 1e3
         cb = stats["count_bytes"]  # sizeof(count) of the matrix the scan reads: 2 for whole-sequence rows, else 4
@@ -507,8 +579,6 @@ def main():
                 "offsets_cache": "off in the timed steps (every step validates its offsets as a first build does; "
                                  "sequences of one length laid end to end -- this workload -- are recognised in that "
                                  "pass and built from (base, stride): nothing is uploaded)",
-                "value_with_offsets_cache": total_seqs / elapsed_cached,
-                "ms_per_step_with_offsets_cache": elapsed_cached / a.steps * 1e3,
             },
             "roofline": {
                 "kernel": (f"persist_nmost_kernel<uint{8 * cb}> (windowed delta-JSD scan + in-kernel set updates behind "
@@ -530,6 +600,9 @@ def main():
                 "avg_launch_us": stats["scan_ms"] * 1e3 / max(1, stats["scan_launches"]),
             },
         }
+        if elapsed_cached is not None:  # (--full)
+            out["config"]["value_with_offsets_cache"] = total_seqs / elapsed_cached
+            out["config"]["ms_per_step_with_offsets_cache"] = elapsed_cached / a.steps * 1e3
         # The average over a selection's launches hides two very different ones when it starts with a head phase
         # (the event-dense first rows on the head CUs beside the histogram, then the full grid): each on its own
         if stats["engine"] == 1 and stats["scan_launches"] == 2 * a.steps and stats["scan_ms_last"] > 0:
@@ -626,7 +699,7 @@ def main():
             if headline:
                 raise SystemExit(f"bench.py: profiles/pmc_traffic.json does not serve the headline workload: {e}")
             out["roofline"]["traffic_source"] = f"none: no PMC profile committed for this workload ({wl})"
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             import oracle
 
             ns = min(a.cpu_sample, a.nseq)

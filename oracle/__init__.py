@@ -1,7 +1,7 @@
 """ctypes/numpy face of the CPU ORACLE (oracle/dvs_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, ``__graft_entry__.smoke()`` and
-the ``cpu_baseline`` leg of ``bench.py``.  Nothing under ``diverseseq_amd/``
+the ``cpu_baseline`` leg of ``bench.py --full``.  Nothing under ``diverseseq_amd/``
 may import this package (tests/test_boundary.py enforces it).
 
 Each helper mirrors one reference entry point; the arithmetic is in the C file,

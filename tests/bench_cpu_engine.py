@@ -74,8 +74,8 @@ class OracleStepper:
 
 
 class _Members:
-    def __init__(self, lab, delta, rows):
-        self.positions, self.delta_jsd, self.kfreqs = lab, delta, rows
+    def __init__(self, lab, delta, ent, rows):
+        self.positions, self.labels, self.delta_jsd, self.entropy, self.kfreqs = lab, lab, delta, ent, rows
 
 
 class Selection:
@@ -88,8 +88,8 @@ class Selection:
                                      size=self._s.size)
 
     def members(self, with_freqs=False):
-        lab, delta, _, rows = self._s.members(with_freqs=with_freqs)
-        return _Members(lab, delta, rows)
+        lab, delta, ent, rows = self._s.members(with_freqs=with_freqs)
+        return _Members(lab, delta, ent, rows)
 
     def close(self):
         pass
@@ -102,6 +102,16 @@ class Matrix:
         self.seqs, self.k, self.freqs = seqs, k, freqs
         self.nrows = len(seqs) if seqs is not None else freqs.shape[0]
         self.nbins = 4 ** k if seqs is not None else freqs.shape[1]
+
+    def counts(self, row0=0, nrows=None):
+        nrows = self.nrows - row0 if nrows is None else nrows
+        return np.stack([oracle.count_kmers(self.seqs[r], 4, self.k) for r in range(row0, row0 + nrows)])
+
+    def totals(self):
+        return np.array([oracle.count_kmers(s, 4, self.k).sum() for s in self.seqs])
+
+    def entropy(self):
+        return np.array([oracle.to_kfreqs(s, 4, self.k)[1] for s in self.seqs])
 
     def nmost(self, n, window=0):
         if self.freqs is not None:

@@ -26,7 +26,7 @@ def _env():
 
 
 def test_bench_gpus_2_launches_two_ranks_itself():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", *ARGS], env=_env(),
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", *ARGS], env=_env(),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -62,3 +62,74 @@ def test_exact_scheme_of_the_stand_in_gives_the_one_process_answer():
     assert r.returncode == 0, r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["config"]["accepts_per_step"] > 0
+
+
+def _line(r):
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_the_headline_only_and_full_adds_the_rest():
+    """without --full: the headline fields and nothing measured beside them; with --full: the offsets-cache
+    timing and the CPU baseline with its oracle check of the last timed step"""
+    args = [a for a in ARGS if a != "--no-cpu-baseline"]
+    plain = _line(subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *args], env=_env(),
+                                 capture_output=True, text=True, timeout=300))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain
+    assert plain["steps"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert "cpu_baseline" not in plain and "verified_vs_oracle" not in plain
+    assert "value_with_offsets_cache" not in plain["config"]
+    full = _line(subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--full", *args], env=_env(),
+                                capture_output=True, text=True, timeout=300))
+    assert full["verified_vs_oracle"] is True
+    assert full["cpu_baseline"]["value"] > 0
+    assert full["config"]["value_with_offsets_cache"] > 0
+
+
+def test_plain_run_with_two_gpus_times_the_chunk_scheme_alone():
+    out = _line(subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", *ARGS], env=_env(),
+                               capture_output=True, text=True, timeout=600))
+    assert out["n_gpus"] == 2 and out["value"] > 0
+    assert "value_exact" not in out and "exact_mode" not in out["config"]
+
+
+def test_dump_outputs_writes_the_last_step_and_repeats_itself(tmp_path):
+    """--dump-outputs DIR: float32 / float64 arrays of what the last timed step computed, the same from run to run,
+    and the members are the oracle's members of the same sequences"""
+    import oracle
+
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        _line(subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *ARGS, "--dump-outputs", str(d)],
+                             env=_env(), capture_output=True, text=True, timeout=300))
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) >= {"members_positions", "members_delta_jsd", "total_jsd", "row_totals", "row_entropy",
+                      "count_sample", "count_sample_rows"}
+    assert a.keys() == b.keys()
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    nseq, k, n = 240, 3, 5
+    assert a["row_totals"].shape == (nseq,) and a["members_positions"].shape == (n,)
+    assert a["count_sample"].shape == (a["count_sample_rows"].size, 4 ** k)
+    assert np.all(a["row_totals"] == 200 - k + 1)
+    # the stand-in's inputs are torch.randint(0, 4) with bench.py's seed; the oracle on the same sequences
+    import torch
+
+    g = torch.Generator(device="cpu")
+    g.manual_seed(20260421)
+    host = torch.randint(0, 4, (nseq * 200,), dtype=torch.uint8, generator=g).numpy()
+    offsets = np.arange(nseq + 1, dtype=np.uint64) * np.uint64(200)
+    oset, _ = oracle.nmost_concat(host, offsets, n, k, 4)
+    elab, edelta, _, _ = oset.members()
+    assert a["members_positions"].tolist() == elab.tolist()
+    assert np.allclose(a["members_delta_jsd"], edelta, rtol=1e-12, atol=0)
+    assert a["total_jsd"][0] == oset.total_jsd
+    for j, r in enumerate(a["count_sample_rows"].astype(int)):
+        assert np.array_equal(a["count_sample"][j], oracle.count_kmers(host[r * 200:(r + 1) * 200], 4, k))
