@@ -769,9 +769,19 @@ static int mash_sketch_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_t
         if (!arc) arc = dvs_dev_alloc(ctx, &d_lens.p, size_t(nseq) * 4, "sketch lengths");
         if (arc) return arc;
     }
-    // (host vectors are the sources of asynchronous copies: the stream is drained before this function returns on
-    // every path -- the round loop below ends each round with a synchronisation -- except the early error
-    // returns, which drain it themselves)
+    // Host memory -- tpre, cap, coff, lo, hi, active, list, the caller's offsets -- is the source of asynchronous
+    // copies, and a kernel may still be reading the blocks above: whenever work is pending on the stream, a return
+    // from here on (an error, the batch whose every sequence is shorter than k) drains it before either goes away.
+    // (Every round of the search ends with a synchronisation, so the usual return has nothing left to wait for.)
+    std::vector<uint8_t> active(nseq, 1);
+    std::vector<uint32_t> status(nseq, 0), lens(nseq, 0), lens_before(nseq, 0), list;
+    struct StreamDrain {
+        hipStream_t st;
+        bool pending = true;
+        ~StreamDrain() {
+            if (pending) (void)hipStreamSynchronize(st);
+        }
+    } drain{ctx->stream};
     hipError_t ue = hipMemcpyAsync(d_off.p, offsets, (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
     if (ue == hipSuccess) ue = hipMemcpyAsync(d_tpre.p, tpre.data(), (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
     if (ue == hipSuccess) ue = hipMemcpyAsync(d_cap.p, cap.data(), size_t(nseq) * 4, hipMemcpyHostToDevice, ctx->stream);
@@ -783,28 +793,43 @@ static int mash_sketch_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_t
                            d_tpre.as<uint64_t>(), nseq, k, n_tiles, d_tiles.as<MTile>());
         ue = hipGetLastError();
     }
-    if (ue != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, ue, "sketch set-up");
-    }
+    if (ue != hipSuccess) return dvs_hip_fail(ctx, ue, "sketch set-up");
 
-    std::vector<uint8_t> active(nseq, 1);
-    std::vector<uint32_t> status(nseq, 0), lens(nseq, 0);
-    for (uint32_t q = 0; q < nseq; q++)
+    // The rounds of the range search of one sequence are bounded.  A round either halves its range (status 2: only
+    // ranges at least 2 wide are halved, so at most 32 halvings come in a row) or advances past it (status 1), and the
+    // search of a sequence ends in a round of status 0.  Call an advance PRODUCTIVE when its range held a hash not in
+    // the sketch yet: each one lengthens the sketch, so a sequence of w windows has at most min(s, w) of them, and
+    // one final round.  Between two productive rounds, let h* be the least hash above lo and d = h* - lo: an
+    // unproductive advance moves lo by the width it covered, which is < d, and (the rule below) at least doubles the
+    // next width; a halving needs width >= d (its range held h*).  So first come at most 33 doubling advances; after
+    // a run of halvings the range is narrower than d but half the last one was not, and the advance past it at least
+    // halves d -- at most 33 such runs of at most 32 halvings, each followed by one advance.  That is at most
+    // 33 + 33 * 33 unproductive rounds between productive ones: a sequence that goes on longer without one is refused
+    // at once (a bug, not a hard input), and the batch as a whole within (min(s, w) + 1) * (STRETCH + 1) rounds.
+    constexpr uint32_t STRETCH = 33 + 33 * 33;
+    std::vector<uint32_t> idle(nseq, 0);  // unproductive rounds in a row, per sequence
+    uint64_t max_productive = 0;
+    for (uint32_t q = 0; q < nseq; q++) {
         if (nwin[q] == 0) active[q] = 0;  // L < k: empty sketch (distance.rs:102-104)
+        max_productive = std::max<uint64_t>(max_productive, std::min<uint64_t>(s, nwin[q]) + 1);
+    }
+    const uint64_t max_rounds = max_productive * (STRETCH + 1);
     const size_t sort_lds = SORT_CAP * 4;
     {
         const int lrc = dvs_raise_dyn_lds(ctx, reinterpret_cast<const void *>(sort_select_kernel), sort_lds);
         if (lrc) return lrc;
     }
 
-    for (int round = 0;; round++) {
-        std::vector<uint32_t> list;
+    for (uint64_t round = 0;; round++) {
+        list.clear();
         for (uint32_t q = 0; q < nseq; q++)
             if (active[q]) list.push_back(q);
         if (list.empty()) break;
-        if (round >= 200)
-            return dvs_set_error(ctx, DVS_ERR_RUNTIME, "mash sketch range search did not converge");
+        if (round >= max_rounds)
+            return dvs_set_error(ctx, DVS_ERR_RUNTIME, "mash sketch range search did not converge in %llu rounds",
+                                 (unsigned long long)max_rounds);
+        lens_before = lens;
+        drain.pending = true;
         DVS_HIP(ctx, hipMemcpyAsync(d_lo.p, lo.data(), nseq * 8, hipMemcpyHostToDevice, ctx->stream));
         DVS_HIP(ctx, hipMemcpyAsync(d_hi.p, hi.data(), nseq * 4, hipMemcpyHostToDevice, ctx->stream));
         DVS_HIP(ctx, hipMemcpyAsync(d_active.p, active.data(), nseq, hipMemcpyHostToDevice, ctx->stream));
@@ -850,16 +875,27 @@ static int mash_sketch_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_t
         DVS_HIP(ctx, hipMemcpyAsync(status.data(), d_status.p, nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
         DVS_HIP(ctx, hipMemcpyAsync(lens.data(), d_lens.p, nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
         DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        drain.pending = false;
         for (uint32_t q : list) {
             const uint64_t width = uint64_t((long long)hi[q] - lo[q]);
+            idle[q] = status[q] == 1 && lens[q] != lens_before[q] ? 0u : idle[q] + 1u;
+            if (status[q] != 0 && idle[q] > STRETCH)
+                return dvs_set_error(ctx, DVS_ERR_RUNTIME,
+                                     "mash sketch range search: sequence %u found no new hash in %u rounds", q, STRETCH);
             if (status[q] == 0) {
                 active[q] = 0;
             } else if (status[q] == 1) {
-                // everything in (lo, hi] is final; continue above it with a range sized by
-                // the density seen so far (at least doubling)
-                const uint64_t found = std::max<uint32_t>(lens[q], 1);
+                // everything in (lo, hi] is final; continue above it with a range sized by the density seen so far:
+                // wide enough for what is still needed (1.5 x) but at most what holds ~SORT_CAP / 2 candidates --
+                // for a large s the estimate reaches the top of the hash space, and shrinking such a range back to
+                // SORT_CAP candidates took a halving round (a hash pass over the sequence) per factor of two.  A range
+                // that held nothing new says nothing about the density: the next one is at least twice as wide.
+                const long double per_hash = (long double)(uint64_t(hi[q]) + 1) / std::max<uint32_t>(lens[q], 1);
                 const uint64_t need = s - lens[q];
-                uint64_t next = std::max<uint64_t>(2 * width, uint64_t((long double)(uint64_t(hi[q]) + 1) / found * need * 1.5L));
+                const uint64_t est = uint64_t(std::min<long double>(per_hash * need * 1.5L, 8589934592.0L));
+                const uint64_t cap_w = uint64_t(std::min<long double>(per_hash * (SORT_CAP / 2), 8589934592.0L));
+                const uint64_t next = lens[q] == lens_before[q] ? std::max<uint64_t>(2 * width, std::min(est, cap_w))
+                                                                : std::min(std::max<uint64_t>(2 * width, est), cap_w);
                 lo[q] = hi[q];
                 const uint64_t nh = uint64_t(hi[q]) + std::max<uint64_t>(next, 1);
                 hi[q] = nh >= 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(nh);

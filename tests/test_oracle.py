@@ -292,3 +292,29 @@ def test_chunk_and_merge_on_threads_equals_the_sequential_scheme():
     exp = oracle.final_nmost(np.vstack(rows), n, labels=np.concatenate(labs))
     assert got.members()[0].tolist() == exp.members()[0].tolist()
     assert got.total_jsd == exp.total_jsd
+
+
+def test_extreme_hash_kmers_fixture():
+    """tests/golden/extreme_hash_kmers.json (gen_extreme_hash_kmers.py): k-mers whose hash is 0, 1, 0xFFFFFFFE or
+    0xFFFFFFFF -- the sketch kernels' range edge, hash-set empty marker and sort padding -- in plain and canonical
+    mode, checked against the oracle's restatement of the reference's hash"""
+    import json
+    import pathlib
+
+    fx = json.loads((pathlib.Path(__file__).parent / "golden" / "extreme_hash_kmers.json").read_text())
+    want = {(k, t) for k in (24, 32, 40) for t in fx["targets"]}
+    have = {(e["k"], e["target"]) for e in fx["entries"]}
+    assert want <= have, "every target has a preimage at k = 24, 32, 40"
+    assert not have & {(a["k"], a["target"]) for a in fx["absent"]}
+    for e in fx["entries"]:
+        kmer = np.array([int(c) for c in e["kmer"]], dtype=np.uint8)
+        assert kmer.size == e["k"] and kmer.max() < 4
+        assert oracle.hash_kmer(kmer, False) == e["target"], e
+        assert oracle.hash_kmer(kmer, True) == (e["target"] if e["canonical"] else oracle.hash_kmer(
+            oracle.reverse_complement(kmer), False)), e
+        if e["revcomp"] is not None:
+            rc = np.array([int(c) for c in e["revcomp"]], dtype=np.uint8)
+            assert (rc == oracle.reverse_complement(kmer)).all()
+            assert oracle.hash_kmer(rc, True) == e["target"], e
+            assert oracle.hash_kmer(rc, False) != e["target"], e
+    assert sum(e["canonical"] for e in fx["entries"]) >= 12
