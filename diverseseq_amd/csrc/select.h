@@ -106,7 +106,6 @@ struct dvs_select {
     bool scan_hot = false;
     // persistent single-launch engine (persist.hip)
     bool persist = false;
-    bool persist_fell_back = false;  // the persistent kernel gave up (not co-resident): multi-launch engine from the seeds
     uint32_t persist_grid = 0, persist_maxn = 0, persist_maxjobs = 0;
     bool persist_small = false;       // the SMALL instantiation: member count rows in every workgroup's LDS
     uint32_t persist_small_rows = 0;  // ... that many of them
@@ -143,7 +142,7 @@ struct dvs_select {
     // stepwise selections, MODE_NMOST without labels: the fast step (select.hip fs_jobs_kernel / fs_step_kernel)
     bool fast_step = false;
     bool fs_need_scan = false;   // the next dvs_select_step_pack must scan first (selection start, behind an arbitration)
-    unsigned long long *h_fshist = nullptr;  // pinned: the status word of every apply launch (FS_HIST of them, dvs_select_step_peek)
+    unsigned long long *h_fshist = nullptr;  // pinned: the status word of every apply launch (FS_HIST of them, dvs_select_step_peek; every fast step has it)
     unsigned long long fs_launches = 0;      // apply launches of the fast step so far
     unsigned long long fs_peek_floor = 0;    // ... of them, those enqueued before the last dvs_select_step_poll
     double *fs_slot = nullptr;   // the caller's slot of the last dvs_select_step_pack (the next step's kernel packs into it)
@@ -170,6 +169,9 @@ int dvs_persist_launch(dvs_ctx *ctx, dvs_select *s);
 int dvs_persist_launch_head(dvs_ctx *ctx, dvs_select *s, uint32_t grid, uint32_t stop_at, hipStream_t on);
 int dvs_persist_prepare_main(dvs_ctx *ctx, dvs_select *s);
 int dvs_persist_prepare_head(dvs_ctx *ctx, dvs_select *s, uint32_t stop_at, hipStream_t on);
-size_t dvs_persist_dbg_offset(void);
-size_t dvs_persist_trace_offset(void);  // 0 unless built with -DDVS_PERSIST_STAMPS
-int dvs_persist_probe_id(void);         // the one interval a -DDVS_PROBE=k build measures (0: none)
+void dvs_persist_debug_report(dvs_ctx *ctx, const dvs_select *s);  // DVS_PERSIST_DEBUG: the launches' phase times
+void dvs_persist_debug_done(const SelCtl &c);                        // ... and why they ended early
+
+// select.hip: s->time_scan -- the next (start, stop) pair of the selection's event pool, the start recorded on `on`;
+// returns the stop, which the caller records behind its launch (the next poll adds the pair up)
+hipEvent_t dvs_scan_timing_start(dvs_ctx *ctx, dvs_select *s, hipStream_t on);

@@ -32,6 +32,7 @@
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 
 namespace {
 
@@ -1575,6 +1576,32 @@ __global__ __launch_bounds__(FS_THREADS, 2) void fs_step_kernel(SelDev d, const 
     }
 }
 
+#ifdef DVS_FS_TRACE
+// the stamps a -DDVS_FS_TRACE build of the step kernel leaves behind the jobs' results (DVS_FS_DEBUG=1: on stderr when
+// the selection goes)
+static void fs_trace_report(const dvs_select *s) {
+    if (!s->d_jobres || !getenv("DVS_FS_DEBUG")) return;
+    std::vector<unsigned long long> t(8 * 1024);
+    (void)hipDeviceSynchronize();
+    if (hipMemcpy(t.data(), reinterpret_cast<char *>(s->d_jobres) + size_t(2048) * 8 * 8, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    unsigned long long t0 = ~0ull;
+    for (uint32_t b = 0; b < s->fs_grid; b++) if (t[b * 8]) t0 = std::min(t0, t[b * 8]);
+    auto us = [&](unsigned long long x) { return x ? (double(x) - double(t0)) / 100.0 : -1.0; };
+    double mx[8] = {0}, mn[8]; for (int k = 0; k < 8; k++) mn[k] = 1e9;
+    for (uint32_t b = 1; b < s->fs_grid; b++) for (int k = 0; k < 7; k++) if (t[b * 8 + k]) { mx[k] = std::max(mx[k], us(t[b * 8 + k])); mn[k] = std::min(mn[k], us(t[b * 8 + k])); }
+    fprintf(stderr, "[fs trace] scanning workgroups (us, min/max): start %.1f/%.1f decided %.1f/%.1f base+arrived %.1f/%.1f scan end %.1f/%.1f\n", mn[0], mx[0], mn[1], mx[1], mn[2], mx[2], mn[6], mx[6]);
+    std::vector<double> e, r1, c1, sc; double posted = -1; unsigned long long nr = 0, nrmax = 0;
+    for (uint32_t b = 1; b < s->fs_grid; b++) { if (t[b * 8 + 6]) e.push_back(us(t[b * 8 + 6])); if (t[b * 8 + 3]) r1.push_back(us(t[b * 8 + 3])); if (t[b * 8 + 4]) c1.push_back(us(t[b * 8 + 4]));
+        if (t[b * 8 + 5]) sc.push_back(us(t[b * 8 + 5])); nr += t[b * 8 + 7]; nrmax = std::max(nrmax, t[b * 8 + 7]); }
+    std::sort(e.begin(), e.end()); std::sort(r1.begin(), r1.end()); std::sort(c1.begin(), c1.end()); std::sort(sc.begin(), sc.end());
+    auto pc = [&](std::vector<double> &v, double q) { return v.empty() ? -1.0 : v[size_t(q * (v.size() - 1))]; };
+    fprintf(stderr, "[fs trace] wave 0s: scan loop entered p10/50/90/max %.1f %.1f %.1f %.1f; first row's data there %.1f %.1f %.1f %.1f; its score %.1f %.1f %.1f %.1f; scan end %.1f %.1f %.1f %.1f; first post (wave 0s only) %.1f; rows read sum %llu max %llu\n",
+            pc(sc, .1), pc(sc, .5), pc(sc, .9), pc(sc, 1), pc(r1, .1), pc(r1, .5), pc(r1, .9), pc(r1, 1), pc(c1, .1), pc(c1, .5), pc(c1, .9), pc(c1, 1), pc(e, .1), pc(e, .5), pc(e, .9), pc(e, 1), posted, nr, nrmax);
+    const uint32_t L = 0;
+    fprintf(stderr, "[fs trace] state writer: start %.1f decided %.1f loaded %.1f all arrived %.1f small stores issued %.1f rows issued %.1f done %.1f\n", us(t[L * 8]), us(t[L * 8 + 1]), us(t[L * 8 + 2]), us(t[L * 8 + 3]), us(t[L * 8 + 4]), us(t[L * 8 + 6]), us(t[L * 8 + 5]));
+}
+#endif
+
 // ---- MODE_MAX while the set may grow: a BATCH of rows against the unchanged set.
 // A tentative push that is rolled back leaves the set as it was (records.rs:439-450), and so does a row that
 // is no event: the rows from the cursor up to the next push that is KEPT all face the same set.  Where
@@ -1944,27 +1971,7 @@ __global__ __launch_bounds__(LOO_THREADS) void pack_event_kernel(SelDev d, const
 static void sel_free(dvs_select *s) {
     if (!s) return;
 #ifdef DVS_FS_TRACE
-    if (s->d_jobres && getenv("DVS_FS_DEBUG")) {
-        std::vector<unsigned long long> t(8 * 1024);
-        (void)hipDeviceSynchronize();
-        if (hipMemcpy(t.data(), reinterpret_cast<char *>(s->d_jobres) + size_t(2048) * 8 * 8, t.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            unsigned long long t0 = ~0ull;
-            for (uint32_t b = 0; b < s->fs_grid; b++) if (t[b * 8]) t0 = std::min(t0, t[b * 8]);
-            auto us = [&](unsigned long long x) { return x ? (double(x) - double(t0)) / 100.0 : -1.0; };
-            double mx[8] = {0}, mn[8]; for (int k = 0; k < 8; k++) mn[k] = 1e9;
-            for (uint32_t b = 1; b < s->fs_grid; b++) for (int k = 0; k < 7; k++) if (t[b * 8 + k]) { mx[k] = std::max(mx[k], us(t[b * 8 + k])); mn[k] = std::min(mn[k], us(t[b * 8 + k])); }
-            fprintf(stderr, "[fs trace] scanning workgroups (us, min/max): start %.1f/%.1f decided %.1f/%.1f base+arrived %.1f/%.1f scan end %.1f/%.1f\n", mn[0], mx[0], mn[1], mx[1], mn[2], mx[2], mn[6], mx[6]);
-            std::vector<double> e, r1, c1, sc; double posted = -1; unsigned long long nr = 0, nrmax = 0;
-            for (uint32_t b = 1; b < s->fs_grid; b++) { if (t[b * 8 + 6]) e.push_back(us(t[b * 8 + 6])); if (t[b * 8 + 3]) r1.push_back(us(t[b * 8 + 3])); if (t[b * 8 + 4]) c1.push_back(us(t[b * 8 + 4]));
-                if (t[b * 8 + 5]) sc.push_back(us(t[b * 8 + 5])); nr += t[b * 8 + 7]; nrmax = std::max(nrmax, t[b * 8 + 7]); }
-            std::sort(e.begin(), e.end()); std::sort(r1.begin(), r1.end()); std::sort(c1.begin(), c1.end()); std::sort(sc.begin(), sc.end());
-            auto pc = [&](std::vector<double> &v, double q) { return v.empty() ? -1.0 : v[size_t(q * (v.size() - 1))]; };
-            fprintf(stderr, "[fs trace] wave 0s: scan loop entered p10/50/90/max %.1f %.1f %.1f %.1f; first row's data there %.1f %.1f %.1f %.1f; its score %.1f %.1f %.1f %.1f; scan end %.1f %.1f %.1f %.1f; first post (wave 0s only) %.1f; rows read sum %llu max %llu\n",
-                    pc(sc, .1), pc(sc, .5), pc(sc, .9), pc(sc, 1), pc(r1, .1), pc(r1, .5), pc(r1, .9), pc(r1, 1), pc(c1, .1), pc(c1, .5), pc(c1, .9), pc(c1, 1), pc(e, .1), pc(e, .5), pc(e, .9), pc(e, 1), posted, nr, nrmax);
-            const uint32_t L = 0;
-            fprintf(stderr, "[fs trace] state writer: start %.1f decided %.1f loaded %.1f all arrived %.1f small stores issued %.1f rows issued %.1f done %.1f\n", us(t[L * 8]), us(t[L * 8 + 1]), us(t[L * 8 + 2]), us(t[L * 8 + 3]), us(t[L * 8 + 4]), us(t[L * 8 + 6]), us(t[L * 8 + 5]));
-        }
-    }
+    fs_trace_report(s);
 #endif
     // Work this selection queued on the context's side streams (the head phase's sync block, the seed
     // list, set-up kernels) may still be pending on an error path; the pool only orders reuse on the
@@ -1981,9 +1988,9 @@ static void sel_free(dvs_select *s) {
         dvs_dev_free(s->ctx, p);
     // (step kernels still queued -- a driver that gave up half-way -- write their status words into the pinned history:
     // they are waited for before the block goes back to the cache, where the next selection's control mirror may take it)
-    if (s->h_fshist && s->fs_launches && s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
+    if (s->fs_launches && s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
     dvs_pinned_put(s->ctx, s->h_ctl);
-    if (s->h_fshist) dvs_pinned_put(s->ctx, s->h_fshist);
+    dvs_pinned_put(s->ctx, s->h_fshist);
     for (hipEvent_t e : s->ev_pool) dvs_event_put(s->ctx, e);
     dvs_dev_free(s->ctx, s->d_mbres);
     dvs_dev_free(s->ctx, s->d_jobres);
@@ -1999,32 +2006,52 @@ static void sel_free(dvs_select *s) {
     delete s;
 }
 
+hipEvent_t dvs_scan_timing_start(dvs_ctx *ctx, dvs_select *s, hipStream_t on) {
+    if (!s->time_scan) return nullptr;
+    if (s->ev_used + 2 > s->ev_pool.size()) {
+        hipEvent_t a = dvs_event_get(ctx), b = dvs_event_get(ctx);
+        s->ev_pool.push_back(a);
+        s->ev_pool.push_back(b);
+    }
+    s->ev_used += 2;
+    (void)hipEventRecord(s->ev_pool[s->ev_used - 2], on);
+    return s->ev_pool[s->ev_used - 1];
+}
+
+// the pairs of the scan launches since the last poll (which synchronised the stream: the events are complete)
+static void sel_add_scan_times(dvs_select *s) {
+    for (size_t i = 0; i + 1 < s->ev_used; i += 2) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, s->ev_pool[i], s->ev_pool[i + 1]) == hipSuccess) {
+            s->scan_ms += ms;
+            s->scan_ms_last = ms;
+        }
+        s->scan_launches++;
+    }
+    s->ev_used = 0;
+}
+
+// one scan_kernel launch with the selection's geometry, against the control block `ctl` and the row counters `wg_rows`
+// (the caller says which instantiation: `hot` picks scan_kernel<T, true>)
+template <typename T>
+static void launch_scan(const dvs_select *s, const T *mat, bool hot, SelCtl *ctl, uint32_t *wg_rows, hipStream_t st) {
+    const SelDev &d = s->dev;
+    if (hot)
+        hipLaunchKernelGGL((scan_kernel<T, true>), dim3(s->scan_grid), dim3(SCAN_THREADS), s->scan_lds, st, ctl, mat, d.totals,
+                           d.rowH, d.order, d.labels, d.inset, d.nlabels, d.base, wg_rows, d.B, s->base_in_lds ? 1 : 0);
+    else
+        hipLaunchKernelGGL((scan_kernel<T, false>), dim3(s->scan_grid), dim3(SCAN_THREADS), s->scan_lds, st, ctl, mat, d.totals,
+                           d.rowH, d.order, d.labels, d.inset, d.nlabels, d.base, wg_rows, d.B, s->base_in_lds ? 1 : 0);
+}
+
 // stage 0: scan + resolve + loo + finalize; 1: resolve + loo + finalize; 2: loo + finalize
 template <typename T>
 static void launch_iteration(dvs_ctx *ctx, dvs_select *s, const T *mat, int stage, hipStream_t on = nullptr) {
     const SelDev &d = s->dev;
     const hipStream_t stream = on ? on : ctx->stream;
     if (stage == 0) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (s->time_scan) {
-            if (s->ev_used + 2 > s->ev_pool.size()) {
-                hipEvent_t a = dvs_event_get(ctx), b = dvs_event_get(ctx);
-                s->ev_pool.push_back(a);
-                s->ev_pool.push_back(b);
-            }
-            e0 = s->ev_pool[s->ev_used];
-            e1 = s->ev_pool[s->ev_used + 1];
-            s->ev_used += 2;
-            (void)hipEventRecord(e0, stream);
-        }
-        if (s->scan_hot)
-            hipLaunchKernelGGL((scan_kernel<T, true>), dim3(s->scan_grid), dim3(SCAN_THREADS),
-                               s->scan_lds, stream, d.ctl, mat, d.totals, d.rowH, d.order, d.labels,
-                               d.inset, d.nlabels, d.base, d.wg_rows, d.B, s->base_in_lds ? 1 : 0);
-        else
-            hipLaunchKernelGGL((scan_kernel<T, false>), dim3(s->scan_grid), dim3(SCAN_THREADS),
-                               s->scan_lds, stream, d.ctl, mat, d.totals, d.rowH, d.order, d.labels,
-                               d.inset, d.nlabels, d.base, d.wg_rows, d.B, s->base_in_lds ? 1 : 0);
+        const hipEvent_t e1 = dvs_scan_timing_start(ctx, s, stream);
+        launch_scan<T>(s, mat, s->scan_hot, d.ctl, d.wg_rows, stream);
         if (s->time_scan) (void)hipEventRecord(e1, stream);
     }
     if (stage <= 1)
@@ -2060,8 +2087,48 @@ static int sel_poll(dvs_ctx *ctx, dvs_select *s) {
 template <typename T>
 static int sel_seed(dvs_ctx *ctx, dvs_select *s, const T *mat, hipStream_t st, bool light = false);
 
+// Drop the seeded start: the set-up kernels set the initial set up after all (enqueued on `st`), and the next
+// persistent launch starts from the state they leave
 template <typename T>
-static int sel_run_loop(dvs_ctx *ctx, dvs_select *s, const T *mat, bool first_unpolled = false) {
+static int sel_drop_seeded(dvs_ctx *ctx, dvs_select *s, const T *mat, hipStream_t st) {
+    s->seeded_start = false;
+    s->persist_seeded = false;
+    return sel_seed<T>(ctx, s, mat, st);
+}
+
+// Leave the persistent engine for good: the multi-launch engine, which needs no co-residency, carries on from the
+// state the engine left or, with `restart`, starts the selection over from its seeds
+template <typename T>
+static int sel_leave_persist(dvs_ctx *ctx, dvs_select *s, const T *mat, bool restart) {
+    s->persist = false;
+    if (!restart) return DVS_OK;
+    dvs_select_arbiter_free(s);  // (its replay of the event log belongs to the abandoned run)
+    return sel_drop_seeded<T>(ctx, s, mat, ctx->stream);
+}
+
+// A decision inside the rounding band (status SEL_ARBITER, h_ctl current): the host arbiter takes it, and the kernels
+// of the stage the device stopped at carry on from its verdict
+template <typename T>
+static int sel_arbitrate(dvs_ctx *ctx, dvs_select *s, const T *mat) {
+    const SelCtl &c = *s->h_ctl;
+    if (s->params.flags & DVS_SELECT_NO_ARBITER)
+        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
+                             "ambiguous decision at stream position %llu (stage %u): "
+                             "|score - threshold| within the rounding band",
+                             (unsigned long long)c.arb_pos, c.arb_stage);
+    const uint32_t stage = c.arb_stage;  // (the arbiter hands it back as it came)
+    const auto t_arb = std::chrono::steady_clock::now();
+    const int rc = dvs_select_arbitrate(ctx, s);
+    s->arbiter_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_arb).count();
+    if (rc) return rc;
+    launch_iteration<T>(ctx, s, mat, stage == ARB_RESOLVE ? 1 : 2);
+    DVS_HIP(ctx, hipGetLastError());
+    return DVS_OK;
+}
+
+// the engine behind the set-up sel_start enqueued, driven to the end of the stream
+template <typename T>
+static int sel_run_loop(dvs_ctx *ctx, dvs_select *s, const T *mat) {
     unsigned long long persist_cursor = 0;
     unsigned persist_launches = 0;
     bool persist_was_last = false;  // nothing but the poll happened since the last persistent launch
@@ -2070,193 +2137,54 @@ static int sel_run_loop(dvs_ctx *ctx, dvs_select *s, const T *mat, bool first_un
     unsigned long long mb_cursor = 0, mb_events = 0;
     bool mb_useful = true;
     uint32_t mb_rows_seen = 0, mb_round_pairs = 0, mb_idle_rounds = 0;
-    if (s->persist && first_unpolled) {
+    // one persistent launch from the state at `cursor`.  A grid the runtime refuses leaves the engine for the
+    // multi-launch kernels -- from the seeds if it was a seeded start's first launch (nothing set the initial set up
+    // yet: the set-up kernels do)
+    auto persist_launch = [&](unsigned long long cursor) {
+        persist_cursor = cursor;
+        persist_launches++;
+        persist_was_last = true;
+        const int rc = dvs_persist_launch(ctx, s);
+        if (rc != DVS_ERR_UNSUPPORTED) return rc;
+        return sel_leave_persist<T>(ctx, s, mat, s->seeded_start && persist_launches == 1);
+    };
+    if (s->persist) {
         // straight behind the set-up kernels, no host round trip in between: the kernel itself
         // returns at once unless the control block says RUN
-        persist_cursor = s->params.n_seed;  // the cursor the set-up leaves behind
-        persist_launches = 1;
-        persist_was_last = true;
-        int rc0 = dvs_persist_launch(ctx, s);
-        if (rc0 == DVS_ERR_UNSUPPORTED) {  // the runtime refused the grid: the multi-launch engine takes over
-            s->persist = false;
-            s->persist_fell_back = true;
-            persist_launches = 0;
-            if (s->seeded_start) {  // (nothing set the initial set up yet: the set-up kernels do)
-                s->seeded_start = false;
-                s->persist_seeded = false;
-                int src = sel_seed<T>(ctx, s, mat, ctx->stream);
-                if (src) return src;
-            }
-        } else if (rc0) {
-            return rc0;
-        }
+        int rc = persist_launch(s->params.n_seed);  // (the cursor the set-up leaves behind)
+        if (rc) return rc;
     }
-    // the loo grid must cover the largest set a batch can reach
     for (;;) {
         int rc = sel_poll(ctx, s);
         if (rc) return rc;
         const SelCtl &c = *s->h_ctl;
-        if (s->time_scan && s->ev_used) {  // the poll synchronised the stream: events are complete
-            for (size_t i = 0; i + 1 < s->ev_used; i += 2) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, s->ev_pool[i], s->ev_pool[i + 1]) == hipSuccess) {
-                    s->scan_ms += ms;
-                    s->scan_ms_last = ms;
-                }
-                s->scan_launches++;
-            }
-            s->ev_used = 0;
-        }
-        for (int which = 0; which < 2 && s->persist && ctx->knobs.persist_debug; which++) {
-            unsigned long long dbg[32];
-            void *blk = which ? s->psync : s->psync_head;  // (the head phase's launch first, then the full grid's)
-            if (!blk) continue;
-            if (hipMemcpy(dbg, static_cast<char *>(blk) + dvs_persist_dbg_offset(), sizeof dbg, hipMemcpyDeviceToHost) == hipSuccess) {
-                fprintf(stderr, "[dvs persist] %s launch\n", which ? "full-grid" : "head-phase");
-                if (dvs_persist_probe_id()) {  // (a one-interval build: [0] ticks, [1] passes; block 0 then the last scanning block)
-                    fprintf(stderr, "[dvs persist probe %d] block 0 (owns a job): %.3f us x %llu; the last scanning block (no job): %.3f us x %llu\n",
-                            dvs_persist_probe_id(), dbg[1] ? dbg[0] / 100.0 / double(dbg[1]) : 0.0, dbg[1],
-                            dbg[17] ? dbg[16] / 100.0 / double(dbg[17]) : 0.0, dbg[17]);
-                    continue;
-                }
-                for (int w = 0; w < 2; w++)
-                    fprintf(stderr, "[dvs persist %s] us: scan %.1f bar1 %.1f resolve %.1f loo %.1f bar2 %.1f | partials %.1f combine %.1f lowest-row fetch %.1f rebuild %.1f\n",
-                            w ? "mirror block" : "block 0", dbg[0 + 16 * w] / 100.0, dbg[1 + 16 * w] / 100.0,
-                            dbg[2 + 16 * w] / 100.0, dbg[3 + 16 * w] / 100.0, dbg[4 + 16 * w] / 100.0,
-                            dbg[6 + 16 * w] / 100.0, dbg[7 + 16 * w] / 100.0, dbg[8 + 16 * w] / 100.0,
-                            dbg[5 + 16 * w] / 100.0);
-                if (dvs_persist_trace_offset()) {  // four windows' timelines across the grid
-                    std::vector<unsigned long long> tr(4 * 8 * 256);
-                    if (hipMemcpy(tr.data(), static_cast<char *>(blk) + dvs_persist_trace_offset(), tr.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                        const uint32_t G = which ? s->persist_grid : uint32_t(ctx->head_cus);
-                        for (int w_ = 0; w_ < 4; w_++) {
-                            const unsigned long long *t0 = &tr[(w_ * 8 + 0) * 256], *t1 = &tr[(w_ * 8 + 1) * 256], *t2 = &tr[(w_ * 8 + 2) * 256], *tg = &tr[(w_ * 8 + 3) * 256];
-                            const unsigned long long *t4 = &tr[(w_ * 8 + 4) * 256], *t5 = &tr[(w_ * 8 + 5) * 256], *t6 = &tr[(w_ * 8 + 6) * 256], *t7 = &tr[(w_ * 8 + 7) * 256];
-                            if (!tg[2] || G < 4) continue;
-                            std::vector<double> top, arr, seen, pub, tot, end_;
-                            unsigned long long first_top = ~0ull;
-                            for (uint32_t b = 0; b + 2 < G; b++) if (t0[b]) first_top = std::min(first_top, t0[b]);
-                            for (uint32_t b = 0; b + 2 < G; b++) {
-                                if (!t0[b] || !t1[b] || !t2[b]) continue;
-                                top.push_back((t0[b] - first_top) / 100.0);
-                                arr.push_back((t1[b] - first_top) / 100.0);
-                                seen.push_back((double(t2[b]) - double(tg[2])) / 100.0);
-                                if (t4[b] > tg[2] && t5[b] > tg[2] && t6[b] > tg[2]) {  // (the window ended in an accept)
-                                    pub.push_back((double(t4[b]) - double(tg[2])) / 100.0);
-                                    tot.push_back((double(t5[b]) - double(tg[2])) / 100.0);
-                                    end_.push_back((double(t6[b]) - double(tg[2])) / 100.0);
-                                }
-                            }
-                            if (arr.empty()) continue;
-                            auto srt = [](std::vector<double> &v) { std::sort(v.begin(), v.end()); };
-                            srt(top); srt(arr); srt(seen);
-                            auto q_ = [](const std::vector<double> &v, double f) { return v[size_t(f * (v.size() - 1))]; };
-                            fprintf(stderr, "[dvs persist trace] window %d: tops 0 / %.2f / %.2f (min/median/max us), records stored %.2f / %.2f / %.2f / %.2f (min/median/90%%/max), "
-                                    "gather begun %.2f, last record seen %.2f, release stored %.2f, release seen +%.2f / +%.2f / +%.2f (min/median/max after it was stored)\n",
-                                    w_ * 12 + 12, q_(top, 0.5), top.back(), arr.front(), q_(arr, 0.5), q_(arr, 0.9), arr.back(),
-                                    (double(tg[0]) - double(first_top)) / 100.0, (double(tg[1]) - double(first_top)) / 100.0, (double(tg[2]) - double(first_top)) / 100.0,
-                                    seen.front(), q_(seen, 0.5), seen.back());
-                            if (!pub.empty()) {
-                                {   // the five workgroups that published last: when each arrived, saw the release, published
-                                    std::vector<std::pair<double, uint32_t>> late;
-                                    for (uint32_t b = 0; b + 2 < G; b++)
-                                        if (t4[b] > tg[2]) late.emplace_back((double(t4[b]) - double(tg[2])) / 100.0, b);
-                                    std::sort(late.rbegin(), late.rend());
-                                    for (size_t i = 0; i < late.size() && i < 5; i++) {
-                                        const uint32_t b = late[i].second;
-                                        fprintf(stderr, "[dvs persist trace] window %d: workgroup %u arrived %.2f before the release was stored, saw it +%.2f, handed its speculative job over +%.2f, was through the job loop +%.2f\n",
-                                                w_ * 12 + 12, b, (double(tg[2]) - double(t1[b])) / 100.0, (double(t2[b]) - double(tg[2])) / 100.0,
-                                                (double(t7[b]) - double(tg[2])) / 100.0, late[i].first);
-                                    }
-                                }
-                                {   // when the speculative jobs were handed over (mailboxes: stored), relative to the release
-                                    std::vector<double> sp;
-                                    for (uint32_t b = 0; b + 2 < G; b++)
-                                        if (t7[b] && t4[b] > tg[2]) sp.push_back((double(t7[b]) - double(tg[2])) / 100.0);
-                                    if (!sp.empty()) {
-                                        srt(sp);
-                                        fprintf(stderr, "[dvs persist trace] window %d: speculative jobs handed over %.2f / %.2f / %.2f / %.2f us after the release was stored "
-                                                "(min/median/90%%/max over %zu workgroups; negative: before)\n", w_ * 12 + 12, sp.front(), q_(sp, 0.5), q_(sp, 0.9), sp.back(), sp.size());
-                                    }
-                                }
-                                srt(pub); srt(tot); srt(end_);
-                                fprintf(stderr, "[dvs persist trace] window %d, its accept (us after the release was stored; min/median/max): job published %.2f / %.2f / %.2f, "
-                                        "totals read %.2f / %.2f / %.2f, rebuild done %.2f / %.2f / %.2f\n", w_ * 12 + 12, pub.front(), q_(pub, 0.5), pub.back(),
-                                        tot.front(), q_(tot, 0.5), tot.back(), end_.front(), q_(end_, 0.5), end_.back());
-                            }
-                        }
-                    }
-                }
-                if (dbg[15] + dbg[14])
-                    fprintf(stderr, "[dvs persist block 0] accepts for which its leave-one-out job was ready when the release came: %llu (the candidate's frequencies: %llu)\n", dbg[15], dbg[14]);
-                if (dbg[9] + dbg[10] + dbg[11] + dbg[12])
-                    fprintf(stderr, "[dvs persist block 0] us inside the phases: window top %.1f own rows scanned %.1f hint look + record %.1f (then: scan = the rest) | behind the rebuild %.1f\n",
-                            dbg[9] / 100.0, dbg[10] / 100.0, dbg[11] / 100.0, dbg[12] / 100.0);
-                if (dbg[16 + 10] + dbg[16 + 12])
-                    fprintf(stderr, "[dvs persist] scan + rendezvous: row-per-workgroup windows %llu (%.1f us, %llu rows), "
-                            "row-per-wave windows %llu (%.1f us, %llu rows)\n", dbg[16 + 10], dbg[16 + 9] / 100.0,
-                            dbg[16 + 13], dbg[16 + 12], dbg[16 + 11] / 100.0, dbg[16 + 14]);
-            }
-        }
+        sel_add_scan_times(s);
+        if (ctx->knobs.persist_debug) dvs_persist_debug_report(ctx, s);
         const bool fake_error = ctx->knobs.test_persist_fake_error;  // (test knob: needs DVS_TEST_KNOBS=1 as well)
         if (s->persist && persist_launches && (c.status == SEL_ERROR || (fake_error && persist_launches == 1))) {
             // The persistent kernel gave up at a grid barrier: its workgroups were not all resident
             // (a CU mask, a partitioned device, another stream's kernels holding CUs).  The
             // replicas may have stopped mid-update, so the selection starts over from its seeds and
             // the multi-launch engine, which needs no co-residency, serves the request.
-            s->persist = false;
-            s->persist_fell_back = true;
             if (!fake_error) ctx->persist_timeouts++;  // (three in a row and the context stops trying)
-            dvs_select_arbiter_free(s);  // (its replay of the event log belongs to the abandoned run)
-            rc = sel_seed<T>(ctx, s, mat, ctx->stream);
-            if (rc) return rc;
-            persist_launches = 0;
+            if ((rc = sel_leave_persist<T>(ctx, s, mat, true))) return rc;
             continue;
         }
         if (s->seeded_start && s->persist && persist_launches == 1 &&
             (c.status == SEL_NEED_SETUP || (c.status == SEL_RUN && c.cursor == s->params.n_seed))) {
             // the seeded launch left the initial set alone (its first argmin too close to call on the
             // device): the set-up kernels after all, and the engine again from the state they leave
-            s->seeded_start = false;
-            s->persist_seeded = false;
-            rc = sel_seed<T>(ctx, s, mat, ctx->stream);
-            if (rc) return rc;
-            persist_cursor = s->params.n_seed;
-            persist_launches = 2;
-            persist_was_last = true;
-            rc = dvs_persist_launch(ctx, s);
-            if (rc == DVS_ERR_UNSUPPORTED) {
-                s->persist = false;
-                s->persist_fell_back = true;
-                persist_launches = 0;
-            } else if (rc) {
-                return rc;
-            }
+            if ((rc = sel_drop_seeded<T>(ctx, s, mat, ctx->stream)) || (rc = persist_launch(s->params.n_seed))) return rc;
             continue;
         }
         if (c.status == SEL_DONE) {
-            if (ctx->knobs.persist_debug)
-                fprintf(stderr, "[dvs persist] launches ended early: replica full %u, sum check %u, push argmin %u, stat comparison %u, "
-                        "candidate in band %u, replace argmin %u, state not taken %u / %u\n", c.why[0], c.why[1], c.why[2], c.why[3],
-                        c.why[4], c.why[5], c.why[6], c.why[7]);
+            if (ctx->knobs.persist_debug) dvs_persist_debug_done(c);
             if (s->persist && persist_launches) ctx->persist_timeouts = 0;
             return DVS_OK;
         }
         if (c.status == SEL_ARBITER) {
-            if (s->params.flags & DVS_SELECT_NO_ARBITER)
-                return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
-                                     "ambiguous decision at stream position %llu (stage %u): "
-                                     "|score - threshold| within the rounding band",
-                                     (unsigned long long)c.arb_pos, c.arb_stage);
-            {
-                const auto t_arb = std::chrono::steady_clock::now();
-                rc = dvs_select_arbitrate(ctx, s);
-                s->arbiter_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_arb).count();
-            }
-            if (rc) return rc;
+            if ((rc = sel_arbitrate<T>(ctx, s, mat))) return rc;
             persist_was_last = false;
-            launch_iteration<T>(ctx, s, mat, c.arb_stage == ARB_RESOLVE ? 1 : 2);
-            DVS_HIP(ctx, hipGetLastError());
             continue;
         }
         if (c.status == SEL_ERROR)
@@ -2276,18 +2204,8 @@ static int sel_run_loop(dvs_ctx *ctx, dvs_select *s, const T *mat, bool first_un
                 persist_idle++;
             } else {
                 if (persist_launches && c.cursor != persist_cursor) persist_idle = 0;
-                persist_cursor = c.cursor;
-                persist_launches++;
-                persist_was_last = true;
-                rc = dvs_persist_launch(ctx, s);
-                if (rc == DVS_ERR_UNSUPPORTED) {
-                    s->persist = false;
-                    s->persist_fell_back = true;
-                } else if (rc) {
-                    return rc;
-                } else {
-                    continue;
-                }
+                if ((rc = persist_launch(c.cursor))) return rc;
+                if (s->persist) continue;  // (refused: the multi-launch kernels below take over)
             }
         }
         // (behind a persistent launch that left ONE event for these kernels -- a decision inside its band --
@@ -2360,13 +2278,9 @@ static int sel_start(dvs_ctx *ctx, dvs_select *s, const T *mat) {
     if (rc) return rc;
     if (head_phase) {
         rc = dvs_persist_launch_head(ctx, s, uint32_t(ctx->head_cus), s->mat->head_rows_built, side);
-        if (rc && rc != DVS_ERR_UNSUPPORTED) return rc;  // (refused: the full-grid launch starts from the seeds)
-        if (rc == DVS_ERR_UNSUPPORTED && s->seeded_start) {  // ... which, unseeded, it needs the set-up kernels for
-            s->seeded_start = false;
-            s->persist_seeded = false;
-            rc = sel_seed<T>(ctx, s, mat, st);
-            if (rc) return rc;
-        }
+        if (rc == DVS_ERR_UNSUPPORTED)  // (refused: the full-grid launch starts from the seeds -- which, unseeded, it needs the set-up kernels for)
+            rc = s->seeded_start ? sel_drop_seeded<T>(ctx, s, mat, st) : DVS_OK;
+        if (rc) return rc;
         // the full-grid launch's sync block and accumulators: behind the histogram on the context's
         // stream, i.e. while the head phase runs, not between the two launches
         rc = dvs_persist_prepare_main(ctx, s);
@@ -2380,7 +2294,7 @@ static int sel_start(dvs_ctx *ctx, dvs_select *s, const T *mat) {
         DVS_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_side_done, 0));
     }
     if (s->params.flags & DVS_SELECT_STEPWISE) return sel_poll(ctx, s);
-    return sel_run_loop<T>(ctx, s, mat, true);
+    return sel_run_loop<T>(ctx, s, mat);
 }
 
 // control block of a fresh selection + the initial set from the seed positions (SummedRecords::new
@@ -2433,12 +2347,17 @@ static int sel_seed(dvs_ctx *ctx, dvs_select *s, const T *mat, hipStream_t st, b
     return DVS_OK;
 }
 
-extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *order,
-                              const uint32_t *labels, uint64_t npos,
-                              const dvs_select_params *params, dvs_select **out) {
-    if (!ctx || !m || !params || !out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    *out = nullptr;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
+// ---- dvs_select_run's phases, in the order it calls them
+
+// The caller's arguments, checked, and what follows from them (host only: nothing is allocated yet)
+struct SelArgs {
+    uint32_t n_seed = 0, max_size = 0, nlabels = 0, cap = 0;
+    const uint32_t *labels = nullptr;         // the labels the engine runs with (nullptr: label = row) ...
+    const uint32_t *caller_labels = nullptr;  // ... and the caller's, when they were all distinct
+};
+
+static int sel_check_args(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *order, const uint32_t *labels,
+                          uint64_t npos, const dvs_select_params *params, SelArgs &a) {
     const uint64_t B = m->nbins;
     if (!order && npos > m->nrows)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "npos %llu exceeds the matrix rows %u",
@@ -2451,7 +2370,6 @@ extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t 
     // ids of a store are unique -- no position can meet its own id in the set, so the engine runs
     // label-free (label = position: the persistent engine qualifies) and the caller's values are
     // put back on the way out (dvs_select_get_members, dvs_select_delta_jsd).
-    const uint32_t *caller_labels = nullptr;
     if (labels && !order && params->mode != DVS_MODE_SET) {
         bool distinct = true;
         bool rising = true;  // (the usual call: the positions themselves -- one pass, no copy)
@@ -2463,10 +2381,11 @@ extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t 
                 distinct = sorted[p] != sorted[p - 1] || sorted[p] == 0xFFFFFFFFu;
         }
         if (distinct) {
-            caller_labels = labels;
+            a.caller_labels = labels;
             labels = nullptr;
         }
     }
+    a.labels = labels;
     // src/records.rs:323-325, 404-410, 369-371, 464-469
     if (npos < n_seed)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "The number of sequences %llu is < n %u",
@@ -2496,93 +2415,72 @@ extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t 
                 return dvs_set_error(ctx, DVS_ERR_VALUE,
                                      "seed position %llu is not local: the first n rows must be replicated",
                                      (unsigned long long)p);
-    dvs_select *s = new dvs_select();
-    // (a failing HIP call after this point releases the half-built selection)
-#define SEL_HIP(call)                                    \
-    do {                                                 \
-        hipError_t e__ = (call);                         \
-        if (e__ != hipSuccess) {                         \
-            sel_free(s);                                 \
-            return dvs_hip_fail(ctx, e__, #call);        \
-        }                                                \
-    } while (0)
-    s->ctx = ctx;
-    dvs_ctx_retain(ctx);
-    s->params = *params;
-    s->params.n_seed = n_seed;
-    s->params.max_size = max_size;
-    s->mat = m;
-    s->mat_kind = m->kind;
-    s->npos = npos;
-    s->h_order.assign(order ? order : nullptr, order ? order + npos : nullptr);
-    s->h_labels.assign(labels ? labels : nullptr, labels ? labels + npos : nullptr);
-    if (caller_labels) s->h_out_labels.assign(caller_labels, caller_labels + npos);
-    SelDev &d = s->dev;
-    d.B = B;
-    d.nlabels = nlabels;
-    d.totals = m->d_totals;
-    d.rowH = m->d_entropy;
     const uint32_t cap = std::max<uint32_t>(std::max<uint32_t>(max_size, n_seed) + 1, 2);  // (seeds <= n_seed)
-    s->cap = cap;
     const size_t need = size_t(cap) * B * 8 + 5 * B * 8 + size_t(npos) * 8 + nlabels + (1 << 20);
     size_t free_b = 0, total_b = 0;
-    if (need > (size_t(1) << 30)) SEL_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (need > (size_t(1) << 30) && need > free_b + ctx->pool_bytes) {
-        sel_free(s);
+    if (need > (size_t(1) << 30)) DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (need > (size_t(1) << 30) && need > free_b + ctx->pool_bytes)
         return dvs_set_error(ctx, DVS_ERR_NOMEM, "selection state needs %zu bytes, %zu free", need,
                              free_b);
-    }
-    // launch geometry
+    a.n_seed = n_seed;
+    a.max_size = max_size;
+    a.nlabels = nlabels;
+    a.cap = cap;
+    return DVS_OK;
+}
+
+// launch geometry of the multi-launch kernels
+static int sel_geometry(dvs_ctx *ctx, dvs_select *s, const uint32_t *order, const uint32_t *labels) {
+    const uint64_t B = s->dev.B;
     s->base_in_lds = B * 8 <= 128 * 1024 && B * 8 + 1024 <= ctx->lds_per_block;
     s->scan_lds = 16 + (s->base_in_lds ? B * 8 : 0);
     const uint32_t wg_fit = s->base_in_lds ? std::max<uint32_t>(1, uint32_t((160 * 1024) / (B * 8 + 512))) : 4;
     uint32_t wg_per_cu = std::min<uint32_t>(wg_fit, 2);  // 16 waves per CU, 16 KB of loads in flight each
     s->scan_grid = std::max<uint32_t>(1, uint32_t(ctx->n_cu) * wg_per_cu);
-    s->loo_grid = cap;
+    s->loo_grid = s->cap;
     // measured slower than three launches (one CU does the whole leave-one-out pass): opt-in only
     s->batch = 16;
     s->time_scan = ctx->timing;
     s->scan_hot = B % (256 * SCAN_CH) == 0 && !order && !labels && s->base_in_lds;
-    if (s->scan_lds > 48 * 1024) {
-        const void *fn = dvs_mat_dispatch(m, [&](auto *mp) -> const void * {
-            using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
-            return s->scan_hot ? reinterpret_cast<const void *>(scan_kernel<T, true>)
-                               : reinterpret_cast<const void *>(scan_kernel<T, false>);
-        });
-        const int lrc = dvs_raise_dyn_lds(ctx, fn, s->scan_lds);
-        if (lrc) {
-            sel_free(s);
-            return lrc;
-        }
-    }
+    if (s->scan_lds <= 48 * 1024) return DVS_OK;
+    const void *fn = dvs_mat_dispatch(s->mat, [&](auto *mp) -> const void * {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
+        return s->scan_hot ? reinterpret_cast<const void *>(scan_kernel<T, true>)
+                           : reinterpret_cast<const void *>(scan_kernel<T, false>);
+    });
+    return dvs_raise_dyn_lds(ctx, fn, s->scan_lds);
+}
 
-#define SEL_ALLOC(ptr, bytes)                                        \
-    do {                                                             \
-        int rc__ = dvs_dev_alloc(ctx, (void **)&(ptr), (bytes), #ptr); \
-        if (rc__) {                                                  \
-            sel_free(s);                                             \
-            return rc__;                                             \
-        }                                                            \
-    } while (0)
+// Device and pinned memory: the set state, the stepwise mode's row ring and fast-step blocks, the engine's copies of
+// the order and labels (uploaded on the context's stream) and the control block's pinned mirror
+static int sel_alloc(dvs_ctx *ctx, dvs_select *s, const uint32_t *order, const uint32_t *labels) {
+    SelDev &d = s->dev;
+    const uint64_t B = d.B, npos = s->npos;
+    const uint32_t cap = s->cap, nlabels = d.nlabels;
+    const size_t nlog = size_t(npos - s->params.n_seed + 2);
     // (the control block and, behind it, the seed list: ONE upload per selection, sel_seed)
     static_assert(sizeof(SelCtl) <= SEL_SEEDS_AT, "the seed list starts behind the control block");
-    SEL_ALLOC(d.ctl, 4096);
-    SEL_ALLOC(d.S, B * 8);
-    SEL_ALLOC(d.Stmp, B * 8);
-    SEL_ALLOC(d.base, B * 8);
-    SEL_ALLOC(d.cand, B * 8);
-    SEL_ALLOC(d.M, size_t(cap) * B * 8);
-    SEL_ALLOC(d.mH, size_t(cap) * 8);
-    SEL_ALLOC(d.mDelta, size_t(cap) * 8);
-    SEL_ALLOC(d.dtmp, size_t(cap) * 8);
-    SEL_ALLOC(d.dsum, size_t(cap) * 8);
-    SEL_ALLOC(d.mLabel, size_t(cap) * 4);
-    SEL_ALLOC(d.mPos, size_t(cap) * 8);
-    SEL_ALLOC(d.ord, size_t(cap) * 4);
-    SEL_ALLOC(d.inset, std::max<size_t>(nlabels, 1));
-    SEL_ALLOC(d.wg_rows, size_t(s->scan_grid) * 8);
-    SEL_ALLOC(d.evlog_pos, size_t(npos - n_seed + 2) * 8);
-    SEL_ALLOC(d.evlog_kind, size_t(npos - n_seed + 2) * 4);
+    const struct { void **ptr; size_t bytes; const char *what; } blocks[] = {
+        {(void **)&d.ctl, 4096, "d.ctl"},
+        {(void **)&d.S, B * 8, "d.S"},
+        {(void **)&d.Stmp, B * 8, "d.Stmp"},
+        {(void **)&d.base, B * 8, "d.base"},
+        {(void **)&d.cand, B * 8, "d.cand"},
+        {(void **)&d.M, size_t(cap) * B * 8, "d.M"},
+        {(void **)&d.mH, size_t(cap) * 8, "d.mH"},
+        {(void **)&d.mDelta, size_t(cap) * 8, "d.mDelta"},
+        {(void **)&d.dtmp, size_t(cap) * 8, "d.dtmp"},
+        {(void **)&d.dsum, size_t(cap) * 8, "d.dsum"},
+        {(void **)&d.mLabel, size_t(cap) * 4, "d.mLabel"},
+        {(void **)&d.mPos, size_t(cap) * 8, "d.mPos"},
+        {(void **)&d.ord, size_t(cap) * 4, "d.ord"},
+        {(void **)&d.inset, std::max<size_t>(nlabels, 1), "d.inset"},
+        {(void **)&d.wg_rows, size_t(s->scan_grid) * 8, "d.wg_rows"},
+        {(void **)&d.evlog_pos, nlog * 8, "d.evlog_pos"},
+        {(void **)&d.evlog_kind, nlog * 4, "d.evlog_kind"},
+    };
+    for (const auto &b : blocks)
+        if (int rc = dvs_dev_alloc(ctx, b.ptr, b.bytes, b.what)) return rc;
     if (s->params.flags & DVS_SELECT_STEPWISE) {
         // The arbiter's row log (rows of accepted candidates may live on other ranks): the frequency row of every
         // accepted event in event-log order.  On the device it is a RING of `ring` rows that dvs_select_step_poll
@@ -2593,143 +2491,128 @@ extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t 
         uint64_t ring = std::min<uint64_t>(256, std::max<uint64_t>(32, (uint64_t(256) << 20) / (B * 8)));
         if (ctx->knobs.test_rowlog_ring >= 4) ring = ctx->knobs.test_rowlog_ring;  // (tests: a ring that wraps after a few accepts)
         d.rowlog_cap = uint32_t(ring);
-        SEL_ALLOC(d.rowlog, size_t(ring) * B * 8);
+        if (int rc = dvs_dev_alloc(ctx, (void **)&d.rowlog, size_t(ring) * B * 8, "d.rowlog")) return rc;
         // the fast step (fs_jobs_kernel / fs_step_kernel): select_nmost_divergent without a caller's labels
         // (the scan vector in f64 and f32, the members' sums, a staging area for the jobs' words)
         uint32_t fsK = 1;
         while (uint64_t(cap + 1) * fsK * 2 <= 96 && uint64_t(fsK) * 2 * FS_JOB_THREADS <= B) fsK *= 2;
         const size_t fs_lds = ((B + 1) & ~1ull) * 16 + size_t(cap + 1) * 3 * 8 + size_t(cap + 1) * fsK * 7 * 8 + 64;
-        if (params->mode == DVS_MODE_NMOST && params->n_seed >= 2 && !labels && !ctx->knobs.no_fast_step && fs_lds <= ctx->lds_per_block &&
-            uint64_t(cap + 1) <= FS_MAXJOBS) {
+        if (s->params.mode == DVS_MODE_NMOST && s->params.n_seed >= 2 && !labels && !ctx->knobs.no_fast_step &&
+            fs_lds <= ctx->lds_per_block && uint64_t(cap + 1) <= FS_MAXJOBS) {
             s->fs_K = fsK;
             s->fs_lds = fs_lds;
             s->fs_grid = uint32_t(ctx->n_cu);  // (one workgroup a CU: 256 registers a lane hold a row in flight across the decisions; all resident at once, the state writer among them)
-            SEL_ALLOC(s->d_jobres, size_t(FS_MAXJOBS) * FS_RES * 8 + 8 * 8 * 1024);
-            SEL_HIP(hipMemsetAsync(s->d_jobres, 0, size_t(FS_MAXJOBS) * FS_RES * 8 + 8 * 8 * 1024, ctx->stream));
-            SEL_ALLOC(s->d_fsync, sizeof(FsSync));
-            SEL_HIP(hipMemsetAsync(s->d_fsync, 0, sizeof(FsSync), ctx->stream));
+            if (int rc = dvs_dev_alloc(ctx, (void **)&s->d_jobres, size_t(FS_MAXJOBS) * FS_RES * 8 + 8 * 8 * 1024, "s->d_jobres")) return rc;
+            DVS_HIP(ctx, hipMemsetAsync(s->d_jobres, 0, size_t(FS_MAXJOBS) * FS_RES * 8 + 8 * 8 * 1024, ctx->stream));
+            if (int rc = dvs_dev_alloc(ctx, (void **)&s->d_fsync, sizeof(FsSync), "s->d_fsync")) return rc;
+            DVS_HIP(ctx, hipMemsetAsync(s->d_fsync, 0, sizeof(FsSync), ctx->stream));
+            // (no fast step without its status history: a rank that polled instead would issue a different number of
+            // exchanges than the others)
             void *hh = nullptr;
-            if (dvs_pinned_get(ctx, &hh) == DVS_OK) {  // (without it the driver polls as before)
-                memset(hh, 0, 4096);
-                s->h_fshist = static_cast<unsigned long long *>(hh);
-            }
+            if (int rc = dvs_pinned_get(ctx, &hh)) return rc;
+            memset(hh, 0, 4096);
+            s->h_fshist = static_cast<unsigned long long *>(hh);
             s->fast_step = true;
             s->fs_need_scan = true;
         }
     }
     if (order) {
-        SEL_ALLOC(d.order, size_t(npos) * 4);
-        SEL_HIP(hipMemcpyAsync((void *)d.order, order, size_t(npos) * 4, hipMemcpyHostToDevice,
-                                    ctx->stream));
+        if (int rc = dvs_dev_alloc(ctx, (void **)&d.order, size_t(npos) * 4, "d.order")) return rc;
+        DVS_HIP(ctx, hipMemcpyAsync((void *)d.order, order, size_t(npos) * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     if (labels) {
-        SEL_ALLOC(d.labels, size_t(npos) * 4);
-        SEL_HIP(hipMemcpyAsync((void *)d.labels, labels, size_t(npos) * 4,
-                                    hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = dvs_dev_alloc(ctx, (void **)&d.labels, size_t(npos) * 4, "d.labels")) return rc;
+        DVS_HIP(ctx, hipMemcpyAsync((void *)d.labels, labels, size_t(npos) * 4, hipMemcpyHostToDevice, ctx->stream));
     }
-#undef SEL_ALLOC
-
     static_assert(sizeof(SelCtl) <= 4096, "control block must fit a cached pinned block");
-    {
-        int prc = dvs_pinned_get(ctx, (void **)&s->h_ctl);
-        if (prc) {
-            sel_free(s);
-            return prc;
-        }
-    }
+    return dvs_pinned_get(ctx, (void **)&s->h_ctl);
+}
 
-    {
-        int prc = dvs_persist_setup(ctx, s);
-        if (prc) {
-            sel_free(s);
-            return prc;
-        }
-    }
+// The engine (persist.hip decides whether the persistent one serves) and the stream of its set-up, with what can go
+// out before the matrix is waited for
+static int sel_prepare_engine(dvs_ctx *ctx, dvs_select *s, const uint32_t *order, const uint32_t *labels) {
+    SelDev &d = s->dev;
+    const dvs_matrix *m = s->mat;
+    const uint32_t n_seed = s->params.n_seed, nlabels = d.nlabels;
+    int rc = dvs_persist_setup(ctx, s);
+    if (rc) return rc;
     // The label flags are cleared NOW, on the stream the set-up will use (same stream: ordered in front of
     // everything that sets one): nothing about them depends on the seeds, so the fill runs while the matrix's
     // head rows are still being built, not between the host's wake-up and the first launch.
     sel_plan_setup_stream(ctx, s);
     if (s->setup_side) s->used_side_streams = true;
-    SEL_HIP(hipMemsetAsync(d.inset, 0, std::max<size_t>(nlabels, 1), s->setup_side ? s->setup_side : ctx->stream));
+    DVS_HIP(ctx, hipMemsetAsync(d.inset, 0, std::max<size_t>(nlabels, 1), s->setup_side ? s->setup_side : ctx->stream));
     s->inset_clean = true;
     // ... and so are the scan workgroups' row counters, which the set-up's own leave-one-out launch adds up (on the
     // context's stream this fill raced with a set-up on a side stream: `rows_scored` of a selection with a set of
     // more than 32 came out 4.4 M too high whenever the pool's block still held another selection's counters)
-    SEL_HIP(hipMemsetAsync(d.wg_rows, 0, size_t(s->scan_grid) * 8, s->setup_side ? s->setup_side : ctx->stream));
+    DVS_HIP(ctx, hipMemsetAsync(d.wg_rows, 0, size_t(s->scan_grid) * 8, s->setup_side ? s->setup_side : ctx->stream));
     // SEEDED start (persist.hip): an nmost selection whose state fits the persistent kernel's register
     // cache is begun by that kernel itself -- S, the entropy sum, the leave-one-out pass and the first
     // lowest member from nothing but the seed positions -- instead of four launches in front of it
     // (sets of up to 32: beyond that the S of the seeds -- a memory round trip per four members -- costs
     // what the launches cost; DVS_PERSIST_NO_SEEDED=1 turns it off)
     // (a STEPWISE selection never launches the persistent kernel: its set-up kernels must run)
-    s->seeded_start = s->persist && params->mode == DVS_MODE_NMOST && B <= 4096 && !order && !labels &&
+    s->seeded_start = s->persist && s->params.mode == DVS_MODE_NMOST && d.B <= 4096 && !order && !labels &&
                       !(s->params.flags & DVS_SELECT_STEPWISE) && n_seed >= 2 && n_seed <= 32 && !ctx->knobs.persist_no_seeded;
     s->persist_seeded = s->seeded_start;
     if (size_t(n_seed) * sizeof(uint64_t) <= 4096 - SEL_SEEDS_AT) {
         s->d_seed_list = reinterpret_cast<unsigned char *>(d.ctl) + SEL_SEEDS_AT;
         s->seed_list_in_ctl = true;
     } else if (s->seeded_start) {
-        int arc = dvs_dev_alloc(ctx, &s->d_seed_list, size_t(n_seed) * sizeof(uint64_t), "seed list");
-        if (arc) {
-            sel_free(s);
-            return arc;
-        }
+        if ((rc = dvs_dev_alloc(ctx, &s->d_seed_list, size_t(n_seed) * sizeof(uint64_t), "seed list"))) return rc;
     }
     // (what the head phase needs besides the seeds goes out before the wait below, on its stream)
-    if (s->persist && m->rest_beside_head && ctx->stream_head && m->head_rows_built && params->mode == DVS_MODE_NMOST &&
+    if (s->persist && m->rest_beside_head && ctx->stream_head && m->head_rows_built && s->params.mode == DVS_MODE_NMOST &&
         !order && !labels) {
         s->used_side_streams = true;
-        int prc = dvs_persist_prepare_head(ctx, s, m->head_rows_built, ctx->stream_head);
-        if (prc) {
-            sel_free(s);
-            return prc;
-        }
+        return dvs_persist_prepare_head(ctx, s, m->head_rows_built, ctx->stream_head);
     }
-    std::vector<uint64_t> seeds;
-    {
-        std::vector<uint32_t> h_tot(n_seed);
-        // (a matrix whose build is still in flight is waited for HERE, with everything above -- the
-        // allocations, the memsets, the engine set-up -- done while its kernels ran)
-        {
-            int src = dvs_matrix_settle(ctx, m);
-            if (src) {
-                sel_free(s);
-                return src;
-            }
-        }
-        hipError_t ce = hipSuccess;
-        if (!order && n_seed && n_seed <= m->h_head_totals.size()) {
-            std::copy(m->h_head_totals.begin(), m->h_head_totals.begin() + n_seed, h_tot.begin());  // no round trip
-        } else if (!order && n_seed) {
-            ce = hipMemcpyAsync(h_tot.data(), m->d_totals, size_t(n_seed) * 4, hipMemcpyDeviceToHost, ctx->stream);
-        } else {
-            for (uint64_t p = 0; p < n_seed && ce == hipSuccess; p++)
-                ce = hipMemcpyAsync(&h_tot[p], m->d_totals + order[p], 4, hipMemcpyDeviceToHost, ctx->stream);
-        }
-        if ((order || n_seed > m->h_head_totals.size()) &&
-            (hipStreamSynchronize(ctx->stream) != hipSuccess || ce != hipSuccess)) {
-            sel_free(s);
-            return dvs_set_error(ctx, DVS_ERR_RUNTIME, "reading the seed rows' totals failed");
-        }
-        for (uint64_t p = 0; p < n_seed; p++)
-            if (h_tot[p] > 0) seeds.push_back(p);
+    return DVS_OK;
+}
+
+// The usable seeds -- positions among the first n whose row has a valid k-mer -- into s->seed_positions
+static int sel_read_seeds(dvs_ctx *ctx, dvs_select *s, const uint32_t *order) {
+    const dvs_matrix *m = s->mat;
+    const uint32_t n_seed = s->params.n_seed;
+    std::vector<uint32_t> h_tot(n_seed);
+    // (a matrix whose build is still in flight is waited for HERE, with everything above -- the
+    // allocations, the memsets, the engine set-up -- done while its kernels ran)
+    int rc = dvs_matrix_settle(ctx, m);
+    if (rc) return rc;
+    hipError_t ce = hipSuccess;
+    if (!order && n_seed && n_seed <= m->h_head_totals.size()) {
+        std::copy(m->h_head_totals.begin(), m->h_head_totals.begin() + n_seed, h_tot.begin());  // no round trip
+    } else if (!order && n_seed) {
+        ce = hipMemcpyAsync(h_tot.data(), m->d_totals, size_t(n_seed) * 4, hipMemcpyDeviceToHost, ctx->stream);
+    } else {
+        for (uint64_t p = 0; p < n_seed && ce == hipSuccess; p++)
+            ce = hipMemcpyAsync(&h_tot[p], m->d_totals + order[p], 4, hipMemcpyDeviceToHost, ctx->stream);
     }
-    if (seeds.size() < 2) {
-        sel_free(s);
+    if ((order || n_seed > m->h_head_totals.size()) &&
+        (hipStreamSynchronize(ctx->stream) != hipSuccess || ce != hipSuccess))
+        return dvs_set_error(ctx, DVS_ERR_RUNTIME, "reading the seed rows' totals failed");
+    std::vector<uint64_t> &seeds = s->seed_positions;
+    for (uint64_t p = 0; p < n_seed; p++)
+        if (h_tot[p] > 0) seeds.push_back(p);
+    if (seeds.size() < 2)
         return seeds.empty() ? dvs_set_error(ctx, DVS_ERR_VALUE, "records cannot be empty")   // :28-30
                              : dvs_set_error(ctx, DVS_ERR_VALUE, "must have > 1 KmerSeq");     // :227-230
-    }
+    return DVS_OK;
+}
 
+// the control block of the fresh selection (sel_seed adds the window policy of the engine in charge and uploads it)
+static void sel_init_ctl(dvs_ctx *ctx, dvs_select *s) {
     SelCtl c;
     std::memset(&c, 0, sizeof c);
-    c.cursor = n_seed;
-    c.npos = npos;
+    c.cursor = s->params.n_seed;
+    c.npos = s->npos;
     c.event_pos = SEL_NONE;
     c.status = SEL_RUN;  // finalize flips to DONE when cursor >= npos
-    c.size = uint32_t(seeds.size());
-    c.mode = params->mode;
-    c.max_size = max_size;
-    c.stat = params->stat;
+    c.size = uint32_t(s->seed_positions.size());
+    c.mode = s->params.mode;
+    c.max_size = s->params.max_size;
+    c.stat = s->params.stat;
     c.forced = FORCE_NONE;
     c.forced_lowest = 0xFFFFFFFFu;
     c.band = 0.0;
@@ -2737,17 +2620,44 @@ extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t 
     // wc * gap^0.5..0.75 for the early stream, are all within 3 % of each other
     c.wscale = 4.0;
     if (ctx->knobs.persist_no_events) c.wscale = 1e5;  // (the pure-stream measurement: a few long windows)
-    s->ctl0 = c;  // (sel_seed adds the window policy of the engine in charge and uploads it)
-    s->seed_positions = seeds;
+    s->ctl0 = c;
+}
 
-    int rc = dvs_mat_dispatch(m, [&](auto *mp) { return sel_start(ctx, s, mp); });
-    if (rc) {
-        sel_free(s);
+extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *order,
+                              const uint32_t *labels, uint64_t npos,
+                              const dvs_select_params *params, dvs_select **out) {
+    if (!ctx || !m || !params || !out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    *out = nullptr;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    SelArgs a;
+    int rc = sel_check_args(ctx, m, order, labels, npos, params, a);
+    if (rc) return rc;
+    labels = a.labels;
+    // (the selection under construction is released on every way out but the last)
+    std::unique_ptr<dvs_select, void (*)(dvs_select *)> s(new dvs_select(), sel_free);
+    s->ctx = ctx;
+    dvs_ctx_retain(ctx);
+    s->params = *params;
+    s->params.n_seed = a.n_seed;
+    s->params.max_size = a.max_size;
+    s->mat = m;
+    s->mat_kind = m->kind;
+    s->npos = npos;
+    s->h_order.assign(order ? order : nullptr, order ? order + npos : nullptr);
+    s->h_labels.assign(labels ? labels : nullptr, labels ? labels + npos : nullptr);
+    if (a.caller_labels) s->h_out_labels.assign(a.caller_labels, a.caller_labels + npos);
+    s->cap = a.cap;
+    s->dev.B = m->nbins;
+    s->dev.nlabels = a.nlabels;
+    s->dev.totals = m->d_totals;
+    s->dev.rowH = m->d_entropy;
+    if ((rc = sel_geometry(ctx, s.get(), order, labels)) || (rc = sel_alloc(ctx, s.get(), order, labels)) ||
+        (rc = sel_prepare_engine(ctx, s.get(), order, labels)) || (rc = sel_read_seeds(ctx, s.get(), order)))
         return rc;
-    }
-    *out = s;
+    sel_init_ctl(ctx, s.get());
+    if ((rc = dvs_mat_dispatch(m, [&](auto *mp) { return sel_start(ctx, s.get(), mp); }))) return rc;
+    *out = s.release();
     return DVS_OK;
-#undef SEL_HIP
 }
 
 extern "C" void dvs_select_destroy(dvs_select *s) { sel_free(s); }
@@ -3014,10 +2924,8 @@ extern "C" int dvs_select_step_pack(dvs_ctx *ctx, dvs_select *s, double *d_slot)
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
         // (scan and pack as ONE launch -- the last workgroup to arrive at a counter packs -- measured
         // slower: 8.79 vs 7.57 ms per selection; every workgroup's arrival is a same-address atomic)
-        const SelDev &d = s->dev;
-        hipLaunchKernelGGL((scan_kernel<T, false>), dim3(s->scan_grid), dim3(SCAN_THREADS), s->scan_lds,
-                           ctx->stream, d.ctl, mp, d.totals, d.rowH, d.order, d.labels, d.inset, d.nlabels,
-                           d.base, d.wg_rows, d.B, s->base_in_lds ? 1 : 0);
+        // (always the plain instantiation, where scan_hot holds too)
+        launch_scan<T>(s, mp, false, s->dev.ctl, s->dev.wg_rows, ctx->stream);
         hipLaunchKernelGGL((pack_event_kernel<T>), dim3(1), dim3(LOO_THREADS), 0, ctx->stream, s->dev, mp,
                            d_slot);
         return 0;
@@ -3062,7 +2970,7 @@ extern "C" int dvs_select_step_apply(dvs_ctx *ctx, dvs_select *s, const double *
 
 extern "C" int dvs_select_step_peek(dvs_ctx *ctx, dvs_select *s, uint32_t lag, uint32_t *status, int *must_poll) {
     if (!ctx || !s || !status || !must_poll) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    if (!s->fast_step || !s->h_fshist || lag == 0 || lag >= FS_HIST / 2)
+    if (!s->fast_step || lag == 0 || lag >= FS_HIST / 2)
         return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "this selection keeps no status history (or the lag is out of range): poll");
     *must_poll = s->dev.rowlog && s->steps_since_poll + lag > s->dev.rowlog_cap / 2;
     *status = SEL_RUN;
@@ -3114,23 +3022,7 @@ extern "C" int dvs_select_step_poll(dvs_ctx *ctx, dvs_select *s, uint32_t *statu
         // A decision inside the rounding band: every rank holds the same replicated state, the same row
         // log and the same pending candidate, so every rank's arbiter reaches the same verdict on its own
         // -- no exchange.  The steps enqueued since the engine stopped were no-ops on every rank alike.
-        if (s->params.flags & DVS_SELECT_NO_ARBITER)
-            return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
-                                 "ambiguous decision at stream position %llu (stage %u): "
-                                 "|score - threshold| within the rounding band",
-                                 (unsigned long long)s->h_ctl->arb_pos, s->h_ctl->arb_stage);
-        const uint32_t stage = s->h_ctl->arb_stage;
-        {
-            const auto t_arb = std::chrono::steady_clock::now();
-            rc = dvs_select_arbitrate(ctx, s);
-            s->arbiter_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_arb).count();
-        }
-        if (rc) return rc;
-        dvs_mat_dispatch(s->mat, [&](auto *mp) {
-            launch_iteration(ctx, s, mp, stage == ARB_RESOLVE ? 1 : 2);
-            return 0;
-        });
-        DVS_HIP(ctx, hipGetLastError());
+        if ((rc = dvs_mat_dispatch(s->mat, [&](auto *mp) { return sel_arbitrate(ctx, s, mp); }))) return rc;
         s->fs_need_scan = true;  // (the kernels just queued leave no event posted: the fast step scans before it packs)
         s->fs_packed = nullptr;
         if (status) *status = SEL_RUN;
@@ -3165,18 +3057,9 @@ extern "C" int dvs_select_bench_scan(dvs_ctx *ctx, const dvs_select *s, int repe
         return rc;
     }
     hipEvent_t e0 = dvs_event_get(ctx), e1 = dvs_event_get(ctx);
-    const SelDev &d = s->dev;
     auto launch = [&]() {
         dvs_mat_dispatch(s->mat, [&](auto *mp) {
-            using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
-            if (s->scan_hot)
-                hipLaunchKernelGGL((scan_kernel<T, true>), dim3(s->scan_grid), dim3(SCAN_THREADS), s->scan_lds,
-                                   ctx->stream, d_c, mp, d.totals, d.rowH, d.order, d.labels, d.inset, d.nlabels,
-                                   d.base, d_rows, d.B, s->base_in_lds ? 1 : 0);
-            else
-                hipLaunchKernelGGL((scan_kernel<T, false>), dim3(s->scan_grid), dim3(SCAN_THREADS), s->scan_lds,
-                                   ctx->stream, d_c, mp, d.totals, d.rowH, d.order, d.labels, d.inset, d.nlabels,
-                                   d.base, d_rows, d.B, s->base_in_lds ? 1 : 0);
+            launch_scan(s, mp, s->scan_hot, d_c, d_rows, ctx->stream);
             return 0;
         });
     };
