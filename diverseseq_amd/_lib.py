@@ -43,6 +43,7 @@ EXPORTS = (
     "dvs_pack_sequences", "dvs_packed_destroy", "dvs_packed_info", "dvs_packed_dev_codes", "dvs_packed_dev_mask",
     "dvs_packed_get", "dvs_matrix_build_packed", "dvs_sketches_build_packed", "dvs_seqbatch_pack",
     "dvs_seqbatch_packed", "dvs_sketches_build_from_seqbatch",
+    "dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage",
 )
 
 
@@ -207,6 +208,9 @@ def load() -> C.CDLL:
         L.dvs_seqbatch_pack.argtypes = [vp, vp]
         L.dvs_sketches_build_from_seqbatch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                                        C.POINTER(vp)]
+        L.dvs_average_linkage.argtypes = [vp, vp, C.c_int, C.c_uint32, u32p, f64p, u32p]
+        L.dvs_sketches_average_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32, u32p, f64p, u32p]
+        L.dvs_matrix_euclidean_average_linkage.argtypes = [vp, vp, u32p, f64p, u32p]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -1,0 +1,384 @@
+// Average-linkage (UPGMA) tree of a precomputed N x N distance matrix: the tree stage of ctree.
+//
+// Replaces, for diverse_seq/cluster.py:216-230 (AgglomerativeClustering(metric="precomputed",
+// linkage="average")), what sklearn runs underneath: scipy.cluster.hierarchy.linkage(X[triu], "average"),
+// i.e. scipy's nearest-neighbour chain (_hierarchy.nn_chain) and its union-find relabelling (`label`).
+// The result is scipy's Z bit for bit -- same pairs, same heights, same sizes -- so every tie resolves
+// the same way:
+//   * an argmin over row x takes the LOWEST index among equal values (scipy's strict `<` in ascending
+//     order), and the previous chain element wins a tie against it;
+//   * a merge of a < b writes row / column b as (double(na) * D[i][a] + double(nb) * D[i][b]) /
+//     double(na + nb): scipy's operands in scipy's order (-ffp-contract=off: no fma; a real division);
+//   * the records are stable-sorted by height and relabelled on the host, as scipy does.
+//
+// Device pipeline (one stream, no host round trip inside the loop):
+//   1. linkage_prepare_kernel: every entry is checked (sklearn's check_array looks at the whole matrix:
+//      NaN / +-inf anywhere -> DVS_ERR_VALUE) and the upper triangle is copied over the lower one (only
+//      D[i][j], i < j, counts: X[np.triu_indices(n, 1)]); 32 x 32 tile pairs through LDS.
+//   2. linkage_nn_chain_kernel: ONE persistent workgroup of 1024 threads runs the whole chain.  Every step
+//      depends on the one before, so a grid would pay a grid barrier per step (~4 us, MI355X barrier-xcd)
+//      where a workgroup barrier costs a few hundred cycles.  The chain, the sizes, the records and a
+//      compacted, ascending list of the active clusters live in global scratch (N may exceed the LDS);
+//      scans walk the list, never a dead column.  Column b is kept consistent by mirrored writes.
+//      The loop is bounded: at most 3 (n - 1) argmin steps (n - 1 of them end in a merge, every other
+//      one pushes a cluster and a merge pops two), else an error word and an early return.
+#include "dvs_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+
+namespace {
+
+constexpr int LNK_THREADS = 1024;
+constexpr int LNK_WAVES = LNK_THREADS / 64;
+constexpr int LNK_UNROLL = 4;  // independent loads in flight per thread and pass
+constexpr uint32_t LNK_TILE = 32;
+constexpr uint32_t LNK_NONE = 0xFFFFFFFFu;
+
+// status words (device): [0] prepare / loop outcome, [1] the distance kernel's zero-division flag
+enum : uint32_t { LNK_OK = 0, LNK_NONFINITE = 1, LNK_NO_CONVERGE = 2 };
+
+__device__ __forceinline__ bool lnk_better(double v, uint32_t i, double bv, uint32_t bi) {
+    return v < bv || (v == bv && i < bi);
+}
+
+// Check + mirror, one 32 x 32 tile pair (bi >= bj) per workgroup: the upper tile (bj, bi) is staged in LDS and
+// written transposed over the lower tile (bi, bj); both are checked.  A diagonal tile mirrors onto itself.
+__global__ __launch_bounds__(256) void linkage_prepare_kernel(double *__restrict__ D, uint32_t n,
+                                                              uint32_t *__restrict__ status) {
+    __shared__ double s_up[LNK_TILE][LNK_TILE + 1];
+    const uint32_t bi = blockIdx.x, bj = blockIdx.y;
+    if (bj > bi) return;
+    const uint32_t tx = threadIdx.x & (LNK_TILE - 1), ty = threadIdx.x / LNK_TILE;  // 32 x 8
+    bool bad = false;
+    // the upper tile: rows bj * 32 + r, columns bi * 32 + tx
+    for (uint32_t r = ty; r < LNK_TILE; r += 256 / LNK_TILE) {
+        const uint32_t row = bj * LNK_TILE + r, col = bi * LNK_TILE + tx;
+        double v = 0.0;
+        if (row < n && col < n) {
+            v = D[size_t(row) * n + col];
+            bad |= !__builtin_isfinite(v);
+        }
+        s_up[r][tx] = v;
+    }
+    // the lower tile's own entries are checked before they are overwritten (a diagonal tile is its own upper tile)
+    if (bi != bj)
+        for (uint32_t r = ty; r < LNK_TILE; r += 256 / LNK_TILE) {
+            const uint32_t row = bi * LNK_TILE + r, col = bj * LNK_TILE + tx;
+            if (row < n && col < n) bad |= !__builtin_isfinite(D[size_t(row) * n + col]);
+        }
+    __syncthreads();
+    // lower tile entry (bi * 32 + r, bj * 32 + tx) = upper entry (bj * 32 + tx, bi * 32 + r)
+    for (uint32_t r = ty; r < LNK_TILE; r += 256 / LNK_TILE) {
+        const uint32_t row = bi * LNK_TILE + r, col = bj * LNK_TILE + tx;
+        if (row < n && col < n && row > col) D[size_t(row) * n + col] = s_up[tx][r];
+    }
+    if (bad) atomicOr(status, LNK_NONFINITE);
+}
+
+// scratch of the loop (global): size[n], chain[n], act[2][n] (the active list and its next compaction)
+// records (global, copied out): rec_h[n - 1], rec_pair[2 (n - 1)], rec_size[n - 1]
+__global__ __launch_bounds__(LNK_THREADS) void linkage_nn_chain_kernel(
+    double *__restrict__ D, uint32_t n, uint32_t *__restrict__ size, uint32_t *__restrict__ chain,
+    uint32_t *act_a, uint32_t *act_b, double *__restrict__ rec_h,  // (act_a / act_b swap roles every merge)
+    uint32_t *__restrict__ rec_pair, uint32_t *__restrict__ rec_size, uint32_t *__restrict__ status) {
+    __shared__ double s_v[2][LNK_WAVES];  // per-wave minima, alternating buffers: one barrier per argmin step
+    __shared__ uint32_t s_i[2][LNK_WAVES];
+    __shared__ uint32_t s_pos;            // position of the merged-away cluster in the active list
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (status[0] != LNK_OK) return;  // (the prepare pass found a non-finite entry)
+    for (uint32_t i = tid; i < n; i += LNK_THREADS) {
+        size[i] = 1;
+        act_a[i] = i;
+    }
+    __syncthreads();
+    uint32_t *act = act_a, *act_next = act_b;
+    uint32_t m = n;               // active clusters
+    uint32_t chain_len = 0;       // (every value below is uniform over the workgroup)
+    uint32_t x = 0, prev = 0;     // chain[chain_len - 1], chain[chain_len - 2]
+    uint32_t steps = 0, ph = 0;
+    const uint32_t max_steps = 3u * (n - 1u);
+    for (uint32_t k = 0; k + 1 < n; k++) {
+        if (chain_len == 0) {  // the smallest active cluster starts a chain
+            x = act[0];
+            if (tid == 0) chain[0] = x;
+            chain_len = 1;
+        }
+        uint32_t y;
+        double cur;
+        for (;;) {
+            if (steps++ >= max_steps) {
+                if (tid == 0) status[0] = LNK_NO_CONVERGE;
+                return;
+            }
+            const double *row = D + size_t(x) * n;
+            const double c_prev = chain_len > 1 ? row[prev] : 0.0;
+            double bv = __builtin_inf();
+            uint32_t bi = LNK_NONE;
+            for (uint32_t t0 = tid; t0 < m; t0 += LNK_UNROLL * LNK_THREADS) {
+                uint32_t ii[LNK_UNROLL];
+                double vv[LNK_UNROLL];
+#pragma unroll
+                for (int u = 0; u < LNK_UNROLL; u++) {
+                    const uint32_t t = t0 + u * LNK_THREADS;
+                    ii[u] = t < m ? act[t] : LNK_NONE;
+                    if (ii[u] == x) ii[u] = LNK_NONE;
+                }
+#pragma unroll
+                for (int u = 0; u < LNK_UNROLL; u++) vv[u] = ii[u] != LNK_NONE ? row[ii[u]] : __builtin_inf();
+#pragma unroll
+                for (int u = 0; u < LNK_UNROLL; u++)
+                    if (ii[u] != LNK_NONE && lnk_better(vv[u], ii[u], bv, bi)) {
+                        bv = vv[u];
+                        bi = ii[u];
+                    }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ov = __shfl_xor(bv, o, 64);
+                const uint32_t oi = __shfl_xor(bi, o, 64);
+                if (lnk_better(ov, oi, bv, bi)) {
+                    bv = ov;
+                    bi = oi;
+                }
+            }
+            if (lane == 0) {
+                s_v[ph][wave] = bv;
+                s_i[ph][wave] = bi;
+            }
+            __syncthreads();
+            bv = s_v[ph][0];
+            bi = s_i[ph][0];
+#pragma unroll
+            for (int w = 1; w < LNK_WAVES; w++)
+                if (lnk_better(s_v[ph][w], s_i[ph][w], bv, bi)) {
+                    bv = s_v[ph][w];
+                    bi = s_i[ph][w];
+                }
+            ph ^= 1u;
+            // scipy: cur = D[x][prev] (or +inf), then `if D[x][i] < cur` in ascending i
+            if (chain_len > 1 && !(bv < c_prev)) {
+                y = prev;
+                cur = c_prev;
+            } else {
+                y = bi;
+                cur = bv;
+            }
+            if (chain_len > 1 && y == prev) break;
+            if (chain_len >= n || y >= n) {  // (cannot happen on a finite matrix; never write past the chain)
+                if (tid == 0) status[0] = LNK_NO_CONVERGE;
+                return;
+            }
+            if (tid == 0) chain[chain_len] = y;
+            chain_len++;
+            prev = x;
+            x = y;
+        }
+        // merge x and y: a < b, b takes the new cluster
+        const uint32_t a = x < y ? x : y, b = x < y ? y : x;
+        const uint32_t na = size[a], nb = size[b];
+        const double dna = double(na), dnb = double(nb), dn = double(na + nb);
+        const double *ra = D + size_t(a) * n;
+        double *rb = D + size_t(b) * n;
+        for (uint32_t t0 = tid; t0 < m; t0 += LNK_UNROLL * LNK_THREADS) {
+            uint32_t ii[LNK_UNROLL];
+            double va[LNK_UNROLL], vb[LNK_UNROLL];
+#pragma unroll
+            for (int u = 0; u < LNK_UNROLL; u++) {
+                const uint32_t t = t0 + u * LNK_THREADS;
+                ii[u] = t < m ? act[t] : LNK_NONE;
+                if (ii[u] == a) s_pos = t;
+                if (ii[u] == a || ii[u] == b) ii[u] = LNK_NONE;
+            }
+#pragma unroll
+            for (int u = 0; u < LNK_UNROLL; u++) {
+                va[u] = ii[u] != LNK_NONE ? ra[ii[u]] : 0.0;
+                vb[u] = ii[u] != LNK_NONE ? rb[ii[u]] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < LNK_UNROLL; u++)
+                if (ii[u] != LNK_NONE) {
+                    const double d = (dna * va[u] + dnb * vb[u]) / dn;
+                    rb[ii[u]] = d;
+                    D[size_t(ii[u]) * n + b] = d;
+                }
+        }
+        __syncthreads();  // (s_pos; every thread has read size[a], size[b])
+        const uint32_t p = s_pos;
+        if (tid == 0) {
+            rec_pair[2 * k] = a;
+            rec_pair[2 * k + 1] = b;
+            rec_h[k] = cur;
+            rec_size[k] = na + nb;
+            size[a] = 0;
+            size[b] = na + nb;
+        }
+        for (uint32_t t = tid; t < m; t += LNK_THREADS)
+            if (t != p) act_next[t - (t > p ? 1u : 0u)] = act[t];
+        __syncthreads();  // (the new list, the chain and the sizes are visible to every thread)
+        uint32_t *sw = act;
+        act = act_next;
+        act_next = sw;
+        m--;
+        chain_len -= 2;
+        if (chain_len > 0) x = chain[chain_len - 1];
+        if (chain_len > 1) prev = chain[chain_len - 2];
+    }
+}
+
+struct PooledBuf {  // a block of the context's cache, handed back on scope exit
+    dvs_ctx *ctx;
+    void *p = nullptr;
+    ~PooledBuf() { dvs_dev_free(ctx, p); }
+    template <typename T>
+    T *as() { return static_cast<T *>(p); }
+};
+
+// byte offsets of the scratch block: what is copied back first, then what stays on the device
+struct LnkLayout {
+    size_t status, rec_h, rec_pair, rec_size, out_bytes, size, chain, act_a, act_b, bytes;
+    explicit LnkLayout(uint32_t n) {
+        auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
+        const size_t m1 = size_t(n) - 1;
+        status = 0;
+        rec_h = 16;
+        rec_pair = rec_h + m1 * 8;
+        rec_size = up8(rec_pair + 2 * m1 * 4);
+        out_bytes = up8(rec_size + m1 * 4);
+        size = out_bytes;
+        chain = size + size_t(n) * 4;
+        act_a = chain + size_t(n) * 4;
+        act_b = act_a + size_t(n) * 4;
+        bytes = act_b + size_t(n) * 4;
+    }
+};
+
+// scipy's label(): the records in height order (stable), union-find roots as cluster ids n, n + 1, ...,
+// the smaller root first, the size from the union
+void linkage_relabel(uint32_t n, const double *rec_h, const uint32_t *rec_pair, uint32_t *pairs, double *heights,
+                     uint32_t *sizes) {
+    const uint32_t m1 = n - 1;
+    std::vector<uint32_t> order(m1);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t p, uint32_t q) { return rec_h[p] < rec_h[q]; });
+    std::vector<uint32_t> parent(2 * size_t(n) - 1), usize(2 * size_t(n) - 1, 1u);
+    std::iota(parent.begin(), parent.end(), 0u);
+    auto find = [&](uint32_t v) {
+        uint32_t r = v;
+        while (parent[r] != r) r = parent[r];
+        while (parent[v] != r) {  // path compression
+            const uint32_t nx = parent[v];
+            parent[v] = r;
+            v = nx;
+        }
+        return r;
+    };
+    for (uint32_t j = 0; j < m1; j++) {
+        const uint32_t q = order[j];
+        const uint32_t xr = find(rec_pair[2 * q]), yr = find(rec_pair[2 * q + 1]);
+        const uint32_t lab = n + j;
+        pairs[2 * j] = std::min(xr, yr);
+        pairs[2 * j + 1] = std::max(xr, yr);
+        heights[j] = rec_h[q];
+        parent[xr] = parent[yr] = lab;
+        usize[lab] = usize[xr] + usize[yr];
+        sizes[j] = usize[lab];
+    }
+}
+
+}  // namespace
+
+// the matrix (need_matrix) and the loop's scratch against the device's memory: DVS_ERR_NOMEM when they cannot fit
+static int linkage_fits(dvs_ctx *ctx, uint32_t n, bool need_matrix) {
+    const uint64_t n2 = uint64_t(n) * n;
+    if (n2 > (uint64_t(1) << 58))
+        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix does not fit in memory", n, n);
+    const size_t bytes = (need_matrix ? size_t(n2) * 8 : 0) + LnkLayout(n).bytes;
+    size_t free_b = 0, total_b = 0;
+    DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (bytes + (64u << 20) > free_b + ctx->pool_bytes)
+        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix and its tree need %zu bytes of HBM, %zu free", n,
+                             n, bytes, free_b);
+    return DVS_OK;
+}
+
+int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n) { return linkage_fits(ctx, n, true); }
+
+// The tree of the n x n matrix at d_dist (a working buffer: overwritten).  Everything is enqueued on the context's
+// stream behind whatever wrote the matrix; d_zerodiv (may be NULL): a device word a distance kernel in front set
+// where the reference divides by zero, reported first.  Returns when the host outputs are written.
+int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *pairs,
+                       double *heights, uint32_t *sizes) {
+    int rc = linkage_fits(ctx, n, false);
+    if (rc) return rc;
+    const LnkLayout L(n);
+    PooledBuf scratch{ctx};
+    rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "linkage scratch");
+    if (rc) return rc;
+    char *base = scratch.as<char>();
+    auto at = [&](size_t off) { return reinterpret_cast<void *>(base + off); };
+    uint32_t *d_status = static_cast<uint32_t *>(at(L.status));
+    std::vector<uint64_t> host((L.out_bytes + 7) / 8);
+    const uint32_t tiles = (n + LNK_TILE - 1) / LNK_TILE;
+    hipError_t e = hipMemsetAsync(d_status, 0, 16, ctx->stream);
+    if (e == hipSuccess && d_zerodiv)
+        e = hipMemcpyAsync(d_status + 1, d_zerodiv, 4, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(linkage_prepare_kernel, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n, d_status);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(linkage_nn_chain_kernel, dim3(1), dim3(LNK_THREADS), 0, ctx->stream, d_dist, n,
+                           static_cast<uint32_t *>(at(L.size)), static_cast<uint32_t *>(at(L.chain)),
+                           static_cast<uint32_t *>(at(L.act_a)), static_cast<uint32_t *>(at(L.act_b)),
+                           static_cast<double *>(at(L.rec_h)), static_cast<uint32_t *>(at(L.rec_pair)),
+                           static_cast<uint32_t *>(at(L.rec_size)), d_status);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), base, L.out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "average linkage");
+    if (se != hipSuccess) return dvs_hip_fail(ctx, se, "average linkage");
+    const char *hb = reinterpret_cast<const char *>(host.data());
+    const uint32_t *st = reinterpret_cast<const uint32_t *>(hb + L.status);
+    if (st[1]) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // 0 / 0, distance.py:283
+    if (st[0] == LNK_NONFINITE)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "Input contains NaN or infinity: the %u x %u distance matrix", n, n);
+    if (st[0] != LNK_OK)
+        return dvs_set_error(ctx, DVS_ERR_RUNTIME, "average linkage: the chain did not close within 3 (n - 1) steps");
+    linkage_relabel(n, reinterpret_cast<const double *>(hb + L.rec_h), reinterpret_cast<const uint32_t *>(hb + L.rec_pair),
+                    pairs, heights, sizes);
+    return DVS_OK;
+}
+
+extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
+                                   double *heights, uint32_t *sizes) {
+    if (!ctx || !dist || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (n < 2)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "Found array with %u sample(s) while a minimum of 2 is required", n);
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    if (dist_on_device) {
+        hipPointerAttribute_t attr;
+        const hipError_t e = hipPointerGetAttributes(&attr, dist);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
+        }
+        if (attr.device != ctx->device)
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
+                                 attr.device, ctx->device);
+        return dvs_linkage_device(ctx, dist, n, nullptr, pairs, heights, sizes);
+    }
+    int rc = linkage_fits(ctx, n, true);
+    if (rc) return rc;
+    PooledBuf d_dist{ctx};
+    rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix");
+    if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(d_dist.p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return dvs_hip_fail(ctx, e, "distance matrix upload");
+    }
+    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, pairs, heights, sizes);
+}

@@ -1209,6 +1209,19 @@ extern "C" int dvs_mash_distances(dvs_ctx *ctx, const uint32_t *sketches, uint32
     return rc;
 }
 
+// the euclidean kernel over the rows of m into the device matrix d_dist (every cell off the diagonal)
+static hipError_t euclid_launch(dvs_ctx *ctx, const dvs_matrix *m, double *d_dist) {
+    const uint32_t n = m->nrows;
+    const dim3 grid(n, (n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64));
+    dvs_mat_dispatch(m, [&](auto *mp) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
+        hipLaunchKernelGGL((euclid_kernel<T>), grid, dim3(EUC_THREADS), 0, ctx->stream, mp, m->d_totals, m->nbins, n,
+                           d_dist);
+        return 0;
+    });
+    return hipGetLastError();
+}
+
 extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
     if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     const uint32_t n = m->nrows;
@@ -1225,20 +1238,68 @@ extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double
     int rc = dvs_dev_alloc(ctx, (void **)&d_dist, size_t(n) * n * 8, "distance matrix");
     if (rc) return rc;
     hipError_t e = hipMemsetAsync(d_dist, 0, size_t(n) * n * 8, ctx->stream);  // the diagonal
-    const dim3 grid(n, groups);
-    if (e == hipSuccess) {
-        dvs_mat_dispatch(m, [&](auto *mp) {
-            using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
-            hipLaunchKernelGGL((euclid_kernel<T>), grid, dim3(EUC_THREADS), 0, ctx->stream, mp, m->d_totals, m->nbins,
-                               n, d_dist);
-            return 0;
-        });
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = euclid_launch(ctx, m, d_dist);
     if (e == hipSuccess) e = hipMemcpyAsync(dist, d_dist, size_t(n) * n * 8, hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t se = hipStreamSynchronize(ctx->stream);
     dvs_dev_free(ctx, d_dist);
     if (e != hipSuccess) return dvs_hip_fail(ctx, e, "euclidean distances");
     if (se != hipSuccess) return dvs_hip_fail(ctx, se, "euclidean distances");
     return DVS_OK;
+}
+
+// ---- ctree end to end on the device (diverse_seq/cluster.py:164-188, 216-233): the N x N matrix is written into the
+// context's scratch and read there by the average-linkage tree (linkage.hip); it never crosses PCIe.  The diagonal,
+// which neither distance kernel writes, is zeroed (the tree checks every entry, as sklearn does).
+static int tree_matrix_alloc(dvs_ctx *ctx, uint32_t n, PooledBuf *d_dist) {
+    int rc = dvs_linkage_check_size(ctx, n);
+    if (!rc) rc = dvs_dev_alloc(ctx, &d_dist->p, size_t(n) * n * 8, "distance matrix");
+    if (rc) return rc;
+    DVS_HIP(ctx, hipMemset2DAsync(d_dist->p, (size_t(n) + 1) * 8, 0, 8, n, ctx->stream));
+    return DVS_OK;
+}
+
+extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
+                                            uint32_t *pairs, double *heights, uint32_t *sizes) {
+    if (!ctx || !sk || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    const uint32_t n = sk->nseq;
+    if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
+    if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
+    if (!sk->d_sk) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // every sketch empty
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx}, d_flag{ctx};
+    int rc = tree_matrix_alloc(ctx, n, &d_dist);
+    if (!rc) rc = dvs_dev_alloc(ctx, &d_flag.p, 4, "flag");
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync(d_flag.p, 0, 4, ctx->stream);
+    if (e == hipSuccess) {
+        const dim3 grid(n, (n + PAIR_THREADS - 1) / PAIR_THREADS);
+        const uint32_t row_lds = std::min(sk->stride, PAIR_ROW_LDS);
+        hipLaunchKernelGGL(mash_pairs_kernel, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, sk->d_sk, sk->d_lens,
+                           n, k, sketch_size, sk->stride, 0u, 1u, 1, row_lds, d_dist.as<double>(), d_flag.as<uint32_t>());
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return dvs_hip_fail(ctx, e, "mash distances");
+    }
+    return dvs_linkage_device(ctx, d_dist.as<double>(), n, d_flag.as<uint32_t>(), pairs, heights, sizes);
+}
+
+extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
+                                                    uint32_t *sizes) {
+    if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    const uint32_t n = m->nrows;
+    if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
+    if ((n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64) > 65535u)
+        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%u rows: the %u x %u distance matrix is beyond this path", n, n, n);
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx};
+    int rc = tree_matrix_alloc(ctx, n, &d_dist);
+    if (rc) return rc;
+    const hipError_t e = euclid_launch(ctx, m, d_dist.as<double>());
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return dvs_hip_fail(ctx, e, "euclidean distances");
+    }
+    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, pairs, heights, sizes);
 }

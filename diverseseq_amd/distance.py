@@ -1,7 +1,8 @@
 """Host side of the distance path: mirrors diverse_seq/distance.py's functions
 (mash_sketches :178-227, mash_distances :119-175, mash_distance :230-291,
 euclidean_distances :294-332) and the strided chunks of
-diverse_seq/cluster.py:607-644, with the arithmetic in libdvs_hip.so."""
+diverse_seq/cluster.py:607-644, with the arithmetic in libdvs_hip.so; and the fused ctree stages
+(distances and the average-linkage tree with the N x N matrix left in HBM)."""
 
 from __future__ import annotations
 
@@ -12,6 +13,23 @@ import numpy as np
 from . import _lib, engine
 
 _U32_MAX = 0xFFFFFFFF
+
+
+def tree_outputs(n: int):
+    """host buffers of the dvs_*average_linkage calls for n leaves: pairs uint32 [2 (n - 1)], heights f64 [n - 1],
+    sizes uint32 [n - 1]"""
+    return (np.zeros(2 * (n - 1), dtype=np.uint32), np.zeros(n - 1, dtype=np.float64),
+            np.zeros(n - 1, dtype=np.uint32))
+
+
+def linkage_matrix(pairs: np.ndarray, heights: np.ndarray, sizes: np.ndarray) -> np.ndarray:
+    """the outputs of a dvs_*average_linkage call -> scipy's linkage matrix Z, float64 [n - 1, 4]"""
+    z = np.empty((heights.size, 4), dtype=np.float64)
+    z[:, 0] = pairs[0::2]
+    z[:, 1] = pairs[1::2]
+    z[:, 2] = heights
+    z[:, 3] = sizes
+    return z
 
 
 def sketch_batch(seqs, k: int, sketch_size: int, num_states: int = 4,
@@ -164,6 +182,17 @@ class Sketches:
                                                                  row_start, row_stride, int(symmetric), C.c_void_p(dist_ptr),
                                                                  C.c_void_p(zerodiv_ptr)))
 
+    def average_linkage(self) -> np.ndarray:
+        """scipy's average-linkage matrix Z over the mash distances of every pair (`dvs ctree`'s tree): the N x N
+        matrix is written and read in HBM (dvs_sketches_average_linkage); ZeroDivisionError as `distances`"""
+        if self.n < 2:
+            raise ValueError("need at least two sequences to build a tree")
+        pairs, heights, sizes = tree_outputs(self.n)
+        self.ctx.check(self.ctx._L.dvs_sketches_average_linkage(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX),
+                                                                _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                                                _lib.ptr(sizes, C.c_uint32)))
+        return linkage_matrix(pairs, heights, sizes)
+
     def distances(self, *, row_start: int = 0, row_stride: int = 1, symmetric: bool = True,
                   out: np.ndarray | None = None) -> np.ndarray:
         if out is not None and (not isinstance(out, np.ndarray) or out.shape != (self.n, self.n)
@@ -195,5 +224,31 @@ def euclidean_distances(seqs, k: int, num_states: int = 4,
         dist = np.zeros((m.nrows, m.nrows), dtype=np.float64)
         ctx.check(ctx._L.dvs_euclidean_distances(ctx._h, m._h, _lib.ptr(dist, C.c_double)))
         return dist
+    finally:
+        m.close()
+
+
+def mash_average_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False,
+                         ctx: engine.Context | None = None) -> np.ndarray:
+    """`dvs ctree`'s mash tree on the device: sketches, the N x N distances and the average-linkage Z, every stage in
+    HBM; only Z (n - 1 rows) comes back"""
+    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
+    try:
+        return sk.average_linkage()
+    finally:
+        sk.close()
+
+
+def euclidean_average_linkage(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    ctx = ctx or engine.default_context()
+    m = ctx.build_matrix(seqs, k, num_states)
+    try:
+        if m.nrows < 2:
+            raise ValueError("need at least two sequences to build a tree")
+        pairs, heights, sizes = tree_outputs(m.nrows)
+        ctx.check(ctx._L.dvs_matrix_euclidean_average_linkage(ctx._h, m._h, _lib.ptr(pairs, C.c_uint32),
+                                                              _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
+        return linkage_matrix(pairs, heights, sizes)
     finally:
         m.close()

@@ -368,6 +368,29 @@ int dvs_sketches_distances_device(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t
  * the rows of m, full symmetric nrows x nrows matrix */
 int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist);
 
+/* ---- average-linkage tree (the tree stage of ctree) ----------------------------- *
+ * dvs_average_linkage replaces the clustering of make_cluster_tree (diverse_seq/cluster.py:216-230:
+ * sklearn AgglomerativeClustering(metric="precomputed", linkage="average"), i.e. scipy's
+ * linkage(X[triu_indices(n, 1)], "average") and its nearest-neighbour chain): the n - 1 merges of scipy's
+ * linkage matrix Z bit for bit, row j = (pairs[2 j], pairs[2 j + 1], heights[j], sizes[j]), cluster ids
+ * n, n + 1, ... in merge order.  `dist` is n x n, row-major float64; only D[i][j] with i < j counts (the
+ * diagonal and the lower triangle are checked, not used).  A HOST matrix (dist_on_device == 0) is uploaded
+ * into the context's scratch and left as it is; a DEVICE matrix (dist_on_device != 0) must live on the
+ * context's device and is the working buffer: it is OVERWRITTEN.  Returns when the host outputs are written.
+ * DVS_ERR_VALUE: n < 2, a NaN or +-inf entry anywhere (sklearn's check_array), a device matrix on another
+ * device; DVS_ERR_NOMEM: the matrix does not fit in HBM. */
+int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
+                        double *heights, uint32_t *sizes);
+/* ctree end to end with the N x N matrix left in HBM (it never crosses PCIe): the mash distances of
+ * dvs_sketches_distances over every pair (DVS_ERR_ZERODIV as there when two sketches are empty), or the
+ * euclidean distances of dvs_euclidean_distances over the rows of m (a row without valid k-mers gives NaN
+ * distances, hence DVS_ERR_VALUE, as sklearn raises on that matrix), into the context's scratch; then the
+ * tree above, same outputs. */
+int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
+                                 uint32_t *pairs, double *heights, uint32_t *sizes);
+int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
+                                         uint32_t *sizes);
+
 #ifdef __cplusplus
 }
 #endif

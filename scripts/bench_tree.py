@@ -1,0 +1,97 @@
+"""Time the tree stage of `dvs ctree`: for N in 1 000, 4 000, 10 000 one JSON line with
+  device_host_ms    cluster.average_linkage of a host float64 N x N matrix (upload + check/mirror + chain + relabel)
+  device_tensor_ms  the same matrix already in HBM (a torch tensor, the working buffer: no upload)
+  fused_mash_ms     distance.mash_average_linkage: sketches -> N x N mash distances -> tree, all in HBM
+                    (N families of 5 kb sequences, k = 12, s = 3 000)
+  sklearn_fit_ms    AgglomerativeClustering(metric="precomputed", linkage="average").fit on the same host matrix
+and whether the device Z equals scipy's (z_equal).  Wall clock around calls that end in a device synchronise;
+median of --reps runs after one warm-up of every shape.
+
+  python scripts/bench_tree.py [--sizes 1000,4000,10000] [--reps 3] [--out FILE]"""
+import argparse
+import json
+import os
+import pathlib
+import sys
+import time
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def family_seqs(n: int, length: int, seed: int) -> list:
+    rng = np.random.default_rng(seed)
+    roots = rng.integers(0, 4, (max(1, n // 20), length), dtype=np.uint8)
+    out = []
+    for i in range(n):
+        s = roots[i % len(roots)].copy()
+        hit = rng.random(length) < rng.uniform(0.005, 0.05)
+        s[hit] = rng.integers(0, 4, int(hit.sum()), dtype=np.uint8)
+        out.append(s)
+    return out
+
+
+def median_ms(fn, reps: int) -> float:
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1000,4000,10000")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--sklearn-reps", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    from scipy.cluster.hierarchy import linkage
+    from sklearn.cluster import AgglomerativeClustering
+
+    from diverseseq_amd import cluster, distance, engine
+
+    ctx = engine.Context(0)
+    info = ctx.device_info()
+    warm = np.random.default_rng(0).random((300, 300))
+    cluster.average_linkage(warm, ctx=ctx)
+    distance.mash_average_linkage(family_seqs(64, 5000, 1), 12, 3000, ctx=ctx)
+    lines = []
+    for n in (int(v) for v in args.sizes.split(",")):
+        d = np.random.default_rng(n).random((n, n))
+        d = np.triu(d, 1) + np.triu(d, 1).T
+        z = cluster.average_linkage(d, ctx=ctx)
+        z_equal = bool(np.array_equal(z, linkage(d[np.triu_indices(n, 1)], "average")))
+        host_ms = median_ms(lambda: cluster.average_linkage(d, ctx=ctx), args.reps)
+        dev = torch.from_numpy(d).to("cuda:0")
+        tensor_ts = []
+        for _ in range(args.reps):
+            t = dev.clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cluster.average_linkage(t, ctx=ctx)
+            tensor_ts.append((time.perf_counter() - t0) * 1e3)
+            del t
+        del dev
+        seqs = family_seqs(n, 5000, n)
+        distance.mash_average_linkage(seqs, 12, 3000, ctx=ctx)
+        fused_ms = median_ms(lambda: distance.mash_average_linkage(seqs, 12, 3000, ctx=ctx), args.reps)
+        sk_ms = median_ms(lambda: AgglomerativeClustering(metric="precomputed", linkage="average").fit(d),
+                          args.sklearn_reps)
+        line = {"n": n, "device_host_ms": round(host_ms, 3), "device_tensor_ms": round(float(np.median(tensor_ts)), 3),
+                "fused_mash_ms": round(fused_ms, 3), "sklearn_fit_ms": round(sk_ms, 3), "z_equal": z_equal,
+                "reps": args.reps, "device": info["name"], "host_cpus": len(os.sched_getaffinity(0))}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        ctx.check(ctx._L.dvs_ctx_trim(ctx._h))
+    if args.out:
+        pathlib.Path(args.out).write_text("".join(json.dumps(x) + "\n" for x in lines))
+
+
+if __name__ == "__main__":
+    main()
