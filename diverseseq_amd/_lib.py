@@ -44,6 +44,7 @@ EXPORTS = (
     "dvs_packed_get", "dvs_matrix_build_packed", "dvs_sketches_build_packed", "dvs_seqbatch_pack",
     "dvs_seqbatch_packed", "dvs_sketches_build_from_seqbatch",
     "dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage",
+    "dvs_linkage", "dvs_sketches_linkage", "dvs_matrix_euclidean_linkage",
 )
 
 
@@ -211,6 +212,9 @@ def load() -> C.CDLL:
         L.dvs_average_linkage.argtypes = [vp, vp, C.c_int, C.c_uint32, u32p, f64p, u32p]
         L.dvs_sketches_average_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32, u32p, f64p, u32p]
         L.dvs_matrix_euclidean_average_linkage.argtypes = [vp, vp, u32p, f64p, u32p]
+        L.dvs_linkage.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_int, u32p, f64p, u32p]
+        L.dvs_sketches_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, u32p, f64p, u32p]
+        L.dvs_matrix_euclidean_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

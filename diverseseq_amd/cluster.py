@@ -1,12 +1,13 @@
-"""`dvs ctree` path: distances and the average-linkage tree on the GPU.
+"""`dvs ctree` path: distances and the linkage tree on the GPU.
 
 Mirrors diverse_seq/cluster.py: `make_cluster_tree` (:191-237 -- sklearn
 AgglomerativeClustering(metric="precomputed", linkage="average"), children_ folded into a
 nested tuple, printed without quotes) and the argument checks of `dvs_ctree.__init__`
 (:113-162).  The reference hands the string to cogent3's make_tree; here it is returned as a
-Newick string.  `ctree` builds the tree on the device by default (`average_linkage`: scipy's
-nearest-neighbour chain in one persistent workgroup, csrc/linkage.hip, the same linkage matrix
-bit for bit); `tree="sklearn"` keeps the reference's host path (`make_cluster_tree`).
+Newick string.  `ctree` builds the tree on the device by default (`linkage`: scipy's
+nearest-neighbour chain, or for single linkage its minimum spanning tree, in one persistent
+workgroup, csrc/linkage.hip, the same linkage matrix bit for bit); `tree="sklearn"` keeps the
+reference's host path (`make_cluster_tree`, average linkage only).
 """
 
 from __future__ import annotations
@@ -41,23 +42,23 @@ def make_cluster_tree(seq_names: Sequence[str], pairwise_distances: np.ndarray) 
     return str(nested_tuple_tree(seq_names, pairwise_distances)).replace("'", "") + ";"
 
 
-def average_linkage(dist, *, ctx: engine.Context | None = None) -> np.ndarray:
-    """scipy.cluster.hierarchy.linkage(dist[np.triu_indices(n, 1)], "average") on the GPU -> Z, float64 [n - 1, 4]
-    in scipy's layout, bit for bit (what sklearn's AgglomerativeClustering(metric="precomputed",
-    linkage="average") runs; its children_ is Z[:, :2]).  Only the upper triangle counts; a NaN or inf anywhere
-    raises ValueError, as sklearn's check does.
+def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None) -> np.ndarray:
+    """scipy.cluster.hierarchy.linkage(dist[np.triu_indices(n, 1)], method) on the GPU -> Z, float64 [n - 1, 4] in
+    scipy's layout, bit for bit, for method "single", "complete", "average", "weighted" or "ward" ("centroid" and
+    "median", which scipy builds by another algorithm, raise ValueError).  Only the upper triangle counts; a NaN or
+    inf anywhere raises ValueError, as sklearn's check does, and so does a negative entry above the diagonal for
+    "ward".  The method and the shape are checked before any device work.
 
     `dist`: anything np.asarray(dist, float64) takes (left as it is), or a square, contiguous float64 torch tensor
     on the GPU, which is used as the working buffer and OVERWRITTEN.  Such a tensor must live on the context's
     device (ValueError otherwise); the call waits for the work torch has queued on that device's current stream."""
-    ctx = ctx or engine.default_context()
+    code = distance.linkage_method_code(method)
     torch = sys.modules.get("torch")
     if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
         if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
             raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
         n = int(dist.shape[0])
         src, on_device = C.c_void_p(dist.data_ptr()), 1
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
     else:
         d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
         if d.ndim != 2 or d.shape[0] != d.shape[1]:
@@ -66,10 +67,19 @@ def average_linkage(dist, *, ctx: engine.Context | None = None) -> np.ndarray:
         src, on_device = d.ctypes.data_as(C.c_void_p), 0
     if n < 2:
         raise ValueError(f"Found array with {n} sample(s) while a minimum of 2 is required")
+    ctx = ctx or engine.default_context()
+    if on_device:
+        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
     pairs, heights, sizes = distance.tree_outputs(n)
-    ctx.check(ctx._L.dvs_average_linkage(ctx._h, src, on_device, n, _lib.ptr(pairs, C.c_uint32),
-                                         _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
+    ctx.check(ctx._L.dvs_linkage(ctx._h, src, on_device, n, code, _lib.ptr(pairs, C.c_uint32),
+                                 _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
     return distance.linkage_matrix(pairs, heights, sizes)
+
+
+def average_linkage(dist, *, ctx: engine.Context | None = None) -> np.ndarray:
+    """`linkage(dist, "average")`: what sklearn's AgglomerativeClustering(metric="precomputed", linkage="average")
+    runs (its children_ is Z[:, :2]), the tree of `dvs ctree`"""
+    return linkage(dist, "average", ctx=ctx)
 
 
 def linkage_to_newick(names: Sequence, Z) -> str:
@@ -99,16 +109,18 @@ def linkage_to_newick(names: Sequence, Z) -> str:
 
 
 def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
-          mash_canonical_kmers: bool | None = None, num_states: int = 4, tree: str = "device") -> str:
+          mash_canonical_kmers: bool | None = None, num_states: int = 4, tree: str = "device",
+          linkage: str = "average") -> str:
     """sequences {name: uint8 codes} -> Newick string (dvs_ctree.main, cluster.py:164-188).
     Argument checks as dvs_ctree.__init__ (cluster.py:139-162).
 
-    tree="device": the distances and the average-linkage tree both on the GPU, the N x N matrix never leaves
-    HBM (dvs_sketches_average_linkage / dvs_matrix_euclidean_average_linkage), the string from
-    `linkage_to_newick`.  tree="sklearn": the reference's path (the matrix copied to the host, sklearn, nested
-    tuples; `make_cluster_tree`).  Both give the same string wherever the sklearn path returns one; the one
-    intended difference is a tree deeper than Python's recursion limit (e.g. a caterpillar of a few thousand
-    leaves), for which the device path returns the Newick string where the sklearn path raises RecursionError."""
+    tree="device": the distances and the tree both on the GPU, the N x N matrix never leaves HBM
+    (dvs_sketches_linkage / dvs_matrix_euclidean_linkage), the string from `linkage_to_newick`; `linkage`: any
+    method the module's `linkage` function builds.  tree="sklearn": the reference's path (the matrix copied to the host, sklearn, nested
+    tuples; `make_cluster_tree`), average linkage only.  Both give the same string wherever the sklearn path
+    returns one; the one intended difference is a tree deeper than Python's recursion limit (e.g. a caterpillar of
+    a few thousand leaves), for which the device path returns the Newick string where the sklearn path raises
+    RecursionError."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
     if distance_mode not in ("mash", "euclidean"):
@@ -121,6 +133,9 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
         raise ValueError("Canonical kmers should only be specified for the mash distance.")
     if tree not in ("device", "sklearn"):
         raise ValueError(f"Unexpected tree {tree!r}: 'device' or 'sklearn'.")
+    distance.linkage_method_code(linkage)
+    if tree == "sklearn" and linkage != "average":
+        raise ValueError(f"tree='sklearn' builds average linkage only, not {linkage!r}: use tree='device'")
     names = list(seqs)
     arrays = [seqs[n] for n in names]
     if tree == "sklearn":
@@ -130,7 +145,7 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
             dists = distance.euclidean_distances(arrays, k, num_states)
         return make_cluster_tree(names, dists)
     if distance_mode == "mash":
-        z = distance.mash_average_linkage(arrays, k, int(sketch_size), num_states, mash_canonical_kmers)
+        z = distance.mash_linkage(arrays, k, int(sketch_size), num_states, mash_canonical_kmers, method=linkage)
     else:
-        z = distance.euclidean_average_linkage(arrays, k, num_states)
+        z = distance.euclidean_linkage(arrays, k, num_states, method=linkage)
     return linkage_to_newick(names, z)

@@ -210,12 +210,14 @@ int dvs_packed_fill_from_device(dvs_ctx *ctx, dvs_packed *p, const uint8_t *d_se
 int dvs_packed_fill_from_host(dvs_ctx *ctx, dvs_packed *p, const uint8_t *seqs);             // host threads pack, chunks cross PCIe packed
 bool dvs_packed_upload_wanted(const dvs_ctx *ctx, uint32_t num_states, uint64_t nbytes);
 
-// linkage.hip: DVS_ERR_NOMEM unless an n x n f64 matrix and the tree's scratch fit the device; the average-linkage
-// tree of the n x n matrix at d_dist (a working buffer, overwritten), enqueued behind whatever wrote it on the
-// context's stream (d_zerodiv, may be NULL: a flag the distance kernel set, reported as DVS_ERR_ZERODIV first);
-// returns when the host outputs (dvs_average_linkage's) are written
+// linkage.hip: DVS_ERR_NOMEM unless an n x n f64 matrix and the tree's scratch fit the device; DVS_ERR_UNSUPPORTED /
+// DVS_ERR_VALUE unless `method` (scipy's code) is one the device builds; the tree of that method over the n x n
+// matrix at d_dist (a working buffer, overwritten), enqueued behind whatever wrote it on the context's stream
+// (d_zerodiv, may be NULL: a flag the distance kernel set, reported as DVS_ERR_ZERODIV first); returns when the host
+// outputs (dvs_linkage's) are written
 int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n);
-int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *pairs,
+int dvs_linkage_check_method(dvs_ctx *ctx, int method);
+int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
                        double *heights, uint32_t *sizes);
 
 // f(typed row pointer) for the matrix's element type

@@ -1,27 +1,41 @@
-// Average-linkage (UPGMA) tree of a precomputed N x N distance matrix: the tree stage of ctree.
+// Hierarchical-clustering tree of a precomputed N x N distance matrix: the tree stage of ctree.
 //
 // Replaces, for diverse_seq/cluster.py:216-230 (AgglomerativeClustering(metric="precomputed",
 // linkage="average")), what sklearn runs underneath: scipy.cluster.hierarchy.linkage(X[triu], "average"),
-// i.e. scipy's nearest-neighbour chain (_hierarchy.nn_chain) and its union-find relabelling (`label`).
+// i.e. scipy's nearest-neighbour chain (_hierarchy.nn_chain) and its union-find relabelling (`label`);
+// and, with the same kernels, scipy's other methods built by the same two algorithms: "complete",
+// "weighted" and "ward" (nn_chain, another update of the merged row) and "single" (_hierarchy.
+// mst_single_linkage, Prim's loop).  ("centroid" and "median" are scipy's fast_linkage: not built.)
 // The result is scipy's Z bit for bit -- same pairs, same heights, same sizes -- so every tie resolves
 // the same way:
 //   * an argmin over row x takes the LOWEST index among equal values (scipy's strict `<` in ascending
 //     order), and the previous chain element wins a tie against it;
-//   * a merge of a < b writes row / column b as (double(na) * D[i][a] + double(nb) * D[i][b]) /
-//     double(na + nb): scipy's operands in scipy's order (-ffp-contract=off: no fma; a real division);
-//   * the records are stable-sorted by height and relabelled on the host, as scipy does.
+//   * a merge of a < b writes row / column b by scipy's _hierarchy_distance_update.pxi, same operands in
+//     the same order (-ffp-contract=off: no fma; real divisions and square roots), d_xi = D[i][a],
+//     d_yi = D[i][b], d_xy the merge height:
+//       average   (double(na) * d_xi + double(nb) * d_yi) / double(na + nb)
+//       complete  d_yi > d_xi ? d_yi : d_xi                      (Cython's max(d_xi, d_yi), not fmax)
+//       weighted  0.5 * (d_xi + d_yi)
+//       ward      t = 1.0 / double(na + nb + ni); sqrt(double(ni + na) * t * d_xi * d_xi
+//                 + double(ni + nb) * t * d_yi * d_yi - double(ni) * t * d_xy * d_xy)
+//   * the records are stable-sorted by height and relabelled on the host, as scipy does (single
+//     linkage's records too: mst_single_linkage ends in the same sort and `label`).
 //
 // Device pipeline (one stream, no host round trip inside the loop):
 //   1. linkage_prepare_kernel: every entry is checked (sklearn's check_array looks at the whole matrix:
 //      NaN / +-inf anywhere -> DVS_ERR_VALUE) and the upper triangle is copied over the lower one (only
-//      D[i][j], i < j, counts: X[np.triu_indices(n, 1)]); 32 x 32 tile pairs through LDS.
-//   2. linkage_nn_chain_kernel: ONE persistent workgroup of 1024 threads runs the whole chain.  Every step
-//      depends on the one before, so a grid would pay a grid barrier per step (~4 us, MI355X barrier-xcd)
+//      D[i][j], i < j, counts: X[np.triu_indices(n, 1)]); 32 x 32 tile pairs through LDS.  For ward, a
+//      negative entry of the upper triangle is flagged too (DVS_ERR_VALUE: scipy's sqrt of a negative
+//      gives NaN heights, whose stable sort is undefined).
+//   2. linkage_nn_chain_kernel<method>: ONE persistent workgroup of 1024 threads runs the whole chain.  Every
+//      step depends on the one before, so a grid would pay a grid barrier per step (~4 us, MI355X barrier-xcd)
 //      where a workgroup barrier costs a few hundred cycles.  The chain, the sizes, the records and a
 //      compacted, ascending list of the active clusters live in global scratch (N may exceed the LDS);
 //      scans walk the list, never a dead column.  Column b is kept consistent by mirrored writes.
 //      The loop is bounded: at most 3 (n - 1) argmin steps (n - 1 of them end in a merge, every other
 //      one pushes a cluster and a merge pops two), else an error word and an early return.
+//   2'. linkage_mst_single_kernel (single): the same workgroup shape runs Prim's loop, exactly n - 1 steps of
+//      one row read and one argmin over the compacted list of unmerged points; D is only read.
 #include "dvs_internal.h"
 
 #include <algorithm>
@@ -36,22 +50,62 @@ constexpr int LNK_UNROLL = 4;  // independent loads in flight per thread and pas
 constexpr uint32_t LNK_TILE = 32;
 constexpr uint32_t LNK_NONE = 0xFFFFFFFFu;
 
-// status words (device): [0] prepare / loop outcome, [1] the distance kernel's zero-division flag
-enum : uint32_t { LNK_OK = 0, LNK_NONFINITE = 1, LNK_NO_CONVERGE = 2 };
+// status words (device): [0] prepare / loop outcome (LNK_NONFINITE and LNK_NEGATIVE are bits), [1] the distance
+// kernel's zero-division flag
+enum : uint32_t { LNK_OK = 0, LNK_NONFINITE = 1, LNK_NO_CONVERGE = 2, LNK_NEGATIVE = 4 };
 
-__device__ __forceinline__ bool lnk_better(double v, uint32_t i, double bv, uint32_t bi) {
+// scipy's _LINKAGE_METHODS codes (the ABI's `method`)
+enum : int { LNK_SINGLE = 0, LNK_COMPLETE = 1, LNK_AVERAGE = 2, LNK_CENTROID = 3, LNK_MEDIAN = 4, LNK_WARD = 5,
+             LNK_WEIGHTED = 6 };
+
+template <typename K>
+__device__ __forceinline__ bool lnk_better(double v, K i, double bv, K bi) {
     return v < bv || (v == bv && i < bi);
+}
+
+// The workgroup's least (value, key) by lnk_better, into every thread's bv / bk: shuffles within each wave, then the
+// per-wave minima through LDS buffer ph and one barrier.  Callers alternate ph: a buffer is written again only after
+// the next call's barrier, which every reader of this call has passed.  (The chain kernel writes the same reduction
+// out inline: through this helper its average instantiation compiles to other code, 66 VGPRs instead of 70.)
+template <typename K>
+__device__ __forceinline__ void lnk_block_argmin(double &bv, K &bk, double (&s_v)[2][LNK_WAVES], K (&s_k)[2][LNK_WAVES],
+                                                 uint32_t ph) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(bv, o, 64);
+        const K ok = __shfl_xor(bk, o, 64);
+        if (lnk_better(ov, ok, bv, bk)) {
+            bv = ov;
+            bk = ok;
+        }
+    }
+    if (lane == 0) {
+        s_v[ph][wave] = bv;
+        s_k[ph][wave] = bk;
+    }
+    __syncthreads();
+    bv = s_v[ph][0];
+    bk = s_k[ph][0];
+#pragma unroll
+    for (int w = 1; w < LNK_WAVES; w++)
+        if (lnk_better(s_v[ph][w], s_k[ph][w], bv, bk)) {
+            bv = s_v[ph][w];
+            bk = s_k[ph][w];
+        }
 }
 
 // Check + mirror, one 32 x 32 tile pair (bi >= bj) per workgroup: the upper tile (bj, bi) is staged in LDS and
 // written transposed over the lower tile (bi, bj); both are checked.  A diagonal tile mirrors onto itself.
+// SIGN (ward): a negative entry above the diagonal sets LNK_NEGATIVE.
+template <bool SIGN>
 __global__ __launch_bounds__(256) void linkage_prepare_kernel(double *__restrict__ D, uint32_t n,
                                                               uint32_t *__restrict__ status) {
     __shared__ double s_up[LNK_TILE][LNK_TILE + 1];
     const uint32_t bi = blockIdx.x, bj = blockIdx.y;
     if (bj > bi) return;
     const uint32_t tx = threadIdx.x & (LNK_TILE - 1), ty = threadIdx.x / LNK_TILE;  // 32 x 8
-    bool bad = false;
+    bool bad = false, neg = false;
     // the upper tile: rows bj * 32 + r, columns bi * 32 + tx
     for (uint32_t r = ty; r < LNK_TILE; r += 256 / LNK_TILE) {
         const uint32_t row = bj * LNK_TILE + r, col = bi * LNK_TILE + tx;
@@ -59,6 +113,7 @@ __global__ __launch_bounds__(256) void linkage_prepare_kernel(double *__restrict
         if (row < n && col < n) {
             v = D[size_t(row) * n + col];
             bad |= !__builtin_isfinite(v);
+            if constexpr (SIGN) neg |= row < col && v < 0.0;
         }
         s_up[r][tx] = v;
     }
@@ -75,10 +130,31 @@ __global__ __launch_bounds__(256) void linkage_prepare_kernel(double *__restrict
         if (row < n && col < n && row > col) D[size_t(row) * n + col] = s_up[tx][r];
     }
     if (bad) atomicOr(status, LNK_NONFINITE);
+    if constexpr (SIGN)
+        if (neg) atomicOr(status, LNK_NEGATIVE);
+}
+
+// scipy's _hierarchy_distance_update.pxi for the merge of x = a < y = b (see the top of the file); dna, dnb, dn:
+// double(na), double(nb), double(na + nb), hoisted out of the loop
+template <int METHOD>
+__device__ __forceinline__ double lnk_merged(double d_xi, double d_yi, double d_xy, uint32_t na, uint32_t nb,
+                                             uint32_t ni, double dna, double dnb, double dn) {
+    if constexpr (METHOD == LNK_AVERAGE) {
+        return (dna * d_xi + dnb * d_yi) / dn;
+    } else if constexpr (METHOD == LNK_COMPLETE) {
+        return d_yi > d_xi ? d_yi : d_xi;
+    } else if constexpr (METHOD == LNK_WEIGHTED) {
+        return 0.5 * (d_xi + d_yi);
+    } else {
+        static_assert(METHOD == LNK_WARD, "nn_chain methods: average, complete, weighted, ward");
+        const double t = 1.0 / double(na + nb + ni);
+        return sqrt(double(ni + na) * t * d_xi * d_xi + double(ni + nb) * t * d_yi * d_yi - double(ni) * t * d_xy * d_xy);
+    }
 }
 
 // scratch of the loop (global): size[n], chain[n], act[2][n] (the active list and its next compaction)
 // records (global, copied out): rec_h[n - 1], rec_pair[2 (n - 1)], rec_size[n - 1]
+template <int METHOD>
 __global__ __launch_bounds__(LNK_THREADS) void linkage_nn_chain_kernel(
     double *__restrict__ D, uint32_t n, uint32_t *__restrict__ size, uint32_t *__restrict__ chain,
     uint32_t *act_a, uint32_t *act_b, double *__restrict__ rec_h,  // (act_a / act_b swap roles every merge)
@@ -87,7 +163,7 @@ __global__ __launch_bounds__(LNK_THREADS) void linkage_nn_chain_kernel(
     __shared__ uint32_t s_i[2][LNK_WAVES];
     __shared__ uint32_t s_pos;            // position of the merged-away cluster in the active list
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (status[0] != LNK_OK) return;  // (the prepare pass found a non-finite entry)
+    if (status[0] != LNK_OK) return;  // (the prepare pass found a non-finite entry, or a negative one for ward)
     for (uint32_t i = tid; i < n; i += LNK_THREADS) {
         size[i] = 1;
         act_a[i] = i;
@@ -182,7 +258,7 @@ __global__ __launch_bounds__(LNK_THREADS) void linkage_nn_chain_kernel(
         const double *ra = D + size_t(a) * n;
         double *rb = D + size_t(b) * n;
         for (uint32_t t0 = tid; t0 < m; t0 += LNK_UNROLL * LNK_THREADS) {
-            uint32_t ii[LNK_UNROLL];
+            uint32_t ii[LNK_UNROLL], ni[LNK_UNROLL] = {};
             double va[LNK_UNROLL], vb[LNK_UNROLL];
 #pragma unroll
             for (int u = 0; u < LNK_UNROLL; u++) {
@@ -195,16 +271,17 @@ __global__ __launch_bounds__(LNK_THREADS) void linkage_nn_chain_kernel(
             for (int u = 0; u < LNK_UNROLL; u++) {
                 va[u] = ii[u] != LNK_NONE ? ra[ii[u]] : 0.0;
                 vb[u] = ii[u] != LNK_NONE ? rb[ii[u]] : 0.0;
+                if constexpr (METHOD == LNK_WARD) ni[u] = ii[u] != LNK_NONE ? size[ii[u]] : 0u;
             }
 #pragma unroll
             for (int u = 0; u < LNK_UNROLL; u++)
                 if (ii[u] != LNK_NONE) {
-                    const double d = (dna * va[u] + dnb * vb[u]) / dn;
+                    const double d = lnk_merged<METHOD>(va[u], vb[u], cur, na, nb, ni[u], dna, dnb, dn);
                     rb[ii[u]] = d;
                     D[size_t(ii[u]) * n + b] = d;
                 }
         }
-        __syncthreads();  // (s_pos; every thread has read size[a], size[b])
+        __syncthreads();  // (s_pos; every thread has read size[a], size[b] and, for ward, size[i])
         const uint32_t p = s_pos;
         if (tid == 0) {
             rec_pair[2 * k] = a;
@@ -227,6 +304,82 @@ __global__ __launch_bounds__(LNK_THREADS) void linkage_nn_chain_kernel(
     }
 }
 
+// scipy's mst_single_linkage: from x = 0, each of the n - 1 steps marks x merged, lowers dm[i] to D[x][i] where that is
+// smaller (strict >), takes the argmin of dm over the unmerged points (strict <, ascending: the lowest index wins a
+// tie), records (x, y, dm[y]) and goes on from x = y.  Scratch (global): dm[n], act[2][n].  act holds the unmerged
+// points in ascending order with x among them, at position p; the pass that reads them writes the list without x into
+// act_next, and the argmin's key (index << 32 | position in act_next) hands y and its position to the next step.
+// One barrier per step (the argmin's); D is only read.
+__global__ __launch_bounds__(LNK_THREADS) void linkage_mst_single_kernel(
+    const double *__restrict__ D, uint32_t n, double *__restrict__ dm, uint32_t *act_a, uint32_t *act_b,
+    double *__restrict__ rec_h, uint32_t *__restrict__ rec_pair, uint32_t *__restrict__ status) {
+    __shared__ double s_v[2][LNK_WAVES];
+    __shared__ uint64_t s_k[2][LNK_WAVES];
+    const uint32_t tid = threadIdx.x;
+    if (status[0] != LNK_OK) return;  // (the prepare pass found a non-finite entry)
+    for (uint32_t i = tid; i < n; i += LNK_THREADS) {
+        dm[i] = __builtin_inf();
+        act_a[i] = i;
+    }
+    __syncthreads();
+    uint32_t *act = act_a, *act_next = act_b;
+    uint32_t m = n;            // points in act, x included (every value below is uniform over the workgroup)
+    uint32_t x = 0, p = 0, ph = 0;
+    for (uint32_t k = 0; k + 1 < n; k++) {
+        const double *row = D + size_t(x) * n;
+        double bv = __builtin_inf();
+        uint64_t bk = ~uint64_t(0);
+        for (uint32_t t0 = tid; t0 < m; t0 += LNK_UNROLL * LNK_THREADS) {
+            uint32_t ii[LNK_UNROLL];
+            double dv[LNK_UNROLL], mv[LNK_UNROLL];
+#pragma unroll
+            for (int u = 0; u < LNK_UNROLL; u++) {
+                const uint32_t t = t0 + u * LNK_THREADS;
+                ii[u] = t < m ? act[t] : LNK_NONE;
+                if (t == p) ii[u] = LNK_NONE;
+                if (ii[u] != LNK_NONE) act_next[t - (t > p ? 1u : 0u)] = ii[u];
+            }
+#pragma unroll
+            for (int u = 0; u < LNK_UNROLL; u++) {
+                dv[u] = ii[u] != LNK_NONE ? row[ii[u]] : 0.0;
+                mv[u] = ii[u] != LNK_NONE ? dm[ii[u]] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < LNK_UNROLL; u++)
+                if (ii[u] != LNK_NONE) {
+                    if (mv[u] > dv[u]) {
+                        mv[u] = dv[u];
+                        dm[ii[u]] = dv[u];
+                    }
+                    const uint32_t t = t0 + u * LNK_THREADS;
+                    const uint64_t key = uint64_t(ii[u]) << 32 | (t - (t > p ? 1u : 0u));
+                    if (lnk_better(mv[u], key, bv, bk)) {
+                        bv = mv[u];
+                        bk = key;
+                    }
+                }
+        }
+        lnk_block_argmin(bv, bk, s_v, s_k, ph);  // (also orders this step's act_next / dm writes before the next step)
+        ph ^= 1u;
+        const uint32_t y = uint32_t(bk >> 32);
+        if (y >= n) {  // (cannot happen: an unmerged point is left and every dm is finite)
+            if (tid == 0) status[0] = LNK_NO_CONVERGE;
+            return;
+        }
+        if (tid == 0) {
+            rec_pair[2 * k] = x;
+            rec_pair[2 * k + 1] = y;
+            rec_h[k] = bv;
+        }
+        uint32_t *sw = act;
+        act = act_next;
+        act_next = sw;
+        m--;
+        x = y;
+        p = uint32_t(bk);
+    }
+}
+
 struct PooledBuf {  // a block of the context's cache, handed back on scope exit
     dvs_ctx *ctx;
     void *p = nullptr;
@@ -235,9 +388,9 @@ struct PooledBuf {  // a block of the context's cache, handed back on scope exit
     T *as() { return static_cast<T *>(p); }
 };
 
-// byte offsets of the scratch block: what is copied back first, then what stays on the device
+// byte offsets of the scratch block: what is copied back first, then what stays on the device (dm: single linkage's)
 struct LnkLayout {
-    size_t status, rec_h, rec_pair, rec_size, out_bytes, size, chain, act_a, act_b, bytes;
+    size_t status, rec_h, rec_pair, rec_size, out_bytes, size, chain, act_a, act_b, dm, bytes;
     explicit LnkLayout(uint32_t n) {
         auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
         const size_t m1 = size_t(n) - 1;
@@ -250,9 +403,43 @@ struct LnkLayout {
         chain = size + size_t(n) * 4;
         act_a = chain + size_t(n) * 4;
         act_b = act_a + size_t(n) * 4;
-        bytes = act_b + size_t(n) * 4;
+        dm = up8(act_b + size_t(n) * 4);
+        bytes = dm + size_t(n) * 8;
     }
 };
+
+const char *lnk_name(int method) {
+    switch (method) {
+        case LNK_SINGLE: return "single";
+        case LNK_COMPLETE: return "complete";
+        case LNK_AVERAGE: return "average";
+        case LNK_WARD: return "ward";
+        case LNK_WEIGHTED: return "weighted";
+        default: return "unknown";
+    }
+}
+
+// the chain kernel of one nn_chain method, or single linkage's loop, enqueued behind the prepare pass
+hipError_t lnk_launch_tree(dvs_ctx *ctx, int method, double *d_dist, uint32_t n, char *base, const LnkLayout &L) {
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
+    auto f64 = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+    auto chain = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(LNK_THREADS), 0, ctx->stream, d_dist, n, u32(L.size), u32(L.chain),
+                           u32(L.act_a), u32(L.act_b), f64(L.rec_h), u32(L.rec_pair), u32(L.rec_size), u32(L.status));
+    };
+    switch (method) {
+        case LNK_SINGLE:
+            hipLaunchKernelGGL(linkage_mst_single_kernel, dim3(1), dim3(LNK_THREADS), 0, ctx->stream, d_dist, n, f64(L.dm),
+                               u32(L.act_a), u32(L.act_b), f64(L.rec_h), u32(L.rec_pair), u32(L.status));
+            break;
+        case LNK_COMPLETE: chain(linkage_nn_chain_kernel<LNK_COMPLETE>); break;
+        case LNK_AVERAGE: chain(linkage_nn_chain_kernel<LNK_AVERAGE>); break;
+        case LNK_WARD: chain(linkage_nn_chain_kernel<LNK_WARD>); break;
+        case LNK_WEIGHTED: chain(linkage_nn_chain_kernel<LNK_WEIGHTED>); break;
+        default: return hipErrorInvalidValue;  // (the entries check the method first)
+    }
+    return hipGetLastError();
+}
 
 // scipy's label(): the records in height order (stable), union-find roots as cluster ids n, n + 1, ...,
 // the smaller root first, the size from the union
@@ -305,56 +492,72 @@ static int linkage_fits(dvs_ctx *ctx, uint32_t n, bool need_matrix) {
 
 int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n) { return linkage_fits(ctx, n, true); }
 
-// The tree of the n x n matrix at d_dist (a working buffer: overwritten).  Everything is enqueued on the context's
-// stream behind whatever wrote the matrix; d_zerodiv (may be NULL): a device word a distance kernel in front set
-// where the reference divides by zero, reported first.  Returns when the host outputs are written.
-int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *pairs,
+int dvs_linkage_check_method(dvs_ctx *ctx, int method) {
+    if (method == LNK_CENTROID || method == LNK_MEDIAN)
+        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
+                             "%s linkage is scipy's fast_linkage, not built on the device (single, complete, average, "
+                             "weighted, ward)", method == LNK_CENTROID ? "centroid" : "median");
+    if (method != LNK_SINGLE && method != LNK_COMPLETE && method != LNK_AVERAGE && method != LNK_WARD &&
+        method != LNK_WEIGHTED)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "unknown linkage method %d", method);
+    return DVS_OK;
+}
+
+// The tree of the n x n matrix at d_dist (a working buffer: overwritten; single linkage only reads it once it is
+// mirrored).  Everything is enqueued on the context's stream behind whatever wrote the matrix; d_zerodiv (may be
+// NULL): a device word a distance kernel in front set where the reference divides by zero, reported first.  Returns
+// when the host outputs are written.
+int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
                        double *heights, uint32_t *sizes) {
-    int rc = linkage_fits(ctx, n, false);
+    int rc = dvs_linkage_check_method(ctx, method);
+    if (!rc) rc = linkage_fits(ctx, n, false);
     if (rc) return rc;
     const LnkLayout L(n);
     PooledBuf scratch{ctx};
     rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "linkage scratch");
     if (rc) return rc;
     char *base = scratch.as<char>();
-    auto at = [&](size_t off) { return reinterpret_cast<void *>(base + off); };
-    uint32_t *d_status = static_cast<uint32_t *>(at(L.status));
+    uint32_t *d_status = reinterpret_cast<uint32_t *>(base + L.status);
     std::vector<uint64_t> host((L.out_bytes + 7) / 8);
     const uint32_t tiles = (n + LNK_TILE - 1) / LNK_TILE;
+    const char *what = lnk_name(method);
     hipError_t e = hipMemsetAsync(d_status, 0, 16, ctx->stream);
     if (e == hipSuccess && d_zerodiv)
         e = hipMemcpyAsync(d_status + 1, d_zerodiv, 4, hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(linkage_prepare_kernel, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n, d_status);
+        if (method == LNK_WARD)
+            hipLaunchKernelGGL(linkage_prepare_kernel<true>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n,
+                               d_status);
+        else
+            hipLaunchKernelGGL(linkage_prepare_kernel<false>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n,
+                               d_status);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(linkage_nn_chain_kernel, dim3(1), dim3(LNK_THREADS), 0, ctx->stream, d_dist, n,
-                           static_cast<uint32_t *>(at(L.size)), static_cast<uint32_t *>(at(L.chain)),
-                           static_cast<uint32_t *>(at(L.act_a)), static_cast<uint32_t *>(at(L.act_b)),
-                           static_cast<double *>(at(L.rec_h)), static_cast<uint32_t *>(at(L.rec_pair)),
-                           static_cast<uint32_t *>(at(L.rec_size)), d_status);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = lnk_launch_tree(ctx, method, d_dist, n, base, L);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), base, L.out_bytes, hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "average linkage");
-    if (se != hipSuccess) return dvs_hip_fail(ctx, se, "average linkage");
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, what);
+    if (se != hipSuccess) return dvs_hip_fail(ctx, se, what);
     const char *hb = reinterpret_cast<const char *>(host.data());
     const uint32_t *st = reinterpret_cast<const uint32_t *>(hb + L.status);
     if (st[1]) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // 0 / 0, distance.py:283
-    if (st[0] == LNK_NONFINITE)
+    if (st[0] & LNK_NONFINITE)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "Input contains NaN or infinity: the %u x %u distance matrix", n, n);
+    if (st[0] & LNK_NEGATIVE)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "ward linkage needs non-negative distances: the %u x %u distance matrix "
+                             "has a negative entry above its diagonal", n, n);
     if (st[0] != LNK_OK)
-        return dvs_set_error(ctx, DVS_ERR_RUNTIME, "average linkage: the chain did not close within 3 (n - 1) steps");
+        return dvs_set_error(ctx, DVS_ERR_RUNTIME, "%s linkage: the loop did not finish within its bound of steps", what);
     linkage_relabel(n, reinterpret_cast<const double *>(hb + L.rec_h), reinterpret_cast<const uint32_t *>(hb + L.rec_pair),
                     pairs, heights, sizes);
     return DVS_OK;
 }
 
-extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
-                                   double *heights, uint32_t *sizes) {
+extern "C" int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
+                           double *heights, uint32_t *sizes) {
     if (!ctx || !dist || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    int rc = dvs_linkage_check_method(ctx, method);
+    if (rc) return rc;
     if (n < 2)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "Found array with %u sample(s) while a minimum of 2 is required", n);
     DVS_HIP(ctx, hipSetDevice(ctx->device));
@@ -368,9 +571,9 @@ extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_devic
         if (attr.device != ctx->device)
             return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
                                  attr.device, ctx->device);
-        return dvs_linkage_device(ctx, dist, n, nullptr, pairs, heights, sizes);
+        return dvs_linkage_device(ctx, dist, n, nullptr, method, pairs, heights, sizes);
     }
-    int rc = linkage_fits(ctx, n, true);
+    rc = linkage_fits(ctx, n, true);
     if (rc) return rc;
     PooledBuf d_dist{ctx};
     rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix");
@@ -380,5 +583,10 @@ extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_devic
         (void)hipStreamSynchronize(ctx->stream);
         return dvs_hip_fail(ctx, e, "distance matrix upload");
     }
-    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, pairs, heights, sizes);
+    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, method, pairs, heights, sizes);
+}
+
+extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
+                                   double *heights, uint32_t *sizes) {
+    return dvs_linkage(ctx, dist, dist_on_device, n, LNK_AVERAGE, pairs, heights, sizes);
 }

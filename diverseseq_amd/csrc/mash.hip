@@ -1248,7 +1248,7 @@ extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double
 }
 
 // ---- ctree end to end on the device (diverse_seq/cluster.py:164-188, 216-233): the N x N matrix is written into the
-// context's scratch and read there by the average-linkage tree (linkage.hip); it never crosses PCIe.  The diagonal,
+// context's scratch and read there by the linkage tree (linkage.hip); it never crosses PCIe.  The diagonal,
 // which neither distance kernel writes, is zeroed (the tree checks every entry, as sklearn does).
 static int tree_matrix_alloc(dvs_ctx *ctx, uint32_t n, PooledBuf *d_dist) {
     int rc = dvs_linkage_check_size(ctx, n);
@@ -1258,9 +1258,10 @@ static int tree_matrix_alloc(dvs_ctx *ctx, uint32_t n, PooledBuf *d_dist) {
     return DVS_OK;
 }
 
-extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
-                                            uint32_t *pairs, double *heights, uint32_t *sizes) {
+extern "C" int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, int method,
+                                    uint32_t *pairs, double *heights, uint32_t *sizes) {
     if (!ctx || !sk || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (int rc = dvs_linkage_check_method(ctx, method)) return rc;
     const uint32_t n = sk->nseq;
     if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
     if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
@@ -1282,12 +1283,18 @@ extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk
         (void)hipStreamSynchronize(ctx->stream);
         return dvs_hip_fail(ctx, e, "mash distances");
     }
-    return dvs_linkage_device(ctx, d_dist.as<double>(), n, d_flag.as<uint32_t>(), pairs, heights, sizes);
+    return dvs_linkage_device(ctx, d_dist.as<double>(), n, d_flag.as<uint32_t>(), method, pairs, heights, sizes);
 }
 
-extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
-                                                    uint32_t *sizes) {
+extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
+                                            uint32_t *pairs, double *heights, uint32_t *sizes) {
+    return dvs_sketches_linkage(ctx, sk, k, sketch_size, 2, pairs, heights, sizes);  // (scipy's code of "average")
+}
+
+extern "C" int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs,
+                                            double *heights, uint32_t *sizes) {
     if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (int rc = dvs_linkage_check_method(ctx, method)) return rc;
     const uint32_t n = m->nrows;
     if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
     if ((n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64) > 65535u)
@@ -1301,5 +1308,10 @@ extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matr
         (void)hipStreamSynchronize(ctx->stream);
         return dvs_hip_fail(ctx, e, "euclidean distances");
     }
-    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, pairs, heights, sizes);
+    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, method, pairs, heights, sizes);
+}
+
+extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
+                                                    uint32_t *sizes) {
+    return dvs_matrix_euclidean_linkage(ctx, m, 2, pairs, heights, sizes);  // (scipy's code of "average")
 }

@@ -2,7 +2,7 @@
 (mash_sketches :178-227, mash_distances :119-175, mash_distance :230-291,
 euclidean_distances :294-332) and the strided chunks of
 diverse_seq/cluster.py:607-644, with the arithmetic in libdvs_hip.so; and the fused ctree stages
-(distances and the average-linkage tree with the N x N matrix left in HBM)."""
+(distances and the linkage tree with the N x N matrix left in HBM)."""
 
 from __future__ import annotations
 
@@ -15,15 +15,30 @@ from . import _lib, engine
 _U32_MAX = 0xFFFFFFFF
 
 
+# scipy's _LINKAGE_METHODS codes of the methods the device builds (include/dvs_hip.h DVS_LINKAGE_*)
+LINKAGE_METHODS = {"single": 0, "complete": 1, "average": 2, "weighted": 6, "ward": 5}
+
+
+def linkage_method_code(method) -> int:
+    """a linkage method's name -> its code; ValueError for centroid and median (scipy's fast_linkage, not built on
+    the device) and for any other name"""
+    if method in ("centroid", "median"):
+        raise ValueError(f"{method!r} linkage is not built on the device (scipy builds it by fast_linkage); "
+                         f"supported: {', '.join(LINKAGE_METHODS)}")
+    if not isinstance(method, str) or method not in LINKAGE_METHODS:
+        raise ValueError(f"Unexpected linkage method {method!r}: one of {', '.join(LINKAGE_METHODS)}")
+    return LINKAGE_METHODS[method]
+
+
 def tree_outputs(n: int):
-    """host buffers of the dvs_*average_linkage calls for n leaves: pairs uint32 [2 (n - 1)], heights f64 [n - 1],
+    """host buffers of the dvs_*linkage calls for n leaves: pairs uint32 [2 (n - 1)], heights f64 [n - 1],
     sizes uint32 [n - 1]"""
     return (np.zeros(2 * (n - 1), dtype=np.uint32), np.zeros(n - 1, dtype=np.float64),
             np.zeros(n - 1, dtype=np.uint32))
 
 
 def linkage_matrix(pairs: np.ndarray, heights: np.ndarray, sizes: np.ndarray) -> np.ndarray:
-    """the outputs of a dvs_*average_linkage call -> scipy's linkage matrix Z, float64 [n - 1, 4]"""
+    """the outputs of a dvs_*linkage call -> scipy's linkage matrix Z, float64 [n - 1, 4]"""
     z = np.empty((heights.size, 4), dtype=np.float64)
     z[:, 0] = pairs[0::2]
     z[:, 1] = pairs[1::2]
@@ -182,16 +197,21 @@ class Sketches:
                                                                  row_start, row_stride, int(symmetric), C.c_void_p(dist_ptr),
                                                                  C.c_void_p(zerodiv_ptr)))
 
-    def average_linkage(self) -> np.ndarray:
-        """scipy's average-linkage matrix Z over the mash distances of every pair (`dvs ctree`'s tree): the N x N
-        matrix is written and read in HBM (dvs_sketches_average_linkage); ZeroDivisionError as `distances`"""
+    def linkage(self, method: str = "average") -> np.ndarray:
+        """scipy's linkage matrix Z of `method` (LINKAGE_METHODS) over the mash distances of every pair: the N x N
+        matrix is written and read in HBM (dvs_sketches_linkage); ZeroDivisionError as `distances`"""
+        code = linkage_method_code(method)
         if self.n < 2:
             raise ValueError("need at least two sequences to build a tree")
         pairs, heights, sizes = tree_outputs(self.n)
-        self.ctx.check(self.ctx._L.dvs_sketches_average_linkage(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX),
-                                                                _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
-                                                                _lib.ptr(sizes, C.c_uint32)))
+        self.ctx.check(self.ctx._L.dvs_sketches_linkage(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX), code,
+                                                        _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                                        _lib.ptr(sizes, C.c_uint32)))
         return linkage_matrix(pairs, heights, sizes)
+
+    def average_linkage(self) -> np.ndarray:
+        """`linkage("average")`: `dvs ctree`'s tree"""
+        return self.linkage("average")
 
     def distances(self, *, row_start: int = 0, row_stride: int = 1, symmetric: bool = True,
                   out: np.ndarray | None = None) -> np.ndarray:
@@ -228,27 +248,41 @@ def euclidean_distances(seqs, k: int, num_states: int = 4,
         m.close()
 
 
-def mash_average_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False,
-                         ctx: engine.Context | None = None) -> np.ndarray:
-    """`dvs ctree`'s mash tree on the device: sketches, the N x N distances and the average-linkage Z, every stage in
-    HBM; only Z (n - 1 rows) comes back"""
+def mash_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
+                 method: str = "average", ctx: engine.Context | None = None) -> np.ndarray:
+    """`dvs ctree`'s mash tree on the device for any of LINKAGE_METHODS: sketches, the N x N distances and scipy's
+    linkage matrix Z of `method`, every stage in HBM; only Z (n - 1 rows) comes back"""
+    linkage_method_code(method)
     sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
     try:
-        return sk.average_linkage()
+        return sk.linkage(method)
     finally:
         sk.close()
 
 
-def euclidean_average_linkage(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+def euclidean_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
+                      ctx: engine.Context | None = None) -> np.ndarray:
     """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    code = linkage_method_code(method)
     ctx = ctx or engine.default_context()
     m = ctx.build_matrix(seqs, k, num_states)
     try:
         if m.nrows < 2:
             raise ValueError("need at least two sequences to build a tree")
         pairs, heights, sizes = tree_outputs(m.nrows)
-        ctx.check(ctx._L.dvs_matrix_euclidean_average_linkage(ctx._h, m._h, _lib.ptr(pairs, C.c_uint32),
-                                                              _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
+        ctx.check(ctx._L.dvs_matrix_euclidean_linkage(ctx._h, m._h, code, _lib.ptr(pairs, C.c_uint32),
+                                                      _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
         return linkage_matrix(pairs, heights, sizes)
     finally:
         m.close()
+
+
+def mash_average_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False,
+                         ctx: engine.Context | None = None) -> np.ndarray:
+    """`dvs ctree`'s average-linkage mash tree: mash_linkage(..., method="average")"""
+    return mash_linkage(seqs, k, sketch_size, num_states, mash_canonical, method="average", ctx=ctx)
+
+
+def euclidean_average_linkage(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+    """euclidean_linkage(..., method="average")"""
+    return euclidean_linkage(seqs, k, num_states, method="average", ctx=ctx)

@@ -391,6 +391,31 @@ int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t 
 int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
                                          uint32_t *sizes);
 
+/* ---- linkage trees of the other methods ------------------------------------------------------- *
+ * dvs_linkage is scipy.cluster.hierarchy.linkage(X[triu_indices(n, 1)], method) on the device: the same
+ * linkage matrix bit for bit, the same outputs and the same host / device matrix handling as
+ * dvs_average_linkage above.  `method` is scipy's _LINKAGE_METHODS code:
+ *   DVS_LINKAGE_SINGLE    restates scipy's _hierarchy.mst_single_linkage (Prim's minimum spanning tree)
+ *   DVS_LINKAGE_COMPLETE, DVS_LINKAGE_AVERAGE, DVS_LINKAGE_WEIGHTED, DVS_LINKAGE_WARD
+ *                         restate scipy's _hierarchy.nn_chain (nearest-neighbour chain) with the updates
+ *                         of _hierarchy_distance_update.pxi
+ * and both end in scipy's stable sort by height and `label` relabelling.  DVS_ERR_UNSUPPORTED: 3 (centroid)
+ * and 4 (median), which scipy builds by _hierarchy.fast_linkage (not built here); DVS_ERR_VALUE: any other
+ * code, the errors of dvs_average_linkage, and, for ward, a negative entry above the diagonal (scipy's
+ * heights would be NaN).  dvs_linkage(..., DVS_LINKAGE_AVERAGE, ...) is dvs_average_linkage. */
+#define DVS_LINKAGE_SINGLE 0
+#define DVS_LINKAGE_COMPLETE 1
+#define DVS_LINKAGE_AVERAGE 2
+#define DVS_LINKAGE_WARD 5
+#define DVS_LINKAGE_WEIGHTED 6
+int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
+                double *heights, uint32_t *sizes);
+/* the fused ctree entries above for any of those methods: the N x N mash / euclidean matrix stays in HBM */
+int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, int method,
+                         uint32_t *pairs, double *heights, uint32_t *sizes);
+int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
+                                 uint32_t *sizes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,13 +1,16 @@
-"""Time the tree stage of `dvs ctree`: for N in 1 000, 4 000, 10 000 one JSON line with
-  device_host_ms    cluster.average_linkage of a host float64 N x N matrix (upload + check/mirror + chain + relabel)
+"""Time the tree stage of `dvs ctree`: for N in 1 000, 4 000, 10 000 and every linkage method of
+--methods one JSON line with
+  device_host_ms    cluster.linkage of a host float64 N x N matrix (upload + check/mirror + tree loop + relabel)
   device_tensor_ms  the same matrix already in HBM (a torch tensor, the working buffer: no upload)
-  fused_mash_ms     distance.mash_average_linkage: sketches -> N x N mash distances -> tree, all in HBM
+  fused_mash_ms     distance.mash_linkage: sketches -> N x N mash distances -> tree, all in HBM
                     (N families of 5 kb sequences, k = 12, s = 3 000)
-  sklearn_fit_ms    AgglomerativeClustering(metric="precomputed", linkage="average").fit on the same host matrix
+  scipy_ms          scipy.cluster.hierarchy.linkage(condensed, method) on the host (one run)
+  sklearn_fit_ms    average only: AgglomerativeClustering(metric="precomputed", linkage="average").fit on the same
+                    host matrix
 and whether the device Z equals scipy's (z_equal).  Wall clock around calls that end in a device synchronise;
 median of --reps runs after one warm-up of every shape.
 
-  python scripts/bench_tree.py [--sizes 1000,4000,10000] [--reps 3] [--out FILE]"""
+  python scripts/bench_tree.py [--sizes 1000,4000,10000] [--methods average] [--reps 3] [--out FILE]"""
 import argparse
 import json
 import os
@@ -45,6 +48,7 @@ def median_ms(fn, reps: int) -> float:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000,4000,10000")
+    ap.add_argument("--methods", default="average", help="comma-separated: single,complete,average,weighted,ward")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sklearn-reps", type=int, default=1)
     ap.add_argument("--out", default=None)
@@ -56,39 +60,52 @@ def main():
 
     from diverseseq_amd import cluster, distance, engine
 
+    methods = args.methods.split(",")
+    for method in methods:
+        distance.linkage_method_code(method)
     ctx = engine.Context(0)
     info = ctx.device_info()
     warm = np.random.default_rng(0).random((300, 300))
-    cluster.average_linkage(warm, ctx=ctx)
-    distance.mash_average_linkage(family_seqs(64, 5000, 1), 12, 3000, ctx=ctx)
+    warm_seqs = family_seqs(64, 5000, 1)
+    for method in methods:
+        cluster.linkage(warm, method, ctx=ctx)
+        distance.mash_linkage(warm_seqs, 12, 3000, method=method, ctx=ctx)
     lines = []
     for n in (int(v) for v in args.sizes.split(",")):
         d = np.random.default_rng(n).random((n, n))
         d = np.triu(d, 1) + np.triu(d, 1).T
-        z = cluster.average_linkage(d, ctx=ctx)
-        z_equal = bool(np.array_equal(z, linkage(d[np.triu_indices(n, 1)], "average")))
-        host_ms = median_ms(lambda: cluster.average_linkage(d, ctx=ctx), args.reps)
-        dev = torch.from_numpy(d).to("cuda:0")
-        tensor_ts = []
-        for _ in range(args.reps):
-            t = dev.clone()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            cluster.average_linkage(t, ctx=ctx)
-            tensor_ts.append((time.perf_counter() - t0) * 1e3)
-            del t
-        del dev
+        y = d[np.triu_indices(n, 1)]
         seqs = family_seqs(n, 5000, n)
-        distance.mash_average_linkage(seqs, 12, 3000, ctx=ctx)
-        fused_ms = median_ms(lambda: distance.mash_average_linkage(seqs, 12, 3000, ctx=ctx), args.reps)
-        sk_ms = median_ms(lambda: AgglomerativeClustering(metric="precomputed", linkage="average").fit(d),
-                          args.sklearn_reps)
-        line = {"n": n, "device_host_ms": round(host_ms, 3), "device_tensor_ms": round(float(np.median(tensor_ts)), 3),
-                "fused_mash_ms": round(fused_ms, 3), "sklearn_fit_ms": round(sk_ms, 3), "z_equal": z_equal,
-                "reps": args.reps, "device": info["name"], "host_cpus": len(os.sched_getaffinity(0))}
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-        ctx.check(ctx._L.dvs_ctx_trim(ctx._h))
+        for method in methods:
+            z = cluster.linkage(d, method, ctx=ctx)
+            t0 = time.perf_counter()
+            z_ref = linkage(y, method)
+            scipy_ms = (time.perf_counter() - t0) * 1e3
+            z_equal = bool(np.array_equal(z, z_ref))
+            host_ms = median_ms(lambda: cluster.linkage(d, method, ctx=ctx), args.reps)
+            dev = torch.from_numpy(d).to("cuda:0")
+            tensor_ts = []
+            for _ in range(args.reps):
+                t = dev.clone()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                cluster.linkage(t, method, ctx=ctx)
+                tensor_ts.append((time.perf_counter() - t0) * 1e3)
+                del t
+            del dev
+            distance.mash_linkage(seqs, 12, 3000, method=method, ctx=ctx)
+            fused_ms = median_ms(lambda: distance.mash_linkage(seqs, 12, 3000, method=method, ctx=ctx), args.reps)
+            line = {"n": n, "method": method, "device_host_ms": round(host_ms, 3),
+                    "device_tensor_ms": round(float(np.median(tensor_ts)), 3), "fused_mash_ms": round(fused_ms, 3),
+                    "scipy_ms": round(scipy_ms, 3)}
+            if method == "average":
+                line["sklearn_fit_ms"] = round(median_ms(
+                    lambda: AgglomerativeClustering(metric="precomputed", linkage="average").fit(d), args.sklearn_reps), 3)
+            line.update({"z_equal": z_equal, "reps": args.reps, "device": info["name"],
+                         "host_cpus": len(os.sched_getaffinity(0))})
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            ctx.check(ctx._L.dvs_ctx_trim(ctx._h))
     if args.out:
         pathlib.Path(args.out).write_text("".join(json.dumps(x) + "\n" for x in lines))
 
