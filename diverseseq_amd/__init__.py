@@ -2,7 +2,7 @@
 
 ``diverseseq_amd._dvs`` is the drop-in for the reference's ``diverse_seq._dvs``
 extension module; ``diverseseq_amd.engine`` is the object layer over the C ABI
-(include/dvs_hip.h); ``diverseseq_amd.distance`` the mash / euclidean drivers.
+(include/dvs_hip.h); ``diverseseq_amd.distance`` the mash / euclidean / Jensen-Shannon drivers.
 """
 
 __version__ = "0.1.0"

@@ -45,6 +45,7 @@ EXPORTS = (
     "dvs_seqbatch_packed", "dvs_sketches_build_from_seqbatch",
     "dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage",
     "dvs_linkage", "dvs_sketches_linkage", "dvs_matrix_euclidean_linkage",
+    "dvs_jsd_distances", "dvs_matrix_jsd_linkage",
 )
 
 
@@ -215,6 +216,8 @@ def load() -> C.CDLL:
         L.dvs_linkage.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_int, u32p, f64p, u32p]
         L.dvs_sketches_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, u32p, f64p, u32p]
         L.dvs_matrix_euclidean_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
+        L.dvs_jsd_distances.argtypes = [vp, vp, f64p]
+        L.dvs_matrix_jsd_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -1,7 +1,10 @@
 """The reference's app surface over the HIP path: `dvs_nmost`, `dvs_max`, `dvs_delta_jsd`
 (diverse_seq/records.py:254-429) and `dvs_ctree` / `dvs_par_ctree` (diverse_seq/cluster.py:98-188,
 399-495), the five names its pyproject registers under the `cogent3.app` entry-point group
-(pyproject.toml:89-94; `pyproject.toml` here registers the same five).
+(pyproject.toml:89-94; `pyproject.toml` here registers the same five); and `dvs_dist`
+(diverse_seq/distance.py:21-116), the distance-matrix app the reference defines without registering it.
+`dvs_ctree`, `dvs_par_ctree` and `dvs_dist` also take distance_mode="jsd", the pairwise Jensen-Shannon
+divergence of k-mer frequencies (diverseseq_amd.distance.jsd_distances).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -17,6 +20,7 @@ import numpy as np
 
 from . import _dvs as dvs
 from . import cluster as _cluster
+from . import distance as _distance
 
 try:  # pragma: no cover - cogent3 is not in this image
     from cogent3.app.composable import define_app as _define_app
@@ -31,7 +35,7 @@ except Exception:  # noqa: BLE001
             return cls
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
-__all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree"]
+__all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -169,13 +173,13 @@ class _ClusterTreeBase:
                  show_progress: bool = False) -> None:
         if mash_canonical_kmers is None:
             mash_canonical_kmers = False
-        if distance_mode not in ("mash", "euclidean"):
+        if distance_mode not in ("mash", "euclidean", "jsd"):
             raise ValueError(f"Unexpected distance {distance_mode!r}.")
         if moltype not in ("dna", "rna") and mash_canonical_kmers:
             raise ValueError("Canonical kmers only supported for dna/rna sequences.")
         if distance_mode == "mash" and sketch_size is None:
             raise ValueError("Expected sketch size for mash distance measure.")
-        if distance_mode != "mash":  # (the sketch size means nothing to the euclidean mode: cli.py:546-560)
+        if distance_mode != "mash":  # (the sketch size means nothing to the euclidean and jsd modes: cli.py:546-560)
             sketch_size = None
         self._moltype = moltype
         self._k = k
@@ -222,3 +226,45 @@ class dvs_par_ctree(_ClusterTreeBase):
                          mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
         self._max_workers = max_workers
         self._parallel = parallel
+
+
+@_define_app
+class dvs_dist:
+    """Calculate pairwise kmer-based distances between sequences (diverse_seq/distance.py:21-116): the mash
+    distance, the euclidean distance between k-mer frequencies or, beyond the reference, their Jensen-Shannon
+    divergence ("jsd").  Returns cogent3's DistanceMatrix when cogent3 is importable, else (names, float64 [n, n])
+    with the names in input order."""
+
+    def __init__(self, distance_mode: str = "mash", *, k: int = 12, sketch_size: int | None = 3_000,
+                 moltype: str = "dna", mash_canonical_kmers: bool | None = None, show_progress: bool = False) -> None:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        if distance_mode not in ("mash", "euclidean", "jsd"):
+            raise ValueError(f"Unexpected distance {distance_mode!r}.")
+        if moltype not in ("dna", "rna") and mash_canonical_kmers:
+            raise ValueError("Canonical kmers only supported for dna sequences.")
+        if distance_mode == "mash" and sketch_size is None:
+            raise ValueError("Expected sketch size for mash distance measure.")
+        self._moltype = moltype
+        self._k = k
+        self._show_progress = show_progress
+        self._num_states = _num_states(moltype)
+        self._distance_mode = distance_mode
+        self._sketch_size = sketch_size
+        self._mash_canonical = mash_canonical_kmers
+
+    def main(self, seqs):
+        names, data, _ = _as_mapping(seqs, self._moltype)
+        arrays = [np.frombuffer(data[n], dtype=np.uint8) for n in names]
+        if self._distance_mode == "mash":
+            dists = _distance.mash_distances(arrays, self._k, int(self._sketch_size), self._num_states,
+                                             self._mash_canonical)
+        elif self._distance_mode == "jsd":
+            dists = _distance.jsd_distances(arrays, self._k, self._num_states)
+        else:
+            dists = _distance.euclidean_distances(arrays, self._k, self._num_states)
+        if HAVE_COGENT3:  # pragma: no cover
+            from cogent3.evolve.fast_distance import DistanceMatrix
+
+            return DistanceMatrix.from_array_names(matrix=dists, names=names)
+        return names, dists

@@ -112,18 +112,20 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
           mash_canonical_kmers: bool | None = None, num_states: int = 4, tree: str = "device",
           linkage: str = "average") -> str:
     """sequences {name: uint8 codes} -> Newick string (dvs_ctree.main, cluster.py:164-188).
-    Argument checks as dvs_ctree.__init__ (cluster.py:139-162).
+    Argument checks as dvs_ctree.__init__ (cluster.py:139-162).  distance_mode: the reference's "mash" and
+    "euclidean", and "jsd", the Jensen-Shannon divergence of the k-mer frequencies (`distance.jsd_distances`),
+    which takes the euclidean mode's arguments.
 
     tree="device": the distances and the tree both on the GPU, the N x N matrix never leaves HBM
-    (dvs_sketches_linkage / dvs_matrix_euclidean_linkage), the string from `linkage_to_newick`; `linkage`: any
-    method the module's `linkage` function builds.  tree="sklearn": the reference's path (the matrix copied to the host, sklearn, nested
+    (dvs_sketches_linkage / dvs_matrix_euclidean_linkage / dvs_matrix_jsd_linkage), the string from
+    `linkage_to_newick`; `linkage`: any method the module's `linkage` function builds.  tree="sklearn": the reference's path (the matrix copied to the host, sklearn, nested
     tuples; `make_cluster_tree`), average linkage only.  Both give the same string wherever the sklearn path
     returns one; the one intended difference is a tree deeper than Python's recursion limit (e.g. a caterpillar of
     a few thousand leaves), for which the device path returns the Newick string where the sklearn path raises
     RecursionError."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    if distance_mode not in ("mash", "euclidean"):
+    if distance_mode not in ("mash", "euclidean", "jsd"):
         raise ValueError(f"Unexpected distance {distance_mode!r}.")
     if distance_mode == "mash" and sketch_size is None:
         raise ValueError("Expected sketch size for mash distance measure.")
@@ -141,11 +143,15 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     if tree == "sklearn":
         if distance_mode == "mash":
             dists = distance.mash_distances(arrays, k, int(sketch_size), num_states, mash_canonical_kmers)
+        elif distance_mode == "jsd":
+            dists = distance.jsd_distances(arrays, k, num_states)
         else:
             dists = distance.euclidean_distances(arrays, k, num_states)
         return make_cluster_tree(names, dists)
     if distance_mode == "mash":
         z = distance.mash_linkage(arrays, k, int(sketch_size), num_states, mash_canonical_kmers, method=linkage)
+    elif distance_mode == "jsd":
+        z = distance.jsd_linkage(arrays, k, num_states, method=linkage)
     else:
         z = distance.euclidean_linkage(arrays, k, num_states, method=linkage)
     return linkage_to_newick(names, z)

@@ -1,7 +1,9 @@
 """Host side of the distance path: mirrors diverse_seq/distance.py's functions
 (mash_sketches :178-227, mash_distances :119-175, mash_distance :230-291,
 euclidean_distances :294-332) and the strided chunks of
-diverse_seq/cluster.py:607-644, with the arithmetic in libdvs_hip.so; and the fused ctree stages
+diverse_seq/cluster.py:607-644, with the arithmetic in libdvs_hip.so; the pairwise Jensen-Shannon
+divergence of k-mer frequencies (jsd_distances: total_jsd of a two-member set, src/records.rs:27-68);
+and the fused ctree stages
 (distances and the linkage tree with the N x N matrix left in HBM)."""
 
 from __future__ import annotations
@@ -248,6 +250,27 @@ def euclidean_distances(seqs, k: int, num_states: int = 4,
         m.close()
 
 
+def jsd_distances(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+    """the Jensen-Shannon divergence (bits, not its square root) of the k-mer frequencies of every pair,
+    H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2: total_jsd of the two-member set (src/records.rs:27-68; paper Table 1).
+    float64 [n, n], symmetric, in [0, 1], exactly 0 on the diagonal and between sequences of equal counts; NaN off
+    the diagonal for a sequence without a valid k-mer"""
+    ctx = ctx or engine.default_context()
+    m = ctx.build_matrix(seqs, k, num_states)
+    try:
+        return matrix_jsd_distances(m)
+    finally:
+        m.close()
+
+
+def matrix_jsd_distances(m: "engine.CountMatrix") -> np.ndarray:
+    """`jsd_distances` over the rows of a matrix already in HBM (count rows of either width, or the frequency rows
+    of Context.matrix_from_freqs)"""
+    dist = np.zeros((m.nrows, m.nrows), dtype=np.float64)
+    m.ctx.check(m.ctx._L.dvs_jsd_distances(m.ctx._h, m._h, _lib.ptr(dist, C.c_double)))
+    return dist
+
+
 def mash_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
                  method: str = "average", ctx: engine.Context | None = None) -> np.ndarray:
     """`dvs ctree`'s mash tree on the device for any of LINKAGE_METHODS: sketches, the N x N distances and scipy's
@@ -272,6 +295,24 @@ def euclidean_linkage(seqs, k: int, num_states: int = 4, *, method: str = "avera
         pairs, heights, sizes = tree_outputs(m.nrows)
         ctx.check(ctx._L.dvs_matrix_euclidean_linkage(ctx._h, m._h, code, _lib.ptr(pairs, C.c_uint32),
                                                       _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
+        return linkage_matrix(pairs, heights, sizes)
+    finally:
+        m.close()
+
+
+def jsd_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
+                ctx: engine.Context | None = None) -> np.ndarray:
+    """the same for the Jensen-Shannon divergences of `jsd_distances`, the same matrix bit for bit (a sequence
+    without valid k-mers: NaN distances, ValueError)"""
+    code = linkage_method_code(method)
+    ctx = ctx or engine.default_context()
+    m = ctx.build_matrix(seqs, k, num_states)
+    try:
+        if m.nrows < 2:
+            raise ValueError("need at least two sequences to build a tree")
+        pairs, heights, sizes = tree_outputs(m.nrows)
+        ctx.check(ctx._L.dvs_matrix_jsd_linkage(ctx._h, m._h, code, _lib.ptr(pairs, C.c_uint32),
+                                                _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
         return linkage_matrix(pairs, heights, sizes)
     finally:
         m.close()

@@ -416,6 +416,20 @@ int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint3
 int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
                                  uint32_t *sizes);
 
+/* ---- pairwise Jensen-Shannon divergence --------------------------------------------------------- *
+ * D[i][j] = H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2 over the rows of m, f = counts / total, H in bits: the
+ * total_jsd of the two-member set SummedRecords::new([i, j]) (src/records.rs:27-68), the measure of paper/paper.md
+ * Table 1 (identical sequences 0.0, no k-mer in common 1.0); the divergence, not its square root.  Full symmetric
+ * nrows x nrows float64 matrix, every cell in [0, 1], exactly 0 on the diagonal and between rows of equal
+ * counts; a row without a valid k-mer has NaN off the diagonal.  Arguments, limits and errors as
+ * dvs_euclidean_distances. */
+int dvs_jsd_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist);
+/* the fused ctree entry over those distances (src/records.rs:27-68 for the cells, then dvs_linkage's tree): the
+ * N x N matrix, the same bits as dvs_jsd_distances writes, stays in HBM; arguments and errors as
+ * dvs_matrix_euclidean_linkage (a row without a valid k-mer: NaN distances, DVS_ERR_VALUE) */
+int dvs_matrix_jsd_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
+                           uint32_t *sizes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,10 +7,15 @@
   scipy_ms          scipy.cluster.hierarchy.linkage(condensed, method) on the host (one run)
   sklearn_fit_ms    average only: AgglomerativeClustering(metric="precomputed", linkage="average").fit on the same
                     host matrix
+and, with --distance jsd|euclidean (uniform-random 5 kb sequences, k = --k), for that distance mode
+  <mode>_matrix_ms  the N x N distances of a count matrix already in HBM into a host array that exists (the pair
+                    kernel and the copy of the matrix to the host)
+  fused_<mode>_ms   distance.<mode>_linkage: sequences -> counts -> N x N distances -> tree, all in HBM
 and whether the device Z equals scipy's (z_equal).  Wall clock around calls that end in a device synchronise;
 median of --reps runs after one warm-up of every shape.
 
-  python scripts/bench_tree.py [--sizes 1000,4000,10000] [--methods average] [--reps 3] [--out FILE]"""
+  python scripts/bench_tree.py [--sizes 1000,4000,10000] [--methods average] [--distance jsd] [--k 6] [--reps 3]
+                               [--out FILE]"""
 import argparse
 import json
 import os
@@ -36,6 +41,11 @@ def family_seqs(n: int, length: int, seed: int) -> list:
     return out
 
 
+def uniform_seqs(n: int, length: int, seed: int) -> list:
+    rng = np.random.default_rng(seed)
+    return [rng.integers(0, 4, length, dtype=np.uint8) for _ in range(n)]
+
+
 def median_ms(fn, reps: int) -> float:
     ts = []
     for _ in range(reps):
@@ -51,8 +61,13 @@ def main():
     ap.add_argument("--methods", default="average", help="comma-separated: single,complete,average,weighted,ward")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sklearn-reps", type=int, default=1)
+    ap.add_argument("--distance", choices=["jsd", "euclidean"], default=None,
+                    help="also time this distance mode's matrix and its fused sequences -> distances -> tree path")
+    ap.add_argument("--k", type=int, default=6, help="k of the --distance columns")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+
+    import ctypes as C
 
     import torch
     from scipy.cluster.hierarchy import linkage
@@ -70,6 +85,11 @@ def main():
     for method in methods:
         cluster.linkage(warm, method, ctx=ctx)
         distance.mash_linkage(warm_seqs, 12, 3000, method=method, ctx=ctx)
+    if args.distance:
+        dist_entry = getattr(ctx._L, f"dvs_{args.distance}_distances")
+        dist_linkage = getattr(distance, f"{args.distance}_linkage")
+        for method in methods:
+            dist_linkage(uniform_seqs(64, 5000, 1), args.k, method=method, ctx=ctx)
     lines = []
     for n in (int(v) for v in args.sizes.split(",")):
         d = np.random.default_rng(n).random((n, n))
@@ -98,6 +118,19 @@ def main():
             line = {"n": n, "method": method, "device_host_ms": round(host_ms, 3),
                     "device_tensor_ms": round(float(np.median(tensor_ts)), 3), "fused_mash_ms": round(fused_ms, 3),
                     "scipy_ms": round(scipy_ms, 3)}
+            if args.distance:
+                useqs = uniform_seqs(n, 5000, n + 1)
+                m = ctx.build_matrix(useqs, args.k)
+                out = np.zeros((n, n))
+                run = lambda: ctx.check(dist_entry(ctx._h, m._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+                run()
+                line[f"{args.distance}_matrix_ms"] = round(median_ms(run, args.reps), 3)
+                m.close()
+                del out
+                dist_linkage(useqs, args.k, method=method, ctx=ctx)
+                line[f"fused_{args.distance}_ms"] = round(
+                    median_ms(lambda: dist_linkage(useqs, args.k, method=method, ctx=ctx), args.reps), 3)
+                line["k"] = args.k
             if method == "average":
                 line["sklearn_fit_ms"] = round(median_ms(
                     lambda: AgglomerativeClustering(metric="precomputed", linkage="average").fit(d), args.sklearn_reps), 3)
