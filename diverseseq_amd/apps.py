@@ -173,7 +173,7 @@ class _ClusterTreeBase:
                  show_progress: bool = False) -> None:
         if mash_canonical_kmers is None:
             mash_canonical_kmers = False
-        if distance_mode not in ("mash", "euclidean", "jsd"):
+        if distance_mode not in _distance.MODES:
             raise ValueError(f"Unexpected distance {distance_mode!r}.")
         if moltype not in ("dna", "rna") and mash_canonical_kmers:
             raise ValueError("Canonical kmers only supported for dna/rna sequences.")
@@ -239,7 +239,7 @@ class dvs_dist:
                  moltype: str = "dna", mash_canonical_kmers: bool | None = None, show_progress: bool = False) -> None:
         if mash_canonical_kmers is None:
             mash_canonical_kmers = False
-        if distance_mode not in ("mash", "euclidean", "jsd"):
+        if distance_mode not in _distance.MODES:
             raise ValueError(f"Unexpected distance {distance_mode!r}.")
         if moltype not in ("dna", "rna") and mash_canonical_kmers:
             raise ValueError("Canonical kmers only supported for dna sequences.")
@@ -256,13 +256,8 @@ class dvs_dist:
     def main(self, seqs):
         names, data, _ = _as_mapping(seqs, self._moltype)
         arrays = [np.frombuffer(data[n], dtype=np.uint8) for n in names]
-        if self._distance_mode == "mash":
-            dists = _distance.mash_distances(arrays, self._k, int(self._sketch_size), self._num_states,
-                                             self._mash_canonical)
-        elif self._distance_mode == "jsd":
-            dists = _distance.jsd_distances(arrays, self._k, self._num_states)
-        else:
-            dists = _distance.euclidean_distances(arrays, self._k, self._num_states)
+        dists = _distance.MODES[self._distance_mode][0](arrays, *_distance.mode_args(
+            self._distance_mode, self._k, self._sketch_size, self._num_states, self._mash_canonical))
         if HAVE_COGENT3:  # pragma: no cover
             from cogent3.evolve.fast_distance import DistanceMatrix
 

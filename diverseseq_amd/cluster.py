@@ -18,7 +18,7 @@ from collections.abc import Sequence
 
 import numpy as np
 
-from . import _lib, distance, engine
+from . import distance, engine
 
 
 def nested_tuple_tree(seq_names: Sequence[str], pairwise_distances: np.ndarray):
@@ -59,21 +59,15 @@ def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None)
             raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
         n = int(dist.shape[0])
         src, on_device = C.c_void_p(dist.data_ptr()), 1
+        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
     else:
         d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
         if d.ndim != 2 or d.shape[0] != d.shape[1]:
             raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
         n = d.shape[0]
         src, on_device = d.ctypes.data_as(C.c_void_p), 0
-    if n < 2:
-        raise ValueError(f"Found array with {n} sample(s) while a minimum of 2 is required")
-    ctx = ctx or engine.default_context()
-    if on_device:
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
-    pairs, heights, sizes = distance.tree_outputs(n)
-    ctx.check(ctx._L.dvs_linkage(ctx._h, src, on_device, n, code, _lib.ptr(pairs, C.c_uint32),
-                                 _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
-    return distance.linkage_matrix(pairs, heights, sizes)
+    return distance.run_linkage(ctx, n, "dvs_linkage", src, on_device, n, code,
+                                too_few=f"Found array with {n} sample(s) while a minimum of 2 is required")
 
 
 def average_linkage(dist, *, ctx: engine.Context | None = None) -> np.ndarray:
@@ -125,7 +119,7 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     RecursionError."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    if distance_mode not in ("mash", "euclidean", "jsd"):
+    if distance_mode not in distance.MODES:
         raise ValueError(f"Unexpected distance {distance_mode!r}.")
     if distance_mode == "mash" and sketch_size is None:
         raise ValueError("Expected sketch size for mash distance measure.")
@@ -140,18 +134,8 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
         raise ValueError(f"tree='sklearn' builds average linkage only, not {linkage!r}: use tree='device'")
     names = list(seqs)
     arrays = [seqs[n] for n in names]
+    distances, tree_of = distance.MODES[distance_mode]
+    args = distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)
     if tree == "sklearn":
-        if distance_mode == "mash":
-            dists = distance.mash_distances(arrays, k, int(sketch_size), num_states, mash_canonical_kmers)
-        elif distance_mode == "jsd":
-            dists = distance.jsd_distances(arrays, k, num_states)
-        else:
-            dists = distance.euclidean_distances(arrays, k, num_states)
-        return make_cluster_tree(names, dists)
-    if distance_mode == "mash":
-        z = distance.mash_linkage(arrays, k, int(sketch_size), num_states, mash_canonical_kmers, method=linkage)
-    elif distance_mode == "jsd":
-        z = distance.jsd_linkage(arrays, k, num_states, method=linkage)
-    else:
-        z = distance.euclidean_linkage(arrays, k, num_states, method=linkage)
-    return linkage_to_newick(names, z)
+        return make_cluster_tree(names, distances(arrays, *args))
+    return linkage_to_newick(names, tree_of(arrays, *args, method=linkage))

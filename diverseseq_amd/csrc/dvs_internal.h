@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -134,6 +135,15 @@ int dvs_matrix_settle(dvs_ctx *ctx, const dvs_matrix *m);
 int dvs_dev_alloc(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what);
 void dvs_dev_free(dvs_ctx *ctx, void *ptr);
 void dvs_dev_trim(dvs_ctx *ctx);
+// A block of that cache, handed back on scope exit.  dvs_dev_free gives the block to the next allocation at once:
+// the scope ends only after the stream work that uses the block has been waited for.
+struct PooledBuf {
+    dvs_ctx *ctx;
+    void *p = nullptr;
+    ~PooledBuf() { dvs_dev_free(ctx, p); }
+    template <typename T>
+    T *as() { return static_cast<T *>(p); }
+};
 int dvs_pinned_get(dvs_ctx *ctx, void **ptr);  // 4 KiB pinned block from the ctx cache
 void dvs_pinned_put(dvs_ctx *ctx, void *ptr);
 hipEvent_t dvs_event_get(dvs_ctx *ctx);
@@ -219,6 +229,20 @@ int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n);
 int dvs_linkage_check_method(dvs_ctx *ctx, int method);
 int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
                        double *heights, uint32_t *sizes);
+
+// One distance mode of ctree, as the drivers of rowdist.hip take it: "fill this device n x n f64 matrix" on the
+// context's stream, with what differs from mode to mode beside it.
+struct dvs_dist_stage {
+    const char *label;                // what a failed launch is reported as
+    uint32_t n;                       // rows and columns of the matrix
+    std::function<int()> check;       // the mode's own precondition: DVS_OK, or the error it set
+    size_t scratch_bytes;             // extra device scratch of the kernels (0: none) ...
+    const char *scratch_what;         // ... and its name in an allocation error
+    bool scratch_is_zerodiv;          // the scratch is a word the kernel sets where the reference divides by zero
+    bool zero_diagonal;               // the kernels do not write the diagonal: it is zeroed in front of them
+    std::function<hipError_t(double *d_dist, void *d_scratch)> enqueue;
+};
+dvs_dist_stage dvs_mash_stage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size);  // mash.hip
 
 // f(typed row pointer) for the matrix's element type
 template <typename F>

@@ -380,14 +380,6 @@ __global__ __launch_bounds__(LNK_THREADS) void linkage_mst_single_kernel(
     }
 }
 
-struct PooledBuf {  // a block of the context's cache, handed back on scope exit
-    dvs_ctx *ctx;
-    void *p = nullptr;
-    ~PooledBuf() { dvs_dev_free(ctx, p); }
-    template <typename T>
-    T *as() { return static_cast<T *>(p); }
-};
-
 // byte offsets of the scratch block: what is copied back first, then what stays on the device (dm: single linkage's)
 struct LnkLayout {
     size_t status, rec_h, rec_pair, rec_size, out_bytes, size, chain, act_a, act_b, dm, bytes;
@@ -588,5 +580,5 @@ extern "C" int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint3
 
 extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
                                    double *heights, uint32_t *sizes) {
-    return dvs_linkage(ctx, dist, dist_on_device, n, LNK_AVERAGE, pairs, heights, sizes);
+    return dvs_linkage(ctx, dist, dist_on_device, n, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
 }

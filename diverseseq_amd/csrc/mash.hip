@@ -1,4 +1,4 @@
-// MinHash bottom-s sketches and pairwise mash / euclidean distances.
+// MinHash bottom-s sketches and pairwise mash distances.
 //
 // Replaces, for batches:
 //   murmurhash3_32  src/distance.rs:21-49  (NOT standard murmur3: every BYTE is a
@@ -8,7 +8,7 @@
 //   mash_sketch     :151-182 (the sketch_size smallest DISTINCT hashes, ascending)
 //   mash_distance   diverse_seq/distance.py:230-291, N x N driver :165-173 and the
 //                   strided rows of diverse_seq/cluster.py:640-644
-//   euclidean_distance(s) diverse_seq/distance.py:294-336
+// (The distances between the rows of a count matrix, and ctree's distances-to-tree drivers: rowdist.hip.)
 //
 // Device pipeline per sequence:
 //   1. hash_filter_kernel: a tile of windows per workgroup, the tile's bytes staged
@@ -25,7 +25,6 @@
 #include "dvs_internal.h"
 
 #include <algorithm>
-#include <type_traits>
 #include <cmath>
 
 namespace {
@@ -620,44 +619,6 @@ __global__ __launch_bounds__(PAIR_THREADS) void mash_pairs_kernel(
     if (symmetric) dist[uint64_t(j) * nseq + i] = d;
 }
 
-// ||f_i - f_j||_2 (diverse_seq/distance.py:335-336), f = counts / total.  Workgroup (i, g) stages row
-// i's frequencies in LDS chunk by chunk and its eight waves take the rows j = 8 g .. 8 g + 7 below the
-// diagonal, one each: row i is read once per eight pairs, row j streamed by one wave with 16-byte loads
-// where the bin count allows.  Only the lower triangle does work; both mirror cells are written.
-constexpr int EUC_THREADS = 512;
-constexpr uint32_t EUC_CHUNK = 4096;  // bins of row i staged at a time (32 KB)
-template <typename T>
-__global__ __launch_bounds__(EUC_THREADS) void euclid_kernel(const T *__restrict__ mat,
-                                                            const uint32_t *__restrict__ totals, uint64_t B,
-                                                            uint32_t n, double *__restrict__ dist) {
-    __shared__ double fi[EUC_CHUNK];
-    const uint32_t i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.y * (EUC_THREADS / 64) + wave;
-    if (blockIdx.y * (EUC_THREADS / 64) >= i) return;  // the whole group is on or above the diagonal
-    const T *a = mat + uint64_t(i) * B;
-    const bool live = j < i;
-    const T *b = mat + uint64_t(live ? j : 0) * B;
-    const double ta = double(totals[i]), tb = double(totals[live ? j : 0]);
-    double acc = 0.0;
-    for (uint64_t c0 = 0; c0 < B; c0 += EUC_CHUNK) {
-        const uint32_t cn = uint32_t(B - c0 < EUC_CHUNK ? B - c0 : EUC_CHUNK);
-        __syncthreads();
-        for (uint32_t x = threadIdx.x; x < cn; x += EUC_THREADS) fi[x] = double(a[c0 + x]) / ta;
-        __syncthreads();
-        if (live)
-            for (uint32_t x = lane; x < cn; x += 64) {
-                const double d = fi[x] - double(b[c0 + x]) / tb;
-                acc += d * d;
-            }
-    }
-    acc = dvs_wave_sum(acc);
-    if (live && lane == 0) {
-        const double d = sqrt(acc);
-        dist[uint64_t(i) * n + j] = d;
-        dist[uint64_t(j) * n + i] = d;
-    }
-}
-
 // The tile list of a batch, written on the device: tile t belongs to the sequence q with tpre[q] <= t < tpre[q + 1]
 // (binary search by the tile's own thread); every tile but a sequence's first begins on a packed word -- an absolute
 // position that is a multiple of 16 -- and a full tile ends on one, so its windows are exactly 512 groups of sixteen.
@@ -684,14 +645,6 @@ __global__ __launch_bounds__(256) void mash_tiles_kernel(const uint64_t *__restr
     m.seq = lo;
     tiles[t] = m;
 }
-
-struct PooledBuf {  // a block of the context's cache, handed back on scope exit
-    dvs_ctx *ctx;
-    void *p = nullptr;
-    ~PooledBuf() { dvs_dev_free(ctx, p); }
-    template <typename T>
-    T *as() { return static_cast<T *>(p); }
-};
 
 }  // namespace
 
@@ -1072,40 +1025,42 @@ extern "C" int dvs_sketches_get(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t *
 extern "C" const void *dvs_sketches_dev(const dvs_sketches *sk) { return sk ? sk->d_sk : nullptr; }
 extern "C" const void *dvs_sketches_dev_lens(const dvs_sketches *sk) { return sk ? sk->d_lens : nullptr; }
 
+// mash_pairs_kernel over the rows row_start, row_start + row_stride, ... of the lower triangle, enqueued on the context's
+// stream: d_dist (nseq x nseq) receives the visited cells, *d_flag is set where a pair has two empty sketches
+static hipError_t mash_pairs_launch(dvs_ctx *ctx, const uint32_t *d_sk, const uint32_t *d_lens, uint32_t nseq,
+                                    uint32_t stride, uint32_t k, uint32_t sketch_size, uint32_t row_start,
+                                    uint32_t row_stride, int symmetric, double *d_dist, uint32_t *d_flag) {
+    const uint32_t nrows = (nseq - 1 - row_start) / row_stride + 1;
+    const dim3 grid(nrows, (nseq + PAIR_THREADS - 1) / PAIR_THREADS);
+    const uint32_t row_lds = std::min(stride, PAIR_ROW_LDS);  // (no sketch is longer than the stride)
+    hipLaunchKernelGGL(mash_pairs_kernel, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, d_sk, d_lens, nseq, k,
+                       sketch_size, stride, row_start, row_stride, symmetric, row_lds, d_dist, d_flag);
+    return hipGetLastError();
+}
+
 // the pair kernel over sketches in HBM; dist (host, nseq x nseq) receives the visited cells
 static int mash_pairs_device(dvs_ctx *ctx, const uint32_t *d_sk, const uint32_t *d_lens, uint32_t nseq, uint32_t stride,
                              uint32_t k, uint32_t sketch_size, uint32_t row_start, uint32_t row_stride, int symmetric,
                              double *dist) {
-    double *d_dist = nullptr;
-    uint32_t *d_flag = nullptr;
-    int rc = dvs_dev_alloc(ctx, (void **)&d_dist, size_t(nseq) * nseq * 8, "distance matrix");
-    if (!rc) rc = dvs_dev_alloc(ctx, (void **)&d_flag, 4, "flag");
-    if (rc) {
-        dvs_dev_free(ctx, d_dist);
-        return rc;
-    }
+    PooledBuf d_dist{ctx}, d_flag{ctx};
+    int rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(nseq) * nseq * 8, "distance matrix");
+    if (!rc) rc = dvs_dev_alloc(ctx, &d_flag.p, 4, "flag");
+    if (rc) return rc;
     // Cells this call does not visit keep the caller's values.  A call over the whole triangle that
     // mirrors its cells (the usual one) visits everything but the diagonal: only those nseq cells travel
     // up (one strided copy); any other call starts from a copy of the caller's matrix.
     const bool whole = row_start == 0 && row_stride == 1 && symmetric;
-    hipError_t e = whole ? hipMemcpy2DAsync(d_dist, (size_t(nseq) + 1) * 8, dist, (size_t(nseq) + 1) * 8, 8, nseq,
+    hipError_t e = whole ? hipMemcpy2DAsync(d_dist.p, (size_t(nseq) + 1) * 8, dist, (size_t(nseq) + 1) * 8, 8, nseq,
                                             hipMemcpyHostToDevice, ctx->stream)
-                         : hipMemcpyAsync(d_dist, dist, size_t(nseq) * nseq * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 4, ctx->stream);
-    const uint32_t nrows = (nseq - 1 - row_start) / row_stride + 1;
+                         : hipMemcpyAsync(d_dist.p, dist, size_t(nseq) * nseq * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag.p, 0, 4, ctx->stream);
     uint32_t flag = 0;
-    if (e == hipSuccess) {
-        const dim3 grid(nrows, (nseq + PAIR_THREADS - 1) / PAIR_THREADS);
-        const uint32_t row_lds = std::min(stride, PAIR_ROW_LDS);  // (no sketch is longer than the stride)
-        hipLaunchKernelGGL(mash_pairs_kernel, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, d_sk, d_lens, nseq, k,
-                           sketch_size, stride, row_start, row_stride, symmetric, row_lds, d_dist, d_flag);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(dist, d_dist, size_t(nseq) * nseq * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t se = hipStreamSynchronize(ctx->stream);
-    dvs_dev_free(ctx, d_dist);
-    dvs_dev_free(ctx, d_flag);
+    if (e == hipSuccess)
+        e = mash_pairs_launch(ctx, d_sk, d_lens, nseq, stride, k, sketch_size, row_start, row_stride, symmetric,
+                              d_dist.as<double>(), d_flag.as<uint32_t>());
+    if (e == hipSuccess) e = hipMemcpyAsync(dist, d_dist.p, size_t(nseq) * nseq * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);  // (the two blocks go back to the cache behind it)
     if (e != hipSuccess) return dvs_hip_fail(ctx, e, "mash distances");
     if (se != hipSuccess) return dvs_hip_fail(ctx, se, "mash distances");
     if (flag) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // 0 / 0, distance.py:283
@@ -1169,13 +1124,9 @@ extern "C" int dvs_sketches_distances_device(dvs_ctx *ctx, const dvs_sketches *s
     if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
     if (!sk->d_sk) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");
     DVS_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t nseq = sk->nseq;
-    const uint32_t nrows = (nseq - 1 - row_start) / row_stride + 1;
-    const dim3 grid(nrows, (nseq + PAIR_THREADS - 1) / PAIR_THREADS);
-    const uint32_t row_lds = std::min(sk->stride, PAIR_ROW_LDS);
-    hipLaunchKernelGGL(mash_pairs_kernel, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, sk->d_sk, sk->d_lens, nseq, k,
-                       sketch_size, sk->stride, row_start, row_stride, symmetric, row_lds, d_dist, d_zerodiv);
-    DVS_HIP(ctx, hipGetLastError());
+    const hipError_t e = mash_pairs_launch(ctx, sk->d_sk, sk->d_lens, sk->nseq, sk->stride, k, sketch_size, row_start,
+                                           row_stride, symmetric, d_dist, d_zerodiv);
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "hipGetLastError()");  // (what DVS_HIP names a launch check)
     return DVS_OK;
 }
 
@@ -1194,124 +1145,40 @@ extern "C" int dvs_mash_distances(dvs_ctx *ctx, const uint32_t *sketches, uint32
     if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
     DVS_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t s = std::max<uint32_t>(sketch_stride, 1);
-    uint32_t *d_sk = nullptr, *d_lens = nullptr;
-    int rc = dvs_dev_alloc(ctx, (void **)&d_sk, size_t(nseq) * s * 4, "sketches");
-    if (!rc) rc = dvs_dev_alloc(ctx, (void **)&d_lens, size_t(nseq) * 4, "sketch lengths");
+    PooledBuf d_sk{ctx}, d_lens{ctx};
+    int rc = dvs_dev_alloc(ctx, &d_sk.p, size_t(nseq) * s * 4, "sketches");
+    if (!rc) rc = dvs_dev_alloc(ctx, &d_lens.p, size_t(nseq) * 4, "sketch lengths");
+    if (rc) return rc;
     hipError_t e = hipSuccess;
-    if (!rc && sketch_stride)
-        e = hipMemcpyAsync(d_sk, sketches, size_t(nseq) * s * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(d_lens, lens, size_t(nseq) * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (!rc && e != hipSuccess) rc = dvs_hip_fail(ctx, e, "sketch upload");
-    if (!rc) rc = mash_pairs_device(ctx, d_sk, d_lens, nseq, s, k, sketch_size, row_start, row_stride, symmetric, dist);
-    else (void)hipStreamSynchronize(ctx->stream);
-    dvs_dev_free(ctx, d_sk);
-    dvs_dev_free(ctx, d_lens);
-    return rc;
+    if (sketch_stride) e = hipMemcpyAsync(d_sk.p, sketches, size_t(nseq) * s * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lens.p, lens, size_t(nseq) * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return dvs_hip_fail(ctx, e, "sketch upload");
+    }
+    return mash_pairs_device(ctx, d_sk.as<uint32_t>(), d_lens.as<uint32_t>(), nseq, s, k, sketch_size, row_start, row_stride,
+                             symmetric, dist);
 }
 
-// the euclidean kernel over the rows of m into the device matrix d_dist (every cell off the diagonal)
-static hipError_t euclid_launch(dvs_ctx *ctx, const dvs_matrix *m, double *d_dist) {
-    const uint32_t n = m->nrows;
-    const dim3 grid(n, (n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64));
-    dvs_mat_dispatch(m, [&](auto *mp) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
-        hipLaunchKernelGGL((euclid_kernel<T>), grid, dim3(EUC_THREADS), 0, ctx->stream, mp, m->d_totals, m->nbins, n,
-                           d_dist);
-        return 0;
-    });
-    return hipGetLastError();
-}
-
-extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
-    if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    const uint32_t n = m->nrows;
-    if (n == 0) return DVS_OK;
-    if (n == 1) {
-        dist[0] = 0.0;
+// The mash mode of the ctree drivers (rowdist.hip): every pair of the sketches into the matrix, mirrored.  k = 0 and
+// a batch of empty sketches divide by zero before any device work (distance.py:283); the scratch is the word the
+// pair kernel sets for a pair of two empty sketches.  The kernel does not write the diagonal.
+dvs_dist_stage dvs_mash_stage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size) {
+    dvs_dist_stage st{"mash distances", sk->nseq};
+    st.check = [=] {
+        if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
+        if (!sk->d_sk) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // every sketch empty
         return DVS_OK;
-    }
-    const uint32_t groups = (n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64);
-    if (groups > 65535u)
-        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%u rows: the %u x %u distance matrix is beyond this path", n, n, n);
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    double *d_dist = nullptr;
-    int rc = dvs_dev_alloc(ctx, (void **)&d_dist, size_t(n) * n * 8, "distance matrix");
-    if (rc) return rc;
-    hipError_t e = hipMemsetAsync(d_dist, 0, size_t(n) * n * 8, ctx->stream);  // the diagonal
-    if (e == hipSuccess) e = euclid_launch(ctx, m, d_dist);
-    if (e == hipSuccess) e = hipMemcpyAsync(dist, d_dist, size_t(n) * n * 8, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t se = hipStreamSynchronize(ctx->stream);
-    dvs_dev_free(ctx, d_dist);
-    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "euclidean distances");
-    if (se != hipSuccess) return dvs_hip_fail(ctx, se, "euclidean distances");
-    return DVS_OK;
-}
-
-// ---- ctree end to end on the device (diverse_seq/cluster.py:164-188, 216-233): the N x N matrix is written into the
-// context's scratch and read there by the linkage tree (linkage.hip); it never crosses PCIe.  The diagonal,
-// which neither distance kernel writes, is zeroed (the tree checks every entry, as sklearn does).
-static int tree_matrix_alloc(dvs_ctx *ctx, uint32_t n, PooledBuf *d_dist) {
-    int rc = dvs_linkage_check_size(ctx, n);
-    if (!rc) rc = dvs_dev_alloc(ctx, &d_dist->p, size_t(n) * n * 8, "distance matrix");
-    if (rc) return rc;
-    DVS_HIP(ctx, hipMemset2DAsync(d_dist->p, (size_t(n) + 1) * 8, 0, 8, n, ctx->stream));
-    return DVS_OK;
-}
-
-extern "C" int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, int method,
-                                    uint32_t *pairs, double *heights, uint32_t *sizes) {
-    if (!ctx || !sk || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    if (int rc = dvs_linkage_check_method(ctx, method)) return rc;
-    const uint32_t n = sk->nseq;
-    if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
-    if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
-    if (!sk->d_sk) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // every sketch empty
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    PooledBuf d_dist{ctx}, d_flag{ctx};
-    int rc = tree_matrix_alloc(ctx, n, &d_dist);
-    if (!rc) rc = dvs_dev_alloc(ctx, &d_flag.p, 4, "flag");
-    if (rc) return rc;
-    hipError_t e = hipMemsetAsync(d_flag.p, 0, 4, ctx->stream);
-    if (e == hipSuccess) {
-        const dim3 grid(n, (n + PAIR_THREADS - 1) / PAIR_THREADS);
-        const uint32_t row_lds = std::min(sk->stride, PAIR_ROW_LDS);
-        hipLaunchKernelGGL(mash_pairs_kernel, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, sk->d_sk, sk->d_lens,
-                           n, k, sketch_size, sk->stride, 0u, 1u, 1, row_lds, d_dist.as<double>(), d_flag.as<uint32_t>());
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, e, "mash distances");
-    }
-    return dvs_linkage_device(ctx, d_dist.as<double>(), n, d_flag.as<uint32_t>(), method, pairs, heights, sizes);
-}
-
-extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
-                                            uint32_t *pairs, double *heights, uint32_t *sizes) {
-    return dvs_sketches_linkage(ctx, sk, k, sketch_size, 2, pairs, heights, sizes);  // (scipy's code of "average")
-}
-
-extern "C" int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs,
-                                            double *heights, uint32_t *sizes) {
-    if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    if (int rc = dvs_linkage_check_method(ctx, method)) return rc;
-    const uint32_t n = m->nrows;
-    if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
-    if ((n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64) > 65535u)
-        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%u rows: the %u x %u distance matrix is beyond this path", n, n, n);
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    PooledBuf d_dist{ctx};
-    int rc = tree_matrix_alloc(ctx, n, &d_dist);
-    if (rc) return rc;
-    const hipError_t e = euclid_launch(ctx, m, d_dist.as<double>());
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, e, "euclidean distances");
-    }
-    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, method, pairs, heights, sizes);
-}
-
-extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
-                                                    uint32_t *sizes) {
-    return dvs_matrix_euclidean_linkage(ctx, m, 2, pairs, heights, sizes);  // (scipy's code of "average")
+    };
+    st.scratch_bytes = 4;
+    st.scratch_what = "flag";
+    st.scratch_is_zerodiv = st.zero_diagonal = true;
+    st.enqueue = [=](double *d_dist, void *d_flag) {
+        hipError_t e = hipMemsetAsync(d_flag, 0, 4, ctx->stream);
+        if (e == hipSuccess)
+            e = mash_pairs_launch(ctx, sk->d_sk, sk->d_lens, sk->nseq, sk->stride, k, sketch_size, 0u, 1u, 1, d_dist,
+                                  static_cast<uint32_t *>(d_flag));
+        return e;
+    };
+    return st;
 }

@@ -1,0 +1,309 @@
+// Pairwise distances between the rows of a k-mer matrix -- the Jensen-Shannon divergence and the euclidean distance
+// (diverse_seq/distance.py:294-336) -- and the two drivers every ctree distance mode goes through: rows of a matrix to
+// a host N x N array, and distances to linkage tree with the N x N matrix left in HBM.
+//
+// The Jensen-Shannon divergence:
+//   D[i][j] = H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2,   f = counts / total, H in bits,
+// the total_jsd of the two-member set SummedRecords::new([i, j]) (src/records.rs:27-68; paper/paper.md Table 1:
+// identical -> 0, no k-mer in common -> 1).  The divergence itself, not its square root.
+//
+// Two kernels.  jsd_pairs_kernel takes one 32 x 32 tile of the lower triangle per workgroup, the diagonal tiles
+// included: the halved frequencies of its 32 i-rows and 32 j-rows are staged in LDS 64 bins at a time (one correctly
+// rounded quotient per staged count, exact_div_u32), every thread owns a 2 x 2 block of pairs and adds
+// -m log2 m (m = f_i / 2 + f_j / 2, log2_tab through a 2 KB table filled once per workgroup) for its four pairs bin
+// after bin: four LDS reads feed four logarithms, and a count read from HBM feeds 32 pairs.  A pair below the diagonal
+// leaves H(mean) in its cell; a pair ON the diagonal has mean == f_i, so its sum is H(f_i), written to d_h: the row
+// entropies come out of the very expression and bin order of H(mean), once per row.  jsd_finish_kernel then turns
+// every cell below the diagonal into the clamped divergence and mirrors it through an LDS transpose.  Two rows with
+// equal counts have mean == f_i == f_j bit for bit, H(mean) == H(f_i) == H(f_j), and their cell is exactly 0.
+// Each pair is summed by one thread in bin order: no atomics, no cross-lane sums, the same bits on every run and in
+// both entries.  A row without a valid k-mer (total 0) is staged as zeros and gets NaN off the diagonal from the
+// finish kernel, as euclid_kernel's 0 / 0 does.
+//
+// The kernel is bound by FP64 issue: 16 f64 instructions and one 16-byte table read per bin and pair, against four
+// 8-byte LDS reads per bin and thread and one staged count per 32 pairs (DESIGN.md 4.8 has the measurements).
+#include "dvs_internal.h"
+#include "select_dev.h"
+
+#include <type_traits>
+
+namespace {
+
+constexpr int JSD_THREADS = 256;
+constexpr uint32_t JSD_TILE = 32;    // rows of a tile on either side; a thread owns rows t, t + 16 of both
+constexpr uint32_t JSD_CHUNK = 64;   // bins staged at a time
+constexpr uint32_t JSD_LD = 2 * JSD_TILE + 1;  // doubles per staged bin: 32 i-rows, 32 j-rows, one of padding
+
+// acc -= m log2 m.  An empty bin (m == 0) takes the logarithm of 2^-1000 instead and adds -0 * -1000, which leaves
+// acc as it is: no branch, so the chains of a thread's 2 x 2 block interleave.  (A count row's m is 0 or >= 2^-33.)
+__device__ __forceinline__ void jsd_add(double &acc, double m, const double2 *tab) {
+    acc = fma(-m, log2_tab(fmax(m, 0x1p-1000), tab), acc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(JSD_THREADS) void jsd_pairs_kernel(const T *__restrict__ mat,
+                                                                const uint32_t *__restrict__ totals, uint64_t B,
+                                                                uint32_t n, double *__restrict__ dist,
+                                                                double *__restrict__ d_h) {
+    __shared__ double2 tab[128];
+    __shared__ double s_f[JSD_CHUNK * JSD_LD];  // s_f[b * JSD_LD + r]: half the frequency of tile row r in bin b
+    __shared__ double s_tot[2 * JSD_TILE], s_rt[2 * JSD_TILE];
+    const uint32_t bi = blockIdx.x, bj = blockIdx.y;
+    if (bj > bi) return;  // above the diagonal
+    const uint32_t tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    if (tid < 128) log2_tab_fill(tab, int(tid));
+    if (tid < 2 * JSD_TILE) {
+        const uint32_t row = tid < JSD_TILE ? bi * JSD_TILE + tid : bj * JSD_TILE + (tid - JSD_TILE);
+        const double t = row < n ? double(totals[row]) : 0.0;
+        s_tot[tid] = t;
+        s_rt[tid] = t > 0.0 ? 1.0 / t : 0.0;
+    }
+    double acc00 = 0.0, acc01 = 0.0, acc10 = 0.0, acc11 = 0.0;  // acc[a][b]: rows ty + 16 a and tx + 16 b
+    const uint32_t sb = tid & (JSD_CHUNK - 1), sr0 = tid / JSD_CHUNK;  // staging: bin sb of rows sr0, sr0 + 4, ...
+    for (uint64_t c0 = 0; c0 < B; c0 += JSD_CHUNK) {
+        const uint32_t cn = uint32_t(B - c0 < JSD_CHUNK ? B - c0 : JSD_CHUNK);
+        __syncthreads();  // (the table and the totals the first time; the previous chunk's readers after that)
+        if (sb < cn) {
+#pragma unroll 4
+            for (uint32_t r = sr0; r < 2 * JSD_TILE; r += JSD_THREADS / JSD_CHUNK) {
+                const uint32_t row = r < JSD_TILE ? bi * JSD_TILE + r : bj * JSD_TILE + (r - JSD_TILE);
+                const double t = s_tot[r];
+                double f = 0.0;
+                if (row < n && t > 0.0) f = 0.5 * count_freq_x(mat[uint64_t(row) * B + c0 + sb], t, s_rt[r]);
+                s_f[sb * JSD_LD + r] = f;
+            }
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (uint32_t b = 0; b < cn; b++) {
+            const double *s = s_f + b * JSD_LD;
+            const double i0 = s[ty], i1 = s[ty + 16], j0 = s[JSD_TILE + tx], j1 = s[JSD_TILE + tx + 16];
+            jsd_add(acc00, i0 + j0, tab);
+            jsd_add(acc01, i0 + j1, tab);
+            jsd_add(acc10, i1 + j0, tab);
+            jsd_add(acc11, i1 + j1, tab);
+        }
+    }
+    const double acc[2][2] = {{acc00, acc01}, {acc10, acc11}};
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            const uint32_t i = bi * JSD_TILE + ty + 16 * a, j = bj * JSD_TILE + tx + 16 * b;
+            if (i >= n || j > i) continue;
+            if (i == j) d_h[i] = acc[a][b];  // H(f_i)
+            else dist[uint64_t(i) * n + j] = acc[a][b];  // H(mean), finished below
+        }
+}
+
+// below the diagonal: H(mean) -> the divergence, clamped to [0, 1] (NaN where a row has no valid k-mer); the mirror
+// cell through an LDS transpose; 0 on the diagonal
+__global__ __launch_bounds__(JSD_THREADS) void jsd_finish_kernel(const uint32_t *__restrict__ totals,
+                                                                 const double *__restrict__ d_h, uint32_t n,
+                                                                 double *__restrict__ dist) {
+    __shared__ double t[JSD_TILE][JSD_TILE + 1];
+    const uint32_t bi = blockIdx.x, bj = blockIdx.y;
+    if (bj > bi) return;
+    const uint32_t lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+    for (uint32_t q = ly; q < JSD_TILE; q += JSD_THREADS / 32) {
+        const uint32_t i = bi * JSD_TILE + q, j = bj * JSD_TILE + lx;
+        double d = 0.0;
+        if (i < n && j < i) {
+            d = dist[uint64_t(i) * n + j] - 0.5 * (d_h[i] + d_h[j]);
+            d = d < 0.0 ? 0.0 : d;
+            d = d > 1.0 ? 1.0 : d;
+            if (totals[i] == 0 || totals[j] == 0) d = NAN;
+            dist[uint64_t(i) * n + j] = d;
+        } else if (i < n && j == i) {
+            dist[uint64_t(i) * n + j] = 0.0;
+        }
+        t[q][lx] = d;
+    }
+    __syncthreads();
+    for (uint32_t q = ly; q < JSD_TILE; q += JSD_THREADS / 32) {
+        const uint32_t j = bj * JSD_TILE + q, i = bi * JSD_TILE + lx;  // cell (j, i) above the diagonal
+        if (i < n && j < i) dist[uint64_t(j) * n + i] = t[lx][q];
+    }
+}
+
+// ||f_i - f_j||_2 (diverse_seq/distance.py:335-336), f = counts / total.  Workgroup (i, g) stages row
+// i's frequencies in LDS chunk by chunk and its eight waves take the rows j = 8 g .. 8 g + 7 below the
+// diagonal, one each: row i is read once per eight pairs, row j streamed by one wave with 16-byte loads
+// where the bin count allows.  Only the lower triangle does work; both mirror cells are written.
+constexpr int EUC_THREADS = 512;
+constexpr uint32_t EUC_CHUNK = 4096;  // bins of row i staged at a time (32 KB)
+template <typename T>
+__global__ __launch_bounds__(EUC_THREADS) void euclid_kernel(const T *__restrict__ mat,
+                                                            const uint32_t *__restrict__ totals, uint64_t B,
+                                                            uint32_t n, double *__restrict__ dist) {
+    __shared__ double fi[EUC_CHUNK];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t j = blockIdx.y * (EUC_THREADS / 64) + wave;
+    if (blockIdx.y * (EUC_THREADS / 64) >= i) return;  // the whole group is on or above the diagonal
+    const T *a = mat + uint64_t(i) * B;
+    const bool live = j < i;
+    const T *b = mat + uint64_t(live ? j : 0) * B;
+    const double ta = double(totals[i]), tb = double(totals[live ? j : 0]);
+    double acc = 0.0;
+    for (uint64_t c0 = 0; c0 < B; c0 += EUC_CHUNK) {
+        const uint32_t cn = uint32_t(B - c0 < EUC_CHUNK ? B - c0 : EUC_CHUNK);
+        __syncthreads();
+        for (uint32_t x = threadIdx.x; x < cn; x += EUC_THREADS) fi[x] = double(a[c0 + x]) / ta;
+        __syncthreads();
+        if (live)
+            for (uint32_t x = lane; x < cn; x += 64) {
+                const double d = fi[x] - double(b[c0 + x]) / tb;
+                acc += d * d;
+            }
+    }
+    acc = dvs_wave_sum(acc);
+    if (live && lane == 0) {
+        const double d = sqrt(acc);
+        dist[uint64_t(i) * n + j] = d;
+        dist[uint64_t(j) * n + i] = d;
+    }
+}
+
+// ---- the modes over the rows of a matrix (the mash mode: mash.hip dvs_mash_stage)
+
+// both limits of a count-matrix mode: euclid_kernel's grid has a workgroup per EUC_THREADS / 64 rows in y, 65 535 of
+// them at most, and the jsd mode keeps the same limit
+int rows_check(dvs_ctx *ctx, uint32_t n) {
+    if ((n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64) > 65535u)
+        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%u rows: the %u x %u distance matrix is beyond this path", n, n, n);
+    return DVS_OK;
+}
+
+// the two jsd kernels write every cell, the diagonal included; their scratch is the n row entropies
+dvs_dist_stage jsd_stage(dvs_ctx *ctx, const dvs_matrix *m) {
+    const uint32_t n = m->nrows;
+    dvs_dist_stage st{"jsd distances", n};
+    st.check = [=] { return rows_check(ctx, n); };
+    st.scratch_bytes = size_t(n) * 8;
+    st.scratch_what = "row entropies";
+    st.enqueue = [=](double *d_dist, void *d_scratch) {
+        double *d_h = static_cast<double *>(d_scratch);
+        const uint32_t tiles = (n + JSD_TILE - 1) / JSD_TILE;
+        const dim3 grid(tiles, tiles);
+        dvs_mat_dispatch(m, [&](auto *mp) {
+            using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
+            hipLaunchKernelGGL((jsd_pairs_kernel<T>), grid, dim3(JSD_THREADS), 0, ctx->stream, mp, m->d_totals, m->nbins,
+                               n, d_dist, d_h);
+            return 0;
+        });
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(jsd_finish_kernel, grid, dim3(JSD_THREADS), 0, ctx->stream, m->d_totals, d_h, n, d_dist);
+        return hipGetLastError();
+    };
+    return st;
+}
+
+// euclid_kernel writes every cell off the diagonal and needs no scratch
+dvs_dist_stage euclid_stage(dvs_ctx *ctx, const dvs_matrix *m) {
+    const uint32_t n = m->nrows;
+    dvs_dist_stage st{"euclidean distances", n};
+    st.check = [=] { return rows_check(ctx, n); };
+    st.zero_diagonal = true;
+    st.enqueue = [=](double *d_dist, void *) {
+        const dim3 grid(n, (n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64));
+        dvs_mat_dispatch(m, [&](auto *mp) {
+            using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
+            hipLaunchKernelGGL((euclid_kernel<T>), grid, dim3(EUC_THREADS), 0, ctx->stream, mp, m->d_totals, m->nbins, n,
+                               d_dist);
+            return 0;
+        });
+        return hipGetLastError();
+    };
+    return st;
+}
+
+// ---- the two drivers
+
+// The matrix and the mode's scratch from the context's cache, then the mode's kernels, behind a zeroed diagonal where
+// they leave it alone: DVS_OK with everything enqueued and nothing waited for, or the error (the stream drained, so
+// that the caller may let go of the two blocks).
+int stage_enqueue(dvs_ctx *ctx, const dvs_dist_stage &st, PooledBuf *d_dist, PooledBuf *d_scratch) {
+    const size_t n = st.n;
+    int rc = dvs_dev_alloc(ctx, &d_dist->p, n * n * 8, "distance matrix");
+    if (!rc && st.scratch_bytes) rc = dvs_dev_alloc(ctx, &d_scratch->p, st.scratch_bytes, st.scratch_what);
+    if (rc) return rc;
+    hipError_t e = st.zero_diagonal ? hipMemset2DAsync(d_dist->p, (n + 1) * 8, 0, 8, n, ctx->stream) : hipSuccess;
+    if (e == hipSuccess) e = st.enqueue(d_dist->as<double>(), d_scratch->p);
+    if (e == hipSuccess) return DVS_OK;
+    (void)hipStreamSynchronize(ctx->stream);
+    return dvs_hip_fail(ctx, e, st.label);
+}
+
+// the distances of a count-matrix mode into the host array dist (n x n)
+int stage_to_host(dvs_ctx *ctx, const dvs_dist_stage &st, double *dist) {
+    if (st.n == 0) return DVS_OK;
+    if (st.n == 1) {
+        dist[0] = 0.0;
+        return DVS_OK;
+    }
+    if (int rc = st.check()) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx}, d_scratch{ctx};
+    if (int rc = stage_enqueue(ctx, st, &d_dist, &d_scratch)) return rc;
+    const hipError_t e = hipMemcpyAsync(dist, d_dist.p, size_t(st.n) * st.n * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, st.label);
+    if (se != hipSuccess) return dvs_hip_fail(ctx, se, st.label);
+    return DVS_OK;
+}
+
+// ctree end to end on the device (diverse_seq/cluster.py:164-188, 216-233): the mode's N x N matrix is written into the
+// context's scratch and read there by the linkage tree (linkage.hip, which checks every entry, as sklearn does, and
+// returns once the stream is drained); it never crosses PCIe.  The checks come in one order for every mode: the
+// method, n < 2, the mode's own, the device, the fit in HBM.
+int stage_to_tree(dvs_ctx *ctx, const dvs_dist_stage &st, int method, uint32_t *pairs, double *heights, uint32_t *sizes) {
+    if (int rc = dvs_linkage_check_method(ctx, method)) return rc;
+    if (st.n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
+    if (int rc = st.check()) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx}, d_scratch{ctx};
+    int rc = dvs_linkage_check_size(ctx, st.n);
+    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
+    if (rc) return rc;
+    return dvs_linkage_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr,
+                              method, pairs, heights, sizes);
+}
+
+}  // namespace
+
+extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
+    if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_host(ctx, euclid_stage(ctx, m), dist);
+}
+
+extern "C" int dvs_jsd_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
+    if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_host(ctx, jsd_stage(ctx, m), dist);
+}
+
+extern "C" int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, int method,
+                                    uint32_t *pairs, double *heights, uint32_t *sizes) {
+    if (!ctx || !sk || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_tree(ctx, dvs_mash_stage(ctx, sk, k, sketch_size), method, pairs, heights, sizes);
+}
+extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
+                                            uint32_t *pairs, double *heights, uint32_t *sizes) {
+    return dvs_sketches_linkage(ctx, sk, k, sketch_size, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
+}
+
+extern "C" int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs,
+                                            double *heights, uint32_t *sizes) {
+    if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_tree(ctx, euclid_stage(ctx, m), method, pairs, heights, sizes);
+}
+extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
+                                                    uint32_t *sizes) {
+    return dvs_matrix_euclidean_linkage(ctx, m, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
+}
+
+extern "C" int dvs_matrix_jsd_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
+                                      uint32_t *sizes) {
+    if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_tree(ctx, jsd_stage(ctx, m), method, pairs, heights, sizes);
+}

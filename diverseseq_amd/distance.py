@@ -49,6 +49,38 @@ def linkage_matrix(pairs: np.ndarray, heights: np.ndarray, sizes: np.ndarray) ->
     return z
 
 
+def run_linkage(ctx: engine.Context | None, n: int, entry: str, *args,
+                too_few: str = "need at least two sequences to build a tree") -> np.ndarray:
+    """the dvs_*linkage call `entry`(ctx, *args, pairs, heights, sizes) for n leaves -> Z; ValueError(too_few)
+    before any device work when n < 2"""
+    if n < 2:
+        raise ValueError(too_few)
+    ctx = ctx or engine.default_context()
+    pairs, heights, sizes = tree_outputs(n)
+    ctx.check(getattr(ctx._L, entry)(ctx._h, *args, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                     _lib.ptr(sizes, C.c_uint32)))
+    return linkage_matrix(pairs, heights, sizes)
+
+
+def _dist_out(out, n: int) -> np.ndarray:
+    """the n x n matrix a distance call writes into: `out` when it is given (and fits), else zeros"""
+    if out is None:
+        return np.zeros((n, n), dtype=np.float64)
+    if (not isinstance(out, np.ndarray) or out.shape != (n, n) or out.dtype != np.float64
+            or not out.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"out must be a C-contiguous float64 array of shape ({n}, {n})")
+    return out
+
+
+def _sketch_stride(offsets: np.ndarray, k: int, sketch_size: int) -> int:
+    """words per sketch row: min(sketch_size, longest possible sketch of the batch), at least 1"""
+    lens_in = np.diff(offsets.astype(np.int64))
+    longest = int(max(0, (lens_in.max() if lens_in.size else 0) - k + 1))
+    if sketch_size < 0 or sketch_size > _U32_MAX:
+        raise OverflowError("sketch_size out of range for u32")  # pyo3 usize/u32 extraction
+    return max(1, min(int(sketch_size), longest))
+
+
 def sketch_batch(seqs, k: int, sketch_size: int, num_states: int = 4,
                  mash_canonical: bool = False, ctx: engine.Context | None = None):
     """bottom-`sketch_size` sketches of a batch -> (uint32 [n, stride], lens uint32 [n]);
@@ -56,11 +88,7 @@ def sketch_batch(seqs, k: int, sketch_size: int, num_states: int = 4,
     ctx = ctx or engine.default_context()
     data, offsets = engine.concat(seqs)
     n = len(seqs)
-    lens_in = np.diff(offsets.astype(np.int64)) if n else np.zeros(0, dtype=np.int64)
-    longest = int(max(0, (lens_in.max() if n else 0) - k + 1))
-    if sketch_size < 0 or sketch_size > _U32_MAX:
-        raise OverflowError("sketch_size out of range for u32")  # pyo3 usize/u32 extraction
-    stride = max(1, min(int(sketch_size), longest))
+    stride = _sketch_stride(offsets, k, sketch_size)
     sk = np.zeros((n, stride), dtype=np.uint32)
     lens = np.zeros(n, dtype=np.uint32)
     if n and sketch_size:
@@ -87,10 +115,7 @@ def distances_from_sketches(sk: np.ndarray, lens: np.ndarray, k: int, sketch_siz
     sk = np.ascontiguousarray(sk, dtype=np.uint32)
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
     n = sk.shape[0]
-    if out is not None and (not isinstance(out, np.ndarray) or out.shape != (n, n) or out.dtype != np.float64
-                            or not out.flags["C_CONTIGUOUS"]):
-        raise ValueError(f"out must be a C-contiguous float64 array of shape ({n}, {n})")
-    dist = np.zeros((n, n), dtype=np.float64) if out is None else out
+    dist = _dist_out(out, n)
     ctx.check(ctx._L.dvs_mash_distances(ctx._h, _lib.ptr(sk, C.c_uint32), sk.shape[1],
                                         _lib.ptr(lens, C.c_uint32), n, k,
                                         min(int(sketch_size), _U32_MAX), row_start, row_stride,
@@ -127,12 +152,8 @@ class Sketches:
         else:
             data, offsets = engine.concat(seqs)
         self.n = offsets.size - 1
-        lens_in = np.diff(offsets.astype(np.int64)) if self.n else np.zeros(0, dtype=np.int64)
-        longest = int(max(0, (lens_in.max() if self.n else 0) - k + 1))
-        if sketch_size < 0 or sketch_size > _U32_MAX:
-            raise OverflowError("sketch_size out of range for u32")
+        self.stride = _sketch_stride(offsets, k, sketch_size) if sketch_size else 0
         self.k, self.sketch_size = k, int(sketch_size)
-        self.stride = max(1, min(int(sketch_size), longest)) if sketch_size else 0
         h = C.c_void_p()
         L, flag = self.ctx._L, int(bool(mash_canonical))
         if batch is not None:
@@ -203,24 +224,11 @@ class Sketches:
         """scipy's linkage matrix Z of `method` (LINKAGE_METHODS) over the mash distances of every pair: the N x N
         matrix is written and read in HBM (dvs_sketches_linkage); ZeroDivisionError as `distances`"""
         code = linkage_method_code(method)
-        if self.n < 2:
-            raise ValueError("need at least two sequences to build a tree")
-        pairs, heights, sizes = tree_outputs(self.n)
-        self.ctx.check(self.ctx._L.dvs_sketches_linkage(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX), code,
-                                                        _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
-                                                        _lib.ptr(sizes, C.c_uint32)))
-        return linkage_matrix(pairs, heights, sizes)
-
-    def average_linkage(self) -> np.ndarray:
-        """`linkage("average")`: `dvs ctree`'s tree"""
-        return self.linkage("average")
+        return run_linkage(self.ctx, self.n, "dvs_sketches_linkage", self._h, self.k, min(self.sketch_size, _U32_MAX), code)
 
     def distances(self, *, row_start: int = 0, row_stride: int = 1, symmetric: bool = True,
                   out: np.ndarray | None = None) -> np.ndarray:
-        if out is not None and (not isinstance(out, np.ndarray) or out.shape != (self.n, self.n)
-                                or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"out must be a C-contiguous float64 array of shape ({self.n}, {self.n})")
-        dist = np.zeros((self.n, self.n), dtype=np.float64) if out is None else out
+        dist = _dist_out(out, self.n)
         self.ctx.check(self.ctx._L.dvs_sketches_distances(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX),
                                                           row_start, row_stride, int(symmetric), _lib.ptr(dist, C.c_double)))
         return dist
@@ -283,47 +291,37 @@ def mash_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canon
         sk.close()
 
 
-def euclidean_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
-                      ctx: engine.Context | None = None) -> np.ndarray:
-    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+def _count_rows_linkage(entry: str, seqs, k: int, num_states: int, method: str, ctx: engine.Context | None) -> np.ndarray:
+    """the tree of a distance mode over the rows of the batch's count matrix (`entry`: its dvs_matrix_*_linkage)"""
     code = linkage_method_code(method)
     ctx = ctx or engine.default_context()
     m = ctx.build_matrix(seqs, k, num_states)
     try:
-        if m.nrows < 2:
-            raise ValueError("need at least two sequences to build a tree")
-        pairs, heights, sizes = tree_outputs(m.nrows)
-        ctx.check(ctx._L.dvs_matrix_euclidean_linkage(ctx._h, m._h, code, _lib.ptr(pairs, C.c_uint32),
-                                                      _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
-        return linkage_matrix(pairs, heights, sizes)
+        return run_linkage(ctx, m.nrows, entry, m._h, code)
     finally:
         m.close()
+
+
+def euclidean_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
+                      ctx: engine.Context | None = None) -> np.ndarray:
+    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    return _count_rows_linkage("dvs_matrix_euclidean_linkage", seqs, k, num_states, method, ctx)
 
 
 def jsd_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
                 ctx: engine.Context | None = None) -> np.ndarray:
     """the same for the Jensen-Shannon divergences of `jsd_distances`, the same matrix bit for bit (a sequence
     without valid k-mers: NaN distances, ValueError)"""
-    code = linkage_method_code(method)
-    ctx = ctx or engine.default_context()
-    m = ctx.build_matrix(seqs, k, num_states)
-    try:
-        if m.nrows < 2:
-            raise ValueError("need at least two sequences to build a tree")
-        pairs, heights, sizes = tree_outputs(m.nrows)
-        ctx.check(ctx._L.dvs_matrix_jsd_linkage(ctx._h, m._h, code, _lib.ptr(pairs, C.c_uint32),
-                                                _lib.ptr(heights, C.c_double), _lib.ptr(sizes, C.c_uint32)))
-        return linkage_matrix(pairs, heights, sizes)
-    finally:
-        m.close()
+    return _count_rows_linkage("dvs_matrix_jsd_linkage", seqs, k, num_states, method, ctx)
 
 
-def mash_average_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False,
-                         ctx: engine.Context | None = None) -> np.ndarray:
-    """`dvs ctree`'s average-linkage mash tree: mash_linkage(..., method="average")"""
-    return mash_linkage(seqs, k, sketch_size, num_states, mash_canonical, method="average", ctx=ctx)
+# a ctree distance mode -> (its N x N distances, its tree): both take (seqs, *mode_args(...)), the tree also method=
+MODES = {"mash": (mash_distances, mash_linkage), "euclidean": (euclidean_distances, euclidean_linkage),
+         "jsd": (jsd_distances, jsd_linkage)}
 
 
-def euclidean_average_linkage(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
-    """euclidean_linkage(..., method="average")"""
-    return euclidean_linkage(seqs, k, num_states, method="average", ctx=ctx)
+def mode_args(distance_mode: str, k: int, sketch_size, num_states: int, mash_canonical: bool) -> tuple:
+    """what either function of MODES[distance_mode] takes behind the sequences"""
+    if distance_mode == "mash":
+        return k, int(sketch_size), num_states, mash_canonical
+    return k, num_states

@@ -1,4 +1,4 @@
-"""Pairwise Jensen-Shannon distances on the GPU (csrc/jsd.hip): every cell against the oracle's two-member total_jsd
+"""Pairwise Jensen-Shannon distances on the GPU (csrc/rowdist.hip): every cell against the oracle's two-member total_jsd
 (src/records.rs:27-68; tests/test_jsd_host.py pins that yardstick on the CPU) within 1e-9, the bound the project uses
 for a distance cell against the oracle (tests/test_gpu_configs.py); the exact properties of the matrix; the fused tree
 bit for bit against scipy over the device's own matrix; ctree and the apps."""
@@ -16,7 +16,7 @@ from test_linkage_methods_host import METHODS, scipy_z
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-9
-JSD_TILE = 32  # rows of a workgroup's tile on either side (csrc/jsd.hip)
+JSD_TILE = 32  # rows of a workgroup's tile on either side (csrc/rowdist.hip)
 
 
 @pytest.fixture(scope="module")
