@@ -112,6 +112,13 @@ def test_caller_labels_come_back_from_the_label_free_engine(ctx):
     q = ctx.build_matrix([seqs[int(mem.positions[0])], seqs[5]], 5, 4)
     d = sel.delta_jsd(q, [int(mem.labels[0]), 0xFFFFFFF0])
     assert d[0] == 0.0 and d[1] != 0.0
+    # ... and the values: every read-back entry of this selection against the oracle (tests/test_gpu_readback.py)
+    from test_gpu_readback import assert_readback
+    from test_readback_host import oracle_set, readback_cases
+
+    case = next(c for c in readback_cases() if c.name == "k5_n9_labels_distinct")
+    assert all((a == b).all() for a, b in zip(case.seqs, seqs)) and (case.opts["labels"] == labels).all()
+    assert_readback(ctx, sel, oracle_set(case), case)
 
 
 def test_persistent_engine_falls_back_to_the_multi_launch_engine(ctx, monkeypatch):
