@@ -251,11 +251,17 @@ def euclidean_distances(seqs, k: int, num_states: int = 4,
     ctx = ctx or engine.default_context()
     m = ctx.build_matrix(seqs, k, num_states)
     try:
-        dist = np.zeros((m.nrows, m.nrows), dtype=np.float64)
-        ctx.check(ctx._L.dvs_euclidean_distances(ctx._h, m._h, _lib.ptr(dist, C.c_double)))
-        return dist
+        return matrix_euclidean_distances(m)
     finally:
         m.close()
+
+
+def matrix_euclidean_distances(m: "engine.CountMatrix") -> np.ndarray:
+    """`euclidean_distances` over the rows of a matrix already in HBM (count rows of either width, or the frequency
+    rows of Context.matrix_from_freqs)"""
+    dist = np.zeros((m.nrows, m.nrows), dtype=np.float64)
+    m.ctx.check(m.ctx._L.dvs_euclidean_distances(m.ctx._h, m._h, _lib.ptr(dist, C.c_double)))
+    return dist
 
 
 def jsd_distances(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
