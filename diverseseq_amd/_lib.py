@@ -46,6 +46,8 @@ EXPORTS = (
     "dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage",
     "dvs_linkage", "dvs_sketches_linkage", "dvs_matrix_euclidean_linkage",
     "dvs_jsd_distances", "dvs_matrix_jsd_linkage",
+    "dvs_jsd_cross_distances", "dvs_euclidean_cross_distances", "dvs_sketches_cross_distances",
+    "dvs_jsd_nearest", "dvs_euclidean_nearest", "dvs_sketches_nearest",
 )
 
 
@@ -218,6 +220,13 @@ def load() -> C.CDLL:
         L.dvs_matrix_euclidean_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
         L.dvs_jsd_distances.argtypes = [vp, vp, f64p]
         L.dvs_matrix_jsd_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
+        u32 = C.c_uint32
+        for n in ("dvs_jsd_cross_distances", "dvs_euclidean_cross_distances"):
+            getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, f64p]
+        L.dvs_sketches_cross_distances.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, f64p]
+        for n in ("dvs_jsd_nearest", "dvs_euclidean_nearest"):
+            getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32p, f64p]
+        L.dvs_sketches_nearest.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, u32, u32p, f64p]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

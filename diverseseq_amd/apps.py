@@ -4,7 +4,8 @@
 (pyproject.toml:89-94; `pyproject.toml` here registers the same five); and `dvs_dist`
 (diverse_seq/distance.py:21-116), the distance-matrix app the reference defines without registering it.
 `dvs_ctree`, `dvs_par_ctree` and `dvs_dist` also take distance_mode="jsd", the pairwise Jensen-Shannon
-divergence of k-mer frequencies (diverseseq_amd.distance.jsd_distances).
+divergence of k-mer frequencies (diverseseq_amd.distance.jsd_distances).  `dvs_nearest`, beyond the reference: the
+nearest of a fixed set of reference sequences for every query (diverseseq_amd.distance.nearest).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -35,7 +36,7 @@ except Exception:  # noqa: BLE001
             return cls
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
-__all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist"]
+__all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -263,3 +264,56 @@ class dvs_dist:
 
             return DistanceMatrix.from_array_names(matrix=dists, names=names)
         return names, dists
+
+
+@_define_app
+class dvs_nearest:
+    """The nearest of a fixed set of reference sequences for every query, by any distance of `dvs_dist` (beyond the
+    reference, which has no such app).  The references are taken, encoded and sketched (mash) or counted (euclidean,
+    jsd) once, here; `main(seqs)` returns {query name: [(reference name, distance), ...]}, nearest first, a tie to the
+    reference that came first; a reference at NaN distance (jsd, euclidean: no valid k-mer on either side) is not
+    listed, so a list may be shorter than n_nearest."""
+
+    def __init__(self, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k: int = 12,
+                 sketch_size: int | None = 3_000, moltype: str = "dna", mash_canonical_kmers: bool | None = None) -> None:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        if distance_mode not in _distance.CROSS_MODES:
+            raise ValueError(f"Unexpected distance {distance_mode!r}.")
+        if moltype not in ("dna", "rna") and mash_canonical_kmers:
+            raise ValueError("Canonical kmers only supported for dna sequences.")
+        if distance_mode == "mash" and sketch_size is None:
+            raise ValueError("Expected sketch size for mash distance measure.")
+        names, data, _ = _as_mapping(refs, moltype)
+        self._n_nearest = _distance.check_n_nearest(n_nearest, len(names))
+        self._moltype = moltype
+        self._k = k
+        self._num_states = _num_states(moltype)
+        self._distance_mode = distance_mode
+        self._sketch_size = sketch_size
+        self._mash_canonical = mash_canonical_kmers
+        self._ref_names = names
+        self._refs = self._device_side([np.frombuffer(data[n], dtype=np.uint8) for n in names])
+
+    def _device_side(self, arrays):
+        """the sketches (mash) or the count matrix (euclidean, jsd) of a batch, left in HBM"""
+        if self._distance_mode == "mash":
+            return _distance.Sketches(arrays, self._k, self._sketch_size, self._num_states, self._mash_canonical)
+        from . import engine as _engine
+
+        return _engine.default_context().build_matrix(arrays, self._k, self._num_states)
+
+    def main(self, seqs):
+        names, data, _ = _as_mapping(seqs, self._moltype)
+        if not names:
+            return {}
+        q = self._device_side([np.frombuffer(data[n], dtype=np.uint8) for n in names])
+        try:
+            if self._distance_mode == "mash":
+                idx, dist = q.nearest(self._refs, self._n_nearest)
+            else:
+                idx, dist = _distance.matrix_nearest(q, self._refs, self._n_nearest, self._distance_mode)
+        finally:
+            q.close()
+        return {name: [(self._ref_names[j], float(d)) for j, d in zip(idx[i], dist[i]) if j >= 0]
+                for i, name in enumerate(names)}

@@ -39,6 +39,8 @@ struct dvs_knobs {
     bool persist_no_events = false;   // DVS_PERSIST_NO_EVENTS: a threshold no row reaches, long windows (the pure-stream measurement)
     bool persist_debug = false;       // DVS_PERSIST_DEBUG: per-launch report on stderr (phase stamps of a -DDVS_PERSIST_STAMPS build)
     int persist_wg_rounds = -1;       // DVS_PERSIST_WG_ROUNDS: rounds of the grid up to which a window is scanned a row per workgroup (-1: default)
+    // rectangular distances (crossdist.hip)
+    uint32_t cross_strip_rows = 0;    // DVS_CROSS_STRIP_ROWS: query rows per strip of the rectangular drivers (0: from the strip's byte bound)
     // ingest
     bool ingest_no_stream = false;    // DVS_INGEST_NO_STREAM: host files are uploaded whole before they are parsed
     // test-only (DVS_TEST_KNOBS=fake_persist_error): the first persistent launch's outcome is read as SEL_ERROR
@@ -243,6 +245,48 @@ struct dvs_dist_stage {
     std::function<hipError_t(double *d_dist, void *d_scratch)> enqueue;
 };
 dvs_dist_stage dvs_mash_stage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size);  // mash.hip
+
+// One distance mode between two collections, as the drivers of crossdist.hip take it: "fill rows [q0, q0 + mq) of the
+// m x n f64 matrix into this device buffer (mq x n, row-major)" on the context's stream.  The matrix never has to
+// exist whole: the drivers walk the queries in strips.
+struct dvs_cross_stage {
+    const char *label;                // what a failed launch is reported as
+    uint32_t m, n;                    // query rows and reference columns of the matrix
+    std::function<int()> check;       // the mode's own preconditions: DVS_OK, or the error it set
+    size_t scratch_bytes;             // device scratch shared by every strip ...
+    const char *scratch_what;         // ... and its name in an allocation error
+    bool scratch_is_zerodiv;          // its first word is set by the kernel where the reference divides by zero
+    std::function<hipError_t(void *d_scratch)> prepare;  // once, in front of the first strip
+    std::function<hipError_t(uint32_t q0, uint32_t mq, double *d_strip, void *d_scratch)> enqueue;
+};
+dvs_cross_stage dvs_mash_cross_stage(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
+                                     const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
+                                     uint32_t sketch_size);  // mash.hip
+int dvs_rows_check(dvs_ctx *ctx, uint32_t n);  // rowdist.hip: the square path's own row limit
+// a side's optional row list (host; NULL: rows 0 .. nrows - 1) against the `limit` rows its handle holds
+int dvs_cross_rows_check(dvs_ctx *ctx, const uint32_t *rows, uint32_t nrows, uint32_t limit, const char *side);
+// The two optional row lists of a stage in its scratch, behind `head` bytes of the stage's own: uploaded once, read by
+// the kernels of every strip.  (The host lists are the caller's and outlive the call, which waits for the stream.)
+struct dvs_cross_lists {
+    size_t head;
+    const uint32_t *q_rows, *r_rows;
+    uint32_t nq, nr;
+    size_t bytes() const { return head + (q_rows ? size_t(nq) * 4 : 0) + (r_rows ? size_t(nr) * 4 : 0); }
+    const uint32_t *dq(void *scratch) const {
+        return q_rows ? reinterpret_cast<const uint32_t *>(static_cast<char *>(scratch) + head) : nullptr;
+    }
+    const uint32_t *dr(void *scratch) const {
+        return r_rows ? reinterpret_cast<const uint32_t *>(static_cast<char *>(scratch) + head) + (q_rows ? nq : 0) : nullptr;
+    }
+    hipError_t upload(dvs_ctx *ctx, void *scratch) const {
+        hipError_t e = hipSuccess;
+        if (q_rows && nq)
+            e = hipMemcpyAsync(const_cast<uint32_t *>(dq(scratch)), q_rows, size_t(nq) * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && r_rows && nr)
+            e = hipMemcpyAsync(const_cast<uint32_t *>(dr(scratch)), r_rows, size_t(nr) * 4, hipMemcpyHostToDevice, ctx->stream);
+        return e;
+    }
+};
 
 // f(typed row pointer) for the matrix's element type
 template <typename F>

@@ -464,23 +464,44 @@ static_assert(PAIR_AHEAD + PAIR_ADV <= PAIR_SLOTS, "window too small for PAIR_W"
 constexpr int PAIR_THREADS = 256;
 constexpr uint32_t PAIR_ROW_LDS = 8192;  // hashes of row i staged in LDS at most (longer sketches are read through L1)
 
+// CROSS: the same kernel between two sketch sets (crossdist.hip's mash mode).  Workgroup row blockIdx.x is query
+// qrows[q0 + blockIdx.x] (NULL: q0 + blockIdx.x) of `sketches` / `lens` / `stride`, lane j reference rrows[j] (NULL: j)
+// of rsk / rlens / rstride, every j < nseq (the number of reference columns) live; no diagonal, no mirror; cell (i, j)
+// of the strip at dist[i * nseq + j].  A side whose every sketch is empty has no buffers (lens == NULL): length 0.
+// The trailing parameters are the cross instantiation's only: the square one neither loads nor uses them.
+template <bool CROSS>
 __global__ __launch_bounds__(PAIR_THREADS) void mash_pairs_kernel(
     const uint32_t *__restrict__ sketches, const uint32_t *__restrict__ lens, uint32_t nseq,
     uint32_t k, uint32_t s, uint32_t stride, uint32_t row_start, uint32_t row_stride, int symmetric,
-    uint32_t row_lds, double *__restrict__ dist, uint32_t *__restrict__ zerodiv) {
+    uint32_t row_lds, double *__restrict__ dist, uint32_t *__restrict__ zerodiv,
+    const uint32_t *__restrict__ rsk, const uint32_t *__restrict__ rlens, uint32_t rstride,
+    const uint32_t *__restrict__ qrows, const uint32_t *__restrict__ rrows, uint32_t q0) {
     __shared__ uint32_t s_win[PAIR_SLOTS * 4][PAIR_THREADS];
     extern __shared__ uint32_t s_left[];  // row_lds + 4 words
     // grid = (rows, blocks of 256 columns), rows fastest: workgroups go to the XCDs round-robin by their linear
     // index, so with the columns fastest XCD x would get column block x % 4 only -- and column block 0 has
     // work in every row, block 3 in a quarter of them (measured: 3 rounds on two XCDs, half a round on two
     // others).  Longest rows first.
-    const uint32_t i = row_start + (gridDim.x - 1 - blockIdx.x) * row_stride;
+    const uint32_t i = CROSS ? blockIdx.x : row_start + (gridDim.x - 1 - blockIdx.x) * row_stride;
     const uint32_t j = blockIdx.y * PAIR_THREADS + threadIdx.x;
-    if (i >= nseq || blockIdx.y * PAIR_THREADS >= i) return;
-    const bool mine = j < i;
-    const uint32_t *Lg = sketches + uint64_t(i) * stride;
-    const uint32_t *R = sketches + uint64_t(mine ? j : 0u) * stride;
-    const uint32_t nl = lens[i], nr = mine ? lens[j] : 0u;
+    if (!CROSS && (i >= nseq || blockIdx.y * PAIR_THREADS >= i)) return;
+    const bool mine = CROSS ? j < nseq : j < i;
+    const uint32_t *Lg, *R;
+    uint32_t nl, nr;
+    if constexpr (CROSS) {
+        const uint32_t qrow = qrows ? qrows[q0 + i] : q0 + i;
+        const uint32_t jj = mine ? j : 0u, rrow = rrows ? rrows[jj] : jj;
+        Lg = sketches + uint64_t(qrow) * stride;
+        R = rsk + uint64_t(rrow) * rstride;
+        nl = lens ? lens[qrow] : 0u;
+        nr = mine && rlens ? rlens[rrow] : 0u;
+        stride = rstride;  // (from here on: the words readable behind R)
+    } else {
+        Lg = sketches + uint64_t(i) * stride;
+        R = sketches + uint64_t(mine ? j : 0u) * stride;
+        nl = lens[i];
+        nr = mine ? lens[j] : 0u;
+    }
     const bool staged = nl <= row_lds;
     if (staged) {
         for (uint32_t x = threadIdx.x; x < nl; x += PAIR_THREADS) s_left[x] = Lg[x];
@@ -616,7 +637,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void mash_pairs_kernel(
         if (d > 1.0) d = 1.0;
     }
     dist[uint64_t(i) * nseq + j] = d;
-    if (symmetric) dist[uint64_t(j) * nseq + i] = d;
+    if (!CROSS && symmetric) dist[uint64_t(j) * nseq + i] = d;
 }
 
 // The tile list of a batch, written on the device: tile t belongs to the sequence q with tpre[q] <= t < tpre[q + 1]
@@ -1033,8 +1054,9 @@ static hipError_t mash_pairs_launch(dvs_ctx *ctx, const uint32_t *d_sk, const ui
     const uint32_t nrows = (nseq - 1 - row_start) / row_stride + 1;
     const dim3 grid(nrows, (nseq + PAIR_THREADS - 1) / PAIR_THREADS);
     const uint32_t row_lds = std::min(stride, PAIR_ROW_LDS);  // (no sketch is longer than the stride)
-    hipLaunchKernelGGL(mash_pairs_kernel, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, d_sk, d_lens, nseq, k,
-                       sketch_size, stride, row_start, row_stride, symmetric, row_lds, d_dist, d_flag);
+    hipLaunchKernelGGL(mash_pairs_kernel<false>, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, d_sk, d_lens, nseq,
+                       k, sketch_size, stride, row_start, row_stride, symmetric, row_lds, d_dist, d_flag, nullptr, nullptr, 0u,
+                       nullptr, nullptr, 0u);
     return hipGetLastError();
 }
 
@@ -1179,6 +1201,41 @@ dvs_dist_stage dvs_mash_stage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, 
             e = mash_pairs_launch(ctx, sk->d_sk, sk->d_lens, sk->nseq, sk->stride, k, sketch_size, 0u, 1u, 1, d_dist,
                                   static_cast<uint32_t *>(d_flag));
         return e;
+    };
+    return st;
+}
+
+// The mash mode of the rectangular drivers (crossdist.hip): query sketch q_rows[i] (NULL: i) against reference sketch
+// r_rows[j].  The scratch: the zero-division word, then the two row lists where they are given.
+dvs_cross_stage dvs_mash_cross_stage(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
+                                     const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
+                                     uint32_t sketch_size) {
+    dvs_cross_stage st{"mash cross distances", nq, nr};
+    const dvs_cross_lists lists{8, q_rows, r_rows, nq, nr};
+    st.check = [=] {
+        if (q->ctx != r->ctx || q->ctx->device != ctx->device)
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "the two sketch sets and the context are not on one device");
+        if (int rc = dvs_cross_rows_check(ctx, q_rows, nq, q->nseq, "query")) return rc;
+        if (int rc = dvs_cross_rows_check(ctx, r_rows, nr, r->nseq, "reference")) return rc;
+        if (k == 0) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "float division by zero");
+        if (!q->d_sk && !r->d_sk) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // every sketch empty
+        return dvs_rows_check(ctx, nr);
+    };
+    st.scratch_bytes = lists.bytes();
+    st.scratch_what = "flag and row lists";
+    st.scratch_is_zerodiv = true;
+    st.prepare = [=](void *d_scratch) {
+        const hipError_t e = hipMemsetAsync(d_scratch, 0, 4, ctx->stream);
+        return e == hipSuccess ? lists.upload(ctx, d_scratch) : e;
+    };
+    st.enqueue = [=](uint32_t q0, uint32_t mq, double *d_strip, void *d_scratch) {
+        const dim3 grid(mq, (nr + PAIR_THREADS - 1) / PAIR_THREADS);
+        const uint32_t row_lds = std::min(q->stride, PAIR_ROW_LDS);  // (no sketch is longer than its stride)
+        hipLaunchKernelGGL(mash_pairs_kernel<true>, grid, dim3(PAIR_THREADS), (row_lds + 4) * 4, ctx->stream, q->d_sk,
+                           q->d_lens, nr, k, sketch_size, q->stride, 0u, 1u, 0, row_lds, d_strip,
+                           static_cast<uint32_t *>(d_scratch), r->d_sk, r->d_lens, r->stride, lists.dq(d_scratch),
+                           lists.dr(d_scratch), q0);
+        return hipGetLastError();
     };
     return st;
 }

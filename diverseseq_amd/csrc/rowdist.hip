@@ -23,22 +23,11 @@
 // The kernel is bound by FP64 issue: 16 f64 instructions and one 16-byte table read per bin and pair, against four
 // 8-byte LDS reads per bin and thread and one staged count per 32 pairs (DESIGN.md 4.8 has the measurements).
 #include "dvs_internal.h"
-#include "select_dev.h"
+#include "rowdist_dev.h"  // the tile shape and the per-bin term, shared with the rectangular kernels (crossdist.hip)
 
 #include <type_traits>
 
 namespace {
-
-constexpr int JSD_THREADS = 256;
-constexpr uint32_t JSD_TILE = 32;    // rows of a tile on either side; a thread owns rows t, t + 16 of both
-constexpr uint32_t JSD_CHUNK = 64;   // bins staged at a time
-constexpr uint32_t JSD_LD = 2 * JSD_TILE + 1;  // doubles per staged bin: 32 i-rows, 32 j-rows, one of padding
-
-// acc -= m log2 m.  An empty bin (m == 0) takes the logarithm of 2^-1000 instead and adds -0 * -1000, which leaves
-// acc as it is: no branch, so the chains of a thread's 2 x 2 block interleave.  (A count row's m is 0 or >= 2^-33.)
-__device__ __forceinline__ void jsd_add(double &acc, double m, const double2 *tab) {
-    acc = fma(-m, log2_tab(fmax(m, 0x1p-1000), tab), acc);
-}
 
 template <typename T>
 __global__ __launch_bounds__(JSD_THREADS) void jsd_pairs_kernel(const T *__restrict__ mat,
@@ -130,8 +119,6 @@ __global__ __launch_bounds__(JSD_THREADS) void jsd_finish_kernel(const uint32_t 
 // i's frequencies in LDS chunk by chunk and its eight waves take the rows j = 8 g .. 8 g + 7 below the
 // diagonal, one each: row i is read once per eight pairs, row j streamed by one wave with 16-byte loads
 // where the bin count allows.  Only the lower triangle does work; both mirror cells are written.
-constexpr int EUC_THREADS = 512;
-constexpr uint32_t EUC_CHUNK = 4096;  // bins of row i staged at a time (32 KB)
 template <typename T>
 __global__ __launch_bounds__(EUC_THREADS) void euclid_kernel(const T *__restrict__ mat,
                                                             const uint32_t *__restrict__ totals, uint64_t B,
@@ -271,6 +258,8 @@ int stage_to_tree(dvs_ctx *ctx, const dvs_dist_stage &st, int method, uint32_t *
 }
 
 }  // namespace
+
+int dvs_rows_check(dvs_ctx *ctx, uint32_t n) { return rows_check(ctx, n); }
 
 extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
     if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");

@@ -4,7 +4,9 @@ euclidean_distances :294-332) and the strided chunks of
 diverse_seq/cluster.py:607-644, with the arithmetic in libdvs_hip.so; the pairwise Jensen-Shannon
 divergence of k-mer frequencies (jsd_distances: total_jsd of a two-member set, src/records.rs:27-68);
 and the fused ctree stages
-(distances and the linkage tree with the N x N matrix left in HBM)."""
+(distances and the linkage tree with the N x N matrix left in HBM); and the distances between two collections
+(cross_distances: M queries against N references, no counterpart in the reference) with the k nearest references
+of every query (nearest), the M x N matrix computed strip by strip and never leaving the device."""
 
 from __future__ import annotations
 
@@ -233,6 +235,36 @@ class Sketches:
                                                           row_start, row_stride, int(symmetric), _lib.ptr(dist, C.c_double)))
         return dist
 
+    def _other(self, other: "Sketches"):
+        if other.k != self.k or other.sketch_size != self.sketch_size:
+            raise ValueError(f"sketches of k = {self.k}, sketch size {self.sketch_size} against k = {other.k}, "
+                             f"sketch size {other.sketch_size}")
+        return other
+
+    def cross_distances(self, other: "Sketches", rows=None, other_rows=None) -> np.ndarray:
+        """the mash distances of this set's sketches `rows` (None: all) against `other`'s `other_rows`: float64 [M, N],
+        every cell the bits `distances` gives the same two sketches (dvs_sketches_cross_distances);
+        ZeroDivisionError as `distances`"""
+        self._other(other)
+        qr, nq = _row_list(rows, self.n)
+        rr, nr = _row_list(other_rows, other.n)
+        dist = np.zeros((nq, nr), dtype=np.float64)
+        self.ctx.check(self.ctx._L.dvs_sketches_cross_distances(
+            self.ctx._h, self._h, _lib.ptr(qr, C.c_uint32), nq, other._h, _lib.ptr(rr, C.c_uint32), nr, self.k,
+            min(self.sketch_size, _U32_MAX), _lib.ptr(dist, C.c_double)))
+        return dist
+
+    def nearest(self, other: "Sketches", n_nearest: int = 1, rows=None, other_rows=None):
+        """the n_nearest sketches of `other` (positions into other_rows, or rows) nearest to each of this set's, nearest
+        first, a tie to the lower position: (int64 [M, n_nearest], -1 in a slot without a reference; float64 distances,
+        NaN there) (dvs_sketches_nearest)"""
+        self._other(other)
+        qr, nq = _row_list(rows, self.n)
+        rr, nr = _row_list(other_rows, other.n)
+        kk = check_n_nearest(n_nearest, nr)
+        return _run_nearest(self.ctx, "dvs_sketches_nearest", self._h, qr, nq, other._h, rr, nr, kk, self.k,
+                            min(self.sketch_size, _U32_MAX))
+
 
 def mash_distances(seqs, k: int, sketch_size: int, num_states: int = 4,
                    mash_canonical: bool = False, ctx: engine.Context | None = None) -> np.ndarray:
@@ -331,3 +363,186 @@ def mode_args(distance_mode: str, k: int, sketch_size, num_states: int, mash_can
     if distance_mode == "mash":
         return k, int(sketch_size), num_states, mash_canonical
     return k, num_states
+
+
+# ---- distances between two collections, and the nearest references of every query
+
+N_NEAREST_MAX = 64  # include/dvs_hip.h: a caller who wants a full ranking takes the matrix
+
+
+def check_n_nearest(n_nearest, n_refs: int) -> int:
+    """n_nearest as the dvs_*_nearest entries take it, checked before any device work: ValueError unless it is an
+    integer in 1 .. n_refs, NotImplementedError beyond N_NEAREST_MAX"""
+    if isinstance(n_nearest, bool) or not isinstance(n_nearest, (int, np.integer)):
+        raise ValueError(f"n_nearest must be an integer, not {n_nearest!r}")
+    if n_nearest < 1 or n_nearest > n_refs:
+        raise ValueError(f"n_nearest = {n_nearest}: between 1 and the number of references ({n_refs})")
+    if n_nearest > N_NEAREST_MAX:
+        raise NotImplementedError(f"n_nearest = {n_nearest}: {N_NEAREST_MAX} at most (a full ranking takes the matrix "
+                                  "of cross_distances)")
+    return int(n_nearest)
+
+
+def _row_list(rows, limit: int):
+    """a side's row list as the C entries take it: (None, limit) for every row, else (uint32 array, its length);
+    ValueError for an entry outside 0 .. limit - 1"""
+    if rows is None:
+        return None, int(limit)
+    a = np.asarray(rows)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError("a row list is a one-dimensional sequence of integers")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= limit):
+        raise ValueError(f"row list entry outside 0 .. {limit - 1}")
+    return np.ascontiguousarray(a, dtype=np.uint32), int(a.size)
+
+
+def _run_nearest(ctx, entry: str, qh, qr, nq: int, rh, rr, nr: int, kk: int, *mode_args):
+    """the dvs_*_nearest call `entry` -> (int64 [nq, kk] with -1 for an empty slot, float64 [nq, kk])"""
+    idx = np.zeros((nq, kk), dtype=np.uint32)
+    dist = np.zeros((nq, kk), dtype=np.float64)
+    ctx.check(getattr(ctx._L, entry)(ctx._h, qh, _lib.ptr(qr, C.c_uint32), nq, rh, _lib.ptr(rr, C.c_uint32), nr,
+                                     *mode_args, kk, _lib.ptr(idx, C.c_uint32), _lib.ptr(dist, C.c_double)))
+    out = idx.astype(np.int64)
+    out[idx == _U32_MAX] = -1
+    return out, dist
+
+
+# a count-matrix mode -> (its rectangular distances, its nearest references) in the C ABI
+_MATRIX_CROSS = {"jsd": ("dvs_jsd_cross_distances", "dvs_jsd_nearest"),
+                 "euclidean": ("dvs_euclidean_cross_distances", "dvs_euclidean_nearest")}
+
+
+def _matrix_mode(mode: str):
+    if mode not in _MATRIX_CROSS:
+        raise ValueError(f"Unexpected distance {mode!r} between the rows of count matrices: 'jsd' or 'euclidean'.")
+    return _MATRIX_CROSS[mode]
+
+
+def matrix_cross_distances(q: "engine.CountMatrix", r: "engine.CountMatrix", mode: str = "jsd", q_rows=None,
+                           r_rows=None) -> np.ndarray:
+    """the `mode` ("jsd", "euclidean") distances of rows q_rows of q (None: all) against rows r_rows of r: float64
+    [M, N], every cell the bits the square function of the mode gives the same two rows.  q and r may be one matrix
+    (rows against selected rows of the same matrix copy nothing) and may differ in element type, not in nbins."""
+    entry, _ = _matrix_mode(mode)
+    qr, nq = _row_list(q_rows, q.nrows)
+    rr, nr = _row_list(r_rows, r.nrows)
+    dist = np.zeros((nq, nr), dtype=np.float64)
+    q.ctx.check(getattr(q.ctx._L, entry)(q.ctx._h, q._h, _lib.ptr(qr, C.c_uint32), nq, r._h, _lib.ptr(rr, C.c_uint32), nr,
+                                         _lib.ptr(dist, C.c_double)))
+    return dist
+
+
+def matrix_nearest(q: "engine.CountMatrix", r: "engine.CountMatrix", n_nearest: int = 1, mode: str = "jsd", q_rows=None,
+                   r_rows=None):
+    """the n_nearest rows of r (positions into r_rows, or rows) nearest to each row of q by `mode`, nearest first, a
+    tie to the lower position: (int64 [M, n_nearest], -1 in a slot without a reference -- NaN cells are never
+    listed; float64 distances, NaN there)"""
+    _, entry = _matrix_mode(mode)
+    qr, nq = _row_list(q_rows, q.nrows)
+    rr, nr = _row_list(r_rows, r.nrows)
+    kk = check_n_nearest(n_nearest, nr)
+    return _run_nearest(q.ctx, entry, q._h, qr, nq, r._h, rr, nr, kk)
+
+
+def _mash_sides(queries, refs, k, sketch_size, num_states, mash_canonical, ctx):
+    return (Sketches(queries, k, sketch_size, num_states, mash_canonical, ctx=ctx),
+            Sketches(refs, k, sketch_size, num_states, mash_canonical, ctx=ctx))
+
+
+def mash_cross_distances(queries, refs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False,
+                         ctx: engine.Context | None = None) -> np.ndarray:
+    q, r = _mash_sides(queries, refs, k, sketch_size, num_states, mash_canonical, ctx)
+    try:
+        return q.cross_distances(r)
+    finally:
+        q.close()
+        r.close()
+
+
+def mash_nearest(queries, refs, n_nearest: int, k: int, sketch_size: int, num_states: int = 4,
+                 mash_canonical: bool = False, ctx: engine.Context | None = None):
+    q, r = _mash_sides(queries, refs, k, sketch_size, num_states, mash_canonical, ctx)
+    try:
+        return q.nearest(r, n_nearest)
+    finally:
+        q.close()
+        r.close()
+
+
+def _count_rows_cross(mode: str, queries, refs, k: int, num_states: int, ctx, run):
+    """run(q matrix, r matrix) over the count matrices of the two batches"""
+    ctx = ctx or engine.default_context()
+    q = ctx.build_matrix(queries, k, num_states)
+    try:
+        r = ctx.build_matrix(refs, k, num_states)
+        try:
+            return run(q, r)
+        finally:
+            r.close()
+    finally:
+        q.close()
+
+
+def euclidean_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+    return _count_rows_cross("euclidean", queries, refs, k, num_states, ctx,
+                             lambda q, r: matrix_cross_distances(q, r, "euclidean"))
+
+
+def euclidean_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None):
+    return _count_rows_cross("euclidean", queries, refs, k, num_states, ctx,
+                             lambda q, r: matrix_nearest(q, r, n_nearest, "euclidean"))
+
+
+def jsd_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+    return _count_rows_cross("jsd", queries, refs, k, num_states, ctx, lambda q, r: matrix_cross_distances(q, r, "jsd"))
+
+
+def jsd_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None):
+    return _count_rows_cross("jsd", queries, refs, k, num_states, ctx, lambda q, r: matrix_nearest(q, r, n_nearest, "jsd"))
+
+
+# a distance mode -> (its M x N distances, its nearest references): the first takes (queries, refs, *mode_args(...)),
+# the second (queries, refs, n_nearest, *mode_args(...)); both ctx=
+CROSS_MODES = {"mash": (mash_cross_distances, mash_nearest), "euclidean": (euclidean_cross_distances, euclidean_nearest),
+               "jsd": (jsd_cross_distances, jsd_nearest)}
+
+
+def check_mode_args(distance_mode: str, sketch_size, mash_canonical: bool) -> None:
+    """the argument checks of cluster.ctree for a distance mode, with its messages"""
+    if distance_mode not in CROSS_MODES:
+        raise ValueError(f"Unexpected distance {distance_mode!r}.")
+    if distance_mode == "mash" and sketch_size is None:
+        raise ValueError("Expected sketch size for mash distance measure.")
+    if distance_mode != "mash" and sketch_size is not None:
+        raise ValueError("Sketch size should only be specified for the mash distance.")
+    if distance_mode != "mash" and mash_canonical:
+        raise ValueError("Canonical kmers should only be specified for the mash distance.")
+
+
+def cross_distances(queries, refs, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+                    num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None) -> np.ndarray:
+    """the `distance_mode` distance of every query sequence to every reference sequence: float64 [M, N], cell (i, j) the
+    bits MODES[distance_mode] gives the pair (queries[i], refs[j]) inside one collection.  Only the M x N pairs are
+    computed.  Argument checks as cluster.ctree; ZeroDivisionError (mash) when a query and a reference both have an empty
+    sketch; NaN (jsd, euclidean) for a sequence without a valid k-mer."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    queries, refs = list(queries), list(refs)
+    if not queries or not refs:
+        return np.zeros((len(queries), len(refs)), dtype=np.float64)
+    return CROSS_MODES[distance_mode][0](queries, refs, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                                         ctx=ctx)
+
+
+def nearest(queries, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+            num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None):
+    """the n_nearest references of every query by `distance_mode`, nearest first, a tie to the reference that comes first in
+    `refs`: (idx int64 [M, n_nearest], positions in `refs`, -1 in a slot without one; dist float64 [M, n_nearest], NaN
+    there).  A reference at NaN distance is never listed.  1 <= n_nearest <= min(len(refs), N_NEAREST_MAX), checked -- like
+    the arguments cluster.ctree checks -- before any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    queries, refs = list(queries), list(refs)
+    kk = check_n_nearest(n_nearest, len(refs))
+    if not queries:
+        return np.zeros((0, kk), dtype=np.int64), np.zeros((0, kk), dtype=np.float64)
+    return CROSS_MODES[distance_mode][1](queries, refs, kk, *mode_args(distance_mode, k, sketch_size, num_states,
+                                                                        mash_canonical), ctx=ctx)

@@ -422,7 +422,9 @@ class CountMatrix:
                                                   _lib.ptr(order_a, C.c_uint32),
                                                   _lib.ptr(labels_a, C.c_uint32), npos,
                                                   C.byref(p), C.byref(h)))
-        return Selection(self, h)
+        sel = Selection(self, h)
+        sel._order = order_a  # (stream position -> matrix row; None: the position itself)
+        return sel
 
     def nmost(self, n: int, **kw) -> "Selection":
         return self.select(_lib.MODE_NMOST, n, **kw)
@@ -451,6 +453,7 @@ class Selection:
         self.matrix, self.ctx, self._h = matrix, matrix.ctx, handle
         self._gids = None
         self._lazy_gids = None
+        self._order = None
 
     @property
     def global_ids(self):
@@ -511,6 +514,21 @@ class Selection:
                                                         _lib.ptr(ql, C.c_uint32),
                                                         _lib.ptr(out, C.c_double)))
         return out
+
+    def member_rows(self) -> np.ndarray:
+        """the matrix row of every member, in `members()` order (the stream positions through the selection's order)"""
+        pos = self.members(with_freqs=False).positions.astype(np.int64)
+        return pos if self._order is None else self._order[pos].astype(np.int64)
+
+    def assign(self, n_nearest: int = 1, mode: str = "jsd"):
+        """for every row of the selection's matrix its n_nearest members by `mode` ("jsd", "euclidean"), nearest first:
+        (int64 [nrows, n_nearest] positions into `members()` order, -1 in a slot without a member; float64 distances, NaN
+        there).  The members are a row list into the same matrix: nothing is rebuilt or copied.  A member's own row comes
+        back with itself first at distance exactly 0.0 (or a member of equal counts and lower position); a row without a
+        valid k-mer is nearest to none."""
+        from . import distance
+
+        return distance.matrix_nearest(self.matrix, self.matrix, n_nearest, mode, r_rows=self.member_rows())
 
 
 _default_ctx: Context | None = None

@@ -430,6 +430,46 @@ int dvs_jsd_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist);
 int dvs_matrix_jsd_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
                            uint32_t *sizes);
 
+/* ---- distances between two collections, and the k nearest references ------------------------------ *
+ * The rectangular counterpart of the N x N entries above: cell (i, j) of an nq x nr float64 matrix is the distance
+ * between query row q_rows[i] of q and reference row r_rows[j] of r (a NULL list: rows 0 .. n - 1 of its handle).
+ * (No counterpart in the reference: its distance functions fill the square matrix of one collection,
+ * diverse_seq/distance.py:119-175, 294-336.)  The two handles may be one and the same, so "every row against the
+ * selected rows of the same matrix" copies nothing; for the jsd and euclidean entries they may differ in element
+ * type (16-bit counts, 32-bit counts, frequency rows, in any combination) but not in nbins.  A cell is the same bits
+ * as the cell the square entry of its mode writes for the same two rows (dvs_jsd_distances: in [0, 1], exactly 0
+ * between rows of equal counts, NaN where either row has no valid k-mer -- a rectangular matrix has no diagonal, so
+ * also for such a row against itself; dvs_euclidean_distances; dvs_sketches_distances with its k and sketch_size).
+ * The matrix is computed in strips of query rows whose device buffer is bounded (256 MiB, one tile row of 32 queries
+ * at least; DVS_CROSS_STRIP_ROWS overrides the strip height), so nq is not limited by a grid dimension; dist is the
+ * host array, nq x nr row-major.  Return when the host outputs are written.
+ *   DVS_OK with nothing written: nq == 0 or nr == 0
+ *   DVS_ERR_VALUE: a row index beyond its handle (or, with a NULL list, nq / nr beyond its rows), handles of
+ *                  different contexts or devices, unequal nbins
+ *   DVS_ERR_UNSUPPORTED: nr beyond the row limit of the square entries
+ *   DVS_ERR_ZERODIV: (sketches) k == 0, or a visited pair has two empty sketches */
+int dvs_jsd_cross_distances(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
+                            const uint32_t *r_rows, uint32_t nr, double *dist);
+int dvs_euclidean_cross_distances(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
+                                  const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, double *dist);
+int dvs_sketches_cross_distances(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
+                                 const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
+                                 uint32_t sketch_size, double *dist);
+/* The kk nearest references of every query over those cells, the matrix never leaving the device: idx and dist are
+ * host arrays nq x kk; row i lists the kk smallest cells of matrix row i in ascending order of (distance, position
+ * in the reference list 0 .. nr - 1 -- not the matrix row): a tie goes to the lower position, so the result is unique
+ * and the same on every run and for every strip height.  NaN cells are never listed; a row with fewer than kk other
+ * cells ends in slots of position 0xFFFFFFFF and distance NaN.  (No counterpart in the reference.)  Errors as above, and
+ *   DVS_ERR_VALUE: kk == 0 or kk > nr (hence always for nr == 0)
+ *   DVS_ERR_UNSUPPORTED: kk > 64 (a full ranking takes the matrix) */
+int dvs_jsd_nearest(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
+                    const uint32_t *r_rows, uint32_t nr, uint32_t kk, uint32_t *idx, double *dist);
+int dvs_euclidean_nearest(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
+                          const uint32_t *r_rows, uint32_t nr, uint32_t kk, uint32_t *idx, double *dist);
+int dvs_sketches_nearest(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq, const dvs_sketches *r,
+                         const uint32_t *r_rows, uint32_t nr, uint32_t k, uint32_t sketch_size, uint32_t kk,
+                         uint32_t *idx, double *dist);
+
 #ifdef __cplusplus
 }
 #endif
