@@ -19,6 +19,7 @@ _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ["DVS_HIP_LIB"]).resolve() if os.environ.get("DVS_HIP_LIB") else _HERE / "libdvs_hip.so"
 
 OK, ERR_VALUE, ERR_RUNTIME, ERR_NOMEM, ERR_UNSUPPORTED, ERR_ZERODIV = range(6)
+CUT_HEIGHT, CUT_NCLUSTERS = 0, 1
 MODE_NMOST, MODE_MAX, MODE_SET = 0, 1, 2
 STAT_STDEV, STAT_COV = 0, 1
 SELECT_NO_ARBITER = 1
@@ -48,6 +49,8 @@ EXPORTS = (
     "dvs_jsd_distances", "dvs_matrix_jsd_linkage",
     "dvs_jsd_cross_distances", "dvs_euclidean_cross_distances", "dvs_sketches_cross_distances",
     "dvs_jsd_nearest", "dvs_euclidean_nearest", "dvs_sketches_nearest",
+    "dvs_linkage_cut", "dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_sketches_cluster_scores",
+    "dvs_cluster_scores",
 )
 
 
@@ -227,6 +230,12 @@ def load() -> C.CDLL:
         for n in ("dvs_jsd_nearest", "dvs_euclidean_nearest"):
             getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32p, f64p]
         L.dvs_sketches_nearest.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, u32, u32p, f64p]
+        L.dvs_linkage_cut.argtypes = [vp, u32, u32p, f64p, C.c_int, C.c_double, u32p, u32p]
+        scores = [u32p, u32, f64p, f64p, f64p, u32p, f64p, u32p]  # labels, n_clusters, the five per-row outputs, medoids
+        for n in ("dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores"):
+            getattr(L, n).argtypes = [vp, vp, u32p, u32, *scores]
+        L.dvs_sketches_cluster_scores.argtypes = [vp, vp, u32p, u32, u32, u32, *scores]
+        L.dvs_cluster_scores.argtypes = [vp, vp, C.c_int, u32, *scores]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -5,7 +5,9 @@
 (diverse_seq/distance.py:21-116), the distance-matrix app the reference defines without registering it.
 `dvs_ctree`, `dvs_par_ctree` and `dvs_dist` also take distance_mode="jsd", the pairwise Jensen-Shannon
 divergence of k-mer frequencies (diverseseq_amd.distance.jsd_distances).  `dvs_nearest`, beyond the reference: the
-nearest of a fixed set of reference sequences for every query (diverseseq_amd.distance.nearest).
+nearest of a fixed set of reference sequences for every query (diverseseq_amd.distance.nearest); and `dvs_clusters`:
+the tree, its flat clusters at a cut, one representative per cluster and the silhouettes
+(diverseseq_amd.cluster.ctree_clusters).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -36,7 +38,8 @@ except Exception:  # noqa: BLE001
             return cls
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
-__all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest"]
+__all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
+           "dvs_clusters"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -317,3 +320,59 @@ class dvs_nearest:
             q.close()
         return {name: [(self._ref_names[j], float(d)) for j, d in zip(idx[i], dist[i]) if j >= 0]
                 for i, name in enumerate(names)}
+
+
+@_define_app
+class dvs_clusters:
+    """The flat clusters of the `dvs_ctree` tree at a cut, with one representative per cluster (beyond the reference,
+    which has no such app): exactly one of n_clusters (scipy's fcluster "maxclust" partition: a cut never separates
+    merges of equal height, so fewer clusters may come back) and height (its "distance" partition).  `main(seqs)`
+    returns {"tree": Newick string, "clusters": {label: [names]}, "medoids": {label: name}, "silhouette": {name: float},
+    "mean_silhouette": float}; labels count from 0 in the order the clusters first appear among the names; a medoid is
+    the member with the least summed distance to the rest of its cluster (a cluster none of whose members has a
+    number for that sum has no entry)."""
+
+    def __init__(self, n_clusters: int | None = None, height: float | None = None, distance_mode: str = "mash", *,
+                 k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
+                 mash_canonical_kmers: bool | None = None, linkage: str = "average") -> None:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        if distance_mode not in _distance.MODES:
+            raise ValueError(f"Unexpected distance {distance_mode!r}.")
+        if moltype not in ("dna", "rna") and mash_canonical_kmers:
+            raise ValueError("Canonical kmers only supported for dna sequences.")
+        if distance_mode == "mash" and sketch_size is None:
+            raise ValueError("Expected sketch size for mash distance measure.")
+        if distance_mode != "mash":  # (as dvs_ctree: the sketch size means nothing to the other modes)
+            sketch_size = None
+        if (n_clusters is None) == (height is None):
+            raise ValueError("dvs_clusters takes exactly one of n_clusters and height")
+        if n_clusters is not None and (isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer))
+                                       or n_clusters < 1):
+            raise ValueError(f"n_clusters must be an integer of 1 or more, not {n_clusters!r}")
+        if height is not None and np.isnan(float(height)):
+            raise ValueError("the height of a cut cannot be NaN")
+        _distance.linkage_method_code(linkage)
+        self._n_clusters, self._height = n_clusters, height
+        self._moltype = moltype
+        self._k = k
+        self._num_states = _num_states(moltype)
+        self._sketch_size = sketch_size
+        self._distance_mode = distance_mode
+        self._mash_canonical = mash_canonical_kmers
+        self._linkage = linkage
+
+    def main(self, seqs):
+        names, data, _ = _as_mapping(seqs, self._moltype)
+        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
+        newick, _, sc = _cluster.ctree_clusters(
+            arrays, n_clusters=self._n_clusters, height=self._height, k=self._k, sketch_size=self._sketch_size,
+            distance_mode=self._distance_mode, mash_canonical_kmers=self._mash_canonical, num_states=self._num_states,
+            linkage=self._linkage)
+        clusters: dict = {c: [] for c in range(sc.sizes.size)}
+        for name, c in zip(names, sc.labels.tolist()):
+            clusters[c].append(name)
+        return {"tree": newick, "clusters": clusters,
+                "medoids": {c: names[i] for c, i in enumerate(sc.medoids.tolist()) if i >= 0},
+                "silhouette": {name: float(v) for name, v in zip(names, sc.silhouette)},
+                "mean_silhouette": sc.mean_silhouette}

@@ -8,6 +8,10 @@ Newick string.  `ctree` builds the tree on the device by default (`linkage`: sci
 nearest-neighbour chain, or for single linkage its minimum spanning tree, in one persistent
 workgroup, csrc/linkage.hip, the same linkage matrix bit for bit); `tree="sklearn"` keeps the
 reference's host path (`make_cluster_tree`, average linkage only).
+
+Beyond the reference: the flat clusters of a tree (`cut_tree`: scipy's fcluster partitions, on the host), the
+scores of a labelling (`cluster_scores`, csrc/crossdist.hip: sums within a cluster, the nearest other cluster,
+silhouettes, medoids) and both behind one call (`ctree_clusters`).
 """
 
 from __future__ import annotations
@@ -18,7 +22,7 @@ from collections.abc import Sequence
 
 import numpy as np
 
-from . import distance, engine
+from . import _lib, distance, engine
 
 
 def nested_tuple_tree(seq_names: Sequence[str], pairwise_distances: np.ndarray):
@@ -139,3 +143,96 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     if tree == "sklearn":
         return make_cluster_tree(names, distances(arrays, *args))
     return linkage_to_newick(names, tree_of(arrays, *args, method=linkage))
+
+
+def cut_tree(Z, *, n_clusters: int | None = None, height: float | None = None) -> np.ndarray:
+    """the flat clusters of a linkage matrix Z (scipy's layout, as `linkage` returns it) -> int64 [n], the cluster
+    of every leaf, numbered by first appearance in leaf order (leaf 0 is in cluster 0).  Exactly one of:
+    height=t, every merge of height <= t applied: the partition of scipy's fcluster(Z, t, "distance");
+    n_clusters=K, the partition of fcluster(Z, K, "maxclust"): the first n - K merges and every following merge of the
+    same height as the last of them -- a cut never separates merges of equal height, so fewer than K clusters may
+    come back.  scipy's partition, not its label numbers.  Host only (dvs_linkage_cut); ValueError for a Z of the
+    wrong shape, children that are not cluster ids, heights that decrease, K < 1 or not an integer, NaN t."""
+    if (n_clusters is None) == (height is None):
+        raise ValueError("cut_tree takes exactly one of n_clusters and height")
+    z = np.asarray(Z, dtype=np.float64)
+    if z.ndim != 2 or z.shape[1] != 4 or z.shape[0] < 1:
+        raise ValueError(f"a linkage matrix of n >= 2 leaves has shape (n - 1, 4), not {z.shape}")
+    n = z.shape[0] + 1
+    kids = z[:, :2]
+    if not (np.isfinite(kids).all() and (kids >= 0).all() and (kids < 2 * n - 1).all() and (kids == np.floor(kids)).all()):
+        raise ValueError("a linkage matrix's first two columns are cluster ids in 0 .. 2 n - 2")
+    if n_clusters is not None:
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or n_clusters < 1:
+            raise ValueError(f"n_clusters must be an integer of 1 or more, not {n_clusters!r}")
+        criterion, value = _lib.CUT_NCLUSTERS, float(min(int(n_clusters), n))
+    else:
+        criterion, value = _lib.CUT_HEIGHT, float(height)
+    pairs = np.ascontiguousarray(kids, dtype=np.uint32).reshape(-1)
+    heights = np.ascontiguousarray(z[:, 2])
+    labels = np.zeros(n, dtype=np.uint32)
+    count = C.c_uint32()
+    _lib.raise_for(_lib.load().dvs_linkage_cut(None, n, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                               criterion, value, _lib.ptr(labels, C.c_uint32), C.byref(count)), None)
+    return labels.astype(np.int64)
+
+
+def cluster_scores(dist, labels, *, ctx: engine.Context | None = None) -> "distance.ClusterScores":
+    """the scores of a labelling (`distance.ClusterScores`: within, a, b, neighbour, silhouette per row; sizes,
+    medoids, mean silhouette per cluster; the overall mean) of the rows of a caller's n x n distance matrix, reduced
+    on the GPU a strip of rows at a time.  The diagonal is never read.  sklearn's silhouette_samples(dist, labels,
+    metric="precomputed") is `.silhouette`.
+
+    `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
+    as `linkage` handles it (it must live on the context's device) but only READ: it is the same afterwards.  The
+    shapes and the labels are checked before any device work."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
+        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
+            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
+        n = int(dist.shape[0])
+        src, on_device = C.c_void_p(dist.data_ptr()), 1
+    else:
+        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
+        n = d.shape[0]
+        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    lab = distance.check_labels(labels, n)
+    if on_device and n:
+        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    return distance._run_cluster_scores(ctx or (engine.default_context() if n else None), "dvs_cluster_scores", lab, src,
+                                        on_device, n)
+
+
+def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float | None = None, k: int = 12,
+                   sketch_size: int | None = 3000, distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
+                   num_states: int = 4, linkage: str = "average"):
+    """sequences {name: uint8 codes} -> (Newick string, Z, distance.ClusterScores): `ctree`'s device tree, its cut
+    (`cut_tree`: exactly one of n_clusters and height) and the scores of the cut's clusters, row i the i-th name.
+    Argument checks as `ctree`, before any device work.
+
+    The sketches (mash) or the count matrix (euclidean, jsd) are made once and stay in HBM.  The tree stage overwrites
+    its N x N matrix, so the scores compute the distances a second time, strip by strip (the same cells bit for bit):
+    one more pass of the pair kernels and no second N x N buffer."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    code = distance.linkage_method_code(linkage)
+    if (n_clusters is None) == (height is None):
+        raise ValueError("ctree_clusters takes exactly one of n_clusters and height")
+    names = list(seqs)
+    if len(names) < 2:
+        raise ValueError("need at least two sequences to build a tree")
+    dev = distance.device_side([seqs[n] for n in names], distance_mode,
+                               *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
+    try:
+        if distance_mode == "mash":
+            Z = dev.linkage(linkage)
+        else:
+            entry = "dvs_matrix_jsd_linkage" if distance_mode == "jsd" else "dvs_matrix_euclidean_linkage"
+            Z = distance.run_linkage(dev.ctx, dev.nrows, entry, dev._h, code)
+        labels = cut_tree(Z, n_clusters=n_clusters, height=height)
+        return linkage_to_newick(names, Z), Z, distance.device_side_scores(dev, labels, distance_mode)
+    finally:
+        dev.close()

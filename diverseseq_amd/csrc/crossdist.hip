@@ -11,8 +11,9 @@
 // the queries; the mash kernel is another wrapper of the one merge in mash.hip.
 //
 // The M x N matrix never has to exist whole: a stage (dvs_cross_stage) fills rows [q0, q0 + mq) into a strip, and the
-// two drivers walk the queries strip by strip -- to the host matrix, or through cross_topk_kernel to the kk nearest
-// references per query.  The strip is CROSS_STRIP_BYTES at most (and a tile row of 32 queries at least).
+// drivers walk the queries strip by strip -- to the host matrix, through cross_topk_kernel to the kk nearest
+// references per query, or (queries = references) through cluster_scores_kernel to the scores of a labelling of the
+// rows.  The strip is CROSS_STRIP_BYTES at most (and a tile row of 32 queries at least).
 #include "dvs_internal.h"
 #include "rowdist_dev.h"
 
@@ -261,6 +262,78 @@ __global__ __launch_bounds__(TOPK_THREADS) void cross_topk_kernel(const double *
     }
 }
 
+// The scores of a labelling over the rows of a strip (mq x n; row r of the strip is position q0 + r of the n labelled
+// positions, the columns are the same n positions): include/dvs_hip.h "flat clusters".  order[start[c] .. start[c + 1])
+// lists the positions of cluster c in ascending order (a stable counting sort by label, once per call on the host).
+// One workgroup per row; wave w takes the clusters c = w, w + 4, ...: its 64 lanes stride over the cluster's list and
+// add the row's cells, the own position skipped (cell (i, i) is never read), a lane its cells in list order, the 64
+// partials by the xor-shuffle tree -- an order that (n, labels) fix, so the strip height, the grid and the run cannot
+// change a bit.  A wave keeps its own cluster's sum and the least mean of the others (ascending c, strict <: a tie
+// stays with the lower c; a NaN mean compares false and is never taken) in registers; the four waves meet in LDS in
+// wave order under the same rule.  No atomics; LDS does not grow with n or K.
+constexpr int CLS_THREADS = 256;
+constexpr uint32_t CLS_WAVES = CLS_THREADS / 64;
+__global__ __launch_bounds__(CLS_THREADS) void cluster_scores_kernel(
+    const double *__restrict__ strip, uint32_t n, uint32_t q0, const uint32_t *__restrict__ order,
+    const uint32_t *__restrict__ start, const uint32_t *__restrict__ label, uint32_t n_clusters, double *__restrict__ within,
+    double *__restrict__ a_out, double *__restrict__ b_out, uint32_t *__restrict__ neighbour, double *__restrict__ silhouette) {
+    __shared__ double s_mean[CLS_WAVES];
+    __shared__ uint32_t s_c[CLS_WAVES];
+    __shared__ double s_own;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t self = q0 + blockIdx.x, own = label[self];
+    const double *g = strip + uint64_t(blockIdx.x) * n;
+    double best = NAN, own_sum = 0.0;
+    uint32_t bc = NONE;
+    for (uint32_t c = wave; c < n_clusters; c += CLS_WAVES) {
+        const uint32_t p0 = start[c], p1 = start[c + 1];
+        if (p0 == p1) continue;  // an empty cluster
+        double s = 0.0;
+#pragma unroll 4
+        for (uint32_t p = p0 + lane; p < p1; p += 64) {
+            const uint32_t j = order[p];
+            if (j != self) s += g[j];
+        }
+        s = dvs_wave_sum(s);
+        if (c == own) {
+            own_sum = s;
+        } else {
+            const double mean = s / double(p1 - p0);
+            if (bc == NONE ? mean == mean : mean < best) {
+                best = mean;
+                bc = c;
+            }
+        }
+    }
+    if (lane == 0) {
+        s_mean[wave] = best;
+        s_c[wave] = bc;
+        if (own % CLS_WAVES == wave) s_own = own_sum;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    best = s_mean[0];
+    bc = s_c[0];
+#pragma unroll
+    for (uint32_t w = 1; w < CLS_WAVES; w++) {
+        const double e = s_mean[w];
+        const uint32_t ec = s_c[w];
+        if (ec != NONE && (bc == NONE || e < best || (e == best && ec < bc))) {
+            best = e;
+            bc = ec;
+        }
+    }
+    const uint32_t size = start[own + 1] - start[own];
+    const double w_i = s_own, a = size > 1 ? w_i / double(size - 1) : 0.0, b = bc == NONE ? NAN : best;
+    double sil = 0.0;
+    if (size > 1 && !(a == 0.0 && b == 0.0)) sil = (b - a) / (a > b ? a : b);
+    within[blockIdx.x] = w_i;
+    a_out[blockIdx.x] = a;
+    b_out[blockIdx.x] = b;
+    neighbour[blockIdx.x] = bc;
+    silhouette[blockIdx.x] = sil;
+}
+
 // ---- the two count-matrix modes
 
 // what both of them check: one device, equal bin counts, the row lists, the square path's limit on the columns
@@ -349,7 +422,34 @@ dvs_cross_stage euclid_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint
     return st;
 }
 
-// ---- the two drivers
+// A caller's own n x n matrix as a stage: rows [q0, q0 + mq) are copied into the strip, from the host or within the
+// device; the matrix is only read.
+dvs_cross_stage matrix_rows_stage(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n) {
+    dvs_cross_stage st{"distance matrix rows", n, n};
+    st.check = [=] {
+        if (dist_on_device) {
+            hipPointerAttribute_t attr;
+            if (hipPointerGetAttributes(&attr, dist) != hipSuccess) {
+                (void)hipGetLastError();
+                return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
+            }
+            if (attr.device != ctx->device)
+                return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
+                                     attr.device, ctx->device);
+        }
+        return dvs_rows_check(ctx, n);
+    };
+    st.scratch_bytes = 0;
+    st.scratch_what = "";
+    st.prepare = [](void *) { return hipSuccess; };
+    st.enqueue = [=](uint32_t q0, uint32_t mq, double *d_strip, void *) {
+        return hipMemcpyAsync(d_strip, dist + size_t(q0) * n, size_t(mq) * n * 8,
+                              dist_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
+    };
+    return st;
+}
+
+// ---- the three drivers
 
 // query rows per strip: what CROSS_STRIP_BYTES holds, in whole tile rows and one tile row at least; or the knob
 uint32_t strip_rows(const dvs_ctx *ctx, const dvs_cross_stage &st) {
@@ -420,6 +520,81 @@ int cross_to_topk(dvs_ctx *ctx, const dvs_cross_stage &st, uint32_t kk, uint32_t
     });
 }
 
+// The scores of a labelling (include/dvs_hip.h "flat clusters") over a stage whose queries and references are the same
+// n positions: the positions sorted by label once (a stable counting sort: order, start) and uploaded in front of the
+// first strip, cluster_scores_kernel behind each strip's distances, its five outputs copied out strip by strip; the
+// medoids from the n sums on the host.
+int cross_to_cluster_scores(dvs_ctx *ctx, const dvs_cross_stage &st, const uint32_t *labels, uint32_t n_clusters,
+                            double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
+                            uint32_t *medoids) {
+    const uint32_t n = st.n;
+    if (n == 0) return DVS_OK;
+    if (!labels || !within) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    for (uint32_t i = 0; i < n; i++)
+        if (labels[i] >= n_clusters)
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "row %u carries label %u: below the number of clusters (%u)", i,
+                                 labels[i], n_clusters);
+    if (int rc = st.check()) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> start(size_t(n_clusters) + 1, 0), order(n);
+    for (uint32_t i = 0; i < n; i++) start[labels[i] + 1]++;
+    for (uint32_t c = 0; c < n_clusters; c++) start[c + 1] += start[c];
+    {
+        std::vector<uint32_t> next(start.begin(), start.end() - 1);
+        for (uint32_t i = 0; i < n; i++) order[next[labels[i]]++] = i;
+    }
+    const uint32_t rows = strip_rows(ctx, st);
+    // one block: order [n], start [K + 1], label [n], then per strip row four doubles and the neighbour
+    const size_t o_start = size_t(n) * 4, o_label = o_start + (size_t(n_clusters) + 1) * 4;
+    const size_t o_out = (o_label + size_t(n) * 4 + 7) / 8 * 8;
+    PooledBuf d_buf{ctx};
+    int rc = dvs_dev_alloc(ctx, &d_buf.p, o_out + size_t(rows) * 36, "cluster lists and scores");
+    if (rc) return rc;
+    char *base = d_buf.as<char>();
+    uint32_t *d_order = reinterpret_cast<uint32_t *>(base), *d_start = reinterpret_cast<uint32_t *>(base + o_start),
+             *d_label = reinterpret_cast<uint32_t *>(base + o_label);
+    double *d_within = reinterpret_cast<double *>(base + o_out), *d_a = d_within + rows, *d_b = d_a + rows, *d_sil = d_b + rows;
+    uint32_t *d_nb = reinterpret_cast<uint32_t *>(d_sil + rows);
+    hipError_t e = hipMemcpyAsync(d_order, order.data(), size_t(n) * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_start, start.data(), start.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_label, labels, size_t(n) * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return dvs_hip_fail(ctx, e, "cluster lists upload");
+    }
+    rc = cross_walk(ctx, st, rows, [&](uint32_t q0, uint32_t mq, double *d_strip) {
+        hipLaunchKernelGGL(cluster_scores_kernel, dim3(mq), dim3(CLS_THREADS), 0, ctx->stream, d_strip, n, q0, d_order,
+                           d_start, d_label, n_clusters, d_within, d_a, d_b, d_nb, d_sil);
+        hipError_t ce = hipGetLastError();
+        auto out = [&](void *host, const void *dev, size_t width) {
+            if (ce == hipSuccess && host)
+                ce = hipMemcpyAsync(static_cast<char *>(host) + size_t(q0) * width, dev, size_t(mq) * width,
+                                    hipMemcpyDeviceToHost, ctx->stream);
+        };
+        out(within, d_within, 8);
+        out(a, d_a, 8);
+        out(b, d_b, 8);
+        out(silhouette, d_sil, 8);
+        out(neighbour, d_nb, 4);
+        return ce;
+    });
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);  // (the uploads read the lists above)
+        return rc;
+    }
+    if (medoids) {
+        for (uint32_t c = 0; c < n_clusters; c++) {
+            uint32_t best = NONE;
+            for (uint32_t p = start[c]; p < start[c + 1]; p++) {  // ascending rows: strict < keeps the lowest of a tie
+                const uint32_t i = order[p];
+                if (within[i] == within[i] && (best == NONE || within[i] < within[best])) best = i;
+            }
+            medoids[c] = best;
+        }
+    }
+    return DVS_OK;
+}
+
 }  // namespace
 
 int dvs_cross_rows_check(dvs_ctx *ctx, const uint32_t *rows, uint32_t nrows, uint32_t limit, const char *side) {
@@ -470,4 +645,36 @@ extern "C" int dvs_sketches_nearest(dvs_ctx *ctx, const dvs_sketches *q, const u
                                     uint32_t sketch_size, uint32_t kk, uint32_t *idx, double *dist) {
     if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     return cross_to_topk(ctx, dvs_mash_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr, k, sketch_size), kk, idx, dist);
+}
+
+extern "C" int dvs_jsd_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
+                                      const uint32_t *labels, uint32_t n_clusters, double *within, double *a, double *b,
+                                      uint32_t *neighbour, double *silhouette, uint32_t *medoids) {
+    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return cross_to_cluster_scores(ctx, jsd_cross_stage(ctx, m, rows, n, m, rows, n), labels, n_clusters, within, a, b,
+                                   neighbour, silhouette, medoids);
+}
+
+extern "C" int dvs_euclidean_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
+                                            const uint32_t *labels, uint32_t n_clusters, double *within, double *a,
+                                            double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids) {
+    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return cross_to_cluster_scores(ctx, euclid_cross_stage(ctx, m, rows, n, m, rows, n), labels, n_clusters, within, a, b,
+                                   neighbour, silhouette, medoids);
+}
+
+extern "C" int dvs_sketches_cluster_scores(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
+                                           uint32_t sketch_size, const uint32_t *labels, uint32_t n_clusters, double *within,
+                                           double *a, double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids) {
+    if (!ctx || !sk) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return cross_to_cluster_scores(ctx, dvs_mash_cross_stage(ctx, sk, rows, n, sk, rows, n, k, sketch_size), labels,
+                                   n_clusters, within, a, b, neighbour, silhouette, medoids);
+}
+
+extern "C" int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *labels,
+                                  uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour,
+                                  double *silhouette, uint32_t *medoids) {
+    if (!ctx || (!dist && n)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return cross_to_cluster_scores(ctx, matrix_rows_stage(ctx, dist, dist_on_device, n), labels, n_clusters, within, a, b,
+                                   neighbour, silhouette, medoids);
 }

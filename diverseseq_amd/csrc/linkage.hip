@@ -36,6 +36,9 @@
 //      one pushes a cluster and a merge pops two), else an error word and an early return.
 //   2'. linkage_mst_single_kernel (single): the same workgroup shape runs Prim's loop, exactly n - 1 steps of
 //      one row read and one argmin over the compacted list of unmerged points; D is only read.
+//
+// At the end of the file, host only: dvs_linkage_cut, the flat clusters of such a tree at a height or at a number of
+// clusters (the partitions of scipy's fcluster "distance" and "maxclust").
 #include "dvs_internal.h"
 
 #include <algorithm>
@@ -581,4 +584,48 @@ extern "C" int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint3
 extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
                                    double *heights, uint32_t *sizes) {
     return dvs_linkage(ctx, dist, dist_on_device, n, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
+}
+
+// The flat clusters of a cut (host only): the first m merges applied, m from the criterion; the merges name their
+// children by scipy's ids (leaves 0 .. n - 1, merge j makes n + j), so a parent's id is above its children's and one
+// pass from the top hands every node its root.
+extern "C" int dvs_linkage_cut(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, int criterion,
+                               double value, uint32_t *labels_out, uint32_t *n_clusters_out) {
+    if (!pairs || !heights || !labels_out || !n_clusters_out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "a tree of %u leaves cannot be cut: 2 at least", n);
+    const uint32_t nm = n - 1;
+    for (uint32_t j = 0; j < nm; j++)
+        if (heights[j] != heights[j] || (j && heights[j] < heights[j - 1]))
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "merge %u: the heights of a linkage matrix must not decrease (or be NaN)", j);
+    uint32_t m = 0;
+    if (criterion == DVS_CUT_HEIGHT) {
+        if (value != value) return dvs_set_error(ctx, DVS_ERR_VALUE, "the height of a cut cannot be NaN");
+        while (m < nm && heights[m] <= value) m++;
+    } else if (criterion == DVS_CUT_NCLUSTERS) {
+        if (!(value >= 1.0) || value != std::floor(value))
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "the number of clusters must be an integer of 1 or more, not %g", value);
+        m = value >= double(n) ? 0u : n - uint32_t(value);
+        while (m > 0 && m < nm && heights[m] == heights[m - 1]) m++;  // (a cut never separates merges of equal height)
+    } else {
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "unknown cut criterion %d", criterion);
+    }
+    std::vector<uint32_t> up(size_t(n) + m);
+    for (uint32_t v = 0; v < n + m; v++) up[v] = v;
+    for (uint32_t j = 0; j < m; j++) {
+        const uint32_t x = pairs[2 * j], y = pairs[2 * j + 1];
+        if (x >= n + j || y >= n + j || x == y || up[x] != x || up[y] != y)
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "merge %u joins %u and %u: not two clusters that exist at that point", j, x, y);
+        up[x] = up[y] = n + j;
+    }
+    for (uint32_t v = n + m; v-- > 0;)
+        if (up[v] != v) up[v] = up[up[v]];  // (the parent's entry is its root already)
+    std::vector<uint32_t> label_of(size_t(n) + m, 0xFFFFFFFFu);
+    uint32_t count = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t &l = label_of[up[i]];
+        if (l == 0xFFFFFFFFu) l = count++;
+        labels_out[i] = l;
+    }
+    *n_clusters_out = count;
+    return DVS_OK;
 }

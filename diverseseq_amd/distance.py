@@ -6,11 +6,14 @@ divergence of k-mer frequencies (jsd_distances: total_jsd of a two-member set, s
 and the fused ctree stages
 (distances and the linkage tree with the N x N matrix left in HBM); and the distances between two collections
 (cross_distances: M queries against N references, no counterpart in the reference) with the k nearest references
-of every query (nearest), the M x N matrix computed strip by strip and never leaving the device."""
+of every query (nearest), the M x N matrix computed strip by strip and never leaving the device; and the scores of a
+labelling of one collection over the same strips (cluster_scores: sums within a cluster, the nearest other cluster,
+silhouettes, medoids; no counterpart in the reference)."""
 
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -264,6 +267,15 @@ class Sketches:
         kk = check_n_nearest(n_nearest, nr)
         return _run_nearest(self.ctx, "dvs_sketches_nearest", self._h, qr, nq, other._h, rr, nr, kk, self.k,
                             min(self.sketch_size, _U32_MAX))
+
+    def cluster_scores(self, labels, rows=None) -> "ClusterScores":
+        """the scores of a labelling (`ClusterScores`) of this set's sketches `rows` (None: all; labels[i] belongs to
+        rows[i]) over their mash distances, computed strip by strip (dvs_sketches_cluster_scores); ZeroDivisionError
+        as `distances`"""
+        rr, n = _row_list(rows, self.n)
+        lab = check_labels(labels, n)
+        return _run_cluster_scores(self.ctx, "dvs_sketches_cluster_scores", lab, self._h, _lib.ptr(rr, C.c_uint32), n,
+                                   self.k, min(self.sketch_size, _U32_MAX))
 
 
 def mash_distances(seqs, k: int, sketch_size: int, num_states: int = 4,
@@ -546,3 +558,106 @@ def nearest(queries, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k
         return np.zeros((0, kk), dtype=np.int64), np.zeros((0, kk), dtype=np.float64)
     return CROSS_MODES[distance_mode][1](queries, refs, kk, *mode_args(distance_mode, k, sketch_size, num_states,
                                                                         mash_canonical), ctx=ctx)
+
+
+# ---- the scores of a labelling: sums within a cluster, the nearest other cluster, silhouettes, medoids
+
+class ClusterScores(NamedTuple):
+    """The scores of a labelling of n rows into K = labels.max() + 1 clusters (include/dvs_hip.h "flat clusters").
+    Per row: labels int64; within float64, the sum of the distances to the other members of the row's cluster; a =
+    within / (size - 1), 0 for a row alone in its cluster; b, the least mean distance to the members of another
+    cluster, and neighbour int64, that cluster (a tie to the lower one, -1 and NaN where there is none); silhouette,
+    0 for a row alone in its cluster or with a = b = 0, else (b - a) / max(a, b).  Per cluster: sizes int64; medoids
+    int64, the member with the least within (a tie to the lowest row, -1 where there is none); cluster_silhouette,
+    the mean silhouette of its members (NaN for an empty cluster).  mean_silhouette: the mean over all rows."""
+    labels: np.ndarray
+    within: np.ndarray
+    a: np.ndarray
+    b: np.ndarray
+    neighbour: np.ndarray
+    silhouette: np.ndarray
+    sizes: np.ndarray
+    medoids: np.ndarray
+    cluster_silhouette: np.ndarray
+    mean_silhouette: float
+
+
+def check_labels(labels, n: int) -> np.ndarray:
+    """a labelling of n rows as the dvs_*cluster_scores entries take it (uint32 [n]), checked before any device work:
+    ValueError unless it is a one-dimensional sequence of n integers in 0 .. 2^32 - 2"""
+    a = np.asarray(labels)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError("labels: a one-dimensional sequence of integers")
+    if a.size != n:
+        raise ValueError(f"{a.size} labels for {n} rows")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= _U32_MAX):
+        raise ValueError("label out of range: a cluster label is an integer of 0 or more")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _run_cluster_scores(ctx, entry: str, lab: np.ndarray, *front) -> ClusterScores:
+    """the dvs_*cluster_scores call `entry`(ctx, *front, labels, n_clusters, outputs...) -> ClusterScores; the means
+    per cluster and overall from the n silhouettes here"""
+    n = lab.size
+    k = int(lab.max()) + 1 if n else 0
+    within, a, b, sil = (np.zeros(n, dtype=np.float64) for _ in range(4))
+    nb = np.zeros(n, dtype=np.uint32)
+    med = np.zeros(k, dtype=np.uint32)
+    if n:
+        ctx.check(getattr(ctx._L, entry)(ctx._h, *front, _lib.ptr(lab, C.c_uint32), k, _lib.ptr(within, C.c_double),
+                                         _lib.ptr(a, C.c_double), _lib.ptr(b, C.c_double), _lib.ptr(nb, C.c_uint32),
+                                         _lib.ptr(sil, C.c_double), _lib.ptr(med, C.c_uint32)))
+    neighbour, medoids = nb.astype(np.int64), med.astype(np.int64)
+    neighbour[nb == _U32_MAX] = -1
+    medoids[med == _U32_MAX] = -1
+    sizes = np.bincount(lab, minlength=k).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_cluster = np.bincount(lab, weights=sil, minlength=k) / sizes
+    return ClusterScores(lab.astype(np.int64), within, a, b, neighbour, sil, sizes, medoids, per_cluster,
+                         float(sil.mean()) if n else float("nan"))
+
+
+_MATRIX_SCORES = {"jsd": "dvs_jsd_cluster_scores", "euclidean": "dvs_euclidean_cluster_scores"}
+
+
+def matrix_cluster_scores(m: "engine.CountMatrix", labels, mode: str = "jsd", rows=None) -> ClusterScores:
+    """the scores of a labelling of rows `rows` of m (None: all; labels[i] belongs to rows[i]) over their `mode` ("jsd",
+    "euclidean") distances, the cells of `matrix_cross_distances(m, m, mode, rows, rows)` computed strip by strip and
+    reduced on the device: the n x n matrix never exists whole"""
+    _matrix_mode(mode)
+    rr, n = _row_list(rows, m.nrows)
+    lab = check_labels(labels, n)
+    return _run_cluster_scores(m.ctx, _MATRIX_SCORES[mode], lab, m._h, _lib.ptr(rr, C.c_uint32), n)
+
+
+def cluster_scores(seqs, labels, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+                   num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None) -> ClusterScores:
+    """the scores of a labelling of the sequences (`ClusterScores`) over their `distance_mode` distances: the cells
+    MODES[distance_mode] gives the collection (off the diagonal, which is never read), computed strip by strip and never
+    held whole.  Argument checks as cluster.ctree, before any device work; ZeroDivisionError (mash) when two sequences
+    have an empty sketch; NaN (jsd, euclidean) for a sequence without a valid k-mer."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    seqs = list(seqs)
+    lab = check_labels(labels, len(seqs))
+    if not seqs:
+        return _run_cluster_scores(ctx, "", lab)
+    dev = device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx)
+    try:
+        return device_side_scores(dev, lab, distance_mode)
+    finally:
+        dev.close()
+
+
+def device_side(seqs, distance_mode: str, *args, ctx: engine.Context | None = None):
+    """what a distance mode keeps in HBM of a batch, made once: its Sketches (mash) or its count matrix (euclidean,
+    jsd); args: mode_args(...)"""
+    if distance_mode == "mash":
+        return Sketches(seqs, *args, ctx=ctx)
+    return (ctx or engine.default_context()).build_matrix(seqs, *args)
+
+
+def device_side_scores(dev, labels, distance_mode: str) -> ClusterScores:
+    """the scores of a labelling of every row of `device_side`'s result"""
+    if distance_mode == "mash":
+        return dev.cluster_scores(labels)
+    return matrix_cluster_scores(dev, labels, distance_mode)

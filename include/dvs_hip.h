@@ -470,6 +470,58 @@ int dvs_sketches_nearest(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_
                          const uint32_t *r_rows, uint32_t nr, uint32_t k, uint32_t sketch_size, uint32_t kk,
                          uint32_t *idx, double *dist);
 
+/* ---- flat clusters of a tree: the cut, and the scores of a labelling ------------------------------- *
+ * dvs_linkage_cut turns dvs_linkage's outputs (pairs[2 (n - 1)], heights[n - 1], as they are) into flat clusters on
+ * the host (no device work; ctx only takes the error text and may be NULL):
+ *   DVS_CUT_HEIGHT, value t     every merge j with heights[j] <= t is applied: the partition of scipy's
+ *                               fcluster(Z, t, "distance")
+ *   DVS_CUT_NCLUSTERS, value K  the first m = max(n - K, 0) merges, and every following merge of the same height as
+ *                               merge m - 1 (a cut never separates merges of equal height, so fewer than K clusters
+ *                               may come back): the partition of scipy's fcluster(Z, K, "maxclust")
+ * labels_out[n]: the cluster of every leaf, in [0, *n_clusters_out), numbered by first appearance in leaf order (leaf
+ * 0 is in cluster 0): scipy's partition, not its label numbers.  (No counterpart in the reference.)
+ *   DVS_ERR_VALUE: n < 2, K < 1 or not an integer value, NaN t, any other criterion, heights that are not
+ *                  non-decreasing (the five methods built here are monotone; a foreign Z may not be), a pair that
+ *                  names a cluster not yet made or already merged */
+#define DVS_CUT_HEIGHT 0
+#define DVS_CUT_NCLUSTERS 1
+int dvs_linkage_cut(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, int criterion, double value,
+                    uint32_t *labels_out, uint32_t *n_clusters_out);
+/* The scores of a labelling of n rows over the n x n distances D of a mode, computed strip by strip as the cross
+ * entries above compute them (queries = references = `rows` of the handle, NULL: rows 0 .. n - 1; the same cells bit
+ * for bit), the matrix never existing whole.  labels[n] in [0, n_clusters); a label nobody carries is an empty cluster
+ * and is skipped.  With n_c the size of cluster c, for every row i of cluster l:
+ *   within[i]      sum of D(i, j) over the other members j of l.  Cell (i, i) is never read into a sum, whatever it holds
+ *   a[i]           within[i] / (n_l - 1); 0 when i is alone in l
+ *   b[i], neighbour[i]  the least mean distance S(i, c) / n_c to the members of another non-empty cluster c, and that c;
+ *                  a tie goes to the lower c, a NaN mean is never taken; nothing to take: NaN and 0xFFFFFFFF
+ *   silhouette[i]  0 when i is alone in l (sklearn's rule) or a == b == 0, else (b - a) / max(a, b); NaN where a or b is
+ *   medoids[c]     the member of c with the least within, a tie to the lowest row, NaN never taken; 0xFFFFFFFF for a
+ *                  cluster without such a member (empty, or every member's within NaN)
+ * The order in which the terms of a sum are added depends on (n, labels) alone: the same bits on every run and for
+ * every strip height (DVS_CROSS_STRIP_ROWS).  All outputs are host arrays ([n]; medoids [n_clusters]); any may be NULL
+ * except within.  Return when they are written.  (No counterpart in the reference.)
+ * dvs_cluster_scores takes the caller's own n x n matrix (row-major float64; host, or device memory on the context's
+ * device when dist_on_device != 0) and only reads it, rows [q0, q0 + mq) at a time.
+ *   DVS_OK with nothing written: n == 0
+ *   DVS_ERR_VALUE: a label >= n_clusters (hence n_clusters == 0 with n > 0), a row index beyond the handle, a device
+ *                  mismatch, a matrix that is not device memory where it is said to be
+ *   DVS_ERR_UNSUPPORTED: n beyond the row limit of the square entries
+ *   DVS_ERR_ZERODIV: (sketches) as dvs_sketches_cross_distances over the same rows on both sides: the strips hold every
+ *                  cell, a row against itself included, so one empty sketch among the rows is enough */
+int dvs_jsd_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *labels,
+                           uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour,
+                           double *silhouette, uint32_t *medoids);
+int dvs_euclidean_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
+                                 const uint32_t *labels, uint32_t n_clusters, double *within, double *a, double *b,
+                                 uint32_t *neighbour, double *silhouette, uint32_t *medoids);
+int dvs_sketches_cluster_scores(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
+                                uint32_t sketch_size, const uint32_t *labels, uint32_t n_clusters, double *within,
+                                double *a, double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids);
+int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *labels,
+                       uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
+                       uint32_t *medoids);
+
 #ifdef __cplusplus
 }
 #endif
