@@ -51,6 +51,7 @@ EXPORTS = (
     "dvs_jsd_nearest", "dvs_euclidean_nearest", "dvs_sketches_nearest",
     "dvs_linkage_cut", "dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_sketches_cluster_scores",
     "dvs_cluster_scores",
+    "dvs_linkage_cophenet", "dvs_jsd_cophenet", "dvs_euclidean_cophenet", "dvs_sketches_cophenet", "dvs_cophenet",
 )
 
 
@@ -236,6 +237,12 @@ def load() -> C.CDLL:
             getattr(L, n).argtypes = [vp, vp, u32p, u32, *scores]
         L.dvs_sketches_cluster_scores.argtypes = [vp, vp, u32p, u32, u32, u32, *scores]
         L.dvs_cluster_scores.argtypes = [vp, vp, C.c_int, u32, *scores]
+        L.dvs_linkage_cophenet.argtypes = [vp, u32, u32p, f64p, f64p]
+        coph = [u32p, f64p, f64p, f64p, f64p]  # pairs, heights, the correlation, the row sums, the cophenetic matrix
+        for n in ("dvs_jsd_cophenet", "dvs_euclidean_cophenet"):
+            getattr(L, n).argtypes = [vp, vp, u32p, u32, *coph]
+        L.dvs_sketches_cophenet.argtypes = [vp, vp, u32p, u32, u32, u32, *coph]
+        L.dvs_cophenet.argtypes = [vp, vp, C.c_int, u32, *coph]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

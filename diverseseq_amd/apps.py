@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters"]
+           "dvs_clusters", "dvs_cophenet"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -376,3 +376,51 @@ class dvs_clusters:
                 "medoids": {c: names[i] for c, i in enumerate(sc.medoids.tolist()) if i >= 0},
                 "silhouette": {name: float(v) for name, v in zip(names, sc.silhouette)},
                 "mean_silhouette": sc.mean_silhouette}
+
+
+@_define_app
+class dvs_cophenet:
+    """How well the `dvs_ctree` tree of each linkage method represents the distances it was built from (beyond the
+    reference, which has no such app): the cophenetic correlation, scipy's cophenet(Z, Y)[0].  `main(seqs)` returns
+    {"best": method, "correlation": {method: float}, "tree": Newick string of the best method}; the best is the method
+    of the largest correlation, a tie to the one named first, a NaN correlation (two sequences, equal distances) never
+    taken -- with none to take, the first method."""
+
+    def __init__(self, methods=("single", "complete", "average", "weighted", "ward"), distance_mode: str = "mash", *,
+                 k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
+                 mash_canonical_kmers: bool | None = None) -> None:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        if distance_mode not in _distance.MODES:
+            raise ValueError(f"Unexpected distance {distance_mode!r}.")
+        if moltype not in ("dna", "rna") and mash_canonical_kmers:
+            raise ValueError("Canonical kmers only supported for dna sequences.")
+        if distance_mode == "mash" and sketch_size is None:
+            raise ValueError("Expected sketch size for mash distance measure.")
+        if distance_mode != "mash":  # (as dvs_ctree: the sketch size means nothing to the other modes)
+            sketch_size = None
+        methods = [methods] if isinstance(methods, str) else list(methods)
+        if not methods:
+            raise ValueError("dvs_cophenet takes one linkage method at least")
+        for method in methods:
+            _distance.linkage_method_code(method)
+        self._methods = methods
+        self._moltype = moltype
+        self._k = k
+        self._num_states = _num_states(moltype)
+        self._sketch_size = sketch_size
+        self._distance_mode = distance_mode
+        self._mash_canonical = mash_canonical_kmers
+
+    def main(self, seqs):
+        names, data, _ = _as_mapping(seqs, self._moltype)
+        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
+        trees = _cluster.compare_linkages(
+            arrays, self._methods, k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
+            mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+        corr = {method: float(r) for method, (_, r) in trees.items()}
+        best = self._methods[0]
+        for method in self._methods:
+            if corr[method] == corr[method] and not corr[best] >= corr[method]:
+                best = method
+        return {"best": best, "correlation": corr, "tree": _cluster.linkage_to_newick(names, trees[best][0])}

@@ -11,7 +11,9 @@ reference's host path (`make_cluster_tree`, average linkage only).
 
 Beyond the reference: the flat clusters of a tree (`cut_tree`: scipy's fcluster partitions, on the host), the
 scores of a labelling (`cluster_scores`, csrc/crossdist.hip: sums within a cluster, the nearest other cluster,
-silhouettes, medoids) and both behind one call (`ctree_clusters`).
+silhouettes, medoids) and both behind one call (`ctree_clusters`); how well a tree represents its distances (`cophenet`:
+scipy's cophenet, the correlation reduced on the GPU by csrc/crossdist.hip's cophenet_kernel; `ctree_cophenet`,
+`compare_linkages`).
 """
 
 from __future__ import annotations
@@ -155,21 +157,14 @@ def cut_tree(Z, *, n_clusters: int | None = None, height: float | None = None) -
     wrong shape, children that are not cluster ids, heights that decrease, K < 1 or not an integer, NaN t."""
     if (n_clusters is None) == (height is None):
         raise ValueError("cut_tree takes exactly one of n_clusters and height")
-    z = np.asarray(Z, dtype=np.float64)
-    if z.ndim != 2 or z.shape[1] != 4 or z.shape[0] < 1:
-        raise ValueError(f"a linkage matrix of n >= 2 leaves has shape (n - 1, 4), not {z.shape}")
-    n = z.shape[0] + 1
-    kids = z[:, :2]
-    if not (np.isfinite(kids).all() and (kids >= 0).all() and (kids < 2 * n - 1).all() and (kids == np.floor(kids)).all()):
-        raise ValueError("a linkage matrix's first two columns are cluster ids in 0 .. 2 n - 2")
+    pairs, heights = distance.check_linkage_matrix(Z)
+    n = heights.size + 1
     if n_clusters is not None:
         if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or n_clusters < 1:
             raise ValueError(f"n_clusters must be an integer of 1 or more, not {n_clusters!r}")
         criterion, value = _lib.CUT_NCLUSTERS, float(min(int(n_clusters), n))
     else:
         criterion, value = _lib.CUT_HEIGHT, float(height)
-    pairs = np.ascontiguousarray(kids, dtype=np.uint32).reshape(-1)
-    heights = np.ascontiguousarray(z[:, 2])
     labels = np.zeros(n, dtype=np.uint32)
     count = C.c_uint32()
     _lib.raise_for(_lib.load().dvs_linkage_cut(None, n, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
@@ -205,6 +200,14 @@ def cluster_scores(dist, labels, *, ctx: engine.Context | None = None) -> "dista
                                         on_device, n)
 
 
+def device_side_tree(dev, distance_mode: str, method: str) -> np.ndarray:
+    """Z of `method` over every row of `distance.device_side`'s result, by the mode's fused tree entry"""
+    if distance_mode == "mash":
+        return dev.linkage(method)
+    entry = "dvs_matrix_jsd_linkage" if distance_mode == "jsd" else "dvs_matrix_euclidean_linkage"
+    return distance.run_linkage(dev.ctx, dev.nrows, entry, dev._h, distance.linkage_method_code(method))
+
+
 def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float | None = None, k: int = 12,
                    sketch_size: int | None = 3000, distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
                    num_states: int = 4, linkage: str = "average"):
@@ -218,7 +221,7 @@ def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float |
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
     distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
-    code = distance.linkage_method_code(linkage)
+    distance.linkage_method_code(linkage)
     if (n_clusters is None) == (height is None):
         raise ValueError("ctree_clusters takes exactly one of n_clusters and height")
     names = list(seqs)
@@ -227,12 +230,98 @@ def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float |
     dev = distance.device_side([seqs[n] for n in names], distance_mode,
                                *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
     try:
-        if distance_mode == "mash":
-            Z = dev.linkage(linkage)
-        else:
-            entry = "dvs_matrix_jsd_linkage" if distance_mode == "jsd" else "dvs_matrix_euclidean_linkage"
-            Z = distance.run_linkage(dev.ctx, dev.nrows, entry, dev._h, code)
+        Z = device_side_tree(dev, distance_mode, linkage)
         labels = cut_tree(Z, n_clusters=n_clusters, height=height)
         return linkage_to_newick(names, Z), Z, distance.device_side_scores(dev, labels, distance_mode)
+    finally:
+        dev.close()
+
+
+def cophenet(Z, dist=None, *, matrix: bool = False, ctx: engine.Context | None = None):
+    """scipy.cluster.hierarchy.cophenet for a linkage matrix Z in scipy's layout -- any well-formed one: the heights
+    need not be monotone, so scipy's centroid and median trees are fine.
+
+    dist=None: the cophenetic distances as the square matrix, float64 [n, n] -- squareform(scipy's cophenet(Z)) bit for
+    bit; host only (dvs_linkage_cophenet).  Otherwise `distance.CopheneticScores`: the correlation of the rows of a
+    caller's n x n distance matrix with the cophenetic distances (scipy's cophenet(Z, Y)[0] for its condensed form Y),
+    reduced on the GPU a strip of rows at a time; the diagonal is never read; matrix=True also brings the cophenetic
+    matrix back.  `dist`: as `cluster_scores` takes it -- anything np.asarray(dist, float64) takes, or a square,
+    contiguous float64 torch tensor on the context's device, which is only READ.  The shapes are checked before any
+    device work; ValueError for a Z whose merges name a cluster not yet made or already merged."""
+    if dist is None:
+        pairs, heights = distance.check_linkage_matrix(Z)
+        n = heights.size + 1
+        coph = np.zeros((n, n), dtype=np.float64)
+        _lib.raise_for(_lib.load().dvs_linkage_cophenet(None, n, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                                        _lib.ptr(coph, C.c_double)), None)
+        return coph
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
+        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
+            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
+        n = int(dist.shape[0])
+        src, on_device = C.c_void_p(dist.data_ptr()), 1
+    else:
+        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
+        n = d.shape[0]
+        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    if n == 0:  # nothing to compute: no device work either
+        if np.asarray(Z).size:
+            raise ValueError(f"a linkage matrix of 0 leaves is empty, not of shape {np.asarray(Z).shape}")
+        return distance.CopheneticScores(float("nan"), np.zeros((5, 0)), np.zeros((0, 0)) if matrix else None)
+    pairs, heights = distance.check_linkage_matrix(Z, n)
+    if on_device:
+        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    return distance._run_cophenet(ctx or engine.default_context(), "dvs_cophenet", n, pairs, heights, matrix, src, on_device, n)
+
+
+def ctree_cophenet(seqs: dict, *, linkage: str = "average", k: int = 12, sketch_size: int | None = 3000,
+                   distance_mode: str = "mash", mash_canonical_kmers: bool | None = None, num_states: int = 4,
+                   matrix: bool = False):
+    """sequences {name: uint8 codes} -> (Newick string, Z, distance.CopheneticScores): `ctree`'s device tree and its
+    cophenetic correlation with the distances it was built from, leaf i the i-th name.  Argument checks as `ctree`,
+    before any device work.  As in `ctree_clusters` the sketches or the count matrix are made once, and the walk computes
+    the distances a second time, strip by strip (the same cells bit for bit)."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    distance.linkage_method_code(linkage)
+    names = list(seqs)
+    if len(names) < 2:
+        raise ValueError("need at least two sequences to build a tree")
+    dev = distance.device_side([seqs[n] for n in names], distance_mode,
+                               *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
+    try:
+        Z = device_side_tree(dev, distance_mode, linkage)
+        return linkage_to_newick(names, Z), Z, distance.device_side_cophenet(dev, Z, distance_mode, matrix=matrix)
+    finally:
+        dev.close()
+
+
+def compare_linkages(seqs: dict, methods: Sequence[str] = ("single", "complete", "average", "weighted", "ward"), *,
+                     k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
+                     mash_canonical_kmers: bool | None = None, num_states: int = 4) -> dict:
+    """sequences {name: uint8 codes} -> {method: (Z, cophenetic correlation)} for every linkage method of `methods`:
+    which of them represents these distances best.  The sketches or the count matrix are made once; then a tree and a
+    walk per method (`ctree_cophenet`'s, the same bits).  Argument checks as `ctree`, before any device work."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    methods = list(methods)
+    for method in methods:
+        distance.linkage_method_code(method)
+    names = list(seqs)
+    if len(names) < 2:
+        raise ValueError("need at least two sequences to build a tree")
+    dev = distance.device_side([seqs[n] for n in names], distance_mode,
+                               *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
+    try:
+        out = {}
+        for method in methods:
+            Z = device_side_tree(dev, distance_mode, method)
+            out[method] = (Z, distance.device_side_cophenet(dev, Z, distance_mode).correlation)
+        return out
     finally:
         dev.close()

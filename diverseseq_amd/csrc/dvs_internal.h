@@ -232,6 +232,13 @@ int dvs_linkage_check_method(dvs_ctx *ctx, int method);
 int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
                        double *heights, uint32_t *sizes);
 
+// linkage.hip, host only: the in-order walk of the tree behind dvs_linkage's outputs (include/dvs_hip.h "cophenetic
+// distances"): order[n] the leaves in dendrogram order, pos[n] its inverse, gap[n - 1] the merge between positions p
+// and p + 1, *c_bar the mean of all cophenetic distances.  DVS_ERR_VALUE for n < 2 or a pair that names a cluster not
+// yet made or already merged; the heights need not be monotone.
+int dvs_cophenet_walk(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, uint32_t *order,
+                      uint32_t *pos, uint32_t *gap, double *c_bar);
+
 // One distance mode of ctree, as the drivers of rowdist.hip take it: "fill this device n x n f64 matrix" on the
 // context's stream, with what differs from mode to mode beside it.
 struct dvs_dist_stage {

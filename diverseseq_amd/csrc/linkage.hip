@@ -629,3 +629,71 @@ extern "C" int dvs_linkage_cut(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, 
     *n_clusters_out = count;
     return DVS_OK;
 }
+
+// The in-order walk (host only, iterative: a caterpillar of any depth is fine).  A node on the stack is either to be
+// expanded (its right child, the merge itself and its left child pushed, so that they come off left first) or, marked,
+// a merge met between its two subtrees: it owns the gap behind the leaf emitted last.
+int dvs_cophenet_walk(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, uint32_t *order,
+                      uint32_t *pos, uint32_t *gap, double *c_bar) {
+    if (n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "a tree of %u leaves has no cophenetic distances: 2 at least", n);
+    const uint32_t nm = n - 1;
+    std::vector<uint32_t> size(2 * size_t(n) - 1, 1u);
+    std::vector<bool> used(2 * size_t(n) - 1, false);
+    long double sum = 0.0L;
+    for (uint32_t j = 0; j < nm; j++) {
+        const uint32_t x = pairs[2 * j], y = pairs[2 * j + 1];
+        if (x >= n + j || y >= n + j || x == y || used[x] || used[y])
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "merge %u joins %u and %u: not two clusters that exist at that point", j, x, y);
+        used[x] = used[y] = true;
+        size[n + j] = size[x] + size[y];
+        sum += (long double)(uint64_t(size[x]) * size[y]) * (long double)heights[j];
+    }
+    *c_bar = double(sum / ((long double)n * (long double)nm / 2.0L));
+    constexpr uint32_t MARK = 0x80000000u;  // (ids stay below 2^31: n is bounded by the square entries' row limit)
+    std::vector<uint32_t> stack;
+    stack.push_back(2 * n - 2);
+    uint32_t at = 0;
+    while (!stack.empty()) {
+        const uint32_t v = stack.back();
+        stack.pop_back();
+        if (v & MARK) {
+            gap[at - 1] = v & ~MARK;
+        } else if (v < n) {
+            pos[v] = at;
+            order[at++] = v;
+        } else {
+            const uint32_t j = v - n;
+            stack.push_back(pairs[2 * j + 1]);
+            stack.push_back(j | MARK);
+            stack.push_back(pairs[2 * j]);
+        }
+    }
+    return DVS_OK;
+}
+
+// scipy.cluster.hierarchy.cophenet(Z) as the square matrix, on the host: per leaf the running maximum of the gaps to
+// the right of its position and of those to the left
+extern "C" int dvs_linkage_cophenet(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, double *coph) {
+    if (n == 0) return DVS_OK;
+    if (!pairs || !heights || !coph) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (n > 0x40000000u) return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "a tree of %u leaves: 2^30 at most", n);
+    std::vector<uint32_t> order(n), pos(n), gap(n - 1 ? n - 1 : 1);
+    double c_bar;
+    if (int rc = dvs_cophenet_walk(ctx, n, pairs, heights, order.data(), pos.data(), gap.data(), &c_bar)) return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        double *row = coph + size_t(i) * n;
+        const uint32_t p = pos[i];
+        row[i] = 0.0;
+        uint32_t m = 0;
+        for (uint32_t q = p + 1; q < n; q++) {
+            m = std::max(m, gap[q - 1]);
+            row[order[q]] = heights[m];
+        }
+        m = 0;
+        for (uint32_t q = p; q-- > 0;) {
+            m = std::max(m, gap[q]);
+            row[order[q]] = heights[m];
+        }
+    }
+    return DVS_OK;
+}

@@ -8,7 +8,8 @@ and the fused ctree stages
 (cross_distances: M queries against N references, no counterpart in the reference) with the k nearest references
 of every query (nearest), the M x N matrix computed strip by strip and never leaving the device; and the scores of a
 labelling of one collection over the same strips (cluster_scores: sums within a cluster, the nearest other cluster,
-silhouettes, medoids; no counterpart in the reference)."""
+silhouettes, medoids; no counterpart in the reference); and, over the same strips again, the correlation of the distances
+with the cophenetic distances of a tree (cophenet: scipy's cophenet(Z, Y)[0]; no counterpart in the reference)."""
 
 from __future__ import annotations
 
@@ -276,6 +277,15 @@ class Sketches:
         lab = check_labels(labels, n)
         return _run_cluster_scores(self.ctx, "dvs_sketches_cluster_scores", lab, self._h, _lib.ptr(rr, C.c_uint32), n,
                                    self.k, min(self.sketch_size, _U32_MAX))
+
+    def cophenet(self, Z, rows=None, matrix: bool = False) -> "CopheneticScores":
+        """the cophenetic correlation (`CopheneticScores`) of the linkage matrix Z with the mash distances of this set's
+        sketches `rows` (None: all; leaf i of Z is rows[i]), computed strip by strip (dvs_sketches_cophenet);
+        ZeroDivisionError as `cluster_scores`"""
+        rr, n = _row_list(rows, self.n)
+        pairs, heights = check_linkage_matrix(Z, n)
+        return _run_cophenet(self.ctx, "dvs_sketches_cophenet", n, pairs, heights, matrix, self._h, _lib.ptr(rr, C.c_uint32),
+                             n, self.k, min(self.sketch_size, _U32_MAX))
 
 
 def mash_distances(seqs, k: int, sketch_size: int, num_states: int = 4,
@@ -661,3 +671,81 @@ def device_side_scores(dev, labels, distance_mode: str) -> ClusterScores:
     if distance_mode == "mash":
         return dev.cluster_scores(labels)
     return matrix_cluster_scores(dev, labels, distance_mode)
+
+
+# ---- the cophenetic correlation of a tree with the distances it was built from
+
+class CopheneticScores(NamedTuple):
+    """How well a tree represents the distances D of its n leaves (include/dvs_hip.h "cophenetic distances").
+    correlation: Pearson's r between D(i, j) and the cophenetic distance coph(i, j), the height at which i and j first
+    join, over every pair i != j: scipy's cophenet(Z, Y)[0]; NaN when either has no variance (n = 2, a constant matrix).
+    row_sums float64 [5, n]: per leaf i the sums over j != i of x, y, x x, y y and x y with x = D(i, j) - c_bar, y =
+    coph(i, j) - c_bar, c_bar the mean cophenetic distance; the same bits on every run.  cophenetic: float64 [n, n],
+    squareform(scipy's cophenet(Z)) bit for bit, when it was asked for (matrix=True: n^2 doubles come back from the
+    device), else None."""
+    correlation: float
+    row_sums: np.ndarray
+    cophenetic: np.ndarray | None
+
+
+def check_linkage_matrix(Z, n: int | None = None):
+    """a linkage matrix in scipy's layout as the dvs_*cophenet entries take it, checked before any device work ->
+    (pairs uint32 [2 (n - 1)], heights float64 [n - 1]); ValueError unless its shape is (n - 1, 4) for n >= 2 leaves (n:
+    the number of rows it must describe, None: taken from Z) and its first two columns are cluster ids.  (Which ids may
+    meet in which merge is the C entry's check.)"""
+    z = np.asarray(Z, dtype=np.float64)
+    if z.ndim != 2 or z.shape[1] != 4 or z.shape[0] < 1:
+        raise ValueError(f"a linkage matrix of n >= 2 leaves has shape (n - 1, 4), not {z.shape}")
+    if n is not None and z.shape[0] != n - 1:
+        raise ValueError(f"a linkage matrix of {n} leaves has shape ({n - 1}, 4), not {z.shape}")
+    leaves = z.shape[0] + 1
+    kids = z[:, :2]
+    if not (np.isfinite(kids).all() and (kids >= 0).all() and (kids < 2 * leaves - 1).all() and (kids == np.floor(kids)).all()):
+        raise ValueError("a linkage matrix's first two columns are cluster ids in 0 .. 2 n - 2")
+    return np.ascontiguousarray(kids, dtype=np.uint32).reshape(-1), np.ascontiguousarray(z[:, 2])
+
+
+def _run_cophenet(ctx, entry: str, n: int, pairs, heights, matrix: bool, *front) -> CopheneticScores:
+    """the dvs_*cophenet call `entry`(ctx, *front, pairs, heights, outputs...) -> CopheneticScores"""
+    corr = C.c_double(float("nan"))
+    sums = np.zeros((5, n), dtype=np.float64)
+    coph = np.zeros((n, n), dtype=np.float64) if matrix else None
+    ctx.check(getattr(ctx._L, entry)(ctx._h, *front, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                     C.byref(corr), _lib.ptr(sums, C.c_double), _lib.ptr(coph, C.c_double)))
+    return CopheneticScores(float(corr.value), sums, coph)
+
+
+_MATRIX_COPHENET = {"jsd": "dvs_jsd_cophenet", "euclidean": "dvs_euclidean_cophenet"}
+
+
+def matrix_cophenet(m: "engine.CountMatrix", Z, mode: str = "jsd", rows=None, matrix: bool = False) -> CopheneticScores:
+    """the cophenetic correlation of the linkage matrix Z with the `mode` ("jsd", "euclidean") distances of rows `rows`
+    of m (None: all; leaf i of Z is rows[i]): the cells of `matrix_cross_distances(m, m, mode, rows, rows)` computed
+    strip by strip and reduced on the device, the n x n matrix never existing whole"""
+    _matrix_mode(mode)
+    rr, n = _row_list(rows, m.nrows)
+    pairs, heights = check_linkage_matrix(Z, n)
+    return _run_cophenet(m.ctx, _MATRIX_COPHENET[mode], n, pairs, heights, matrix, m._h, _lib.ptr(rr, C.c_uint32), n)
+
+
+def cophenet(seqs, Z, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
+             mash_canonical: bool = False, matrix: bool = False, ctx: engine.Context | None = None) -> CopheneticScores:
+    """the cophenetic correlation (`CopheneticScores`) of the linkage matrix Z over the sequences with their
+    `distance_mode` distances: scipy's cophenet(Z, Y)[0] for the condensed form Y of what MODES[distance_mode] gives the
+    collection, computed strip by strip and never held whole.  Argument checks as cluster.ctree, and the shape of Z,
+    before any device work; ZeroDivisionError (mash) for a sequence with an empty sketch."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    seqs = list(seqs)
+    check_linkage_matrix(Z, len(seqs))
+    dev = device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx)
+    try:
+        return device_side_cophenet(dev, Z, distance_mode, matrix=matrix)
+    finally:
+        dev.close()
+
+
+def device_side_cophenet(dev, Z, distance_mode: str, matrix: bool = False) -> CopheneticScores:
+    """the cophenetic correlation of Z over every row of `device_side`'s result"""
+    if distance_mode == "mash":
+        return dev.cophenet(Z, matrix=matrix)
+    return matrix_cophenet(dev, Z, distance_mode, matrix=matrix)

@@ -522,6 +522,51 @@ int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uin
                        uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
                        uint32_t *medoids);
 
+/* ---- cophenetic distances of a tree, and their correlation with the distances it was built from ---- *
+ * scipy.cluster.hierarchy.cophenet.  The cophenetic distance coph(i, j) of two leaves is the height of the merge at
+ * which they first share a cluster.  Over dvs_linkage's outputs (pairs[2 (n - 1)], heights[n - 1], scipy's ids: leaves
+ * 0 .. n - 1, merge j makes n + j) it is found without a search for the lowest common ancestor: the in-order walk of
+ * the tree (left child, merge, right child) lists the leaves in dendrogram order, order[n], and the merges between
+ * them, gap[n - 1] -- gap[p] is the merge that joins the subtree ending at position p to the one starting at p + 1;
+ * every merge owns exactly one gap, and a parent's index is above its children's, so with pos the inverse of order and
+ * pos[i] < pos[j]
+ *     coph(i, j) = heights[max(gap[pos[i] .. pos[j] - 1])]
+ * an integer range maximum and a lookup: exact, and valid for any well-formed tree -- the heights need not be
+ * monotone (scipy's centroid and median trees are not), unlike dvs_linkage_cut.
+ * dvs_linkage_cophenet is scipy's cophenet(Z) as the square matrix (squareform of its result, bit for bit): coph is a
+ * host array n x n, zero on the diagonal; host only, ctx only takes the error text and may be NULL.
+ * The other four are scipy's cophenet(Z, Y)[0], Pearson's r between D(i, j) and coph(i, j) over the n (n - 1) ordered
+ * pairs i != j, with the n x n distances D of a mode computed strip by strip as for the cluster scores above (queries =
+ * references = `rows` of the handle, NULL: rows 0 .. n - 1; leaf i of the tree is rows[i]); the matrix never exists
+ * whole.  Cell (i, i) is never read.  Both variables are shifted by c_bar, the mean of all cophenetic distances (known
+ * from the tree alone: a merge of clusters of sizes s_a and s_b at height h holds s_a s_b pairs at h), which leaves r
+ * as it is and keeps the moments free of cancellation where the distances crowd near one value.  With x = D(i, j) -
+ * c_bar and y = coph(i, j) - c_bar:
+ *   row_sums  [5][n], optional: per row i the sums over j != i of x, y, x x, y y and x y.  The order in which a sum's
+ *             terms are added depends on (n, the tree) alone: the same bits on every run and for every strip height
+ *   *corr     r = Sxy / sqrt(Sxx Syy) from the 5 n sums in long double on the host (Sxy = sum xy - sum x sum y / M, M =
+ *             n (n - 1), likewise Sxx, Syy); NaN when either variance is zero (n = 2, a constant matrix), as scipy
+ *             gives -- zero meaning not above the rounding error of its own terms, 2 (n + 8) 2^-52 sum xx
+ *   coph      n x n host array, optional: the cophenetic rows the kernel used, copied out strip by strip (N^2
+ *             doubles over PCIe: ask for it only when it is wanted)
+ * dvs_cophenet takes the caller's own n x n matrix as dvs_cluster_scores does and only reads it.
+ *   DVS_OK with nothing written: n == 0
+ *   DVS_ERR_VALUE: n == 1, a pair that names a cluster not yet made or already merged, a row index beyond the handle,
+ *                  a device mismatch, a matrix that is not device memory where it is said to be
+ *   DVS_ERR_UNSUPPORTED: n beyond the row limit of the square entries
+ *   DVS_ERR_ZERODIV: (sketches) one empty sketch among the rows, as dvs_sketches_cluster_scores
+ * All argument checks come before any device work.  (No counterpart in the reference.) */
+int dvs_linkage_cophenet(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, double *coph);
+int dvs_jsd_cophenet(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *pairs,
+                     const double *heights, double *corr, double *row_sums, double *coph);
+int dvs_euclidean_cophenet(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *pairs,
+                           const double *heights, double *corr, double *row_sums, double *coph);
+int dvs_sketches_cophenet(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
+                          uint32_t sketch_size, const uint32_t *pairs, const double *heights, double *corr,
+                          double *row_sums, double *coph);
+int dvs_cophenet(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *pairs,
+                 const double *heights, double *corr, double *row_sums, double *coph);
+
 #ifdef __cplusplus
 }
 #endif
