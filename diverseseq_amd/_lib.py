@@ -52,6 +52,7 @@ EXPORTS = (
     "dvs_linkage_cut", "dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_sketches_cluster_scores",
     "dvs_cluster_scores",
     "dvs_linkage_cophenet", "dvs_jsd_cophenet", "dvs_euclidean_cophenet", "dvs_sketches_cophenet", "dvs_cophenet",
+    "dvs_nj", "dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj", "dvs_nj_patristic",
 )
 
 
@@ -243,6 +244,11 @@ def load() -> C.CDLL:
             getattr(L, n).argtypes = [vp, vp, u32p, u32, *coph]
         L.dvs_sketches_cophenet.argtypes = [vp, vp, u32p, u32, u32, u32, *coph]
         L.dvs_cophenet.argtypes = [vp, vp, C.c_int, u32, *coph]
+        L.dvs_nj.argtypes = [vp, vp, C.c_int, u32, u32p, f64p]
+        L.dvs_sketches_nj.argtypes = [vp, vp, u32, u32, u32p, f64p]
+        for n in ("dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj"):
+            getattr(L, n).argtypes = [vp, vp, u32p, f64p]
+        L.dvs_nj_patristic.argtypes = [vp, u32, u32p, f64p, f64p]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

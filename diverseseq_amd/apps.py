@@ -7,7 +7,8 @@
 divergence of k-mer frequencies (diverseseq_amd.distance.jsd_distances).  `dvs_nearest`, beyond the reference: the
 nearest of a fixed set of reference sequences for every query (diverseseq_amd.distance.nearest); and `dvs_clusters`:
 the tree, its flat clusters at a cut, one representative per cluster and the silhouettes
-(diverseseq_amd.cluster.ctree_clusters).
+(diverseseq_amd.cluster.ctree_clusters); and `dvs_njtree`: the neighbour-joining tree of the same distances, with branch
+lengths (diverseseq_amd.cluster.nj_tree).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -39,7 +40,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -214,6 +215,31 @@ class dvs_ctree(_ClusterTreeBase):
                  show_progress: bool = False) -> None:
         super().__init__(k=k, sketch_size=sketch_size, moltype=moltype, distance_mode=distance_mode,
                          mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
+
+
+@_define_app
+class dvs_njtree(_ClusterTreeBase):
+    """Create a neighbour-joining tree from kmer distances (beyond the reference, which has no such app): the tree
+    of additive distances -- unrooted, with branch lengths, no molecular clock assumed -- where `dvs_ctree` gives the
+    average-linkage tree.  Arguments and their checks as `dvs_ctree`; `main(seqs)` returns the Newick string with
+    branch lengths, or cogent3's tree when cogent3 is importable.  Three sequences at least."""
+
+    def __init__(self, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
+                 distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
+                 show_progress: bool = False) -> None:
+        super().__init__(k=k, sketch_size=sketch_size, moltype=moltype, distance_mode=distance_mode,
+                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
+
+    def main(self, seqs):
+        names, data, _ = _as_mapping(seqs, self._moltype)
+        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
+        newick, _ = _cluster.nj_tree(arrays, k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
+                                     mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+        if HAVE_COGENT3:  # pragma: no cover
+            from cogent3 import make_tree
+
+            return make_tree(newick, underscore_unmunge=True)
+        return newick
 
 
 @_define_app

@@ -13,7 +13,8 @@ Beyond the reference: the flat clusters of a tree (`cut_tree`: scipy's fcluster 
 scores of a labelling (`cluster_scores`, csrc/crossdist.hip: sums within a cluster, the nearest other cluster,
 silhouettes, medoids) and both behind one call (`ctree_clusters`); how well a tree represents its distances (`cophenet`:
 scipy's cophenet, the correlation reduced on the GPU by csrc/crossdist.hip's cophenet_kernel; `ctree_cophenet`,
-`compare_linkages`).
+`compare_linkages`); and the tree of additive distances, neighbour joining (`neighbor_joining`, csrc/nj.hip: an unrooted
+tree with branch lengths and no molecular clock; `nj_to_newick`, `patristic`, `nj_tree`).
 """
 
 from __future__ import annotations
@@ -145,6 +146,102 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     if tree == "sklearn":
         return make_cluster_tree(names, distances(arrays, *args))
     return linkage_to_newick(names, tree_of(arrays, *args, method=linkage))
+
+
+def neighbor_joining(dist, *, ctx: engine.Context | None = None) -> "distance.NJTree":
+    """the neighbour-joining tree (canonical Saitou-Nei / Studier-Keppler, include/dvs_hip.h) of an n x n distance
+    matrix, n >= 3, on the GPU -> `distance.NJTree`: unrooted, with branch lengths, the generating tree wherever the
+    distances are additive.  Only the upper triangle counts (the diagonal counts as 0); a NaN or inf anywhere raises
+    ValueError.  Equal Q values go to the lowest pair of slots, so the records are the same bits wherever the arithmetic
+    is exact; on general input compare two results as unrooted trees.  The shape and n >= 3 are checked before any device
+    work.
+
+    `dist`: as `linkage` takes it -- anything np.asarray(dist, float64) takes (left as it is), or a square, contiguous
+    float64 torch tensor on the context's device, which is the working buffer and OVERWRITTEN; the call waits for the
+    work torch has queued on that device's current stream."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
+        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
+            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
+        n = int(dist.shape[0])
+        src, on_device = C.c_void_p(dist.data_ptr()), 1
+    else:
+        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
+        n = d.shape[0]
+        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    if n < 3:
+        raise ValueError(f"Found array with {n} sample(s) while a minimum of 3 is required for a neighbour-joining tree")
+    if on_device:
+        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    return distance.run_nj(ctx, n, "dvs_nj", src, on_device, n)
+
+
+def nj_to_newick(names: Sequence, tree, *, lengths: bool = True) -> str:
+    """a neighbour-joining tree -> Newick, e.g. "(a:0.1, b:0.2, (c:0.3, d:0.4):0.5);": the three children of the last
+    record at the top level, a record's children in its order, a leaf as `linkage_to_newick` writes it (repr(name), every
+    "'" dropped), every branch length as repr(float) so that it reads back to the same bits; lengths=False: the bare
+    topology.  Host only and iterative (no recursion limit), one "".join."""
+    n, joins, lens = distance.nj_inputs(tree)
+    if len(names) != n:
+        raise ValueError(f"{len(names)} names for a tree of {n} leaves")
+    kids = joins.reshape(-1, 3).tolist()
+    lens = lens.reshape(-1, 3).tolist()
+    parts = []
+    stack: list = [(2 * n - 3, None)]  # (node id, the length above it) and the literal pieces between them
+    while stack:
+        item = stack.pop()
+        if isinstance(item, str):
+            parts.append(item)
+            continue
+        v, above = item
+        tail = f":{float(above)!r}" if lengths and above is not None else ""
+        if v < n:
+            parts.append(repr(names[v]).replace("'", "") + tail)
+            continue
+        t = v - n
+        if not 0 <= t < n - 2:
+            raise ValueError(f"node {v} is not a node of a tree of {n} leaves")
+        count = 3 if t == n - 3 else 2
+        stack.append(")" + tail)
+        for c in range(count - 1, -1, -1):
+            if kids[t][c] >= v:
+                raise ValueError(f"record {t} joins node {kids[t][c]}, which does not exist at that point")
+            stack.append((kids[t][c], lens[t][c]))
+            if c:
+                stack.append(", ")
+        stack.append("(")
+    parts.append(";")
+    return "".join(parts)
+
+
+def patristic(tree) -> np.ndarray:
+    """the path length between every two leaves of a neighbour-joining tree -> float64 [n, n], symmetric, 0 on the
+    diagonal; on additive distances the matrix the tree was built from.  Host only (dvs_nj_patristic), O(n^2);
+    ValueError for records that name a node not yet made or already joined."""
+    n, joins, lens = distance.nj_inputs(tree)
+    out = np.zeros((n, n), dtype=np.float64)
+    _lib.raise_for(_lib.load().dvs_nj_patristic(None, n, _lib.ptr(joins, C.c_uint32), _lib.ptr(lens, C.c_double),
+                                                _lib.ptr(out, C.c_double)), None)
+    return out
+
+
+def nj_tree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
+            mash_canonical_kmers: bool | None = None, num_states: int = 4):
+    """sequences {name: uint8 codes} -> (Newick string with branch lengths, distance.NJTree): the distances of
+    `distance_mode` and their neighbour-joining tree both on the GPU, the N x N matrix never leaving HBM
+    (dvs_sketches_nj / dvs_matrix_euclidean_nj / dvs_matrix_jsd_nj); leaf i is the i-th name.  Argument checks as
+    `ctree`, and three sequences at least, before any device work."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    names = list(seqs)
+    if len(names) < 3:
+        raise ValueError("need at least three sequences for a neighbour-joining tree")
+    tree = distance.NJ_MODES[distance_mode]([seqs[n] for n in names],
+                                            *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
+    return nj_to_newick(names, tree), tree
 
 
 def cut_tree(Z, *, n_clusters: int | None = None, height: float | None = None) -> np.ndarray:

@@ -231,6 +231,16 @@ int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n);
 int dvs_linkage_check_method(dvs_ctx *ctx, int method);
 int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
                        double *heights, uint32_t *sizes);
+// linkage.hip's prepare pass on its own, enqueued on the context's stream: every entry of the n x n matrix checked and
+// the upper triangle copied over the lower one; the bits below are OR-ed into the device word *d_status (`sign`: a
+// negative entry above the diagonal is flagged too)
+constexpr uint32_t DVS_LNK_NONFINITE = 1, DVS_LNK_NEGATIVE = 4;
+hipError_t dvs_linkage_enqueue_prepare(dvs_ctx *ctx, double *d_dist, uint32_t n, bool sign, uint32_t *d_status);
+
+// nj.hip: the neighbour-joining tree of the n x n matrix at d_dist (n >= 3; a working buffer, overwritten), enqueued
+// behind whatever wrote it on the context's stream, d_zerodiv as above; returns when the host outputs (dvs_nj's) are
+// written.  DVS_ERR_NOMEM unless its scratch fits beside the matrix.
+int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *joins, double *lengths);
 
 // linkage.hip, host only: the in-order walk of the tree behind dvs_linkage's outputs (include/dvs_hip.h "cophenetic
 // distances"): order[n] the leaves in dendrogram order, pos[n] its inverse, gap[n - 1] the merge between positions p

@@ -55,7 +55,7 @@ constexpr uint32_t LNK_NONE = 0xFFFFFFFFu;
 
 // status words (device): [0] prepare / loop outcome (LNK_NONFINITE and LNK_NEGATIVE are bits), [1] the distance
 // kernel's zero-division flag
-enum : uint32_t { LNK_OK = 0, LNK_NONFINITE = 1, LNK_NO_CONVERGE = 2, LNK_NEGATIVE = 4 };
+enum : uint32_t { LNK_OK = 0, LNK_NONFINITE = DVS_LNK_NONFINITE, LNK_NO_CONVERGE = 2, LNK_NEGATIVE = DVS_LNK_NEGATIVE };
 
 // scipy's _LINKAGE_METHODS codes (the ABI's `method`)
 enum : int { LNK_SINGLE = 0, LNK_COMPLETE = 1, LNK_AVERAGE = 2, LNK_CENTROID = 3, LNK_MEDIAN = 4, LNK_WARD = 5,
@@ -487,6 +487,17 @@ static int linkage_fits(dvs_ctx *ctx, uint32_t n, bool need_matrix) {
 
 int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n) { return linkage_fits(ctx, n, true); }
 
+// the prepare pass (check + mirror; `sign`: ward's, a negative entry above the diagonal flagged too) on the context's
+// stream; *d_status collects DVS_LNK_NONFINITE / DVS_LNK_NEGATIVE
+hipError_t dvs_linkage_enqueue_prepare(dvs_ctx *ctx, double *d_dist, uint32_t n, bool sign, uint32_t *d_status) {
+    const uint32_t tiles = (n + LNK_TILE - 1) / LNK_TILE;
+    if (sign)
+        hipLaunchKernelGGL(linkage_prepare_kernel<true>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n, d_status);
+    else
+        hipLaunchKernelGGL(linkage_prepare_kernel<false>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n, d_status);
+    return hipGetLastError();
+}
+
 int dvs_linkage_check_method(dvs_ctx *ctx, int method) {
     if (method == LNK_CENTROID || method == LNK_MEDIAN)
         return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
@@ -514,20 +525,11 @@ int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t 
     char *base = scratch.as<char>();
     uint32_t *d_status = reinterpret_cast<uint32_t *>(base + L.status);
     std::vector<uint64_t> host((L.out_bytes + 7) / 8);
-    const uint32_t tiles = (n + LNK_TILE - 1) / LNK_TILE;
     const char *what = lnk_name(method);
     hipError_t e = hipMemsetAsync(d_status, 0, 16, ctx->stream);
     if (e == hipSuccess && d_zerodiv)
         e = hipMemcpyAsync(d_status + 1, d_zerodiv, 4, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (method == LNK_WARD)
-            hipLaunchKernelGGL(linkage_prepare_kernel<true>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n,
-                               d_status);
-        else
-            hipLaunchKernelGGL(linkage_prepare_kernel<false>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, d_dist, n,
-                               d_status);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = dvs_linkage_enqueue_prepare(ctx, d_dist, n, method == LNK_WARD, d_status);
     if (e == hipSuccess) e = lnk_launch_tree(ctx, method, d_dist, n, base, L);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), base, L.out_bytes, hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t se = hipStreamSynchronize(ctx->stream);

@@ -257,6 +257,20 @@ int stage_to_tree(dvs_ctx *ctx, const dvs_dist_stage &st, int method, uint32_t *
                               method, pairs, heights, sizes);
 }
 
+// The same with the neighbour-joining tree (nj.hip) behind the distances; the checks in the same order: n < 3, the
+// mode's own, the device, the fit in HBM.
+int stage_to_nj(dvs_ctx *ctx, const dvs_dist_stage &st, uint32_t *joins, double *lengths) {
+    if (st.n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least three sequences for a neighbour-joining tree");
+    if (int rc = st.check()) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx}, d_scratch{ctx};
+    int rc = dvs_linkage_check_size(ctx, st.n);
+    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
+    if (rc) return rc;
+    return dvs_nj_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr, joins,
+                         lengths);
+}
+
 }  // namespace
 
 int dvs_rows_check(dvs_ctx *ctx, uint32_t n) { return rows_check(ctx, n); }
@@ -295,4 +309,20 @@ extern "C" int dvs_matrix_jsd_linkage(dvs_ctx *ctx, const dvs_matrix *m, int met
                                       uint32_t *sizes) {
     if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     return stage_to_tree(ctx, jsd_stage(ctx, m), method, pairs, heights, sizes);
+}
+
+extern "C" int dvs_sketches_nj(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t *joins,
+                               double *lengths) {
+    if (!ctx || !sk || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_nj(ctx, dvs_mash_stage(ctx, sk, k, sketch_size), joins, lengths);
+}
+
+extern "C" int dvs_matrix_euclidean_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths) {
+    if (!ctx || !m || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_nj(ctx, euclid_stage(ctx, m), joins, lengths);
+}
+
+extern "C" int dvs_matrix_jsd_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths) {
+    if (!ctx || !m || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    return stage_to_nj(ctx, jsd_stage(ctx, m), joins, lengths);
 }

@@ -9,7 +9,9 @@ and the fused ctree stages
 of every query (nearest), the M x N matrix computed strip by strip and never leaving the device; and the scores of a
 labelling of one collection over the same strips (cluster_scores: sums within a cluster, the nearest other cluster,
 silhouettes, medoids; no counterpart in the reference); and, over the same strips again, the correlation of the distances
-with the cophenetic distances of a tree (cophenet: scipy's cophenet(Z, Y)[0]; no counterpart in the reference)."""
+with the cophenetic distances of a tree (cophenet: scipy's cophenet(Z, Y)[0]; no counterpart in the reference); and
+the neighbour-joining tree of each distance mode (mash_nj, euclidean_nj, jsd_nj: csrc/nj.hip, an unrooted tree with
+branch lengths, the matrix left in HBM as for the linkage trees; no counterpart in the reference)."""
 
 from __future__ import annotations
 
@@ -373,6 +375,96 @@ def jsd_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
     """the same for the Jensen-Shannon divergences of `jsd_distances`, the same matrix bit for bit (a sequence
     without valid k-mers: NaN distances, ValueError)"""
     return _count_rows_linkage("dvs_matrix_jsd_linkage", seqs, k, num_states, method, ctx)
+
+
+# ---- neighbour-joining trees
+
+class NJTree(NamedTuple):
+    """A neighbour-joining tree of n leaves (include/dvs_hip.h "neighbour-joining tree"): unrooted, n - 2 records.
+    children int64 [n - 2, 3]: record t joins these node ids (leaves 0 .. n - 1, record t makes node n + t); the third
+    slot is -1 except in the last record, which joins the three nodes left.  lengths float64 [n - 2, 3]: the branch
+    above each child, 0.0 in an unused slot; negative where the distances are not additive."""
+    children: np.ndarray
+    lengths: np.ndarray
+
+
+def nj_outputs(n: int):
+    """host buffers of the dvs_*nj calls for n leaves: joins uint32 [3 (n - 2)], lengths f64 [3 (n - 2)]"""
+    return np.zeros(3 * (n - 2), dtype=np.uint32), np.zeros(3 * (n - 2), dtype=np.float64)
+
+
+def nj_tree_of(joins: np.ndarray, lengths: np.ndarray) -> NJTree:
+    """the outputs of a dvs_*nj call -> NJTree"""
+    children = joins.reshape(-1, 3).astype(np.int64)
+    children[children == _U32_MAX] = -1
+    return NJTree(children, lengths.reshape(-1, 3).copy())
+
+
+def nj_inputs(tree) -> tuple[int, np.ndarray, np.ndarray]:
+    """an NJTree (or any (children, lengths) pair) as dvs_nj_patristic takes it -> (n, joins uint32, lengths f64);
+    ValueError unless both have shape (n - 2, 3) for n >= 3 leaves and the children are node ids or -1"""
+    children, lengths = np.asarray(tree[0]), np.asarray(tree[1], dtype=np.float64)
+    if children.ndim != 2 or children.shape[1] != 3 or children.shape[0] < 1 or children.dtype.kind not in "iu":
+        raise ValueError(f"the children of a neighbour-joining tree of n >= 3 leaves have shape (n - 2, 3), not {children.shape}")
+    if lengths.shape != children.shape:
+        raise ValueError(f"the lengths of a neighbour-joining tree have its children's shape {children.shape}, not {lengths.shape}")
+    n = children.shape[0] + 2
+    c = children.astype(np.int64)
+    if ((c < -1) | (c >= 2 * n - 2)).any():
+        raise ValueError("the children of a neighbour-joining tree are node ids in 0 .. 2 n - 3, or -1 in an unused slot")
+    c[c == -1] = _U32_MAX
+    return n, np.ascontiguousarray(c, dtype=np.uint32).reshape(-1), np.ascontiguousarray(lengths).reshape(-1)
+
+
+def run_nj(ctx: engine.Context | None, n: int, entry: str, *args) -> NJTree:
+    """the dvs_*nj call `entry`(ctx, *args, joins, lengths) for n leaves -> NJTree; ValueError before any device work
+    when n < 3"""
+    if n < 3:
+        raise ValueError("need at least three sequences for a neighbour-joining tree")
+    ctx = ctx or engine.default_context()
+    joins, lengths = nj_outputs(n)
+    ctx.check(getattr(ctx._L, entry)(ctx._h, *args, _lib.ptr(joins, C.c_uint32), _lib.ptr(lengths, C.c_double)))
+    return nj_tree_of(joins, lengths)
+
+
+def mash_nj(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
+            ctx: engine.Context | None = None) -> NJTree:
+    """the neighbour-joining tree of the mash distances on the device: sketches, the N x N distances and the tree,
+    every stage in HBM; only the n - 2 records come back.  ZeroDivisionError as `mash_distances`."""
+    if len(seqs) < 3:
+        raise ValueError("need at least three sequences for a neighbour-joining tree")
+    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
+    try:
+        return run_nj(sk.ctx, sk.n, "dvs_sketches_nj", sk._h, sk.k, min(sk.sketch_size, _U32_MAX))
+    finally:
+        sk.close()
+
+
+def _count_rows_nj(entry: str, seqs, k: int, num_states: int, ctx: engine.Context | None) -> NJTree:
+    """the neighbour-joining tree of a distance mode over the rows of the batch's count matrix (`entry`: its
+    dvs_matrix_*_nj)"""
+    if len(seqs) < 3:
+        raise ValueError("need at least three sequences for a neighbour-joining tree")
+    ctx = ctx or engine.default_context()
+    m = ctx.build_matrix(seqs, k, num_states)
+    try:
+        return run_nj(ctx, m.nrows, entry, m._h)
+    finally:
+        m.close()
+
+
+def euclidean_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None) -> NJTree:
+    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    return _count_rows_nj("dvs_matrix_euclidean_nj", seqs, k, num_states, ctx)
+
+
+def jsd_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None) -> NJTree:
+    """the same for the Jensen-Shannon divergences of `jsd_distances` (a sequence without valid k-mers: ValueError)"""
+    return _count_rows_nj("dvs_matrix_jsd_nj", seqs, k, num_states, ctx)
+
+
+# a ctree distance mode -> its neighbour-joining tree: takes (seqs, *mode_args(...)), and ctx=
+NJ_MODES = {"mash": mash_nj, "euclidean": euclidean_nj, "jsd": jsd_nj}
 
 
 # a ctree distance mode -> (its N x N distances, its tree): both take (seqs, *mode_args(...)), the tree also method=

@@ -567,6 +567,41 @@ int dvs_sketches_cophenet(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *
 int dvs_cophenet(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *pairs,
                  const double *heights, double *corr, double *row_sums, double *coph);
 
+/* ---- neighbour-joining tree (the tree of additive distances) ------------------------------------- *
+ * Canonical Saitou-Nei / Studier-Keppler neighbour joining of an n x n distance matrix, n >= 3, on the device.  As for
+ * the linkage trees only the upper triangle counts (the diagonal counts as 0) and every entry is checked.  Unlike a
+ * linkage tree the result is unrooted, assumes no molecular clock and carries branch lengths; on additive distances it
+ * is the tree that generated them.  The algorithm (f64, no fma, real divisions), with slots 0 .. n - 1, leaf i in slot
+ * i as node i, r active slots and R[s] the sum of D[s][t] over the other active t:
+ *   while r > 3: the least Q(i, j) = double(r - 2) * D[i][j] - R[i] - R[j] over active i < j, equal values to the
+ *     lowest (i, j) in lexicographic slot order; record t joins node[i] and node[j] with the lengths
+ *     li = D[i][j] / 2 + (R[i] - R[j]) / (2 * double(r - 2)) and lj = D[i][j] - li; the new node n + t takes slot i,
+ *     slot j is retired; for every other active k: du = (D[i][k] + D[j][k] - D[i][j]) / 2,
+ *     R[k] = R[k] - D[i][k] - D[j][k] + du, D[i][k] = D[k][i] = du; R[i] is summed afresh;
+ *   at r = 3 (slots x < y < z) the last record joins the three nodes with (Dxy + Dxz - Dyz) / 2,
+ *     (Dxy + Dyz - Dxz) / 2 and (Dxz + Dyz - Dxy) / 2.
+ * The row sums may be added in any order, so the records are defined bit for bit only where the arithmetic is exact;
+ * elsewhere two results are compared as unrooted trees (their splits and lengths).
+ *   joins    uint32 [3 (n - 2)]: record t = (joins[3 t], joins[3 t + 1], joins[3 t + 2]), node ids (leaves 0 .. n - 1,
+ *            record t makes n + t); the third child is 0xFFFFFFFF except in the last record
+ *   lengths  double [3 (n - 2)]: the branch above each child (0.0 in an unused third slot); a negative length is
+ *            neighbour joining's answer on distances that are not additive and is returned as it is
+ * dvs_nj takes a host matrix (copied to the device, left unchanged) or, with dist_on_device, a device matrix, which is
+ * the working buffer and is OVERWRITTEN.  The three fused entries compute the mode's distances into the context's
+ * scratch, as the *_linkage entries do, and build the tree there: the matrix never leaves HBM.
+ *   DVS_ERR_VALUE: n < 3, a NaN or +-inf entry anywhere, a device matrix on another device (and a row without a valid
+ *                  k-mer in the euclidean and jsd modes: NaN distances); DVS_ERR_ZERODIV: (sketches) two empty
+ *                  sketches; DVS_ERR_NOMEM: the matrix and the tree's scratch (a quarter of the matrix) do not fit
+ * dvs_nj_patristic (host only, ctx may be NULL): out, n x n, the path length between every two leaves of such a tree;
+ * O(n^2).  DVS_ERR_VALUE: n < 3, a record that names a node not yet made or already joined, a third child outside
+ * the last record.  (No counterpart in the reference.) */
+int dvs_nj(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths);
+int dvs_sketches_nj(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t *joins,
+                    double *lengths);
+int dvs_matrix_euclidean_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths);
+int dvs_matrix_jsd_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths);
+int dvs_nj_patristic(dvs_ctx *ctx, uint32_t n, const uint32_t *joins, const double *lengths, double *out);
+
 #ifdef __cplusplus
 }
 #endif
