@@ -53,6 +53,7 @@ EXPORTS = (
     "dvs_cluster_scores",
     "dvs_linkage_cophenet", "dvs_jsd_cophenet", "dvs_euclidean_cophenet", "dvs_sketches_cophenet", "dvs_cophenet",
     "dvs_nj", "dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj", "dvs_nj_patristic",
+    "dvs_maxmin", "dvs_sketches_maxmin", "dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin",
 )
 
 
@@ -249,6 +250,12 @@ def load() -> C.CDLL:
         for n in ("dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj"):
             getattr(L, n).argtypes = [vp, vp, u32p, f64p]
         L.dvs_nj_patristic.argtypes = [vp, u32, u32p, f64p, f64p]
+        # n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover
+        maxmin = [u32, u32p, u32, u32, C.c_int, C.c_double, u32p, f64p, u32p, u32p, f64p, f64p]
+        L.dvs_maxmin.argtypes = [vp, vp, C.c_int, *maxmin]
+        L.dvs_sketches_maxmin.argtypes = [vp, vp, u32, u32, *maxmin]
+        for n in ("dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin"):
+            getattr(L, n).argtypes = [vp, vp, *maxmin]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -8,7 +8,8 @@ divergence of k-mer frequencies (diverseseq_amd.distance.jsd_distances).  `dvs_n
 nearest of a fixed set of reference sequences for every query (diverseseq_amd.distance.nearest); and `dvs_clusters`:
 the tree, its flat clusters at a cut, one representative per cluster and the silhouettes
 (diverseseq_amd.cluster.ctree_clusters); and `dvs_njtree`: the neighbour-joining tree of the same distances, with branch
-lengths (diverseseq_amd.cluster.nj_tree).
+lengths (diverseseq_amd.cluster.nj_tree); and `dvs_maxmin`: farthest-first selection of representatives by distance,
+a diverse panel or a dereplication (diverseseq_amd.distance.maxmin).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -40,7 +41,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet", "dvs_njtree"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -450,3 +451,62 @@ class dvs_cophenet:
             if corr[method] == corr[method] and not corr[best] >= corr[method]:
                 best = method
         return {"best": best, "correlation": corr, "tree": _cluster.linkage_to_newick(names, trees[best][0])}
+
+
+@_define_app
+class dvs_maxmin:
+    """Farthest-first (max-min) selection of representatives by any distance of `dvs_dist` (beyond the reference, whose
+    selections are by delta-JSD): from the seeds on, the sequence farthest from those already taken, until `n` are
+    taken or every sequence lies within `min_distance` of one -- a diverse panel, or one representative per group
+    within min_distance.  At least one of n and min_distance; seeds: names taken first, in that order (None: the first
+    sequence).  `main(seqs)` returns {"picks": [names in pick order], "radius": [a pick's distance to the nearest
+    earlier pick, NaN for a seed], "representative": {name: the nearest pick's name, None for a sequence at NaN
+    distance from the picks}, "distance": {name: float}, "cover": the largest distance of a sequence to its
+    representative}."""
+
+    def __init__(self, n: int | None = None, min_distance: float | None = None, distance_mode: str = "mash", *,
+                 k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
+                 mash_canonical_kmers: bool | None = None, seeds: list[str] | str | None = None) -> None:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        if distance_mode not in _distance.MODES:
+            raise ValueError(f"Unexpected distance {distance_mode!r}.")
+        if moltype not in ("dna", "rna") and mash_canonical_kmers:
+            raise ValueError("Canonical kmers only supported for dna sequences.")
+        if distance_mode == "mash" and sketch_size is None:
+            raise ValueError("Expected sketch size for mash distance measure.")
+        if distance_mode != "mash":  # (as dvs_ctree: the sketch size means nothing to the other modes)
+            sketch_size = None
+        if n is None and min_distance is None:
+            raise ValueError("dvs_maxmin takes n, min_distance or both")
+        if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1):
+            raise ValueError(f"n must be an integer of 1 or more, not {n!r}")
+        if min_distance is not None and np.isnan(float(min_distance)):
+            raise ValueError("min_distance cannot be NaN")
+        self._n, self._min_distance = n, min_distance
+        self._seeds = [seeds] if isinstance(seeds, str) else None if seeds is None else [str(s) for s in seeds]
+        if self._seeds is not None and not self._seeds:
+            raise ValueError("dvs_maxmin takes one seed at least")
+        self._moltype = moltype
+        self._k = k
+        self._num_states = _num_states(moltype)
+        self._sketch_size = sketch_size
+        self._distance_mode = distance_mode
+        self._mash_canonical = mash_canonical_kmers
+
+    def main(self, seqs):
+        names, data, _ = _as_mapping(seqs, self._moltype)
+        if not names:
+            raise ValueError("no sequences")
+        at = {name: i for i, name in enumerate(names)}
+        missing = [s for s in self._seeds or [] if s not in at]
+        if missing:
+            raise ValueError(f"seed names not among the sequences: {missing}")
+        seeds = [at[s] for s in self._seeds] if self._seeds else [0]
+        r = _distance.maxmin([np.frombuffer(data[n], dtype=np.uint8) for n in names], self._n, self._distance_mode,
+                             k=self._k, sketch_size=self._sketch_size, num_states=self._num_states,
+                             mash_canonical=self._mash_canonical, seeds=seeds, min_distance=self._min_distance)
+        picked = [names[i] for i in r.picks.tolist()]
+        return {"picks": picked, "radius": [float(v) for v in r.radius],
+                "representative": {name: picked[o] if o >= 0 else None for name, o in zip(names, r.owner.tolist())},
+                "distance": {name: float(d) for name, d in zip(names, r.dist)}, "cover": r.cover}

@@ -14,7 +14,8 @@ scores of a labelling (`cluster_scores`, csrc/crossdist.hip: sums within a clust
 silhouettes, medoids) and both behind one call (`ctree_clusters`); how well a tree represents its distances (`cophenet`:
 scipy's cophenet, the correlation reduced on the GPU by csrc/crossdist.hip's cophenet_kernel; `ctree_cophenet`,
 `compare_linkages`); and the tree of additive distances, neighbour joining (`neighbor_joining`, csrc/nj.hip: an unrooted
-tree with branch lengths and no molecular clock; `nj_to_newick`, `patristic`, `nj_tree`).
+tree with branch lengths and no molecular clock; `nj_to_newick`, `patristic`, `nj_tree`); and farthest-first selection
+of representatives over a caller's own distance matrix (`maxmin`, csrc/maxmin.hip).
 """
 
 from __future__ import annotations
@@ -295,6 +296,33 @@ def cluster_scores(dist, labels, *, ctx: engine.Context | None = None) -> "dista
         torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
     return distance._run_cluster_scores(ctx or (engine.default_context() if n else None), "dvs_cluster_scores", lab, src,
                                         on_device, n)
+
+
+def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None,
+           ctx: engine.Context | None = None) -> "distance.MaxMin":
+    """farthest-first (max-min) selection (`distance.MaxMin`) over a caller's n x n distance matrix: from the seeds
+    on, the row whose distance to the nearest row already taken is largest (a tie to the lowest row), until n_select
+    rows are taken (None: n) or every row lies within min_distance of one; one of the two must be given.  d(p, j) is
+    dist[p, j]: a row is read as it stands (the matrix need not be symmetric), the diagonal never.
+
+    `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
+    as `cluster_scores` handles it and only READ.  The arguments are checked before any device work."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
+        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
+            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
+        n = int(dist.shape[0])
+        src, on_device = C.c_void_p(dist.data_ptr()), 1
+    else:
+        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
+        n = d.shape[0]
+        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    args = distance.check_maxmin_args(n, n_select, seeds, min_distance)
+    if on_device:
+        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    return distance._run_maxmin(ctx, "dvs_maxmin", n, *args, src, on_device)
 
 
 def device_side_tree(dev, distance_mode: str, method: str) -> np.ndarray:

@@ -462,14 +462,7 @@ dvs_cross_stage jsd_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint32_
         hipError_t e = lists.upload(ctx, d_scratch);
         double *d_hq = static_cast<double *>(d_scratch), *d_hr = d_hq + nq;
         auto entropies = [&](const dvs_matrix *m, const uint32_t *d_rows, uint32_t count, double *d_h) {
-            if (e != hipSuccess) return;
-            dvs_mat_dispatch(m, [&](auto *mp) {
-                using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
-                hipLaunchKernelGGL((jsd_entropy_kernel<T>), dim3((count + 63) / 64), dim3(64), 0, ctx->stream, mp, m->d_totals,
-                                   d_rows, count, m->nbins, d_h);
-                return 0;
-            });
-            e = hipGetLastError();
+            if (e == hipSuccess) e = dvs_jsd_entropies_enqueue(ctx, m, d_rows, count, d_h);
         };
         entropies(q, lists.dq(d_scratch), nq, d_hq);
         entropies(r, lists.dr(d_scratch), nr, d_hr);
@@ -492,9 +485,10 @@ dvs_cross_stage jsd_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint32_
 
 // scratch: the row lists only
 dvs_cross_stage euclid_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
-                                   const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr) {
+                                   const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr,
+                                   const uint32_t *d_q_rows = nullptr) {
     dvs_cross_stage st{"euclidean cross distances", nq, nr};
-    const dvs_cross_lists lists{0, q_rows, r_rows, nq, nr};
+    const dvs_cross_lists lists{0, q_rows, r_rows, nq, nr, d_q_rows};
     st.check = [=] { return matrix_sides_check(ctx, q, q_rows, nq, r, r_rows, nr); };
     st.scratch_bytes = lists.bytes();
     st.scratch_what = "row lists";
@@ -763,6 +757,33 @@ int cross_to_cophenet(dvs_ctx *ctx, const dvs_cross_stage &st, const uint32_t *p
 }
 
 }  // namespace
+
+dvs_cross_stage dvs_euclid_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
+                                       const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, const uint32_t *d_q_rows) {
+    return euclid_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr, d_q_rows);
+}
+
+hipError_t dvs_jsd_entropies_enqueue(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *d_rows, uint32_t count, double *d_h) {
+    dvs_mat_dispatch(m, [&](auto *mp) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
+        hipLaunchKernelGGL((jsd_entropy_kernel<T>), dim3((count + 63) / 64), dim3(64), 0, ctx->stream, mp, m->d_totals, d_rows,
+                           count, m->nbins, d_h);
+        return 0;
+    });
+    return hipGetLastError();
+}
+
+hipError_t dvs_jsd_cross_row_enqueue(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *d_q_rows, uint32_t q0, uint32_t n,
+                                     const double *d_hq, const double *d_hr, double *d_row) {
+    dvs_mat_dispatch(m, [&](auto *mp) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
+        hipLaunchKernelGGL((jsd_cross_kernel<T, T>), dim3(1, (n + JSD_TILE - 1) / JSD_TILE), dim3(JSD_THREADS), 0, ctx->stream,
+                           mp, m->d_totals, d_q_rows, q0, 1u, mp, m->d_totals, static_cast<const uint32_t *>(nullptr), n,
+                           m->nbins, d_hq, d_hr, d_row);
+        return 0;
+    });
+    return hipGetLastError();
+}
 
 int dvs_cross_rows_check(dvs_ctx *ctx, const uint32_t *rows, uint32_t nrows, uint32_t limit, const char *side) {
     if (!rows) {

@@ -41,6 +41,9 @@ struct dvs_knobs {
     int persist_wg_rounds = -1;       // DVS_PERSIST_WG_ROUNDS: rounds of the grid up to which a window is scanned a row per workgroup (-1: default)
     // rectangular distances (crossdist.hip)
     uint32_t cross_strip_rows = 0;    // DVS_CROSS_STRIP_ROWS: query rows per strip of the rectangular drivers (0: from the strip's byte bound)
+    // farthest-first selection (maxmin.hip)
+    uint32_t maxmin_batch = 0;        // DVS_MAXMIN_BATCH: steps enqueued between two reads of the status word (0: 64)
+    bool maxmin_jsd_cross = false;    // DVS_MAXMIN_JSD_CROSS: the jsd traversal runs jsd_cross_kernel on one query row (the A/B of DESIGN.md 4.13)
     // ingest
     bool ingest_no_stream = false;    // DVS_INGEST_NO_STREAM: host files are uploaded whole before they are parsed
     // test-only (DVS_TEST_KNOBS=fake_persist_error): the first persistent launch's outcome is read as SEL_ERROR
@@ -276,9 +279,21 @@ struct dvs_cross_stage {
     std::function<hipError_t(void *d_scratch)> prepare;  // once, in front of the first strip
     std::function<hipError_t(uint32_t q0, uint32_t mq, double *d_strip, void *d_scratch)> enqueue;
 };
+// d_q_rows (may be NULL) here and below: the query list already on the device -- nq entries that the kernels of a
+// strip read when they run, so that a kernel enqueued in front of them may still write them (maxmin.hip); q_rows is
+// then not looked at
 dvs_cross_stage dvs_mash_cross_stage(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
                                      const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
-                                     uint32_t sketch_size);  // mash.hip
+                                     uint32_t sketch_size, const uint32_t *d_q_rows = nullptr);  // mash.hip
+dvs_cross_stage dvs_euclid_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
+                                       const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr,
+                                       const uint32_t *d_q_rows = nullptr);  // crossdist.hip
+// crossdist.hip: jsd_entropy_kernel over the rows d_rows[p] (NULL: p), p < count, of m into d_h, on the context's stream
+hipError_t dvs_jsd_entropies_enqueue(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *d_rows, uint32_t count, double *d_h);
+// crossdist.hip: jsd_cross_kernel on ONE query row -- row d_q_rows[q0] of m, entropy d_hq[q0] -- against rows 0 .. n - 1 of
+// m (entropies d_hr) into d_row[n], on the context's stream
+hipError_t dvs_jsd_cross_row_enqueue(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *d_q_rows, uint32_t q0, uint32_t n,
+                                     const double *d_hq, const double *d_hr, double *d_row);
 int dvs_rows_check(dvs_ctx *ctx, uint32_t n);  // rowdist.hip: the square path's own row limit
 // a side's optional row list (host; NULL: rows 0 .. nrows - 1) against the `limit` rows its handle holds
 int dvs_cross_rows_check(dvs_ctx *ctx, const uint32_t *rows, uint32_t nrows, uint32_t limit, const char *side);
@@ -288,16 +303,19 @@ struct dvs_cross_lists {
     size_t head;
     const uint32_t *q_rows, *r_rows;
     uint32_t nq, nr;
-    size_t bytes() const { return head + (q_rows ? size_t(nq) * 4 : 0) + (r_rows ? size_t(nr) * 4 : 0); }
+    const uint32_t *d_q_rows = nullptr;  // the query list where it already is on the device: used as it is, q_rows ignored
+    size_t bytes() const { return head + (up_q() ? size_t(nq) * 4 : 0) + (r_rows ? size_t(nr) * 4 : 0); }
+    bool up_q() const { return q_rows && !d_q_rows; }
     const uint32_t *dq(void *scratch) const {
+        if (d_q_rows) return d_q_rows;
         return q_rows ? reinterpret_cast<const uint32_t *>(static_cast<char *>(scratch) + head) : nullptr;
     }
     const uint32_t *dr(void *scratch) const {
-        return r_rows ? reinterpret_cast<const uint32_t *>(static_cast<char *>(scratch) + head) + (q_rows ? nq : 0) : nullptr;
+        return r_rows ? reinterpret_cast<const uint32_t *>(static_cast<char *>(scratch) + head) + (up_q() ? nq : 0) : nullptr;
     }
     hipError_t upload(dvs_ctx *ctx, void *scratch) const {
         hipError_t e = hipSuccess;
-        if (q_rows && nq)
+        if (up_q() && nq)
             e = hipMemcpyAsync(const_cast<uint32_t *>(dq(scratch)), q_rows, size_t(nq) * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess && r_rows && nr)
             e = hipMemcpyAsync(const_cast<uint32_t *>(dr(scratch)), r_rows, size_t(nr) * 4, hipMemcpyHostToDevice, ctx->stream);

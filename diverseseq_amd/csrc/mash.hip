@@ -1043,6 +1043,7 @@ extern "C" int dvs_sketches_get(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t *
     DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DVS_OK;
 }
+uint32_t dvs_sketches_nseq(const dvs_sketches *sk) { return sk->nseq; }  // (the struct is this file's: maxmin.hip)
 extern "C" const void *dvs_sketches_dev(const dvs_sketches *sk) { return sk ? sk->d_sk : nullptr; }
 extern "C" const void *dvs_sketches_dev_lens(const dvs_sketches *sk) { return sk ? sk->d_lens : nullptr; }
 
@@ -1209,9 +1210,9 @@ dvs_dist_stage dvs_mash_stage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, 
 // r_rows[j].  The scratch: the zero-division word, then the two row lists where they are given.
 dvs_cross_stage dvs_mash_cross_stage(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
                                      const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
-                                     uint32_t sketch_size) {
+                                     uint32_t sketch_size, const uint32_t *d_q_rows) {
     dvs_cross_stage st{"mash cross distances", nq, nr};
-    const dvs_cross_lists lists{8, q_rows, r_rows, nq, nr};
+    const dvs_cross_lists lists{8, q_rows, r_rows, nq, nr, d_q_rows};
     st.check = [=] {
         if (q->ctx != r->ctx || q->ctx->device != ctx->device)
             return dvs_set_error(ctx, DVS_ERR_VALUE, "the two sketch sets and the context are not on one device");

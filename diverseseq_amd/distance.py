@@ -11,7 +11,9 @@ labelling of one collection over the same strips (cluster_scores: sums within a 
 silhouettes, medoids; no counterpart in the reference); and, over the same strips again, the correlation of the distances
 with the cophenetic distances of a tree (cophenet: scipy's cophenet(Z, Y)[0]; no counterpart in the reference); and
 the neighbour-joining tree of each distance mode (mash_nj, euclidean_nj, jsd_nj: csrc/nj.hip, an unrooted tree with
-branch lengths, the matrix left in HBM as for the linkage trees; no counterpart in the reference)."""
+branch lengths, the matrix left in HBM as for the linkage trees; no counterpart in the reference); and farthest-first
+(max-min) selection of representatives by any of these distances (maxmin, matrix_maxmin, Sketches.maxmin:
+csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterpart in the reference)."""
 
 from __future__ import annotations
 
@@ -288,6 +290,12 @@ class Sketches:
         pairs, heights = check_linkage_matrix(Z, n)
         return _run_cophenet(self.ctx, "dvs_sketches_cophenet", n, pairs, heights, matrix, self._h, _lib.ptr(rr, C.c_uint32),
                              n, self.k, min(self.sketch_size, _U32_MAX))
+
+    def maxmin(self, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None) -> "MaxMin":
+        """farthest-first selection (`MaxMin`) among this set's sketches by their mash distances, a row of distances
+        per pick (dvs_sketches_maxmin); ZeroDivisionError where a pair the traversal visits has two empty sketches"""
+        args = check_maxmin_args(self.n, n_select, seeds, min_distance)
+        return _run_maxmin(self.ctx, "dvs_sketches_maxmin", self.n, *args, self._h, self.k, min(self.sketch_size, _U32_MAX))
 
 
 def mash_distances(seqs, k: int, sketch_size: int, num_states: int = 4,
@@ -841,3 +849,135 @@ def device_side_cophenet(dev, Z, distance_mode: str, matrix: bool = False) -> Co
     if distance_mode == "mash":
         return dev.cophenet(Z, matrix=matrix)
     return matrix_cophenet(dev, Z, distance_mode, matrix=matrix)
+
+
+# ---- farthest-first (max-min) selection of representatives
+
+class MaxMin(NamedTuple):
+    """A farthest-first traversal of n items (include/dvs_hip.h "farthest-first selection").  picks int64 [m]: the rows
+    in pick order, the seeds first; radius float64 [m]: a pick's distance to the nearest earlier pick when it was taken
+    (NaN for a seed; non-increasing behind the seeds); owner int64 [n]: the position in `picks` of every item's nearest
+    pick, a tie to the earlier pick, -1 for an item that is out (NaN distance to a pick) or at +inf from every pick;
+    dist float64 [n]: the distance to that pick (0.0 for a pick, NaN where out); cover: the largest dist over the items
+    that are neither picks nor out -- the covering radius of the picks -- 0.0 when there are none."""
+    picks: np.ndarray
+    radius: np.ndarray
+    owner: np.ndarray
+    dist: np.ndarray
+    cover: float
+
+
+def check_maxmin_args(n: int, n_select, seeds, min_distance):
+    """the arguments of a farthest-first selection over n items as the dvs_*maxmin entries take them, checked before
+    any device work -> (n_select, seeds uint32, use_min_distance, min_distance).  n_select None: n.  ValueError unless
+    at least one of n_select and min_distance is given, the seeds are one or more distinct rows, n_seeds <= n_select <=
+    n and min_distance is not NaN."""
+    if n_select is None and min_distance is None:
+        raise ValueError("farthest-first selection takes n_select, min_distance or both")
+    sd = np.asarray(list(seeds) if not isinstance(seeds, np.ndarray) else seeds)
+    if sd.ndim != 1 or sd.size == 0 or sd.dtype.kind not in "iu":
+        raise ValueError("seeds: one or more row indices")
+    if int(sd.min()) < 0 or int(sd.max()) >= n:
+        raise ValueError(f"seed outside 0 .. {n - 1}")
+    if np.unique(sd).size != sd.size:
+        raise ValueError("a row is a seed more than once")
+    if n_select is None:
+        n_select = n
+    if isinstance(n_select, bool) or not isinstance(n_select, (int, np.integer)):
+        raise ValueError(f"n_select must be an integer, not {n_select!r}")
+    if n_select < sd.size or n_select > n:
+        raise ValueError(f"n_select = {n_select}: between the number of seeds ({sd.size}) and the number of rows ({n})")
+    md = 0.0
+    if min_distance is not None:
+        md = float(min_distance)
+        if md != md:
+            raise ValueError("min_distance cannot be NaN")
+    return int(n_select), np.ascontiguousarray(sd, dtype=np.uint32), int(min_distance is not None), md
+
+
+def _run_maxmin(ctx, entry: str, n: int, n_select: int, seeds: np.ndarray, use_min: int, min_distance: float, *front) -> MaxMin:
+    """the dvs_*maxmin call `entry`(ctx, *front, n, seeds, ..., outputs) -> MaxMin"""
+    ctx = ctx or engine.default_context()
+    picks = np.zeros(n_select, dtype=np.uint32)
+    radius = np.zeros(n_select, dtype=np.float64)
+    owner = np.zeros(n, dtype=np.uint32)
+    dist = np.zeros(n, dtype=np.float64)
+    count, cover = C.c_uint32(0), C.c_double(0.0)
+    ctx.check(getattr(ctx._L, entry)(ctx._h, *front, n, _lib.ptr(seeds, C.c_uint32), seeds.size, n_select, use_min,
+                                     min_distance, _lib.ptr(picks, C.c_uint32), _lib.ptr(radius, C.c_double),
+                                     C.byref(count), _lib.ptr(owner, C.c_uint32), _lib.ptr(dist, C.c_double),
+                                     C.byref(cover)))
+    own = owner.astype(np.int64)
+    own[owner == _U32_MAX] = -1
+    m = int(count.value)
+    return MaxMin(picks[:m].astype(np.int64), radius[:m].copy(), own, dist, float(cover.value))
+
+
+_MATRIX_MAXMIN = {"jsd": "dvs_matrix_jsd_maxmin", "euclidean": "dvs_matrix_euclidean_maxmin"}
+
+
+def matrix_maxmin(m: "engine.CountMatrix", n_select: int | None = None, *, mode: str = "jsd", seeds=(0,),
+                  min_distance: float | None = None) -> MaxMin:
+    """farthest-first selection (`MaxMin`) among the rows of m by their `mode` ("jsd", "euclidean") distances: from the
+    seeds on, the row farthest from the rows already taken (a tie to the lowest row), until n_select rows are taken or
+    every row lies within min_distance of one.  The cells are those of the mode's square function bit for bit, one row
+    of them per pick: the n x n matrix never exists.  A row without a valid k-mer is at NaN from every other: never
+    picked, owner -1."""
+    _matrix_mode(mode)
+    args = check_maxmin_args(m.nrows, n_select, seeds, min_distance)
+    return _run_maxmin(m.ctx, _MATRIX_MAXMIN[mode], m.nrows, *args, m._h)
+
+
+def mash_maxmin(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
+                n_select: int | None = None, seeds=(0,), min_distance: float | None = None,
+                ctx: engine.Context | None = None) -> MaxMin:
+    """farthest-first selection among the sequences by their mash distances: sketches, then a row of distances per
+    pick, everything in HBM.  ZeroDivisionError where a pair the traversal visits has two empty sketches."""
+    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
+    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
+    try:
+        return sk.maxmin(n_select, seeds=seeds, min_distance=min_distance)
+    finally:
+        sk.close()
+
+
+def _count_rows_maxmin(mode: str, seqs, k: int, num_states: int, n_select, seeds, min_distance, ctx) -> MaxMin:
+    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
+    ctx = ctx or engine.default_context()
+    m = ctx.build_matrix(seqs, k, num_states)
+    try:
+        return matrix_maxmin(m, n_select, mode=mode, seeds=seeds, min_distance=min_distance)
+    finally:
+        m.close()
+
+
+def euclidean_maxmin(seqs, k: int, num_states: int = 4, *, n_select: int | None = None, seeds=(0,),
+                     min_distance: float | None = None, ctx: engine.Context | None = None) -> MaxMin:
+    """the same by the euclidean distances of the k-mer frequencies"""
+    return _count_rows_maxmin("euclidean", seqs, k, num_states, n_select, seeds, min_distance, ctx)
+
+
+def jsd_maxmin(seqs, k: int, num_states: int = 4, *, n_select: int | None = None, seeds=(0,),
+               min_distance: float | None = None, ctx: engine.Context | None = None) -> MaxMin:
+    """the same by the Jensen-Shannon divergences of `jsd_distances`"""
+    return _count_rows_maxmin("jsd", seqs, k, num_states, n_select, seeds, min_distance, ctx)
+
+
+# a distance mode -> its farthest-first selection: takes (seqs, *mode_args(...)), and n_select=, seeds=, min_distance=, ctx=
+MAXMIN_MODES = {"mash": mash_maxmin, "euclidean": euclidean_maxmin, "jsd": jsd_maxmin}
+
+
+def maxmin(seqs, n_select: int | None = None, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+           num_states: int = 4, mash_canonical: bool = False, seeds=(0,), min_distance: float | None = None,
+           ctx: engine.Context | None = None) -> MaxMin:
+    """farthest-first (max-min) selection of representatives among the sequences by `distance_mode`: the seeds, then
+    again and again the sequence farthest from those already taken, until n_select are taken (None: all) or every
+    sequence lies within min_distance of one (dereplication: one representative per group within min_distance).  One
+    of the two must be given.  `MaxMin` also names every sequence's nearest representative and the covering radius.
+    Only n_select rows of distances are computed, never the N x N matrix.  Argument checks as cluster.ctree, and those
+    of `check_maxmin_args`, before any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    seqs = list(seqs)
+    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
+    return MAXMIN_MODES[distance_mode](seqs, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                                       n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)

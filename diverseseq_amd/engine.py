@@ -530,6 +530,15 @@ class Selection:
 
         return distance.matrix_nearest(self.matrix, self.matrix, n_nearest, mode, r_rows=self.member_rows())
 
+    def diversify(self, n_select: int | None, mode: str = "jsd", min_distance: float | None = None):
+        """grow the selection by distance: farthest-first selection (`distance.MaxMin`) over the rows of the selection's
+        matrix by `mode` ("jsd", "euclidean"), seeded with the members in `members()` order -- the first picks are the
+        members, the following ones the rows farthest from everything taken so far, until n_select rows are taken in
+        all (None: every row) or every row lies within min_distance of one"""
+        from . import distance
+
+        return distance.matrix_maxmin(self.matrix, n_select, mode=mode, seeds=self.member_rows(), min_distance=min_distance)
+
 
 _default_ctx: Context | None = None
 

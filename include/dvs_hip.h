@@ -602,6 +602,54 @@ int dvs_matrix_euclidean_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, 
 int dvs_matrix_jsd_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths);
 int dvs_nj_patristic(dvs_ctx *ctx, uint32_t n, const uint32_t *joins, const double *lengths, double *out);
 
+/* ---- farthest-first selection (max-min diversity, Gonzalez' greedy for k-center) ------------------- *
+ * Representatives by distance: from one or more seeds on, the item whose distance to the nearest item already taken
+ * is largest, until n_select items are taken or every item lies within min_distance of one.  A pick costs one row of
+ * distances; the n x n matrix of a mode never exists.  (No counterpart in the reference.)  The algorithm:
+ *   items and distances  items 0 .. n - 1; d(p, j) is the mode's cell for rows p and j (the bits of the square entry
+ *       of the mode: dvs_jsd_distances, dvs_euclidean_distances, dvs_sketches_distances), on a caller's matrix
+ *       dist[p * n + j]: a row is read as it stands, the diagonal never
+ *   state per item  mind[j], +inf at first; owner[j], the position in the pick list of the nearest pick, NONE
+ *       (0xFFFFFFFF) at first; a flag `taken`; a flag `out`
+ *   take(p, r)  p is appended to the picks with radius r; mind[p] = 0, owner[p] = its own position; for every other j
+ *       that is neither taken nor out, with c = d(p, j): if c is NaN, j goes out for good (mind[j] = NaN, owner[j] =
+ *       NONE; never picked); else if c < mind[j] (strict: a tie stays with the earlier pick) mind[j] = c and owner[j] =
+ *       p's position
+ *   seeds   one or more distinct rows, taken in the given order with radius NaN
+ *   picking while fewer than n_select picks exist: the candidate is the j, neither taken nor out, of the largest
+ *       mind[j], equal values to the lowest j; no candidate: stop; use_min_distance and not mind[j] > min_distance:
+ *       stop (a row exactly at min_distance counts as covered); else take(j, mind[j])
+ *   result  picks[*n_picked] in pick order, the seeds first; radius[*n_picked]; owner[n] and dist_to_owner[n] (the
+ *       final mind); *cover, the largest mind over the items neither taken nor out, 0.0 when there are none
+ * A seed that is NaN against everything puts every other row out and the picks are the seeds: no special case.  An item
+ * at +inf from every pick keeps owner NONE and is the next candidate.  Everything is a comparison or a copy of a cell,
+ * so the result is exact and the same on every run and for every batch length (DVS_MAXMIN_BATCH: the steps enqueued
+ * between two reads of the device's status word, 64 by default).
+ * The three mode entries take rows 0 .. n - 1 of their handle (n <= its rows).  dvs_maxmin takes the caller's n x n
+ * matrix (row-major float64; host: uploaded whole and left unchanged; dist_on_device != 0: device memory on the
+ * context's device, only read).  picks and radius hold n_select entries, owner and dist_to_owner n; all are host
+ * arrays.  Return when they are written.
+ *   DVS_ERR_VALUE, before any device work: no seed, a seed >= n, a repeated seed, n_select < n_seeds or > n, NaN
+ *                  min_distance (with use_min_distance), n beyond the handle's rows; a device mismatch
+ *   DVS_ERR_ZERODIV: (sketches) k == 0, or a pair the traversal visits -- (p, j) with p a pick and j neither taken nor
+ *                  out at that point -- has two empty sketches, exactly where dvs_sketches_distances divides by zero
+ *                  for the same pair.  A pick's own cell is not a pair: one empty sketch among the rows does not raise
+ *   DVS_ERR_UNSUPPORTED: (euclidean) n beyond 524 280, the grid of the distance kernel
+ * The row limit of the square entries does not apply otherwise: nothing here is n x n but a caller's matrix. */
+int dvs_maxmin(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
+               uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks, double *radius,
+               uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover);
+int dvs_sketches_maxmin(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t n,
+                        const uint32_t *seeds, uint32_t n_seeds, uint32_t n_select, int use_min_distance,
+                        double min_distance, uint32_t *picks, double *radius, uint32_t *n_picked, uint32_t *owner,
+                        double *dist_to_owner, double *cover);
+int dvs_matrix_jsd_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
+                          uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks, double *radius,
+                          uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover);
+int dvs_matrix_euclidean_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
+                                uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks,
+                                double *radius, uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover);
+
 #ifdef __cplusplus
 }
 #endif
