@@ -99,6 +99,48 @@ def _populate_inmem_zstore(data: dict):
     return zstore
 
 
+def _as_arrays(seqs, moltype: str):
+    """(names, the sequences as uint8 arrays of alphabet indices, in that order) of what `_as_mapping` takes"""
+    names, data, _ = _as_mapping(seqs, moltype)
+    return names, [np.frombuffer(data[n], dtype=np.uint8) for n in names]
+
+
+class _DistanceApp:
+    """what the apps over a distance mode share: the constructor checks of ClusterTreeBase.__init__
+    (cluster.py:36-95) and the attributes they leave"""
+
+    @staticmethod
+    def _check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers, *, moltypes: str = "dna",
+                    keep_sketch_size: bool = False):
+        """-> (sketch_size, mash_canonical_kmers) as the app keeps them; `moltypes`: how the message names the
+        molecule types that have canonical k-mers; the sketch size means nothing to the euclidean and jsd modes
+        (cli.py:546-560) and is dropped for them unless keep_sketch_size"""
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        if distance_mode not in _distance.MODES:
+            raise ValueError(f"Unexpected distance {distance_mode!r}.")
+        if moltype not in ("dna", "rna") and mash_canonical_kmers:
+            raise ValueError(f"Canonical kmers only supported for {moltypes} sequences.")
+        if distance_mode == "mash" and sketch_size is None:
+            raise ValueError("Expected sketch size for mash distance measure.")
+        if distance_mode != "mash" and not keep_sketch_size:
+            sketch_size = None
+        return sketch_size, mash_canonical_kmers
+
+    def _keep_mode(self, distance_mode, k, sketch_size, moltype, mash_canonical_kmers) -> None:
+        self._moltype = moltype
+        self._k = k
+        self._num_states = _num_states(moltype)
+        self._sketch_size = sketch_size
+        self._distance_mode = distance_mode
+        self._mash_canonical = mash_canonical_kmers
+
+    def _mode_kwargs(self) -> dict:
+        """the keyword arguments of the diverseseq_amd.cluster functions over sequences"""
+        return dict(k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
+                    mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+
+
 @_define_app
 class dvs_max:
     """select the maximally divergent seqs from a sequence collection (records.py:254-321)"""
@@ -171,35 +213,20 @@ class dvs_delta_jsd:
         return name, self._sr.delta_jsd(name, arr)
 
 
-class _ClusterTreeBase:
+class _ClusterTreeBase(_DistanceApp):
     """argument checks of ClusterTreeBase.__init__ (cluster.py:36-95)"""
 
     def __init__(self, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
                  show_progress: bool = False) -> None:
-        if mash_canonical_kmers is None:
-            mash_canonical_kmers = False
-        if distance_mode not in _distance.MODES:
-            raise ValueError(f"Unexpected distance {distance_mode!r}.")
-        if moltype not in ("dna", "rna") and mash_canonical_kmers:
-            raise ValueError("Canonical kmers only supported for dna/rna sequences.")
-        if distance_mode == "mash" and sketch_size is None:
-            raise ValueError("Expected sketch size for mash distance measure.")
-        if distance_mode != "mash":  # (the sketch size means nothing to the euclidean and jsd modes: cli.py:546-560)
-            sketch_size = None
-        self._moltype = moltype
-        self._k = k
-        self._num_states = _num_states(moltype)
-        self._sketch_size = sketch_size
-        self._distance_mode = distance_mode
-        self._mash_canonical = mash_canonical_kmers
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             moltypes="dna/rna")
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
         self._progress = show_progress
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
-        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
-        newick = _cluster.ctree(arrays, k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
-                                mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+        names, arrays = _as_arrays(seqs, self._moltype)
+        newick = _cluster.ctree(dict(zip(names, arrays)), **self._mode_kwargs())
         if HAVE_COGENT3:  # pragma: no cover
             from cogent3 import make_tree
 
@@ -232,10 +259,8 @@ class dvs_njtree(_ClusterTreeBase):
                          mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
-        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
-        newick, _ = _cluster.nj_tree(arrays, k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
-                                     mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+        names, arrays = _as_arrays(seqs, self._moltype)
+        newick, _ = _cluster.nj_tree(dict(zip(names, arrays)), **self._mode_kwargs())
         if HAVE_COGENT3:  # pragma: no cover
             from cogent3 import make_tree
 
@@ -260,7 +285,7 @@ class dvs_par_ctree(_ClusterTreeBase):
 
 
 @_define_app
-class dvs_dist:
+class dvs_dist(_DistanceApp):
     """Calculate pairwise kmer-based distances between sequences (diverse_seq/distance.py:21-116): the mash
     distance, the euclidean distance between k-mer frequencies or, beyond the reference, their Jensen-Shannon
     divergence ("jsd").  Returns cogent3's DistanceMatrix when cogent3 is importable, else (names, float64 [n, n])
@@ -268,25 +293,13 @@ class dvs_dist:
 
     def __init__(self, distance_mode: str = "mash", *, k: int = 12, sketch_size: int | None = 3_000,
                  moltype: str = "dna", mash_canonical_kmers: bool | None = None, show_progress: bool = False) -> None:
-        if mash_canonical_kmers is None:
-            mash_canonical_kmers = False
-        if distance_mode not in _distance.MODES:
-            raise ValueError(f"Unexpected distance {distance_mode!r}.")
-        if moltype not in ("dna", "rna") and mash_canonical_kmers:
-            raise ValueError("Canonical kmers only supported for dna sequences.")
-        if distance_mode == "mash" and sketch_size is None:
-            raise ValueError("Expected sketch size for mash distance measure.")
-        self._moltype = moltype
-        self._k = k
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             keep_sketch_size=True)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
         self._show_progress = show_progress
-        self._num_states = _num_states(moltype)
-        self._distance_mode = distance_mode
-        self._sketch_size = sketch_size
-        self._mash_canonical = mash_canonical_kmers
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
-        arrays = [np.frombuffer(data[n], dtype=np.uint8) for n in names]
+        names, arrays = _as_arrays(seqs, self._moltype)
         dists = _distance.MODES[self._distance_mode][0](arrays, *_distance.mode_args(
             self._distance_mode, self._k, self._sketch_size, self._num_states, self._mash_canonical))
         if HAVE_COGENT3:  # pragma: no cover
@@ -297,7 +310,7 @@ class dvs_dist:
 
 
 @_define_app
-class dvs_nearest:
+class dvs_nearest(_DistanceApp):
     """The nearest of a fixed set of reference sequences for every query, by any distance of `dvs_dist` (beyond the
     reference, which has no such app).  The references are taken, encoded and sketched (mash) or counted (euclidean,
     jsd) once, here; `main(seqs)` returns {query name: [(reference name, distance), ...]}, nearest first, a tie to the
@@ -306,51 +319,28 @@ class dvs_nearest:
 
     def __init__(self, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k: int = 12,
                  sketch_size: int | None = 3_000, moltype: str = "dna", mash_canonical_kmers: bool | None = None) -> None:
-        if mash_canonical_kmers is None:
-            mash_canonical_kmers = False
-        if distance_mode not in _distance.CROSS_MODES:
-            raise ValueError(f"Unexpected distance {distance_mode!r}.")
-        if moltype not in ("dna", "rna") and mash_canonical_kmers:
-            raise ValueError("Canonical kmers only supported for dna sequences.")
-        if distance_mode == "mash" and sketch_size is None:
-            raise ValueError("Expected sketch size for mash distance measure.")
-        names, data, _ = _as_mapping(refs, moltype)
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             keep_sketch_size=True)
+        names, arrays = _as_arrays(refs, moltype)
         self._n_nearest = _distance.check_n_nearest(n_nearest, len(names))
-        self._moltype = moltype
-        self._k = k
-        self._num_states = _num_states(moltype)
-        self._distance_mode = distance_mode
-        self._sketch_size = sketch_size
-        self._mash_canonical = mash_canonical_kmers
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
         self._ref_names = names
-        self._refs = self._device_side([np.frombuffer(data[n], dtype=np.uint8) for n in names])
-
-    def _device_side(self, arrays):
-        """the sketches (mash) or the count matrix (euclidean, jsd) of a batch, left in HBM"""
-        if self._distance_mode == "mash":
-            return _distance.Sketches(arrays, self._k, self._sketch_size, self._num_states, self._mash_canonical)
-        from . import engine as _engine
-
-        return _engine.default_context().build_matrix(arrays, self._k, self._num_states)
+        self._mode_args = _distance.mode_args(distance_mode, k, sketch_size, self._num_states, mash_canonical_kmers)
+        # (kept for the life of the app: the handle's finaliser frees it)
+        self._refs = _distance.device_side(arrays, distance_mode, *self._mode_args)
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
+        names, arrays = _as_arrays(seqs, self._moltype)
         if not names:
             return {}
-        q = self._device_side([np.frombuffer(data[n], dtype=np.uint8) for n in names])
-        try:
-            if self._distance_mode == "mash":
-                idx, dist = q.nearest(self._refs, self._n_nearest)
-            else:
-                idx, dist = _distance.matrix_nearest(q, self._refs, self._n_nearest, self._distance_mode)
-        finally:
-            q.close()
+        with _distance.device_side(arrays, self._distance_mode, *self._mode_args) as q:
+            idx, dist = q.nearest(self._refs, self._n_nearest)
         return {name: [(self._ref_names[j], float(d)) for j, d in zip(idx[i], dist[i]) if j >= 0]
                 for i, name in enumerate(names)}
 
 
 @_define_app
-class dvs_clusters:
+class dvs_clusters(_DistanceApp):
     """The flat clusters of the `dvs_ctree` tree at a cut, with one representative per cluster (beyond the reference,
     which has no such app): exactly one of n_clusters (scipy's fcluster "maxclust" partition: a cut never separates
     merges of equal height, so fewer clusters may come back) and height (its "distance" partition).  `main(seqs)`
@@ -362,16 +352,7 @@ class dvs_clusters:
     def __init__(self, n_clusters: int | None = None, height: float | None = None, distance_mode: str = "mash", *,
                  k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  mash_canonical_kmers: bool | None = None, linkage: str = "average") -> None:
-        if mash_canonical_kmers is None:
-            mash_canonical_kmers = False
-        if distance_mode not in _distance.MODES:
-            raise ValueError(f"Unexpected distance {distance_mode!r}.")
-        if moltype not in ("dna", "rna") and mash_canonical_kmers:
-            raise ValueError("Canonical kmers only supported for dna sequences.")
-        if distance_mode == "mash" and sketch_size is None:
-            raise ValueError("Expected sketch size for mash distance measure.")
-        if distance_mode != "mash":  # (as dvs_ctree: the sketch size means nothing to the other modes)
-            sketch_size = None
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers)
         if (n_clusters is None) == (height is None):
             raise ValueError("dvs_clusters takes exactly one of n_clusters and height")
         if n_clusters is not None and (isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer))
@@ -381,21 +362,13 @@ class dvs_clusters:
             raise ValueError("the height of a cut cannot be NaN")
         _distance.linkage_method_code(linkage)
         self._n_clusters, self._height = n_clusters, height
-        self._moltype = moltype
-        self._k = k
-        self._num_states = _num_states(moltype)
-        self._sketch_size = sketch_size
-        self._distance_mode = distance_mode
-        self._mash_canonical = mash_canonical_kmers
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
         self._linkage = linkage
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
-        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
-        newick, _, sc = _cluster.ctree_clusters(
-            arrays, n_clusters=self._n_clusters, height=self._height, k=self._k, sketch_size=self._sketch_size,
-            distance_mode=self._distance_mode, mash_canonical_kmers=self._mash_canonical, num_states=self._num_states,
-            linkage=self._linkage)
+        names, arrays = _as_arrays(seqs, self._moltype)
+        newick, _, sc = _cluster.ctree_clusters(dict(zip(names, arrays)), n_clusters=self._n_clusters, height=self._height,
+                                                linkage=self._linkage, **self._mode_kwargs())
         clusters: dict = {c: [] for c in range(sc.sizes.size)}
         for name, c in zip(names, sc.labels.tolist()):
             clusters[c].append(name)
@@ -406,7 +379,7 @@ class dvs_clusters:
 
 
 @_define_app
-class dvs_cophenet:
+class dvs_cophenet(_DistanceApp):
     """How well the `dvs_ctree` tree of each linkage method represents the distances it was built from (beyond the
     reference, which has no such app): the cophenetic correlation, scipy's cophenet(Z, Y)[0].  `main(seqs)` returns
     {"best": method, "correlation": {method: float}, "tree": Newick string of the best method}; the best is the method
@@ -416,35 +389,18 @@ class dvs_cophenet:
     def __init__(self, methods=("single", "complete", "average", "weighted", "ward"), distance_mode: str = "mash", *,
                  k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  mash_canonical_kmers: bool | None = None) -> None:
-        if mash_canonical_kmers is None:
-            mash_canonical_kmers = False
-        if distance_mode not in _distance.MODES:
-            raise ValueError(f"Unexpected distance {distance_mode!r}.")
-        if moltype not in ("dna", "rna") and mash_canonical_kmers:
-            raise ValueError("Canonical kmers only supported for dna sequences.")
-        if distance_mode == "mash" and sketch_size is None:
-            raise ValueError("Expected sketch size for mash distance measure.")
-        if distance_mode != "mash":  # (as dvs_ctree: the sketch size means nothing to the other modes)
-            sketch_size = None
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers)
         methods = [methods] if isinstance(methods, str) else list(methods)
         if not methods:
             raise ValueError("dvs_cophenet takes one linkage method at least")
         for method in methods:
             _distance.linkage_method_code(method)
         self._methods = methods
-        self._moltype = moltype
-        self._k = k
-        self._num_states = _num_states(moltype)
-        self._sketch_size = sketch_size
-        self._distance_mode = distance_mode
-        self._mash_canonical = mash_canonical_kmers
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
-        arrays = {n: np.frombuffer(data[n], dtype=np.uint8) for n in names}
-        trees = _cluster.compare_linkages(
-            arrays, self._methods, k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
-            mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+        names, arrays = _as_arrays(seqs, self._moltype)
+        trees = _cluster.compare_linkages(dict(zip(names, arrays)), self._methods, **self._mode_kwargs())
         corr = {method: float(r) for method, (_, r) in trees.items()}
         best = self._methods[0]
         for method in self._methods:
@@ -454,7 +410,7 @@ class dvs_cophenet:
 
 
 @_define_app
-class dvs_maxmin:
+class dvs_maxmin(_DistanceApp):
     """Farthest-first (max-min) selection of representatives by any distance of `dvs_dist` (beyond the reference, whose
     selections are by delta-JSD): from the seeds on, the sequence farthest from those already taken, until `n` are
     taken or every sequence lies within `min_distance` of one -- a diverse panel, or one representative per group
@@ -467,16 +423,7 @@ class dvs_maxmin:
     def __init__(self, n: int | None = None, min_distance: float | None = None, distance_mode: str = "mash", *,
                  k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  mash_canonical_kmers: bool | None = None, seeds: list[str] | str | None = None) -> None:
-        if mash_canonical_kmers is None:
-            mash_canonical_kmers = False
-        if distance_mode not in _distance.MODES:
-            raise ValueError(f"Unexpected distance {distance_mode!r}.")
-        if moltype not in ("dna", "rna") and mash_canonical_kmers:
-            raise ValueError("Canonical kmers only supported for dna sequences.")
-        if distance_mode == "mash" and sketch_size is None:
-            raise ValueError("Expected sketch size for mash distance measure.")
-        if distance_mode != "mash":  # (as dvs_ctree: the sketch size means nothing to the other modes)
-            sketch_size = None
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers)
         if n is None and min_distance is None:
             raise ValueError("dvs_maxmin takes n, min_distance or both")
         if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1):
@@ -487,15 +434,10 @@ class dvs_maxmin:
         self._seeds = [seeds] if isinstance(seeds, str) else None if seeds is None else [str(s) for s in seeds]
         if self._seeds is not None and not self._seeds:
             raise ValueError("dvs_maxmin takes one seed at least")
-        self._moltype = moltype
-        self._k = k
-        self._num_states = _num_states(moltype)
-        self._sketch_size = sketch_size
-        self._distance_mode = distance_mode
-        self._mash_canonical = mash_canonical_kmers
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
 
     def main(self, seqs):
-        names, data, _ = _as_mapping(seqs, self._moltype)
+        names, arrays = _as_arrays(seqs, self._moltype)
         if not names:
             raise ValueError("no sequences")
         at = {name: i for i, name in enumerate(names)}
@@ -503,9 +445,9 @@ class dvs_maxmin:
         if missing:
             raise ValueError(f"seed names not among the sequences: {missing}")
         seeds = [at[s] for s in self._seeds] if self._seeds else [0]
-        r = _distance.maxmin([np.frombuffer(data[n], dtype=np.uint8) for n in names], self._n, self._distance_mode,
-                             k=self._k, sketch_size=self._sketch_size, num_states=self._num_states,
-                             mash_canonical=self._mash_canonical, seeds=seeds, min_distance=self._min_distance)
+        r = _distance.maxmin(arrays, self._n, self._distance_mode, k=self._k, sketch_size=self._sketch_size,
+                             num_states=self._num_states, mash_canonical=self._mash_canonical, seeds=seeds,
+                             min_distance=self._min_distance)
         picked = [names[i] for i in r.picks.tolist()]
         return {"picks": picked, "radius": [float(v) for v in r.radius],
                 "representative": {name: picked[o] if o >= 0 else None for name, o in zip(names, r.owner.tolist())},

@@ -50,6 +50,23 @@ def make_cluster_tree(seq_names: Sequence[str], pairwise_distances: np.ndarray) 
     return str(nested_tuple_tree(seq_names, pairwise_distances)).replace("'", "") + ";"
 
 
+def _caller_matrix(dist):
+    """a caller's n x n distance matrix -- a square, contiguous float64 torch tensor on the GPU, or anything
+    np.asarray(dist, float64) takes -> (its pointer, whether that is device memory, n, wait); wait() returns once the
+    work torch has queued on the tensor's device's current stream is done (torch's stream -> the library's), at once
+    for host memory"""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
+        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
+            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
+        wait = lambda: torch.cuda.current_stream(dist.device).synchronize()  # noqa: E731
+        return C.c_void_p(dist.data_ptr()), 1, int(dist.shape[0]), wait
+    d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
+    return d.ctypes.data_as(C.c_void_p), 0, d.shape[0], lambda: None  # (the pointer keeps d alive)
+
+
 def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None) -> np.ndarray:
     """scipy.cluster.hierarchy.linkage(dist[np.triu_indices(n, 1)], method) on the GPU -> Z, float64 [n - 1, 4] in
     scipy's layout, bit for bit, for method "single", "complete", "average", "weighted" or "ward" ("centroid" and
@@ -61,19 +78,8 @@ def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None)
     on the GPU, which is used as the working buffer and OVERWRITTEN.  Such a tensor must live on the context's
     device (ValueError otherwise); the call waits for the work torch has queued on that device's current stream."""
     code = distance.linkage_method_code(method)
-    torch = sys.modules.get("torch")
-    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
-        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
-            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
-        n = int(dist.shape[0])
-        src, on_device = C.c_void_p(dist.data_ptr()), 1
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
-    else:
-        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
-        if d.ndim != 2 or d.shape[0] != d.shape[1]:
-            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
-        n = d.shape[0]
-        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    src, on_device, n, wait = _caller_matrix(dist)
+    wait()
     return distance.run_linkage(ctx, n, "dvs_linkage", src, on_device, n, code,
                                 too_few=f"Found array with {n} sample(s) while a minimum of 2 is required")
 
@@ -127,14 +133,7 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     RecursionError."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    if distance_mode not in distance.MODES:
-        raise ValueError(f"Unexpected distance {distance_mode!r}.")
-    if distance_mode == "mash" and sketch_size is None:
-        raise ValueError("Expected sketch size for mash distance measure.")
-    if distance_mode != "mash" and sketch_size is not None:
-        raise ValueError("Sketch size should only be specified for the mash distance.")
-    if distance_mode != "mash" and mash_canonical_kmers:
-        raise ValueError("Canonical kmers should only be specified for the mash distance.")
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
     if tree not in ("device", "sklearn"):
         raise ValueError(f"Unexpected tree {tree!r}: 'device' or 'sklearn'.")
     distance.linkage_method_code(linkage)
@@ -160,22 +159,10 @@ def neighbor_joining(dist, *, ctx: engine.Context | None = None) -> "distance.NJ
     `dist`: as `linkage` takes it -- anything np.asarray(dist, float64) takes (left as it is), or a square, contiguous
     float64 torch tensor on the context's device, which is the working buffer and OVERWRITTEN; the call waits for the
     work torch has queued on that device's current stream."""
-    torch = sys.modules.get("torch")
-    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
-        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
-            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
-        n = int(dist.shape[0])
-        src, on_device = C.c_void_p(dist.data_ptr()), 1
-    else:
-        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
-        if d.ndim != 2 or d.shape[0] != d.shape[1]:
-            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
-        n = d.shape[0]
-        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    src, on_device, n, wait = _caller_matrix(dist)
     if n < 3:
         raise ValueError(f"Found array with {n} sample(s) while a minimum of 3 is required for a neighbour-joining tree")
-    if on_device:
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    wait()
     return distance.run_nj(ctx, n, "dvs_nj", src, on_device, n)
 
 
@@ -240,8 +227,9 @@ def nj_tree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance
     names = list(seqs)
     if len(names) < 3:
         raise ValueError("need at least three sequences for a neighbour-joining tree")
-    tree = distance.NJ_MODES[distance_mode]([seqs[n] for n in names],
-                                            *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
+    with distance.device_side([seqs[n] for n in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+        tree = dev.nj()
     return nj_to_newick(names, tree), tree
 
 
@@ -279,21 +267,10 @@ def cluster_scores(dist, labels, *, ctx: engine.Context | None = None) -> "dista
     `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
     as `linkage` handles it (it must live on the context's device) but only READ: it is the same afterwards.  The
     shapes and the labels are checked before any device work."""
-    torch = sys.modules.get("torch")
-    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
-        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
-            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
-        n = int(dist.shape[0])
-        src, on_device = C.c_void_p(dist.data_ptr()), 1
-    else:
-        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
-        if d.ndim != 2 or d.shape[0] != d.shape[1]:
-            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
-        n = d.shape[0]
-        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    src, on_device, n, wait = _caller_matrix(dist)
     lab = distance.check_labels(labels, n)
-    if on_device and n:
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    if n:
+        wait()
     return distance._run_cluster_scores(ctx or (engine.default_context() if n else None), "dvs_cluster_scores", lab, src,
                                         on_device, n)
 
@@ -307,30 +284,10 @@ def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float
 
     `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
     as `cluster_scores` handles it and only READ.  The arguments are checked before any device work."""
-    torch = sys.modules.get("torch")
-    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
-        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
-            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
-        n = int(dist.shape[0])
-        src, on_device = C.c_void_p(dist.data_ptr()), 1
-    else:
-        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
-        if d.ndim != 2 or d.shape[0] != d.shape[1]:
-            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
-        n = d.shape[0]
-        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    src, on_device, n, wait = _caller_matrix(dist)
     args = distance.check_maxmin_args(n, n_select, seeds, min_distance)
-    if on_device:
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    wait()
     return distance._run_maxmin(ctx, "dvs_maxmin", n, *args, src, on_device)
-
-
-def device_side_tree(dev, distance_mode: str, method: str) -> np.ndarray:
-    """Z of `method` over every row of `distance.device_side`'s result, by the mode's fused tree entry"""
-    if distance_mode == "mash":
-        return dev.linkage(method)
-    entry = "dvs_matrix_jsd_linkage" if distance_mode == "jsd" else "dvs_matrix_euclidean_linkage"
-    return distance.run_linkage(dev.ctx, dev.nrows, entry, dev._h, distance.linkage_method_code(method))
 
 
 def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float | None = None, k: int = 12,
@@ -352,14 +309,11 @@ def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float |
     names = list(seqs)
     if len(names) < 2:
         raise ValueError("need at least two sequences to build a tree")
-    dev = distance.device_side([seqs[n] for n in names], distance_mode,
-                               *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
-    try:
-        Z = device_side_tree(dev, distance_mode, linkage)
+    with distance.device_side([seqs[n] for n in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+        Z = dev.linkage(linkage)
         labels = cut_tree(Z, n_clusters=n_clusters, height=height)
-        return linkage_to_newick(names, Z), Z, distance.device_side_scores(dev, labels, distance_mode)
-    finally:
-        dev.close()
+        return linkage_to_newick(names, Z), Z, dev.cluster_scores(labels)
 
 
 def cophenet(Z, dist=None, *, matrix: bool = False, ctx: engine.Context | None = None):
@@ -380,25 +334,13 @@ def cophenet(Z, dist=None, *, matrix: bool = False, ctx: engine.Context | None =
         _lib.raise_for(_lib.load().dvs_linkage_cophenet(None, n, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
                                                         _lib.ptr(coph, C.c_double)), None)
         return coph
-    torch = sys.modules.get("torch")
-    if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
-        if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
-            raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
-        n = int(dist.shape[0])
-        src, on_device = C.c_void_p(dist.data_ptr()), 1
-    else:
-        d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
-        if d.ndim != 2 or d.shape[0] != d.shape[1]:
-            raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
-        n = d.shape[0]
-        src, on_device = d.ctypes.data_as(C.c_void_p), 0
+    src, on_device, n, wait = _caller_matrix(dist)
     if n == 0:  # nothing to compute: no device work either
         if np.asarray(Z).size:
             raise ValueError(f"a linkage matrix of 0 leaves is empty, not of shape {np.asarray(Z).shape}")
         return distance.CopheneticScores(float("nan"), np.zeros((5, 0)), np.zeros((0, 0)) if matrix else None)
     pairs, heights = distance.check_linkage_matrix(Z, n)
-    if on_device:
-        torch.cuda.current_stream(dist.device).synchronize()  # (torch's stream -> the library's)
+    wait()
     return distance._run_cophenet(ctx or engine.default_context(), "dvs_cophenet", n, pairs, heights, matrix, src, on_device, n)
 
 
@@ -416,13 +358,10 @@ def ctree_cophenet(seqs: dict, *, linkage: str = "average", k: int = 12, sketch_
     names = list(seqs)
     if len(names) < 2:
         raise ValueError("need at least two sequences to build a tree")
-    dev = distance.device_side([seqs[n] for n in names], distance_mode,
-                               *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
-    try:
-        Z = device_side_tree(dev, distance_mode, linkage)
-        return linkage_to_newick(names, Z), Z, distance.device_side_cophenet(dev, Z, distance_mode, matrix=matrix)
-    finally:
-        dev.close()
+    with distance.device_side([seqs[n] for n in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+        Z = dev.linkage(linkage)
+        return linkage_to_newick(names, Z), Z, dev.cophenet(Z, matrix=matrix)
 
 
 def compare_linkages(seqs: dict, methods: Sequence[str] = ("single", "complete", "average", "weighted", "ward"), *,
@@ -440,13 +379,10 @@ def compare_linkages(seqs: dict, methods: Sequence[str] = ("single", "complete",
     names = list(seqs)
     if len(names) < 2:
         raise ValueError("need at least two sequences to build a tree")
-    dev = distance.device_side([seqs[n] for n in names], distance_mode,
-                               *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers))
-    try:
+    with distance.device_side([seqs[n] for n in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
         out = {}
         for method in methods:
-            Z = device_side_tree(dev, distance_mode, method)
-            out[method] = (Z, distance.device_side_cophenet(dev, Z, distance_mode).correlation)
+            Z = dev.linkage(method)
+            out[method] = (Z, dev.cophenet(Z).correlation)
         return out
-    finally:
-        dev.close()

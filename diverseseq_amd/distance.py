@@ -13,7 +13,9 @@ with the cophenetic distances of a tree (cophenet: scipy's cophenet(Z, Y)[0]; no
 the neighbour-joining tree of each distance mode (mash_nj, euclidean_nj, jsd_nj: csrc/nj.hip, an unrooted tree with
 branch lengths, the matrix left in HBM as for the linkage trees; no counterpart in the reference); and farthest-first
 (max-min) selection of representatives by any of these distances (maxmin, matrix_maxmin, Sketches.maxmin:
-csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterpart in the reference)."""
+csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterpart in the reference).  `DeviceSide`
+is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
+matrix_* functions and the Sketches methods are a few lines over it."""
 
 from __future__ import annotations
 
@@ -222,110 +224,228 @@ class Sketches:
         self.ctx.check(self.ctx._L.dvs_sketches_copy_to_device(self.ctx._h, self._h, C.c_void_p(dst_ptr), int(dst_stride),
                                                                C.c_void_p(dst_lens_ptr)))
 
+    @property
+    def sketch_size_u32(self) -> int:
+        """the sketch size as the C entries take it"""
+        return min(self.sketch_size, _U32_MAX)
+
     def distances_device(self, dist_ptr: int, zerodiv_ptr: int, *, row_start: int = 0, row_stride: int = 1,
                          symmetric: bool = True):
         """the visited cells into a device matrix (float64 [n, n]) of the caller's; enqueued, not waited for;
         the uint32 at zerodiv_ptr is set where `distances` would raise ZeroDivisionError"""
-        self.ctx.check(self.ctx._L.dvs_sketches_distances_device(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX),
+        self.ctx.check(self.ctx._L.dvs_sketches_distances_device(self.ctx._h, self._h, self.k, self.sketch_size_u32,
                                                                  row_start, row_stride, int(symmetric), C.c_void_p(dist_ptr),
                                                                  C.c_void_p(zerodiv_ptr)))
-
-    def linkage(self, method: str = "average") -> np.ndarray:
-        """scipy's linkage matrix Z of `method` (LINKAGE_METHODS) over the mash distances of every pair: the N x N
-        matrix is written and read in HBM (dvs_sketches_linkage); ZeroDivisionError as `distances`"""
-        code = linkage_method_code(method)
-        return run_linkage(self.ctx, self.n, "dvs_sketches_linkage", self._h, self.k, min(self.sketch_size, _U32_MAX), code)
 
     def distances(self, *, row_start: int = 0, row_stride: int = 1, symmetric: bool = True,
                   out: np.ndarray | None = None) -> np.ndarray:
         dist = _dist_out(out, self.n)
-        self.ctx.check(self.ctx._L.dvs_sketches_distances(self.ctx._h, self._h, self.k, min(self.sketch_size, _U32_MAX),
+        self.ctx.check(self.ctx._L.dvs_sketches_distances(self.ctx._h, self._h, self.k, self.sketch_size_u32,
                                                           row_start, row_stride, int(symmetric), _lib.ptr(dist, C.c_double)))
         return dist
 
-    def _other(self, other: "Sketches"):
-        if other.k != self.k or other.sketch_size != self.sketch_size:
-            raise ValueError(f"sketches of k = {self.k}, sketch size {self.sketch_size} against k = {other.k}, "
-                             f"sketch size {other.sketch_size}")
-        return other
+    # every other operation over the mash distances of these sketches: `DeviceSide`'s, for the mode "mash"
+
+    def linkage(self, method: str = "average") -> np.ndarray:
+        """scipy's linkage matrix Z of `method` (LINKAGE_METHODS) over the mash distances of every pair: the N x N
+        matrix is written and read in HBM (dvs_sketches_linkage); ZeroDivisionError as `distances`"""
+        return DeviceSide(self, "mash").linkage(method)
 
     def cross_distances(self, other: "Sketches", rows=None, other_rows=None) -> np.ndarray:
         """the mash distances of this set's sketches `rows` (None: all) against `other`'s `other_rows`: float64 [M, N],
         every cell the bits `distances` gives the same two sketches (dvs_sketches_cross_distances);
         ZeroDivisionError as `distances`"""
-        self._other(other)
-        qr, nq = _row_list(rows, self.n)
-        rr, nr = _row_list(other_rows, other.n)
-        dist = np.zeros((nq, nr), dtype=np.float64)
-        self.ctx.check(self.ctx._L.dvs_sketches_cross_distances(
-            self.ctx._h, self._h, _lib.ptr(qr, C.c_uint32), nq, other._h, _lib.ptr(rr, C.c_uint32), nr, self.k,
-            min(self.sketch_size, _U32_MAX), _lib.ptr(dist, C.c_double)))
-        return dist
+        return DeviceSide(self, "mash").cross_distances(DeviceSide(other, "mash"), rows, other_rows)
 
     def nearest(self, other: "Sketches", n_nearest: int = 1, rows=None, other_rows=None):
         """the n_nearest sketches of `other` (positions into other_rows, or rows) nearest to each of this set's, nearest
         first, a tie to the lower position: (int64 [M, n_nearest], -1 in a slot without a reference; float64 distances,
         NaN there) (dvs_sketches_nearest)"""
-        self._other(other)
-        qr, nq = _row_list(rows, self.n)
-        rr, nr = _row_list(other_rows, other.n)
-        kk = check_n_nearest(n_nearest, nr)
-        return _run_nearest(self.ctx, "dvs_sketches_nearest", self._h, qr, nq, other._h, rr, nr, kk, self.k,
-                            min(self.sketch_size, _U32_MAX))
+        return DeviceSide(self, "mash").nearest(DeviceSide(other, "mash"), n_nearest, rows, other_rows)
 
     def cluster_scores(self, labels, rows=None) -> "ClusterScores":
         """the scores of a labelling (`ClusterScores`) of this set's sketches `rows` (None: all; labels[i] belongs to
         rows[i]) over their mash distances, computed strip by strip (dvs_sketches_cluster_scores); ZeroDivisionError
         as `distances`"""
-        rr, n = _row_list(rows, self.n)
-        lab = check_labels(labels, n)
-        return _run_cluster_scores(self.ctx, "dvs_sketches_cluster_scores", lab, self._h, _lib.ptr(rr, C.c_uint32), n,
-                                   self.k, min(self.sketch_size, _U32_MAX))
+        return DeviceSide(self, "mash").cluster_scores(labels, rows)
 
     def cophenet(self, Z, rows=None, matrix: bool = False) -> "CopheneticScores":
         """the cophenetic correlation (`CopheneticScores`) of the linkage matrix Z with the mash distances of this set's
         sketches `rows` (None: all; leaf i of Z is rows[i]), computed strip by strip (dvs_sketches_cophenet);
         ZeroDivisionError as `cluster_scores`"""
-        rr, n = _row_list(rows, self.n)
-        pairs, heights = check_linkage_matrix(Z, n)
-        return _run_cophenet(self.ctx, "dvs_sketches_cophenet", n, pairs, heights, matrix, self._h, _lib.ptr(rr, C.c_uint32),
-                             n, self.k, min(self.sketch_size, _U32_MAX))
+        return DeviceSide(self, "mash").cophenet(Z, rows, matrix)
 
     def maxmin(self, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None) -> "MaxMin":
         """farthest-first selection (`MaxMin`) among this set's sketches by their mash distances, a row of distances
         per pick (dvs_sketches_maxmin); ZeroDivisionError where a pair the traversal visits has two empty sketches"""
+        return DeviceSide(self, "mash").maxmin(n_select, seeds=seeds, min_distance=min_distance)
+
+
+class DeviceSide:
+    """What a distance mode keeps in HBM of one batch -- its `Sketches` (mash) or its count matrix (euclidean, jsd) --
+    together with the mode: every operation over "the distances of a collection", whatever the mode.  `device_side`
+    makes one that owns its handle; DeviceSide(handle, mode) wraps a handle of the caller's, which close() then leaves
+    alone.  Every method checks its arguments before it touches the handle; what the results hold is told where the
+    public functions of each operation are.  A new operation over distances is one row of ENTRIES and one method."""
+
+    MODE_NAMES = ("mash", "euclidean", "jsd")
+    # operation -> the C entry of each of MODE_NAMES.  Behind the context every entry takes its side or sides (a handle;
+    # or a handle, a row list and the number of rows; or two of those), then the mode's own arguments (k and the sketch
+    # size for mash, none for the count-matrix modes), then what the operation adds: `_entry` gives the first two in
+    # that order.  (mash's whole matrix is `Sketches.distances`, which also serves strided rows.)
+    ENTRIES = {
+        "distances": (None, "dvs_euclidean_distances", "dvs_jsd_distances"),
+        "linkage": ("dvs_sketches_linkage", "dvs_matrix_euclidean_linkage", "dvs_matrix_jsd_linkage"),
+        "nj": ("dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj"),
+        "cross_distances": ("dvs_sketches_cross_distances", "dvs_euclidean_cross_distances", "dvs_jsd_cross_distances"),
+        "nearest": ("dvs_sketches_nearest", "dvs_euclidean_nearest", "dvs_jsd_nearest"),
+        "cluster_scores": ("dvs_sketches_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_jsd_cluster_scores"),
+        "cophenet": ("dvs_sketches_cophenet", "dvs_euclidean_cophenet", "dvs_jsd_cophenet"),
+        "maxmin": ("dvs_sketches_maxmin", "dvs_matrix_euclidean_maxmin", "dvs_matrix_jsd_maxmin"),
+    }
+
+    def __init__(self, handle, mode: str, *, owns: bool = False):
+        if mode not in self.MODE_NAMES:
+            raise ValueError(f"Unexpected distance {mode!r}.")
+        self.handle, self.mode, self._owns = handle, mode, owns
+
+    @property
+    def ctx(self):
+        return self.handle.ctx
+
+    @property
+    def n(self) -> int:
+        return self.handle.n if self.mode == "mash" else self.handle.nrows
+
+    def close(self):
+        """frees the handle if this side owns it; once, however often it is called"""
+        if self._owns:
+            self._owns = False
+            self.handle.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _entry(self, op: str, *sides):
+        """(the name of the mode's entry for `op`, its arguments behind the context up to the operation's own)"""
+        mode_args = (self.handle.k, self.handle.sketch_size_u32) if self.mode == "mash" else ()
+        return self.ENTRIES[op][self.MODE_NAMES.index(self.mode)], (*sides, *mode_args)
+
+    def _against(self, other: "DeviceSide"):
+        if other.mode != self.mode:
+            raise ValueError(f"a side of mode {self.mode!r} against one of mode {other.mode!r}")
+        if self.mode == "mash" and (other.handle.k != self.handle.k or other.handle.sketch_size != self.handle.sketch_size):
+            raise ValueError(f"sketches of k = {self.handle.k}, sketch size {self.handle.sketch_size} against "
+                             f"k = {other.handle.k}, sketch size {other.handle.sketch_size}")
+
+    def distances(self) -> np.ndarray:
+        """the symmetric n x n matrix of the distances, float64"""
+        if self.mode == "mash":
+            return self.handle.distances()
+        dist = np.zeros((self.n, self.n), dtype=np.float64)
+        entry, front = self._entry("distances", self.handle._h)
+        self.ctx.check(getattr(self.ctx._L, entry)(self.ctx._h, *front, _lib.ptr(dist, C.c_double)))
+        return dist
+
+    def linkage(self, method: str = "average") -> np.ndarray:
+        """scipy's linkage matrix Z of `method` (LINKAGE_METHODS), the N x N matrix written and read in HBM"""
+        code = linkage_method_code(method)
+        entry, front = self._entry("linkage", self.handle._h)
+        return run_linkage(self.ctx, self.n, entry, *front, code)
+
+    def nj(self) -> "NJTree":
+        """the neighbour-joining tree, the N x N matrix left in HBM"""
+        entry, front = self._entry("nj", self.handle._h)
+        return run_nj(self.ctx, self.n, entry, *front)
+
+    def cross_distances(self, other: "DeviceSide", rows=None, other_rows=None) -> np.ndarray:
+        """this side's `rows` (None: all) against `other`'s `other_rows`: float64 [M, N], the cells of `distances`"""
+        self._against(other)
+        qr, nq = _row_list(rows, self.n)
+        rr, nr = _row_list(other_rows, other.n)
+        dist = np.zeros((nq, nr), dtype=np.float64)
+        entry, front = self._entry("cross_distances", self.handle._h, _lib.ptr(qr, C.c_uint32), nq, other.handle._h,
+                                   _lib.ptr(rr, C.c_uint32), nr)
+        self.ctx.check(getattr(self.ctx._L, entry)(self.ctx._h, *front, _lib.ptr(dist, C.c_double)))
+        return dist
+
+    def nearest(self, other: "DeviceSide", n_nearest: int = 1, rows=None, other_rows=None):
+        """the n_nearest rows of `other` nearest to each of this side's -> (int64 [M, n_nearest] positions into
+        other_rows with -1 for an empty slot, float64 [M, n_nearest])"""
+        self._against(other)
+        qr, nq = _row_list(rows, self.n)
+        rr, nr = _row_list(other_rows, other.n)
+        kk = check_n_nearest(n_nearest, nr)
+        idx = np.zeros((nq, kk), dtype=np.uint32)
+        dist = np.zeros((nq, kk), dtype=np.float64)
+        entry, front = self._entry("nearest", self.handle._h, _lib.ptr(qr, C.c_uint32), nq, other.handle._h,
+                                   _lib.ptr(rr, C.c_uint32), nr)
+        self.ctx.check(getattr(self.ctx._L, entry)(self.ctx._h, *front, kk, _lib.ptr(idx, C.c_uint32),
+                                                   _lib.ptr(dist, C.c_double)))
+        out = idx.astype(np.int64)
+        out[idx == _U32_MAX] = -1
+        return out, dist
+
+    def cluster_scores(self, labels, rows=None) -> "ClusterScores":
+        """the scores of a labelling of this side's `rows` (None: all; labels[i] belongs to rows[i])"""
+        rr, n = _row_list(rows, self.n)
+        lab = check_labels(labels, n)
+        entry, front = self._entry("cluster_scores", self.handle._h, _lib.ptr(rr, C.c_uint32), n)
+        return _run_cluster_scores(self.ctx, entry, lab, *front)
+
+    def cophenet(self, Z, rows=None, matrix: bool = False) -> "CopheneticScores":
+        """the cophenetic correlation of Z with the distances of this side's `rows` (None: all; leaf i is rows[i])"""
+        rr, n = _row_list(rows, self.n)
+        pairs, heights = check_linkage_matrix(Z, n)
+        entry, front = self._entry("cophenet", self.handle._h, _lib.ptr(rr, C.c_uint32), n)
+        return _run_cophenet(self.ctx, entry, n, pairs, heights, matrix, *front)
+
+    def maxmin(self, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None) -> "MaxMin":
+        """farthest-first selection among this side's rows, a row of distances per pick"""
         args = check_maxmin_args(self.n, n_select, seeds, min_distance)
-        return _run_maxmin(self.ctx, "dvs_sketches_maxmin", self.n, *args, self._h, self.k, min(self.sketch_size, _U32_MAX))
+        entry, front = self._entry("maxmin", self.handle._h)
+        return _run_maxmin(self.ctx, entry, self.n, *args, *front)
+
+
+def device_side(seqs, distance_mode: str, *args, ctx: engine.Context | None = None) -> DeviceSide:
+    """what a distance mode keeps in HBM of a batch, made once: a `DeviceSide` that owns its Sketches (mash) or its
+    count matrix (euclidean, jsd); args: mode_args(...)"""
+    if distance_mode not in DeviceSide.MODE_NAMES:
+        raise ValueError(f"Unexpected distance {distance_mode!r}.")
+    if distance_mode == "mash":
+        return DeviceSide(Sketches(seqs, *args, ctx=ctx), distance_mode, owns=True)
+    return DeviceSide((ctx or engine.default_context()).build_matrix(seqs, *args), distance_mode, owns=True)
+
+
+def _count_side(m: "engine.CountMatrix", mode: str) -> DeviceSide:
+    """a count matrix of the caller's as a `DeviceSide` that does not own it"""
+    if mode not in ("jsd", "euclidean"):
+        raise ValueError(f"Unexpected distance {mode!r} between the rows of count matrices: 'jsd' or 'euclidean'.")
+    return DeviceSide(m, mode)
 
 
 def mash_distances(seqs, k: int, sketch_size: int, num_states: int = 4,
                    mash_canonical: bool = False, ctx: engine.Context | None = None) -> np.ndarray:
     """diverse_seq/distance.py:119-175: sketches, then the symmetric N x N matrix; the sketches stay in
     HBM between the two stages"""
-    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
-    try:
-        return sk.distances()
-    finally:
-        sk.close()
+    with device_side(seqs, "mash", k, sketch_size, num_states, mash_canonical, ctx=ctx) as dev:
+        return dev.distances()
 
 
 def euclidean_distances(seqs, k: int, num_states: int = 4,
                         ctx: engine.Context | None = None) -> np.ndarray:
     """diverse_seq/distance.py:294-332: ||kfreqs_i - kfreqs_j||_2"""
-    ctx = ctx or engine.default_context()
-    m = ctx.build_matrix(seqs, k, num_states)
-    try:
-        return matrix_euclidean_distances(m)
-    finally:
-        m.close()
+    with device_side(seqs, "euclidean", k, num_states, ctx=ctx) as dev:
+        return dev.distances()
 
 
 def matrix_euclidean_distances(m: "engine.CountMatrix") -> np.ndarray:
     """`euclidean_distances` over the rows of a matrix already in HBM (count rows of either width, or the frequency
     rows of Context.matrix_from_freqs)"""
-    dist = np.zeros((m.nrows, m.nrows), dtype=np.float64)
-    m.ctx.check(m.ctx._L.dvs_euclidean_distances(m.ctx._h, m._h, _lib.ptr(dist, C.c_double)))
-    return dist
+    return DeviceSide(m, "euclidean").distances()
 
 
 def jsd_distances(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
@@ -333,20 +453,14 @@ def jsd_distances(seqs, k: int, num_states: int = 4, ctx: engine.Context | None 
     H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2: total_jsd of the two-member set (src/records.rs:27-68; paper Table 1).
     float64 [n, n], symmetric, in [0, 1], exactly 0 on the diagonal and between sequences of equal counts; NaN off
     the diagonal for a sequence without a valid k-mer"""
-    ctx = ctx or engine.default_context()
-    m = ctx.build_matrix(seqs, k, num_states)
-    try:
-        return matrix_jsd_distances(m)
-    finally:
-        m.close()
+    with device_side(seqs, "jsd", k, num_states, ctx=ctx) as dev:
+        return dev.distances()
 
 
 def matrix_jsd_distances(m: "engine.CountMatrix") -> np.ndarray:
     """`jsd_distances` over the rows of a matrix already in HBM (count rows of either width, or the frequency rows
     of Context.matrix_from_freqs)"""
-    dist = np.zeros((m.nrows, m.nrows), dtype=np.float64)
-    m.ctx.check(m.ctx._L.dvs_jsd_distances(m.ctx._h, m._h, _lib.ptr(dist, C.c_double)))
-    return dist
+    return DeviceSide(m, "jsd").distances()
 
 
 def mash_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
@@ -354,35 +468,25 @@ def mash_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canon
     """`dvs ctree`'s mash tree on the device for any of LINKAGE_METHODS: sketches, the N x N distances and scipy's
     linkage matrix Z of `method`, every stage in HBM; only Z (n - 1 rows) comes back"""
     linkage_method_code(method)
-    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
-    try:
-        return sk.linkage(method)
-    finally:
-        sk.close()
-
-
-def _count_rows_linkage(entry: str, seqs, k: int, num_states: int, method: str, ctx: engine.Context | None) -> np.ndarray:
-    """the tree of a distance mode over the rows of the batch's count matrix (`entry`: its dvs_matrix_*_linkage)"""
-    code = linkage_method_code(method)
-    ctx = ctx or engine.default_context()
-    m = ctx.build_matrix(seqs, k, num_states)
-    try:
-        return run_linkage(ctx, m.nrows, entry, m._h, code)
-    finally:
-        m.close()
+    with device_side(seqs, "mash", k, sketch_size, num_states, mash_canonical, ctx=ctx) as dev:
+        return dev.linkage(method)
 
 
 def euclidean_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
                       ctx: engine.Context | None = None) -> np.ndarray:
     """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
-    return _count_rows_linkage("dvs_matrix_euclidean_linkage", seqs, k, num_states, method, ctx)
+    linkage_method_code(method)
+    with device_side(seqs, "euclidean", k, num_states, ctx=ctx) as dev:
+        return dev.linkage(method)
 
 
 def jsd_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
                 ctx: engine.Context | None = None) -> np.ndarray:
     """the same for the Jensen-Shannon divergences of `jsd_distances`, the same matrix bit for bit (a sequence
     without valid k-mers: NaN distances, ValueError)"""
-    return _count_rows_linkage("dvs_matrix_jsd_linkage", seqs, k, num_states, method, ctx)
+    linkage_method_code(method)
+    with device_side(seqs, "jsd", k, num_states, ctx=ctx) as dev:
+        return dev.linkage(method)
 
 
 # ---- neighbour-joining trees
@@ -439,36 +543,24 @@ def mash_nj(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical:
             ctx: engine.Context | None = None) -> NJTree:
     """the neighbour-joining tree of the mash distances on the device: sketches, the N x N distances and the tree,
     every stage in HBM; only the n - 2 records come back.  ZeroDivisionError as `mash_distances`."""
-    if len(seqs) < 3:
-        raise ValueError("need at least three sequences for a neighbour-joining tree")
-    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
-    try:
-        return run_nj(sk.ctx, sk.n, "dvs_sketches_nj", sk._h, sk.k, min(sk.sketch_size, _U32_MAX))
-    finally:
-        sk.close()
-
-
-def _count_rows_nj(entry: str, seqs, k: int, num_states: int, ctx: engine.Context | None) -> NJTree:
-    """the neighbour-joining tree of a distance mode over the rows of the batch's count matrix (`entry`: its
-    dvs_matrix_*_nj)"""
-    if len(seqs) < 3:
-        raise ValueError("need at least three sequences for a neighbour-joining tree")
-    ctx = ctx or engine.default_context()
-    m = ctx.build_matrix(seqs, k, num_states)
-    try:
-        return run_nj(ctx, m.nrows, entry, m._h)
-    finally:
-        m.close()
+    return _nj(seqs, "mash", k, sketch_size, num_states, mash_canonical, ctx=ctx)
 
 
 def euclidean_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None) -> NJTree:
     """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
-    return _count_rows_nj("dvs_matrix_euclidean_nj", seqs, k, num_states, ctx)
+    return _nj(seqs, "euclidean", k, num_states, ctx=ctx)
 
 
 def jsd_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None) -> NJTree:
     """the same for the Jensen-Shannon divergences of `jsd_distances` (a sequence without valid k-mers: ValueError)"""
-    return _count_rows_nj("dvs_matrix_jsd_nj", seqs, k, num_states, ctx)
+    return _nj(seqs, "jsd", k, num_states, ctx=ctx)
+
+
+def _nj(seqs, distance_mode: str, *args, ctx) -> NJTree:
+    if len(seqs) < 3:
+        raise ValueError("need at least three sequences for a neighbour-joining tree")
+    with device_side(seqs, distance_mode, *args, ctx=ctx) as dev:
+        return dev.nj()
 
 
 # a ctree distance mode -> its neighbour-joining tree: takes (seqs, *mode_args(...)), and ctx=
@@ -518,40 +610,12 @@ def _row_list(rows, limit: int):
     return np.ascontiguousarray(a, dtype=np.uint32), int(a.size)
 
 
-def _run_nearest(ctx, entry: str, qh, qr, nq: int, rh, rr, nr: int, kk: int, *mode_args):
-    """the dvs_*_nearest call `entry` -> (int64 [nq, kk] with -1 for an empty slot, float64 [nq, kk])"""
-    idx = np.zeros((nq, kk), dtype=np.uint32)
-    dist = np.zeros((nq, kk), dtype=np.float64)
-    ctx.check(getattr(ctx._L, entry)(ctx._h, qh, _lib.ptr(qr, C.c_uint32), nq, rh, _lib.ptr(rr, C.c_uint32), nr,
-                                     *mode_args, kk, _lib.ptr(idx, C.c_uint32), _lib.ptr(dist, C.c_double)))
-    out = idx.astype(np.int64)
-    out[idx == _U32_MAX] = -1
-    return out, dist
-
-
-# a count-matrix mode -> (its rectangular distances, its nearest references) in the C ABI
-_MATRIX_CROSS = {"jsd": ("dvs_jsd_cross_distances", "dvs_jsd_nearest"),
-                 "euclidean": ("dvs_euclidean_cross_distances", "dvs_euclidean_nearest")}
-
-
-def _matrix_mode(mode: str):
-    if mode not in _MATRIX_CROSS:
-        raise ValueError(f"Unexpected distance {mode!r} between the rows of count matrices: 'jsd' or 'euclidean'.")
-    return _MATRIX_CROSS[mode]
-
-
 def matrix_cross_distances(q: "engine.CountMatrix", r: "engine.CountMatrix", mode: str = "jsd", q_rows=None,
                            r_rows=None) -> np.ndarray:
     """the `mode` ("jsd", "euclidean") distances of rows q_rows of q (None: all) against rows r_rows of r: float64
     [M, N], every cell the bits the square function of the mode gives the same two rows.  q and r may be one matrix
     (rows against selected rows of the same matrix copy nothing) and may differ in element type, not in nbins."""
-    entry, _ = _matrix_mode(mode)
-    qr, nq = _row_list(q_rows, q.nrows)
-    rr, nr = _row_list(r_rows, r.nrows)
-    dist = np.zeros((nq, nr), dtype=np.float64)
-    q.ctx.check(getattr(q.ctx._L, entry)(q.ctx._h, q._h, _lib.ptr(qr, C.c_uint32), nq, r._h, _lib.ptr(rr, C.c_uint32), nr,
-                                         _lib.ptr(dist, C.c_double)))
-    return dist
+    return _count_side(q, mode).cross_distances(_count_side(r, mode), q_rows, r_rows)
 
 
 def matrix_nearest(q: "engine.CountMatrix", r: "engine.CountMatrix", n_nearest: int = 1, mode: str = "jsd", q_rows=None,
@@ -559,68 +623,41 @@ def matrix_nearest(q: "engine.CountMatrix", r: "engine.CountMatrix", n_nearest: 
     """the n_nearest rows of r (positions into r_rows, or rows) nearest to each row of q by `mode`, nearest first, a
     tie to the lower position: (int64 [M, n_nearest], -1 in a slot without a reference -- NaN cells are never
     listed; float64 distances, NaN there)"""
-    _, entry = _matrix_mode(mode)
-    qr, nq = _row_list(q_rows, q.nrows)
-    rr, nr = _row_list(r_rows, r.nrows)
-    kk = check_n_nearest(n_nearest, nr)
-    return _run_nearest(q.ctx, entry, q._h, qr, nq, r._h, rr, nr, kk)
+    return _count_side(q, mode).nearest(_count_side(r, mode), n_nearest, q_rows, r_rows)
 
 
-def _mash_sides(queries, refs, k, sketch_size, num_states, mash_canonical, ctx):
-    return (Sketches(queries, k, sketch_size, num_states, mash_canonical, ctx=ctx),
-            Sketches(refs, k, sketch_size, num_states, mash_canonical, ctx=ctx))
+def _two_sides(queries, refs, distance_mode: str, args, ctx, run):
+    """run(the queries' side, the references' side), both made for the call; the first is closed also where making
+    the second fails"""
+    with device_side(queries, distance_mode, *args, ctx=ctx) as q, device_side(refs, distance_mode, *args, ctx=ctx) as r:
+        return run(q, r)
 
 
 def mash_cross_distances(queries, refs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False,
                          ctx: engine.Context | None = None) -> np.ndarray:
-    q, r = _mash_sides(queries, refs, k, sketch_size, num_states, mash_canonical, ctx)
-    try:
-        return q.cross_distances(r)
-    finally:
-        q.close()
-        r.close()
+    return _two_sides(queries, refs, "mash", (k, sketch_size, num_states, mash_canonical), ctx, DeviceSide.cross_distances)
 
 
 def mash_nearest(queries, refs, n_nearest: int, k: int, sketch_size: int, num_states: int = 4,
                  mash_canonical: bool = False, ctx: engine.Context | None = None):
-    q, r = _mash_sides(queries, refs, k, sketch_size, num_states, mash_canonical, ctx)
-    try:
-        return q.nearest(r, n_nearest)
-    finally:
-        q.close()
-        r.close()
-
-
-def _count_rows_cross(mode: str, queries, refs, k: int, num_states: int, ctx, run):
-    """run(q matrix, r matrix) over the count matrices of the two batches"""
-    ctx = ctx or engine.default_context()
-    q = ctx.build_matrix(queries, k, num_states)
-    try:
-        r = ctx.build_matrix(refs, k, num_states)
-        try:
-            return run(q, r)
-        finally:
-            r.close()
-    finally:
-        q.close()
+    return _two_sides(queries, refs, "mash", (k, sketch_size, num_states, mash_canonical), ctx,
+                      lambda q, r: q.nearest(r, n_nearest))
 
 
 def euclidean_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
-    return _count_rows_cross("euclidean", queries, refs, k, num_states, ctx,
-                             lambda q, r: matrix_cross_distances(q, r, "euclidean"))
+    return _two_sides(queries, refs, "euclidean", (k, num_states), ctx, DeviceSide.cross_distances)
 
 
 def euclidean_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None):
-    return _count_rows_cross("euclidean", queries, refs, k, num_states, ctx,
-                             lambda q, r: matrix_nearest(q, r, n_nearest, "euclidean"))
+    return _two_sides(queries, refs, "euclidean", (k, num_states), ctx, lambda q, r: q.nearest(r, n_nearest))
 
 
 def jsd_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
-    return _count_rows_cross("jsd", queries, refs, k, num_states, ctx, lambda q, r: matrix_cross_distances(q, r, "jsd"))
+    return _two_sides(queries, refs, "jsd", (k, num_states), ctx, DeviceSide.cross_distances)
 
 
 def jsd_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None):
-    return _count_rows_cross("jsd", queries, refs, k, num_states, ctx, lambda q, r: matrix_nearest(q, r, n_nearest, "jsd"))
+    return _two_sides(queries, refs, "jsd", (k, num_states), ctx, lambda q, r: q.nearest(r, n_nearest))
 
 
 # a distance mode -> (its M x N distances, its nearest references): the first takes (queries, refs, *mode_args(...)),
@@ -651,8 +688,8 @@ def cross_distances(queries, refs, distance_mode: str = "mash", *, k: int, sketc
     queries, refs = list(queries), list(refs)
     if not queries or not refs:
         return np.zeros((len(queries), len(refs)), dtype=np.float64)
-    return CROSS_MODES[distance_mode][0](queries, refs, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
-                                         ctx=ctx)
+    return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                      ctx, DeviceSide.cross_distances)
 
 
 def nearest(queries, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
@@ -666,8 +703,8 @@ def nearest(queries, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k
     kk = check_n_nearest(n_nearest, len(refs))
     if not queries:
         return np.zeros((0, kk), dtype=np.int64), np.zeros((0, kk), dtype=np.float64)
-    return CROSS_MODES[distance_mode][1](queries, refs, kk, *mode_args(distance_mode, k, sketch_size, num_states,
-                                                                        mash_canonical), ctx=ctx)
+    return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                      ctx, lambda q, r: q.nearest(r, kk))
 
 
 # ---- the scores of a labelling: sums within a cluster, the nearest other cluster, silhouettes, medoids
@@ -727,17 +764,11 @@ def _run_cluster_scores(ctx, entry: str, lab: np.ndarray, *front) -> ClusterScor
                          float(sil.mean()) if n else float("nan"))
 
 
-_MATRIX_SCORES = {"jsd": "dvs_jsd_cluster_scores", "euclidean": "dvs_euclidean_cluster_scores"}
-
-
 def matrix_cluster_scores(m: "engine.CountMatrix", labels, mode: str = "jsd", rows=None) -> ClusterScores:
     """the scores of a labelling of rows `rows` of m (None: all; labels[i] belongs to rows[i]) over their `mode` ("jsd",
     "euclidean") distances, the cells of `matrix_cross_distances(m, m, mode, rows, rows)` computed strip by strip and
     reduced on the device: the n x n matrix never exists whole"""
-    _matrix_mode(mode)
-    rr, n = _row_list(rows, m.nrows)
-    lab = check_labels(labels, n)
-    return _run_cluster_scores(m.ctx, _MATRIX_SCORES[mode], lab, m._h, _lib.ptr(rr, C.c_uint32), n)
+    return _count_side(m, mode).cluster_scores(labels, rows)
 
 
 def cluster_scores(seqs, labels, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
@@ -751,26 +782,8 @@ def cluster_scores(seqs, labels, distance_mode: str = "mash", *, k: int, sketch_
     lab = check_labels(labels, len(seqs))
     if not seqs:
         return _run_cluster_scores(ctx, "", lab)
-    dev = device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx)
-    try:
-        return device_side_scores(dev, lab, distance_mode)
-    finally:
-        dev.close()
-
-
-def device_side(seqs, distance_mode: str, *args, ctx: engine.Context | None = None):
-    """what a distance mode keeps in HBM of a batch, made once: its Sketches (mash) or its count matrix (euclidean,
-    jsd); args: mode_args(...)"""
-    if distance_mode == "mash":
-        return Sketches(seqs, *args, ctx=ctx)
-    return (ctx or engine.default_context()).build_matrix(seqs, *args)
-
-
-def device_side_scores(dev, labels, distance_mode: str) -> ClusterScores:
-    """the scores of a labelling of every row of `device_side`'s result"""
-    if distance_mode == "mash":
-        return dev.cluster_scores(labels)
-    return matrix_cluster_scores(dev, labels, distance_mode)
+    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx) as dev:
+        return dev.cluster_scores(lab)
 
 
 # ---- the cophenetic correlation of a tree with the distances it was built from
@@ -815,17 +828,11 @@ def _run_cophenet(ctx, entry: str, n: int, pairs, heights, matrix: bool, *front)
     return CopheneticScores(float(corr.value), sums, coph)
 
 
-_MATRIX_COPHENET = {"jsd": "dvs_jsd_cophenet", "euclidean": "dvs_euclidean_cophenet"}
-
-
 def matrix_cophenet(m: "engine.CountMatrix", Z, mode: str = "jsd", rows=None, matrix: bool = False) -> CopheneticScores:
     """the cophenetic correlation of the linkage matrix Z with the `mode` ("jsd", "euclidean") distances of rows `rows`
     of m (None: all; leaf i of Z is rows[i]): the cells of `matrix_cross_distances(m, m, mode, rows, rows)` computed
     strip by strip and reduced on the device, the n x n matrix never existing whole"""
-    _matrix_mode(mode)
-    rr, n = _row_list(rows, m.nrows)
-    pairs, heights = check_linkage_matrix(Z, n)
-    return _run_cophenet(m.ctx, _MATRIX_COPHENET[mode], n, pairs, heights, matrix, m._h, _lib.ptr(rr, C.c_uint32), n)
+    return _count_side(m, mode).cophenet(Z, rows, matrix)
 
 
 def cophenet(seqs, Z, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
@@ -837,18 +844,8 @@ def cophenet(seqs, Z, distance_mode: str = "mash", *, k: int, sketch_size: int |
     check_mode_args(distance_mode, sketch_size, mash_canonical)
     seqs = list(seqs)
     check_linkage_matrix(Z, len(seqs))
-    dev = device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx)
-    try:
-        return device_side_cophenet(dev, Z, distance_mode, matrix=matrix)
-    finally:
-        dev.close()
-
-
-def device_side_cophenet(dev, Z, distance_mode: str, matrix: bool = False) -> CopheneticScores:
-    """the cophenetic correlation of Z over every row of `device_side`'s result"""
-    if distance_mode == "mash":
+    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx) as dev:
         return dev.cophenet(Z, matrix=matrix)
-    return matrix_cophenet(dev, Z, distance_mode, matrix=matrix)
 
 
 # ---- farthest-first (max-min) selection of representatives
@@ -913,9 +910,6 @@ def _run_maxmin(ctx, entry: str, n: int, n_select: int, seeds: np.ndarray, use_m
     return MaxMin(picks[:m].astype(np.int64), radius[:m].copy(), own, dist, float(cover.value))
 
 
-_MATRIX_MAXMIN = {"jsd": "dvs_matrix_jsd_maxmin", "euclidean": "dvs_matrix_euclidean_maxmin"}
-
-
 def matrix_maxmin(m: "engine.CountMatrix", n_select: int | None = None, *, mode: str = "jsd", seeds=(0,),
                   min_distance: float | None = None) -> MaxMin:
     """farthest-first selection (`MaxMin`) among the rows of m by their `mode` ("jsd", "euclidean") distances: from the
@@ -923,9 +917,7 @@ def matrix_maxmin(m: "engine.CountMatrix", n_select: int | None = None, *, mode:
     every row lies within min_distance of one.  The cells are those of the mode's square function bit for bit, one row
     of them per pick: the n x n matrix never exists.  A row without a valid k-mer is at NaN from every other: never
     picked, owner -1."""
-    _matrix_mode(mode)
-    args = check_maxmin_args(m.nrows, n_select, seeds, min_distance)
-    return _run_maxmin(m.ctx, _MATRIX_MAXMIN[mode], m.nrows, *args, m._h)
+    return _count_side(m, mode).maxmin(n_select, seeds=seeds, min_distance=min_distance)
 
 
 def mash_maxmin(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
@@ -933,34 +925,26 @@ def mash_maxmin(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canoni
                 ctx: engine.Context | None = None) -> MaxMin:
     """farthest-first selection among the sequences by their mash distances: sketches, then a row of distances per
     pick, everything in HBM.  ZeroDivisionError where a pair the traversal visits has two empty sketches."""
-    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
-    sk = Sketches(seqs, k, sketch_size, num_states, mash_canonical, ctx=ctx)
-    try:
-        return sk.maxmin(n_select, seeds=seeds, min_distance=min_distance)
-    finally:
-        sk.close()
-
-
-def _count_rows_maxmin(mode: str, seqs, k: int, num_states: int, n_select, seeds, min_distance, ctx) -> MaxMin:
-    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
-    ctx = ctx or engine.default_context()
-    m = ctx.build_matrix(seqs, k, num_states)
-    try:
-        return matrix_maxmin(m, n_select, mode=mode, seeds=seeds, min_distance=min_distance)
-    finally:
-        m.close()
+    return _maxmin(seqs, "mash", k, sketch_size, num_states, mash_canonical, n_select=n_select, seeds=seeds,
+                   min_distance=min_distance, ctx=ctx)
 
 
 def euclidean_maxmin(seqs, k: int, num_states: int = 4, *, n_select: int | None = None, seeds=(0,),
                      min_distance: float | None = None, ctx: engine.Context | None = None) -> MaxMin:
     """the same by the euclidean distances of the k-mer frequencies"""
-    return _count_rows_maxmin("euclidean", seqs, k, num_states, n_select, seeds, min_distance, ctx)
+    return _maxmin(seqs, "euclidean", k, num_states, n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)
 
 
 def jsd_maxmin(seqs, k: int, num_states: int = 4, *, n_select: int | None = None, seeds=(0,),
                min_distance: float | None = None, ctx: engine.Context | None = None) -> MaxMin:
     """the same by the Jensen-Shannon divergences of `jsd_distances`"""
-    return _count_rows_maxmin("jsd", seqs, k, num_states, n_select, seeds, min_distance, ctx)
+    return _maxmin(seqs, "jsd", k, num_states, n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)
+
+
+def _maxmin(seqs, distance_mode: str, *args, n_select, seeds, min_distance, ctx) -> MaxMin:
+    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
+    with device_side(seqs, distance_mode, *args, ctx=ctx) as dev:
+        return dev.maxmin(n_select, seeds=seeds, min_distance=min_distance)
 
 
 # a distance mode -> its farthest-first selection: takes (seqs, *mode_args(...)), and n_select=, seeds=, min_distance=, ctx=
@@ -978,6 +962,5 @@ def maxmin(seqs, n_select: int | None = None, distance_mode: str = "mash", *, k:
     of `check_maxmin_args`, before any device work."""
     check_mode_args(distance_mode, sketch_size, mash_canonical)
     seqs = list(seqs)
-    check_maxmin_args(len(seqs), n_select, seeds, min_distance)
-    return MAXMIN_MODES[distance_mode](seqs, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
-                                       n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)
+    return _maxmin(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                   n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)

@@ -36,7 +36,7 @@ def device_side(ctx, mode, n):
 
     rng = np.random.default_rng(1)
     seqs = [rng.integers(0, 4, LENGTH, dtype=np.uint8) for _ in range(n)]
-    return distance.Sketches(seqs, MASH_K, MASH_S, ctx=ctx) if mode == "mash" else ctx.build_matrix(seqs, K)
+    return distance.device_side(seqs, mode, *((MASH_K, MASH_S) if mode == "mash" else (K,)), ctx=ctx)
 
 
 def depth(Z):
@@ -49,7 +49,7 @@ def depth(Z):
 
 
 def run(wall, only_cophenet):
-    from diverseseq_amd import cluster, distance, engine
+    from diverseseq_amd import engine
 
     ctx = engine.Context(0)
     side = {}
@@ -59,12 +59,8 @@ def run(wall, only_cophenet):
                 h.close()
             side = {(mode, n): device_side(ctx, mode, n)}
         dev = side[mode, n]
-        Z = cluster.device_side_tree(dev, mode, method)
-        if mode == "mash":
-            calls = [("cophenet", lambda: dev.cophenet(Z)), ("nearest 1", lambda: dev.nearest(dev, 1))]
-        else:
-            calls = [("cophenet", lambda: distance.matrix_cophenet(dev, Z, mode)),
-                     ("nearest 1", lambda: distance.matrix_nearest(dev, dev, 1, mode))]
+        Z = dev.linkage(method)
+        calls = [("cophenet", lambda: dev.cophenet(Z)), ("nearest 1", lambda: dev.nearest(dev, 1))]
         if only_cophenet:
             calls = calls[:1]
         times = {what: [] for what, _ in calls}
@@ -92,15 +88,15 @@ def run(wall, only_cophenet):
 def host_baseline():
     from scipy.cluster.hierarchy import cophenet
 
-    from diverseseq_amd import cluster, distance, engine
+    from diverseseq_amd import engine
 
     ctx = engine.Context(0)
     name, mode, n, method = SHAPES[0]
     dev = device_side(ctx, mode, n)
-    Z = cluster.device_side_tree(dev, mode, method)
-    got = distance.matrix_cophenet(dev, Z, mode).correlation
+    Z = dev.linkage(method)
+    got = dev.cophenet(Z).correlation
     t0 = time.perf_counter()
-    d = distance.matrix_jsd_distances(dev)  # the N x N matrix computed again and copied out of HBM
+    d = dev.distances()  # the N x N matrix computed again and copied out of HBM
     t1 = time.perf_counter()
     y = d[np.triu_indices(n, 1)]
     t2 = time.perf_counter()

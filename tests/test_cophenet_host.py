@@ -133,8 +133,9 @@ def gpu_case(n: int, kind: str, method: str):
 
 # ------------------------------------------------------------------ the names
 def test_public_names_exist():
-    for name in ("CopheneticScores", "cophenet", "matrix_cophenet", "device_side_cophenet", "check_linkage_matrix"):
+    for name in ("CopheneticScores", "cophenet", "matrix_cophenet", "DeviceSide", "check_linkage_matrix"):
         assert hasattr(distance, name), name
+    assert callable(distance.DeviceSide.cophenet)
     assert callable(distance.Sketches.cophenet)
     for name in ("cophenet", "ctree_cophenet", "compare_linkages"):
         assert callable(getattr(cluster, name, None)), name

@@ -198,14 +198,11 @@ def test_modes_over_family_sequences(ctx, case):
         # a row list, through the handle
         ds = d[np.ix_(rows, rows)]
         Zs = cluster.linkage(ds, "complete", ctx=ctx)
-        dev = distance.device_side(seqs, mode, *distance.mode_args(mode, kw["k"], kw.get("sketch_size"), 4, False), ctx=ctx)
-        try:
-            got = dev.cophenet(Zs, rows=rows) if mode == "mash" else distance.matrix_cophenet(dev, Zs, mode, rows=rows)
+        with distance.device_side(seqs, mode, *distance.mode_args(mode, kw["k"], kw.get("sketch_size"), 4, False), ctx=ctx) as dev:
+            got = dev.cophenet(Zs, rows=rows)
             assert_scores(got, ds, Zs, f"{mode} k={kw['k']} row list")
-            whole = distance.device_side_cophenet(dev, Z, mode)
-        finally:
-            dev.close()
-        assert_same_scores(whole, distance.cophenet(seqs, Z, mode, ctx=ctx, **kw), f"{mode} device_side_cophenet")
+            whole = dev.cophenet(Z)
+        assert_same_scores(whole, distance.cophenet(seqs, Z, mode, ctx=ctx, **kw), f"{mode} DeviceSide.cophenet")
         assert_same_scores(got, distance.cophenet(sub, Zs, mode, ctx=ctx, **kw), f"{mode} the listed rows as a batch")
 
 
