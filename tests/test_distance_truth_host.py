@@ -236,7 +236,8 @@ def _freq_rows_case(k):
     return Case(name, None, np.vstack([f, extra]), 0, 0, ())
 
 
-BINS_STATES_K = ((2, 1), (3, 1), (4, 1), (5, 2), (20, 1), (4, 3), (3, 4), (5, 3), (2, 7), (20, 2), (20, 3), (4, 6), (4, 7))
+BINS_STATES_K = ((2, 1), (3, 1), (4, 1), (5, 2), (20, 1), (4, 3), (3, 4), (5, 3), (2, 7), (20, 2), (20, 3), (4, 6), (4, 7),
+                 (4, 8), (5, 7))  # (the last two: rows beyond 16 384 bins, tests/test_wide_rows_host.py)
 BINS_FREQS = (1, 63, 64, 65, 127, 129, 4097)
 
 
@@ -389,8 +390,9 @@ def test_tol_derived_is_below_the_old_constant():
 
 def test_case_table_is_complete():
     by = {c.name: c for c in _CASES}
-    assert [c.nbins for c in _CASES[:13]] == [2, 3, 4, 25, 20, 64, 81, 125, 128, 400, 8000, 4096, 16384]
-    assert [c.nbins for c in _CASES[13:20]] == list(BINS_FREQS)
+    nb = len(BINS_STATES_K)
+    assert [c.nbins for c in _CASES[:nb]] == [2, 3, 4, 25, 20, 64, 81, 125, 128, 400, 8000, 4096, 16384, 65536, 78125]
+    assert [c.nbins for c in _CASES[nb:nb + 7]] == list(BINS_FREQS)
     for c in _CASES:
         rows = case_rows(c)
         assert rows.shape == (c.nrows, c.nbins)
@@ -399,12 +401,12 @@ def test_case_table_is_complete():
         else:                   # matrix_from_freqs takes every row (src/record.rs:90-104)
             for f in rows:
                 assert abs(np.add.accumulate(f[f != 0])[-1] - 1.0) <= f.size * np.finfo(np.float64).eps, c.name
-    for c in _CASES[:13]:
+    for c in _CASES[:nb]:
         assert c.nrows == 12 and len({s.size for s in c.seqs}) > 6 and (c.seqs[0] == c.num_states).any()
         if c.k == 1:  # counts in proportion, quotients that round alike
             rows = case_rows(c)
             assert (rows[11] == 2 * rows[3]).all() and (f64_quotients(rows[11]) == f64_quotients(rows[3])).all()
-    for c in _CASES[13:20]:
+    for c in _CASES[nb:nb + 7]:
         assert ((c.freqs == 0).sum(axis=1) == int(0.9 * c.nbins))[1::2].all() and (c.freqs[0::2] > 0).all()
     assert by["tiles"].nrows == 100
     for k in (3, 6, 7):
