@@ -33,6 +33,15 @@ int dvs_hip_fail(dvs_ctx *ctx, hipError_t e, const char *what) {
     return dvs_set_error(ctx, code, "HIP error %d (%s) in %s", int(e), hipGetErrorString(e), what);
 }
 
+// DVS_TEST_KNOBS=poison_blocks: the whole rounded block filled with 0xFF bytes behind whatever the context's stream
+// still holds (a cached block may be read by work enqueued there before it was handed back), and waited for, so that a
+// first use on any of the context's streams finds the fill done
+static int dev_poison(dvs_ctx *ctx, void *p, size_t sz, const char *what) {
+    hipError_t e = hipMemsetAsync(p, 0xFF, sz, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? DVS_OK : dvs_hip_fail(ctx, e, what);
+}
+
 int dvs_dev_alloc(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what) {
     const size_t sz = ((bytes ? bytes : 1) + 4095) & ~size_t(4095);
     auto it = ctx->pool.find(sz);
@@ -41,6 +50,7 @@ int dvs_dev_alloc(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what) {
         ctx->pool.erase(it);
         ctx->pool_bytes -= sz;
         ctx->live[*ptr] = sz;
+        if (__builtin_expect(ctx->knobs.test_poison_blocks, 0)) return dev_poison(ctx, *ptr, sz, what);
         return DVS_OK;
     }
     hipError_t e = hipMalloc(ptr, sz);
@@ -54,6 +64,7 @@ int dvs_dev_alloc(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what) {
         return dvs_hip_fail(ctx, e, what);
     }
     ctx->live[*ptr] = sz;
+    if (__builtin_expect(ctx->knobs.test_poison_blocks, 0)) return dev_poison(ctx, *ptr, sz, what);
     return DVS_OK;
 }
 
@@ -73,10 +84,12 @@ int dvs_pinned_get(dvs_ctx *ctx, void **ptr) {
     if (!ctx->pinned_pool.empty()) {
         *ptr = ctx->pinned_pool.back();
         ctx->pinned_pool.pop_back();
+        if (__builtin_expect(ctx->knobs.test_poison_blocks, 0)) memset(*ptr, 0xFF, 4096);
         return DVS_OK;
     }
     hipError_t e = hipHostMalloc(ptr, 4096, hipHostMallocDefault);
     if (e != hipSuccess) return dvs_hip_fail(ctx, e, "hipHostMalloc");
+    if (__builtin_expect(ctx->knobs.test_poison_blocks, 0)) memset(*ptr, 0xFF, 4096);
     return DVS_OK;
 }
 void dvs_pinned_put(dvs_ctx *ctx, void *ptr) {
@@ -136,6 +149,7 @@ void dvs_knobs_from_env(dvs_knobs *k) {
     if (const char *lt = tk ? strstr(tk, "long_tile_") : nullptr) k->test_long_tile = uint32_t(strtoul(lt + 10, nullptr, 10));
     k->test_rowlog_ring = 0;
     if (const char *rr = tk ? strstr(tk, "rowlog_ring_") : nullptr) k->test_rowlog_ring = uint32_t(strtoul(rr + 12, nullptr, 10));
+    k->test_poison_blocks = tk && strstr(tk, "poison_blocks") != nullptr;
 }
 
 extern "C" {

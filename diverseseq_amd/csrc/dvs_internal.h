@@ -54,6 +54,10 @@ struct dvs_knobs {
     // test-only (DVS_TEST_KNOBS=rowlog_ring_<n>): the stepwise selections' device-side ring of accepted rows holds n rows
     // (>= 4), so that a few dozen accepts wrap it several times before a tie is arbitrated
     uint32_t test_rowlog_ring = 0;
+    // test-only (DVS_TEST_KNOBS=poison_blocks): every block dvs_dev_alloc hands out, cached or fresh, is filled with 0xFF
+    // bytes over its whole rounded size and the fill waited for; dvs_pinned_get fills its 4 KiB host block likewise.  A
+    // read before the first write then sees NaN / all-ones instead of zeros or the last call's values
+    bool test_poison_blocks = false;
 };
 void dvs_knobs_from_env(dvs_knobs *k);
 
@@ -120,6 +124,9 @@ struct dvs_ctx {
         // the last build's sequences all had one length and lay end to end: no offsets on the device
         bool uniform = false;
         uint64_t uni_base = 0, uni_stride = 0;
+        // a build that was not waited for may still read d_off / d_rows / d_tiles: the stream is drained before one of
+        // them goes back to the block cache (dvs_hist_prepare)
+        bool lists_in_flight = false;
     } off_cache;
     // packed upload of host sequences (pack.hip): the pinned staging block, kept between calls, and the
     // event behind the last copy that read it
@@ -192,6 +199,10 @@ struct dvs_matrix {
     // ... and that rest was launched on the context's stream_rest (CU split): the head CUs are free
     // for a selection's head phase until the context's stream, which waits for it, moves on
     bool rest_beside_head = false;
+    // the build was not waited for and nothing has drained the context's stream behind it yet (a selection's poll does):
+    // dvs_matrix_free_fields drains it before the rows, totals and entropies go back to the block cache, where a
+    // selection's set-up may take them and write them on a side stream that nothing orders behind the histogram
+    bool in_flight = false;
     int device = 0;
     dvs_ctx *ctx = nullptr;  // owner of the allocations
 };

@@ -388,6 +388,12 @@ extern "C" int dvs_seqbatch_from_fasta(dvs_ctx *ctx, const uint8_t *raw, int raw
             chunk_blocks = CH_BLOCKS;
             ING_TRY(hipStreamCreateWithFlags(&scopy, hipStreamNonBlocking));
             for (int i = 0; i < NSLOT; i++) ev_copied.push_back(dvs_event_get(ctx));
+            // (d_raw comes from the block cache, which orders reuse on the context's stream only: work queued there may
+            // still read the block -- dvs_seqbatch_pack hands a batch's bytes back behind its kernel -- so the copy
+            // stream starts behind it; the event goes back to the pool with the others, after the stream is drained)
+            ev_copied.push_back(dvs_event_get(ctx));
+            ING_TRY(hipEventRecord(ev_copied[NSLOT], ctx->stream));
+            ING_TRY(hipStreamWaitEvent(scopy, ev_copied[NSLOT], 0));
         } else {
             ING_TRY(hipMemcpyAsync(d_raw, raw, nbytes, hipMemcpyHostToDevice, ctx->stream));
         }
@@ -533,7 +539,8 @@ extern "C" int dvs_seqbatch_pack(dvs_ctx *ctx, dvs_seqbatch *b) {
         return rc;
     }
     b->packed = p;
-    dvs_dev_free(b->ctx, b->d_codes);  // (back to the cache: stream order protects it until the kernel has run)
+    (void)hipStreamSynchronize(ctx->stream);  // (the pack kernel reads the bytes; the cache's next user may be on another stream)
+    dvs_dev_free(b->ctx, b->d_codes);
     b->d_codes = nullptr;
     return DVS_OK;
 }

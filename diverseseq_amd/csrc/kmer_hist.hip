@@ -473,6 +473,9 @@ int dvs_matrix_settle(dvs_ctx *ctx, const dvs_matrix *cm) {
 void dvs_matrix_free_fields(dvs_matrix *m) {
     if (!m) return;
     (void)dvs_matrix_settle(m->ctx, m);  // the pinned block must not go back to the cache with a copy pending
+    // (the rest of an unwaited build may still be writing the rows: the context's stream holds it, or the wait for it)
+    if (m->in_flight && m->ctx) (void)hipStreamSynchronize(m->ctx->stream);
+    m->in_flight = false;
     if (m->ev_join) dvs_event_put(m->ctx, m->ev_join);
     m->ev_join = nullptr;
     dvs_dev_free(m->ctx, m->d_counts);
@@ -512,6 +515,10 @@ int dvs_hist_prepare(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint3
             uni = diff == 0;
         }
         if (uni && base + uint64_t(nseq) * stride <= nbytes) {
+            if (oc.lists_in_flight && (oc.d_rows || oc.d_tiles)) {
+                (void)hipStreamSynchronize(ctx->stream);
+                oc.lists_in_flight = false;
+            }
             dvs_dev_free(ctx, oc.d_rows);
             dvs_dev_free(ctx, oc.d_tiles);
             oc.d_rows = oc.d_tiles = nullptr;
@@ -594,8 +601,13 @@ int dvs_hist_prepare(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint3
                 }
             }
         }
-        // (the previous lists go back to the block cache; stream order protects them until the
-        // kernels that read them have run; the offsets block is kept while it is large enough)
+        // (the previous lists go back to the block cache: behind a build that was not waited for the stream is
+        // drained first -- the cache's next user may write the block on another stream; the offsets block is kept
+        // while it is large enough)
+        if (oc.lists_in_flight && (oc.d_rows || oc.d_tiles || oc.d_off_cap < n_off)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            oc.lists_in_flight = false;
+        }
         dvs_dev_free(ctx, oc.d_rows);
         dvs_dev_free(ctx, oc.d_tiles);
         oc.d_rows = oc.d_tiles = nullptr;
@@ -841,7 +853,10 @@ int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, 
 #undef DVS_LAUNCH_HIST_ANY
 #undef DVS_LAUNCH_HIST
     if (!rc && (e = hipGetLastError()) != hipSuccess) rc = dvs_hip_fail(ctx, e, "histogram launch");
-    if (!rc && no_wait && head_event_done) return DVS_OK;  // (the head's totals are already on their way)
+    if (!rc && no_wait && head_event_done) {  // (the head's totals are already on their way)
+        m->in_flight = oc.lists_in_flight = true;
+        return DVS_OK;
+    }
     if (!rc && no_wait) {
         // Device-resident input: nothing here needs the host to wait.  The first rows' totals are
         // copied to a pinned block behind the kernels and an event marks their arrival; whoever
@@ -856,7 +871,7 @@ int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, 
                 hipMemcpyAsync(m->h_head_pinned, m->d_totals, size_t(m->head_count) * 4, hipMemcpyDeviceToHost,
                                ctx->stream) == hipSuccess &&
                 hipEventRecord(m->ev_built, ctx->stream) == hipSuccess) {
-                cleanup();  // (the lists go back to the cache; stream order protects them)
+                m->in_flight = oc.lists_in_flight = true;
                 return DVS_OK;
             }
             if (m->ev_built) dvs_event_put(ctx, m->ev_built);

@@ -2081,6 +2081,7 @@ static int sel_poll(dvs_ctx *ctx, dvs_select *s) {
     DVS_HIP(ctx, hipMemcpyAsync(s->h_ctl, s->dev.ctl, sizeof(SelCtl), hipMemcpyDeviceToHost,
                                 ctx->stream));
     DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const_cast<dvs_matrix *>(s->mat)->in_flight = false;  // (the stream held the matrix's build, or the wait for it)
     return DVS_OK;
 }
 
