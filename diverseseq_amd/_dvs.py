@@ -36,7 +36,7 @@ class SummedRecordsResult:
     """src/records_py.rs:7-88: read-only result of a selection, picklable"""
 
     __slots__ = ("total_jsd", "records", "mean_delta_jsd", "std_delta_jsd", "cov_delta_jsd",
-                 "size", "k", "num_states", "stats")
+                 "size", "k", "num_states", "stats", "canonical")
 
     def __init__(self):
         self.total_jsd = 0.0
@@ -48,21 +48,26 @@ class SummedRecordsResult:
         self.k = 0
         self.num_states = 0
         self.stats = None  # engine statistics (not part of the reference's object)
+        self.canonical = False  # the records' frequency rows are over canonical k-mer bins (not part of the reference's object)
 
     @property
     def record_names(self) -> list[str]:
         return [r[0] for r in self.records]
 
     def __getstate__(self) -> dict:
-        return {n: getattr(self, n) for n in ("total_jsd", "records", "mean_delta_jsd",
-                                              "std_delta_jsd", "cov_delta_jsd", "size", "k",
-                                              "num_states")}
+        state = {n: getattr(self, n) for n in ("total_jsd", "records", "mean_delta_jsd",
+                                               "std_delta_jsd", "cov_delta_jsd", "size", "k",
+                                               "num_states")}
+        if self.canonical:  # (a plain result pickles to the reference's fields alone)
+            state["canonical"] = True
+        return state
 
     def __setstate__(self, state: dict) -> None:
         for n in ("total_jsd", "records", "mean_delta_jsd", "std_delta_jsd", "cov_delta_jsd",
                   "size", "k", "num_states"):
             setattr(self, n, state[n])  # KeyError on a missing field, as the reference
         self.stats = None
+        self.canonical = bool(state.get("canonical", False))
 
     def __repr__(self):
         return f"SummedRecordsResult(size={self.size}, total_jsd={self.total_jsd})"
@@ -307,7 +312,7 @@ def _gather(store: ZarrStoreWrapper, seqids):
     return ids, data, offsets, _labels(ids)
 
 
-def _result(sel: engine.Selection, ids, k: int, num_states: int) -> SummedRecordsResult:
+def _result(sel: engine.Selection, ids, k: int, num_states: int, canonical: bool = False) -> SummedRecordsResult:
     s = sel.summary()
     mem = sel.members(with_freqs=True)
     r = SummedRecordsResult()
@@ -317,6 +322,7 @@ def _result(sel: engine.Selection, ids, k: int, num_states: int) -> SummedRecord
     r.cov_delta_jsd = s.cov_delta_jsd
     r.size = int(s.size)
     r.k, r.num_states = k, num_states
+    r.canonical = bool(canonical)
     r.records = [(ids[int(p)], mem.kfreqs[i].tolist(), float(mem.delta_jsd[i]))
                  for i, p in enumerate(mem.positions)]
     r.stats = {n: getattr(s, n) for n in ("rows_scored", "rows_rechecked", "n_windows", "n_events",
@@ -329,7 +335,12 @@ def _check_k(k: int):
         raise ValueError("k cannot be 0")  # src/record.rs:126
 
 
-def _gather_and_build(store: ZarrStoreWrapper, seqids, n_min: int, k: int, num_states: int):
+def _check_canonical(canonical: bool, num_states: int):
+    if canonical and num_states != 4:
+        raise ValueError(f"Canonical kmers only supported for four-state (dna/rna) sequences, not {num_states} states.")
+
+
+def _gather_and_build(store: ZarrStoreWrapper, seqids, n_min: int, k: int, num_states: int, canonical: bool = False):
     """ids, count matrix and labels of a selection's stream.  `data` may be a VIEW of the in-memory
     store's arena: it is let go on every way out of here -- also when the checks or the build raise, since
     a traceback would otherwise keep the frame's view alive and the store's next write fail (BufferError)."""
@@ -338,19 +349,22 @@ def _gather_and_build(store: ZarrStoreWrapper, seqids, n_min: int, k: int, num_s
         if len(ids) < n_min:
             raise ValueError(f"The number of sequences {len(ids)} is < n {n_min}")
         _check_k(k)
-        return ids, engine.default_context().build_matrix_concat(data, offsets, k, num_states), labels
+        _check_canonical(canonical, num_states)
+        return ids, engine.default_context().build_matrix_concat(data, offsets, k, num_states, canonical=canonical), labels
     finally:
         data = None
 
 
 def nmost_divergent(store: ZarrStoreWrapper, n: int, k: int, num_states: int = 4,
-                    seqids=None) -> SummedRecordsResult:
-    """src/lib.rs:59-73 -> select_nmost_divergent (src/records.rs:311-342)"""
-    ids, m, labels = _gather_and_build(store, seqids, n, k, num_states)
+                    seqids=None, canonical: bool = False) -> SummedRecordsResult:
+    """src/lib.rs:59-73 -> select_nmost_divergent (src/records.rs:311-342); canonical (beyond the reference): over
+    count rows folded onto the canonical k-mer bins (`engine.CountMatrix.canonical`), so that a sequence and its
+    reverse complement count as the same"""
+    ids, m, labels = _gather_and_build(store, seqids, n, k, num_states, canonical)
     try:
         sel = m.nmost(n, labels=labels)
         try:
-            return _result(sel, ids, k, num_states)
+            return _result(sel, ids, k, num_states, canonical)
         finally:
             sel.close()
     finally:
@@ -358,13 +372,14 @@ def nmost_divergent(store: ZarrStoreWrapper, n: int, k: int, num_states: int = 4
 
 
 def max_divergent(store: ZarrStoreWrapper, min_size: int, max_size: int, k: int,
-                  num_states: int = 4, seqids=None, stat: str = "stdev") -> SummedRecordsResult:
-    """src/lib.rs:105-137 -> select_max_divergent (src/records.rs:390-454)"""
-    ids, m, labels = _gather_and_build(store, seqids, min_size, k, num_states)
+                  num_states: int = 4, seqids=None, stat: str = "stdev",
+                  canonical: bool = False) -> SummedRecordsResult:
+    """src/lib.rs:105-137 -> select_max_divergent (src/records.rs:390-454); canonical: as `nmost_divergent`"""
+    ids, m, labels = _gather_and_build(store, seqids, min_size, k, num_states, canonical)
     try:
         sel = m.max_divergent(min_size, max_size, stat, labels=labels)
         try:
-            return _result(sel, ids, k, num_states)
+            return _result(sel, ids, k, num_states, canonical)
         finally:
             sel.close()
     finally:
@@ -385,8 +400,18 @@ def _merge_inputs(records):
     return ids, rows, np.asarray(labels, dtype=np.uint32), k, ns
 
 
+def _merged_flag(records) -> bool:
+    """whether the results being merged are over canonical bins; ValueError when only some of them are (their rows
+    have different bins)"""
+    flags = {bool(getattr(sr, "canonical", False)) for sr in records}
+    if len(flags) > 1:
+        raise ValueError("cannot merge results over canonical k-mers with results over plain k-mers")
+    return bool(flags and flags.pop())
+
+
 def final_nmost(records: list[SummedRecordsResult], n: int) -> SummedRecordsResult:
     """src/lib.rs:95-103 -> select_nmost_divergent_final (src/records.rs:363-382)"""
+    canonical = _merged_flag(records)
     ids, rows, labels, k, ns = _merge_inputs(records)
     if len(ids) < n:
         raise ValueError(f"The number of sequences {len(ids)} is < n {n}")
@@ -397,7 +422,7 @@ def final_nmost(records: list[SummedRecordsResult], n: int) -> SummedRecordsResu
     try:
         sel = m.nmost(n, labels=labels)
         try:
-            return _result(sel, ids, k, ns)
+            return _result(sel, ids, k, ns, canonical)
         finally:
             sel.close()
     finally:
@@ -407,6 +432,7 @@ def final_nmost(records: list[SummedRecordsResult], n: int) -> SummedRecordsResu
 def final_max(records: list[SummedRecordsResult], min_size: int, max_size: int,
               stat: str = "stdev") -> SummedRecordsResult:
     """src/lib.rs:139-160 -> select_max_divergent_final (src/records.rs:456-507)"""
+    canonical = _merged_flag(records)
     ids, rows, labels, k, ns = _merge_inputs(records)
     if len(ids) < min_size:
         raise ValueError(f"The number of sequences {len(ids)} is < n {min_size}")
@@ -417,7 +443,7 @@ def final_max(records: list[SummedRecordsResult], min_size: int, max_size: int,
     try:
         sel = m.max_divergent(min_size, max_size, stat, labels=labels)
         try:
-            return _result(sel, ids, k, ns)
+            return _result(sel, ids, k, ns, canonical)
         finally:
             sel.close()
     finally:
@@ -428,20 +454,21 @@ class SummedRecordsWrapper:
     """src/records_py.rs:90-125: stateful delta-JSD calculator"""
 
 
-    def __init__(self, records, k: int, num_states: int = 4):
+    def __init__(self, records, k: int, num_states: int = 4, canonical: bool = False):
         _check_k(k)
-        self._k, self._num_states = k, num_states
+        _check_canonical(canonical, num_states)
+        self._k, self._num_states, self._canonical = k, num_states, bool(canonical)
         self._ctx = engine.default_context()
         self._ids = [sid for sid, _ in records]
         label_of: dict[str, int] = {}
         labels = np.asarray([label_of.setdefault(sid, len(label_of)) for sid in self._ids],
                             dtype=np.uint32)
         self._label_of = label_of
-        self._matrix = self._ctx.build_matrix([seq for _, seq in records], k, num_states)
+        self._matrix = self._ctx.build_matrix([seq for _, seq in records], k, num_states, canonical=self._canonical)
         self._sel = self._matrix.as_set(labels=labels)  # make_summed_records, records.rs:509-524
 
     def delta_jsd(self, seqid: str, seq) -> float:
-        q = self._ctx.build_matrix([bytes(seq)], self._k, self._num_states)
+        q = self._ctx.build_matrix([bytes(seq)], self._k, self._num_states, canonical=self._canonical)
         try:
             if int(q.totals()[0]) == 0:
                 raise ValueError(f"delta_jsd('{seqid}') failed: No valid k-mers for '{seqid}'")
@@ -451,12 +478,12 @@ class SummedRecordsWrapper:
             q.close()
 
     def get_result(self) -> SummedRecordsResult:
-        return _result(self._sel, self._ids, self._k, self._num_states)
+        return _result(self._sel, self._ids, self._k, self._num_states, self._canonical)
 
 
-def get_delta_jsd_calculator(seqids_seqs, k: int, num_states: int = 4) -> SummedRecordsWrapper:
-    """src/lib.rs:162-171"""
-    return SummedRecordsWrapper(list(seqids_seqs), k, num_states)
+def get_delta_jsd_calculator(seqids_seqs, k: int, num_states: int = 4, canonical: bool = False) -> SummedRecordsWrapper:
+    """src/lib.rs:162-171; canonical: the set and every query folded onto the canonical k-mer bins"""
+    return SummedRecordsWrapper(list(seqids_seqs), k, num_states, canonical)
 
 
 def mash_sketch(seq_array, k: int, sketch_size: int, num_states: int = 4,

@@ -54,6 +54,7 @@ EXPORTS = (
     "dvs_linkage_cophenet", "dvs_jsd_cophenet", "dvs_euclidean_cophenet", "dvs_sketches_cophenet", "dvs_cophenet",
     "dvs_nj", "dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj", "dvs_nj_patristic",
     "dvs_maxmin", "dvs_sketches_maxmin", "dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin",
+    "dvs_canonical_bins", "dvs_matrix_fold_canonical", "dvs_matrix_is_canonical",
 )
 
 
@@ -256,6 +257,10 @@ def load() -> C.CDLL:
         L.dvs_sketches_maxmin.argtypes = [vp, vp, u32, u32, *maxmin]
         for n in ("dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin"):
             getattr(L, n).argtypes = [vp, vp, *maxmin]
+        L.dvs_canonical_bins.argtypes = [u32, u32p, u64p]
+        L.dvs_matrix_fold_canonical.argtypes = [vp, vp, C.POINTER(vp)]
+        L.dvs_matrix_is_canonical.argtypes = [vp]
+        L.dvs_matrix_is_canonical.restype = C.c_uint32
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -57,6 +57,13 @@ def _num_states(moltype: str) -> int:
         raise ValueError(f"unknown moltype {moltype!r}") from None
 
 
+def _check_canonical(canonical: bool, moltype: str, moltypes: str = "dna") -> None:
+    """canonical count rows fold a k-mer with its reverse complement: nucleotides only (the message is the one the
+    mash apps give for their canonical k-mers)"""
+    if canonical and moltype not in ("dna", "rna"):
+        raise ValueError(f"Canonical kmers only supported for {moltypes} sequences.")
+
+
 def _encode(seq, moltype: str) -> bytes:
     """sequence -> alphabet indices, one byte per symbol (diverse_seq/util.py:32-45 str2arr); gaps and
     ambiguity codes become indices >= num_states and invalidate the k-mers that contain them"""
@@ -111,34 +118,39 @@ class _DistanceApp:
 
     @staticmethod
     def _check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers, *, moltypes: str = "dna",
-                    keep_sketch_size: bool = False):
+                    keep_sketch_size: bool = False, canonical: bool = False):
         """-> (sketch_size, mash_canonical_kmers) as the app keeps them; `moltypes`: how the message names the
         molecule types that have canonical k-mers; the sketch size means nothing to the euclidean and jsd modes
-        (cli.py:546-560) and is dropped for them unless keep_sketch_size"""
+        (cli.py:546-560) and is dropped for them unless keep_sketch_size; canonical: the count rows of the jsd and
+        euclidean modes folded onto the canonical k-mer bins (dna / rna only; mash has mash_canonical_kmers)"""
         if mash_canonical_kmers is None:
             mash_canonical_kmers = False
         if distance_mode not in _distance.MODES:
             raise ValueError(f"Unexpected distance {distance_mode!r}.")
         if moltype not in ("dna", "rna") and mash_canonical_kmers:
             raise ValueError(f"Canonical kmers only supported for {moltypes} sequences.")
+        _check_canonical(canonical, moltype, moltypes)
+        if distance_mode == "mash" and canonical:
+            raise ValueError(_distance.CANONICAL_MASH)
         if distance_mode == "mash" and sketch_size is None:
             raise ValueError("Expected sketch size for mash distance measure.")
         if distance_mode != "mash" and not keep_sketch_size:
             sketch_size = None
         return sketch_size, mash_canonical_kmers
 
-    def _keep_mode(self, distance_mode, k, sketch_size, moltype, mash_canonical_kmers) -> None:
+    def _keep_mode(self, distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical: bool = False) -> None:
         self._moltype = moltype
         self._k = k
         self._num_states = _num_states(moltype)
         self._sketch_size = sketch_size
         self._distance_mode = distance_mode
         self._mash_canonical = mash_canonical_kmers
+        self._canonical = bool(canonical)
 
     def _mode_kwargs(self) -> dict:
         """the keyword arguments of the diverseseq_amd.cluster functions over sequences"""
         return dict(k=self._k, sketch_size=self._sketch_size, distance_mode=self._distance_mode,
-                    mash_canonical_kmers=self._mash_canonical, num_states=self._num_states)
+                    mash_canonical_kmers=self._mash_canonical, num_states=self._num_states, canonical=self._canonical)
 
 
 @_define_app
@@ -146,7 +158,10 @@ class dvs_max:
     """select the maximally divergent seqs from a sequence collection (records.py:254-321)"""
 
     def __init__(self, min_size: int = 5, max_size: int = 30, stat: str = "stdev", moltype: str = "dna",
-                 include: list[str] | str | None = None, k: int = 6, seed: int | None = None) -> None:
+                 include: list[str] | str | None = None, k: int = 6, seed: int | None = None,
+                 canonical: bool = False) -> None:
+        _check_canonical(canonical, moltype)
+        self._canonical = bool(canonical)
         self._k = k
         self._moltype = moltype
         self._num_states = _num_states(moltype)
@@ -162,7 +177,8 @@ class dvs_max:
         seqids = list(zstore.unique_seqids)
         self._rng.shuffle(seqids)
         result = dvs.max_divergent(zstore, min_size=self._min_size, max_size=self._max_size, k=self._k,
-                                   num_states=self._num_states, seqids=seqids, stat=self._stat)
+                                   num_states=self._num_states, seqids=seqids, stat=self._stat,
+                                   canonical=self._canonical)
         return take(set(result.record_names) | set(self._include or []))
 
 
@@ -171,7 +187,9 @@ class dvs_nmost:
     """select the n-most diverse seqs from a sequence collection (records.py:324-373)"""
 
     def __init__(self, n: int = 10, moltype: str = "dna", include: list[str] | str | None = None, k: int = 6,
-                 seed: int | None = None) -> None:
+                 seed: int | None = None, canonical: bool = False) -> None:
+        _check_canonical(canonical, moltype)
+        self._canonical = bool(canonical)
         self._k = k
         self._n = n
         self._moltype = moltype
@@ -183,7 +201,8 @@ class dvs_nmost:
         zstore = _populate_inmem_zstore(data)
         seqids = list(zstore.unique_seqids)
         self._rng.shuffle(seqids)
-        result = dvs.nmost_divergent(zstore, n=self._n, k=self._k, seqids=seqids)  # (num_states left at 4, :371)
+        result = dvs.nmost_divergent(zstore, n=self._n, k=self._k, seqids=seqids,  # (num_states left at 4, :371)
+                                     canonical=self._canonical)
         return take(set(result.record_names) | set(self._include or []))
 
 
@@ -191,13 +210,14 @@ class dvs_nmost:
 class dvs_delta_jsd:
     """delta JSD of a sequence against a fixed reference set (records.py:376-429)"""
 
-    def __init__(self, seqs, moltype: str = "dna", k: int = 6) -> None:
+    def __init__(self, seqs, moltype: str = "dna", k: int = 6, canonical: bool = False) -> None:
+        _check_canonical(canonical, moltype)
         _, data, _ = _as_mapping(seqs, moltype)
         zero_len = ", ".join(n for n, s in data.items() if len(s) == 0)
         if zero_len:
             raise ValueError(f"cannot compute delta_jsd with zero-length sequences: {zero_len}")
         self.moltype = moltype
-        self._sr = dvs.get_delta_jsd_calculator(list(data.items()), k, _num_states(moltype))
+        self._sr = dvs.get_delta_jsd_calculator(list(data.items()), k, _num_states(moltype), canonical=bool(canonical))
 
     def main(self, seq):
         if HAVE_COGENT3 and hasattr(seq, "moltype"):  # pragma: no cover
@@ -218,10 +238,10 @@ class _ClusterTreeBase(_DistanceApp):
 
     def __init__(self, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
-                 show_progress: bool = False) -> None:
+                 show_progress: bool = False, canonical: bool = False) -> None:
         sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
-                                                             moltypes="dna/rna")
-        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
+                                                             moltypes="dna/rna", canonical=canonical)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
         self._progress = show_progress
 
     def main(self, seqs):
@@ -240,9 +260,9 @@ class dvs_ctree(_ClusterTreeBase):
 
     def __init__(self, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
-                 show_progress: bool = False) -> None:
+                 show_progress: bool = False, canonical: bool = False) -> None:
         super().__init__(k=k, sketch_size=sketch_size, moltype=moltype, distance_mode=distance_mode,
-                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
+                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress, canonical=canonical)
 
 
 @_define_app
@@ -254,9 +274,9 @@ class dvs_njtree(_ClusterTreeBase):
 
     def __init__(self, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
-                 show_progress: bool = False) -> None:
+                 show_progress: bool = False, canonical: bool = False) -> None:
         super().__init__(k=k, sketch_size=sketch_size, moltype=moltype, distance_mode=distance_mode,
-                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
+                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress, canonical=canonical)
 
     def main(self, seqs):
         names, arrays = _as_arrays(seqs, self._moltype)
@@ -277,9 +297,10 @@ class dvs_par_ctree(_ClusterTreeBase):
 
     def __init__(self, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
                  distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
-                 show_progress: bool = False, max_workers: int | None = None, parallel: bool = True) -> None:
+                 show_progress: bool = False, max_workers: int | None = None, parallel: bool = True,
+                 canonical: bool = False) -> None:
         super().__init__(k=k, sketch_size=sketch_size, moltype=moltype, distance_mode=distance_mode,
-                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress)
+                         mash_canonical_kmers=mash_canonical_kmers, show_progress=show_progress, canonical=canonical)
         self._max_workers = max_workers
         self._parallel = parallel
 
@@ -292,16 +313,18 @@ class dvs_dist(_DistanceApp):
     with the names in input order."""
 
     def __init__(self, distance_mode: str = "mash", *, k: int = 12, sketch_size: int | None = 3_000,
-                 moltype: str = "dna", mash_canonical_kmers: bool | None = None, show_progress: bool = False) -> None:
+                 moltype: str = "dna", mash_canonical_kmers: bool | None = None, show_progress: bool = False,
+                 canonical: bool = False) -> None:
         sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
-                                                             keep_sketch_size=True)
-        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
+                                                             keep_sketch_size=True, canonical=canonical)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
         self._show_progress = show_progress
 
     def main(self, seqs):
         names, arrays = _as_arrays(seqs, self._moltype)
         dists = _distance.MODES[self._distance_mode][0](arrays, *_distance.mode_args(
-            self._distance_mode, self._k, self._sketch_size, self._num_states, self._mash_canonical))
+            self._distance_mode, self._k, self._sketch_size, self._num_states, self._mash_canonical),
+            **({"canonical": True} if self._canonical else {}))
         if HAVE_COGENT3:  # pragma: no cover
             from cogent3.evolve.fast_distance import DistanceMatrix
 
@@ -318,22 +341,23 @@ class dvs_nearest(_DistanceApp):
     listed, so a list may be shorter than n_nearest."""
 
     def __init__(self, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k: int = 12,
-                 sketch_size: int | None = 3_000, moltype: str = "dna", mash_canonical_kmers: bool | None = None) -> None:
+                 sketch_size: int | None = 3_000, moltype: str = "dna", mash_canonical_kmers: bool | None = None,
+                 canonical: bool = False) -> None:
         sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
-                                                             keep_sketch_size=True)
+                                                             keep_sketch_size=True, canonical=canonical)
         names, arrays = _as_arrays(refs, moltype)
         self._n_nearest = _distance.check_n_nearest(n_nearest, len(names))
-        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
         self._ref_names = names
         self._mode_args = _distance.mode_args(distance_mode, k, sketch_size, self._num_states, mash_canonical_kmers)
         # (kept for the life of the app: the handle's finaliser frees it)
-        self._refs = _distance.device_side(arrays, distance_mode, *self._mode_args)
+        self._refs = _distance.device_side(arrays, distance_mode, *self._mode_args, canonical=self._canonical)
 
     def main(self, seqs):
         names, arrays = _as_arrays(seqs, self._moltype)
         if not names:
             return {}
-        with _distance.device_side(arrays, self._distance_mode, *self._mode_args) as q:
+        with _distance.device_side(arrays, self._distance_mode, *self._mode_args, canonical=self._canonical) as q:
             idx, dist = q.nearest(self._refs, self._n_nearest)
         return {name: [(self._ref_names[j], float(d)) for j, d in zip(idx[i], dist[i]) if j >= 0]
                 for i, name in enumerate(names)}
@@ -351,8 +375,9 @@ class dvs_clusters(_DistanceApp):
 
     def __init__(self, n_clusters: int | None = None, height: float | None = None, distance_mode: str = "mash", *,
                  k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
-                 mash_canonical_kmers: bool | None = None, linkage: str = "average") -> None:
-        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers)
+                 mash_canonical_kmers: bool | None = None, linkage: str = "average", canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
         if (n_clusters is None) == (height is None):
             raise ValueError("dvs_clusters takes exactly one of n_clusters and height")
         if n_clusters is not None and (isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer))
@@ -362,7 +387,7 @@ class dvs_clusters(_DistanceApp):
             raise ValueError("the height of a cut cannot be NaN")
         _distance.linkage_method_code(linkage)
         self._n_clusters, self._height = n_clusters, height
-        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
         self._linkage = linkage
 
     def main(self, seqs):
@@ -388,15 +413,16 @@ class dvs_cophenet(_DistanceApp):
 
     def __init__(self, methods=("single", "complete", "average", "weighted", "ward"), distance_mode: str = "mash", *,
                  k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
-                 mash_canonical_kmers: bool | None = None) -> None:
-        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers)
+                 mash_canonical_kmers: bool | None = None, canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
         methods = [methods] if isinstance(methods, str) else list(methods)
         if not methods:
             raise ValueError("dvs_cophenet takes one linkage method at least")
         for method in methods:
             _distance.linkage_method_code(method)
         self._methods = methods
-        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
 
     def main(self, seqs):
         names, arrays = _as_arrays(seqs, self._moltype)
@@ -422,8 +448,10 @@ class dvs_maxmin(_DistanceApp):
 
     def __init__(self, n: int | None = None, min_distance: float | None = None, distance_mode: str = "mash", *,
                  k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
-                 mash_canonical_kmers: bool | None = None, seeds: list[str] | str | None = None) -> None:
-        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers)
+                 mash_canonical_kmers: bool | None = None, seeds: list[str] | str | None = None,
+                 canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
         if n is None and min_distance is None:
             raise ValueError("dvs_maxmin takes n, min_distance or both")
         if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1):
@@ -434,7 +462,7 @@ class dvs_maxmin(_DistanceApp):
         self._seeds = [seeds] if isinstance(seeds, str) else None if seeds is None else [str(s) for s in seeds]
         if self._seeds is not None and not self._seeds:
             raise ValueError("dvs_maxmin takes one seed at least")
-        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
 
     def main(self, seqs):
         names, arrays = _as_arrays(seqs, self._moltype)
@@ -447,7 +475,7 @@ class dvs_maxmin(_DistanceApp):
         seeds = [at[s] for s in self._seeds] if self._seeds else [0]
         r = _distance.maxmin(arrays, self._n, self._distance_mode, k=self._k, sketch_size=self._sketch_size,
                              num_states=self._num_states, mash_canonical=self._mash_canonical, seeds=seeds,
-                             min_distance=self._min_distance)
+                             min_distance=self._min_distance, canonical=self._canonical)
         picked = [names[i] for i in r.picks.tolist()]
         return {"picks": picked, "radius": [float(v) for v in r.radius],
                 "representative": {name: picked[o] if o >= 0 else None for name, o in zip(names, r.owner.tolist())},

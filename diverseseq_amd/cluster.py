@@ -118,11 +118,13 @@ def linkage_to_newick(names: Sequence, Z) -> str:
 
 def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
           mash_canonical_kmers: bool | None = None, num_states: int = 4, tree: str = "device",
-          linkage: str = "average") -> str:
+          linkage: str = "average", canonical: bool = False) -> str:
     """sequences {name: uint8 codes} -> Newick string (dvs_ctree.main, cluster.py:164-188).
     Argument checks as dvs_ctree.__init__ (cluster.py:139-162).  distance_mode: the reference's "mash" and
     "euclidean", and "jsd", the Jensen-Shannon divergence of the k-mer frequencies (`distance.jsd_distances`),
-    which takes the euclidean mode's arguments.
+    which takes the euclidean mode's arguments.  canonical (euclidean, jsd; here and in the functions over sequences
+    below): the count rows folded onto the canonical k-mer bins (`distance.device_side`), so that the tree does not tell a
+    sequence from its reverse complement; ValueError for mash, which has mash_canonical_kmers.
 
     tree="device": the distances and the tree both on the GPU, the N x N matrix never leaves HBM
     (dvs_sketches_linkage / dvs_matrix_euclidean_linkage / dvs_matrix_jsd_linkage), the string from
@@ -133,7 +135,7 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     RecursionError."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
     if tree not in ("device", "sklearn"):
         raise ValueError(f"Unexpected tree {tree!r}: 'device' or 'sklearn'.")
     distance.linkage_method_code(linkage)
@@ -143,9 +145,10 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     arrays = [seqs[n] for n in names]
     distances, tree_of = distance.MODES[distance_mode]
     args = distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)
+    fold = {"canonical": True} if canonical else {}
     if tree == "sklearn":
-        return make_cluster_tree(names, distances(arrays, *args))
-    return linkage_to_newick(names, tree_of(arrays, *args, method=linkage))
+        return make_cluster_tree(names, distances(arrays, *args, **fold))
+    return linkage_to_newick(names, tree_of(arrays, *args, method=linkage, **fold))
 
 
 def neighbor_joining(dist, *, ctx: engine.Context | None = None) -> "distance.NJTree":
@@ -216,19 +219,20 @@ def patristic(tree) -> np.ndarray:
 
 
 def nj_tree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
-            mash_canonical_kmers: bool | None = None, num_states: int = 4):
+            mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False):
     """sequences {name: uint8 codes} -> (Newick string with branch lengths, distance.NJTree): the distances of
     `distance_mode` and their neighbour-joining tree both on the GPU, the N x N matrix never leaving HBM
     (dvs_sketches_nj / dvs_matrix_euclidean_nj / dvs_matrix_jsd_nj); leaf i is the i-th name.  Argument checks as
     `ctree`, and three sequences at least, before any device work."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
     names = list(seqs)
     if len(names) < 3:
         raise ValueError("need at least three sequences for a neighbour-joining tree")
     with distance.device_side([seqs[n] for n in names], distance_mode,
-                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
         tree = dev.nj()
     return nj_to_newick(names, tree), tree
 
@@ -292,7 +296,7 @@ def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float
 
 def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float | None = None, k: int = 12,
                    sketch_size: int | None = 3000, distance_mode: str = "mash", mash_canonical_kmers: bool | None = None,
-                   num_states: int = 4, linkage: str = "average"):
+                   num_states: int = 4, linkage: str = "average", canonical: bool = False):
     """sequences {name: uint8 codes} -> (Newick string, Z, distance.ClusterScores): `ctree`'s device tree, its cut
     (`cut_tree`: exactly one of n_clusters and height) and the scores of the cut's clusters, row i the i-th name.
     Argument checks as `ctree`, before any device work.
@@ -302,7 +306,7 @@ def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float |
     one more pass of the pair kernels and no second N x N buffer."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
     distance.linkage_method_code(linkage)
     if (n_clusters is None) == (height is None):
         raise ValueError("ctree_clusters takes exactly one of n_clusters and height")
@@ -310,7 +314,8 @@ def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float |
     if len(names) < 2:
         raise ValueError("need at least two sequences to build a tree")
     with distance.device_side([seqs[n] for n in names], distance_mode,
-                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
         Z = dev.linkage(linkage)
         labels = cut_tree(Z, n_clusters=n_clusters, height=height)
         return linkage_to_newick(names, Z), Z, dev.cluster_scores(labels)
@@ -346,33 +351,34 @@ def cophenet(Z, dist=None, *, matrix: bool = False, ctx: engine.Context | None =
 
 def ctree_cophenet(seqs: dict, *, linkage: str = "average", k: int = 12, sketch_size: int | None = 3000,
                    distance_mode: str = "mash", mash_canonical_kmers: bool | None = None, num_states: int = 4,
-                   matrix: bool = False):
+                   matrix: bool = False, canonical: bool = False):
     """sequences {name: uint8 codes} -> (Newick string, Z, distance.CopheneticScores): `ctree`'s device tree and its
     cophenetic correlation with the distances it was built from, leaf i the i-th name.  Argument checks as `ctree`,
     before any device work.  As in `ctree_clusters` the sketches or the count matrix are made once, and the walk computes
     the distances a second time, strip by strip (the same cells bit for bit)."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
     distance.linkage_method_code(linkage)
     names = list(seqs)
     if len(names) < 2:
         raise ValueError("need at least two sequences to build a tree")
     with distance.device_side([seqs[n] for n in names], distance_mode,
-                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
         Z = dev.linkage(linkage)
         return linkage_to_newick(names, Z), Z, dev.cophenet(Z, matrix=matrix)
 
 
 def compare_linkages(seqs: dict, methods: Sequence[str] = ("single", "complete", "average", "weighted", "ward"), *,
                      k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
-                     mash_canonical_kmers: bool | None = None, num_states: int = 4) -> dict:
+                     mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False) -> dict:
     """sequences {name: uint8 codes} -> {method: (Z, cophenetic correlation)} for every linkage method of `methods`:
     which of them represents these distances best.  The sketches or the count matrix are made once; then a tree and a
     walk per method (`ctree_cophenet`'s, the same bits).  Argument checks as `ctree`, before any device work."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
-    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers)
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
     methods = list(methods)
     for method in methods:
         distance.linkage_method_code(method)
@@ -380,7 +386,8 @@ def compare_linkages(seqs: dict, methods: Sequence[str] = ("single", "complete",
     if len(names) < 2:
         raise ValueError("need at least two sequences to build a tree")
     with distance.device_side([seqs[n] for n in names], distance_mode,
-                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers)) as dev:
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
         out = {}
         for method in methods:
             Z = dev.linkage(method)

@@ -270,6 +270,7 @@ void dvs_ctx_release(dvs_ctx *ctx) {
     if (ctx->pack_ev) (void)hipEventDestroy(ctx->pack_ev);
     if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
     dvs_dev_free(ctx, ctx->d_clog_tbl);
+    for (auto &kv : ctx->canon_reps) dvs_dev_free(ctx, kv.second);
     dvs_dev_trim(ctx);
     for (void *p : ctx->pinned_pool) (void)hipHostFree(p);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -619,3 +620,6 @@ int dvs_kmer_counts(dvs_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, 
 }
 
 }  // extern "C"
+
+// matrix_alloc for the other files that make a count matrix (canon.hip's folded one)
+int dvs_matrix_alloc_fields(dvs_ctx *ctx, dvs_matrix *m) { return matrix_alloc(ctx, m); }

@@ -133,6 +133,8 @@ struct dvs_ctx {
     void *h_pack = nullptr;
     size_t h_pack_cap = 0;
     hipEvent_t pack_ev = nullptr;
+    // canonical fold (canon.hip): k -> the C(k) representatives min(idx, rc(idx)) on the device, uploaded on first use
+    std::map<uint32_t, uint32_t *> canon_reps;
 };
 // hipFuncAttributeMaxDynamicSharedMemorySize >= bytes for kernel fn on this context's device
 int dvs_raise_dyn_lds(dvs_ctx *ctx, const void *fn, size_t bytes);
@@ -203,6 +205,8 @@ struct dvs_matrix {
     // dvs_matrix_free_fields drains it before the rows, totals and entropies go back to the block cache, where a
     // selection's set-up may take them and write them on a side stream that nothing orders behind the histogram
     bool in_flight = false;
+    // count rows folded onto the canonical bins of k (canon.hip): nbins = C(k), everything else as the source's kind
+    bool canonical = false;
     int device = 0;
     dvs_ctx *ctx = nullptr;  // owner of the allocations
 };

@@ -410,14 +410,22 @@ class DeviceSide:
         return _run_maxmin(self.ctx, entry, self.n, *args, *front)
 
 
-def device_side(seqs, distance_mode: str, *args, ctx: engine.Context | None = None) -> DeviceSide:
+CANONICAL_MASH = "Canonical count rows should only be specified for the jsd and euclidean distances (mash: mash_canonical)."
+
+
+def device_side(seqs, distance_mode: str, *args, ctx: engine.Context | None = None, canonical: bool = False) -> DeviceSide:
     """what a distance mode keeps in HBM of a batch, made once: a `DeviceSide` that owns its Sketches (mash) or its
-    count matrix (euclidean, jsd); args: mode_args(...)"""
+    count matrix (euclidean, jsd); args: mode_args(...).  canonical (euclidean, jsd; four states): the count rows folded
+    onto the canonical k-mer bins (`engine.CountMatrix.canonical`), so that the distances do not tell a sequence from its
+    reverse complement; ValueError for mash, whose sketches have mash_canonical"""
     if distance_mode not in DeviceSide.MODE_NAMES:
         raise ValueError(f"Unexpected distance {distance_mode!r}.")
     if distance_mode == "mash":
+        if canonical:
+            raise ValueError(CANONICAL_MASH)
         return DeviceSide(Sketches(seqs, *args, ctx=ctx), distance_mode, owns=True)
-    return DeviceSide((ctx or engine.default_context()).build_matrix(seqs, *args), distance_mode, owns=True)
+    fold = {"canonical": True} if canonical else {}
+    return DeviceSide((ctx or engine.default_context()).build_matrix(seqs, *args, **fold), distance_mode, owns=True)
 
 
 def _count_side(m: "engine.CountMatrix", mode: str) -> DeviceSide:
@@ -436,9 +444,10 @@ def mash_distances(seqs, k: int, sketch_size: int, num_states: int = 4,
 
 
 def euclidean_distances(seqs, k: int, num_states: int = 4,
-                        ctx: engine.Context | None = None) -> np.ndarray:
-    """diverse_seq/distance.py:294-332: ||kfreqs_i - kfreqs_j||_2"""
-    with device_side(seqs, "euclidean", k, num_states, ctx=ctx) as dev:
+                        ctx: engine.Context | None = None, canonical: bool = False) -> np.ndarray:
+    """diverse_seq/distance.py:294-332: ||kfreqs_i - kfreqs_j||_2; canonical (here and in every jsd / euclidean function
+    over sequences below): over count rows folded onto the canonical k-mer bins, as `device_side` takes it"""
+    with device_side(seqs, "euclidean", k, num_states, ctx=ctx, canonical=canonical) as dev:
         return dev.distances()
 
 
@@ -448,12 +457,13 @@ def matrix_euclidean_distances(m: "engine.CountMatrix") -> np.ndarray:
     return DeviceSide(m, "euclidean").distances()
 
 
-def jsd_distances(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
+def jsd_distances(seqs, k: int, num_states: int = 4, ctx: engine.Context | None = None,
+                  canonical: bool = False) -> np.ndarray:
     """the Jensen-Shannon divergence (bits, not its square root) of the k-mer frequencies of every pair,
     H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2: total_jsd of the two-member set (src/records.rs:27-68; paper Table 1).
     float64 [n, n], symmetric, in [0, 1], exactly 0 on the diagonal and between sequences of equal counts; NaN off
     the diagonal for a sequence without a valid k-mer"""
-    with device_side(seqs, "jsd", k, num_states, ctx=ctx) as dev:
+    with device_side(seqs, "jsd", k, num_states, ctx=ctx, canonical=canonical) as dev:
         return dev.distances()
 
 
@@ -473,19 +483,19 @@ def mash_linkage(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canon
 
 
 def euclidean_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
-                      ctx: engine.Context | None = None) -> np.ndarray:
+                      ctx: engine.Context | None = None, canonical: bool = False) -> np.ndarray:
     """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
     linkage_method_code(method)
-    with device_side(seqs, "euclidean", k, num_states, ctx=ctx) as dev:
+    with device_side(seqs, "euclidean", k, num_states, ctx=ctx, canonical=canonical) as dev:
         return dev.linkage(method)
 
 
 def jsd_linkage(seqs, k: int, num_states: int = 4, *, method: str = "average",
-                ctx: engine.Context | None = None) -> np.ndarray:
+                ctx: engine.Context | None = None, canonical: bool = False) -> np.ndarray:
     """the same for the Jensen-Shannon divergences of `jsd_distances`, the same matrix bit for bit (a sequence
     without valid k-mers: NaN distances, ValueError)"""
     linkage_method_code(method)
-    with device_side(seqs, "jsd", k, num_states, ctx=ctx) as dev:
+    with device_side(seqs, "jsd", k, num_states, ctx=ctx, canonical=canonical) as dev:
         return dev.linkage(method)
 
 
@@ -546,20 +556,21 @@ def mash_nj(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical:
     return _nj(seqs, "mash", k, sketch_size, num_states, mash_canonical, ctx=ctx)
 
 
-def euclidean_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None) -> NJTree:
+def euclidean_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None,
+                 canonical: bool = False) -> NJTree:
     """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
-    return _nj(seqs, "euclidean", k, num_states, ctx=ctx)
+    return _nj(seqs, "euclidean", k, num_states, ctx=ctx, canonical=canonical)
 
 
-def jsd_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None) -> NJTree:
+def jsd_nj(seqs, k: int, num_states: int = 4, *, ctx: engine.Context | None = None, canonical: bool = False) -> NJTree:
     """the same for the Jensen-Shannon divergences of `jsd_distances` (a sequence without valid k-mers: ValueError)"""
-    return _nj(seqs, "jsd", k, num_states, ctx=ctx)
+    return _nj(seqs, "jsd", k, num_states, ctx=ctx, canonical=canonical)
 
 
-def _nj(seqs, distance_mode: str, *args, ctx) -> NJTree:
+def _nj(seqs, distance_mode: str, *args, ctx, canonical: bool = False) -> NJTree:
     if len(seqs) < 3:
         raise ValueError("need at least three sequences for a neighbour-joining tree")
-    with device_side(seqs, distance_mode, *args, ctx=ctx) as dev:
+    with device_side(seqs, distance_mode, *args, ctx=ctx, canonical=canonical) as dev:
         return dev.nj()
 
 
@@ -626,10 +637,11 @@ def matrix_nearest(q: "engine.CountMatrix", r: "engine.CountMatrix", n_nearest: 
     return _count_side(q, mode).nearest(_count_side(r, mode), n_nearest, q_rows, r_rows)
 
 
-def _two_sides(queries, refs, distance_mode: str, args, ctx, run):
+def _two_sides(queries, refs, distance_mode: str, args, ctx, run, canonical: bool = False):
     """run(the queries' side, the references' side), both made for the call; the first is closed also where making
     the second fails"""
-    with device_side(queries, distance_mode, *args, ctx=ctx) as q, device_side(refs, distance_mode, *args, ctx=ctx) as r:
+    with device_side(queries, distance_mode, *args, ctx=ctx, canonical=canonical) as q, \
+            device_side(refs, distance_mode, *args, ctx=ctx, canonical=canonical) as r:
         return run(q, r)
 
 
@@ -644,20 +656,24 @@ def mash_nearest(queries, refs, n_nearest: int, k: int, sketch_size: int, num_st
                       lambda q, r: q.nearest(r, n_nearest))
 
 
-def euclidean_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
-    return _two_sides(queries, refs, "euclidean", (k, num_states), ctx, DeviceSide.cross_distances)
+def euclidean_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None,
+                              canonical: bool = False) -> np.ndarray:
+    return _two_sides(queries, refs, "euclidean", (k, num_states), ctx, DeviceSide.cross_distances, canonical)
 
 
-def euclidean_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None):
-    return _two_sides(queries, refs, "euclidean", (k, num_states), ctx, lambda q, r: q.nearest(r, n_nearest))
+def euclidean_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None,
+                      canonical: bool = False):
+    return _two_sides(queries, refs, "euclidean", (k, num_states), ctx, lambda q, r: q.nearest(r, n_nearest), canonical)
 
 
-def jsd_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None) -> np.ndarray:
-    return _two_sides(queries, refs, "jsd", (k, num_states), ctx, DeviceSide.cross_distances)
+def jsd_cross_distances(queries, refs, k: int, num_states: int = 4, ctx: engine.Context | None = None,
+                        canonical: bool = False) -> np.ndarray:
+    return _two_sides(queries, refs, "jsd", (k, num_states), ctx, DeviceSide.cross_distances, canonical)
 
 
-def jsd_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None):
-    return _two_sides(queries, refs, "jsd", (k, num_states), ctx, lambda q, r: q.nearest(r, n_nearest))
+def jsd_nearest(queries, refs, n_nearest: int, k: int, num_states: int = 4, ctx: engine.Context | None = None,
+                canonical: bool = False):
+    return _two_sides(queries, refs, "jsd", (k, num_states), ctx, lambda q, r: q.nearest(r, n_nearest), canonical)
 
 
 # a distance mode -> (its M x N distances, its nearest references): the first takes (queries, refs, *mode_args(...)),
@@ -666,8 +682,9 @@ CROSS_MODES = {"mash": (mash_cross_distances, mash_nearest), "euclidean": (eucli
                "jsd": (jsd_cross_distances, jsd_nearest)}
 
 
-def check_mode_args(distance_mode: str, sketch_size, mash_canonical: bool) -> None:
-    """the argument checks of cluster.ctree for a distance mode, with its messages"""
+def check_mode_args(distance_mode: str, sketch_size, mash_canonical: bool, canonical: bool = False) -> None:
+    """the argument checks of cluster.ctree for a distance mode, with its messages; canonical: the count rows of the jsd
+    and euclidean modes folded onto the canonical k-mer bins (`device_side`)"""
     if distance_mode not in CROSS_MODES:
         raise ValueError(f"Unexpected distance {distance_mode!r}.")
     if distance_mode == "mash" and sketch_size is None:
@@ -676,35 +693,38 @@ def check_mode_args(distance_mode: str, sketch_size, mash_canonical: bool) -> No
         raise ValueError("Sketch size should only be specified for the mash distance.")
     if distance_mode != "mash" and mash_canonical:
         raise ValueError("Canonical kmers should only be specified for the mash distance.")
+    if distance_mode == "mash" and canonical:
+        raise ValueError(CANONICAL_MASH)
 
 
 def cross_distances(queries, refs, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
-                    num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None) -> np.ndarray:
+                    num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None,
+                    canonical: bool = False) -> np.ndarray:
     """the `distance_mode` distance of every query sequence to every reference sequence: float64 [M, N], cell (i, j) the
     bits MODES[distance_mode] gives the pair (queries[i], refs[j]) inside one collection.  Only the M x N pairs are
     computed.  Argument checks as cluster.ctree; ZeroDivisionError (mash) when a query and a reference both have an empty
     sketch; NaN (jsd, euclidean) for a sequence without a valid k-mer."""
-    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
     queries, refs = list(queries), list(refs)
     if not queries or not refs:
         return np.zeros((len(queries), len(refs)), dtype=np.float64)
     return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
-                      ctx, DeviceSide.cross_distances)
+                      ctx, DeviceSide.cross_distances, canonical)
 
 
 def nearest(queries, refs, n_nearest: int = 1, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
-            num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None):
+            num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None, canonical: bool = False):
     """the n_nearest references of every query by `distance_mode`, nearest first, a tie to the reference that comes first in
     `refs`: (idx int64 [M, n_nearest], positions in `refs`, -1 in a slot without one; dist float64 [M, n_nearest], NaN
     there).  A reference at NaN distance is never listed.  1 <= n_nearest <= min(len(refs), N_NEAREST_MAX), checked -- like
     the arguments cluster.ctree checks -- before any device work."""
-    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
     queries, refs = list(queries), list(refs)
     kk = check_n_nearest(n_nearest, len(refs))
     if not queries:
         return np.zeros((0, kk), dtype=np.int64), np.zeros((0, kk), dtype=np.float64)
     return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
-                      ctx, lambda q, r: q.nearest(r, kk))
+                      ctx, lambda q, r: q.nearest(r, kk), canonical)
 
 
 # ---- the scores of a labelling: sums within a cluster, the nearest other cluster, silhouettes, medoids
@@ -772,17 +792,19 @@ def matrix_cluster_scores(m: "engine.CountMatrix", labels, mode: str = "jsd", ro
 
 
 def cluster_scores(seqs, labels, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
-                   num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None) -> ClusterScores:
+                   num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None,
+                   canonical: bool = False) -> ClusterScores:
     """the scores of a labelling of the sequences (`ClusterScores`) over their `distance_mode` distances: the cells
     MODES[distance_mode] gives the collection (off the diagonal, which is never read), computed strip by strip and never
     held whole.  Argument checks as cluster.ctree, before any device work; ZeroDivisionError (mash) when two sequences
     have an empty sketch; NaN (jsd, euclidean) for a sequence without a valid k-mer."""
-    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
     seqs = list(seqs)
     lab = check_labels(labels, len(seqs))
     if not seqs:
         return _run_cluster_scores(ctx, "", lab)
-    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx) as dev:
+    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
+                     canonical=canonical) as dev:
         return dev.cluster_scores(lab)
 
 
@@ -836,15 +858,17 @@ def matrix_cophenet(m: "engine.CountMatrix", Z, mode: str = "jsd", rows=None, ma
 
 
 def cophenet(seqs, Z, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
-             mash_canonical: bool = False, matrix: bool = False, ctx: engine.Context | None = None) -> CopheneticScores:
+             mash_canonical: bool = False, matrix: bool = False, ctx: engine.Context | None = None,
+             canonical: bool = False) -> CopheneticScores:
     """the cophenetic correlation (`CopheneticScores`) of the linkage matrix Z over the sequences with their
     `distance_mode` distances: scipy's cophenet(Z, Y)[0] for the condensed form Y of what MODES[distance_mode] gives the
     collection, computed strip by strip and never held whole.  Argument checks as cluster.ctree, and the shape of Z,
     before any device work; ZeroDivisionError (mash) for a sequence with an empty sketch."""
-    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
     seqs = list(seqs)
     check_linkage_matrix(Z, len(seqs))
-    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx) as dev:
+    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
+                     canonical=canonical) as dev:
         return dev.cophenet(Z, matrix=matrix)
 
 
@@ -930,20 +954,22 @@ def mash_maxmin(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canoni
 
 
 def euclidean_maxmin(seqs, k: int, num_states: int = 4, *, n_select: int | None = None, seeds=(0,),
-                     min_distance: float | None = None, ctx: engine.Context | None = None) -> MaxMin:
+                     min_distance: float | None = None, ctx: engine.Context | None = None, canonical: bool = False) -> MaxMin:
     """the same by the euclidean distances of the k-mer frequencies"""
-    return _maxmin(seqs, "euclidean", k, num_states, n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)
+    return _maxmin(seqs, "euclidean", k, num_states, n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx,
+                   canonical=canonical)
 
 
 def jsd_maxmin(seqs, k: int, num_states: int = 4, *, n_select: int | None = None, seeds=(0,),
-               min_distance: float | None = None, ctx: engine.Context | None = None) -> MaxMin:
+               min_distance: float | None = None, ctx: engine.Context | None = None, canonical: bool = False) -> MaxMin:
     """the same by the Jensen-Shannon divergences of `jsd_distances`"""
-    return _maxmin(seqs, "jsd", k, num_states, n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)
+    return _maxmin(seqs, "jsd", k, num_states, n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx,
+                   canonical=canonical)
 
 
-def _maxmin(seqs, distance_mode: str, *args, n_select, seeds, min_distance, ctx) -> MaxMin:
+def _maxmin(seqs, distance_mode: str, *args, n_select, seeds, min_distance, ctx, canonical: bool = False) -> MaxMin:
     check_maxmin_args(len(seqs), n_select, seeds, min_distance)
-    with device_side(seqs, distance_mode, *args, ctx=ctx) as dev:
+    with device_side(seqs, distance_mode, *args, ctx=ctx, canonical=canonical) as dev:
         return dev.maxmin(n_select, seeds=seeds, min_distance=min_distance)
 
 
@@ -953,14 +979,14 @@ MAXMIN_MODES = {"mash": mash_maxmin, "euclidean": euclidean_maxmin, "jsd": jsd_m
 
 def maxmin(seqs, n_select: int | None = None, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
            num_states: int = 4, mash_canonical: bool = False, seeds=(0,), min_distance: float | None = None,
-           ctx: engine.Context | None = None) -> MaxMin:
+           ctx: engine.Context | None = None, canonical: bool = False) -> MaxMin:
     """farthest-first (max-min) selection of representatives among the sequences by `distance_mode`: the seeds, then
     again and again the sequence farthest from those already taken, until n_select are taken (None: all) or every
     sequence lies within min_distance of one (dereplication: one representative per group within min_distance).  One
     of the two must be given.  `MaxMin` also names every sequence's nearest representative and the covering radius.
     Only n_select rows of distances are computed, never the N x N matrix.  Argument checks as cluster.ctree, and those
     of `check_maxmin_args`, before any device work."""
-    check_mode_args(distance_mode, sketch_size, mash_canonical)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
     seqs = list(seqs)
     return _maxmin(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
-                   n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx)
+                   n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx, canonical=canonical)

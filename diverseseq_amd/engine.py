@@ -70,6 +70,28 @@ def genbank_to_fasta(raw: bytes) -> bytes:
     return b"".join(out)
 
 
+def canonical_bins(k: int) -> np.ndarray:
+    """the canonical k-mer bins of four-state sequences (include/dvs_hip.h "canonical k-mer count rows"): the
+    representatives min(idx, rc(idx)) in ascending order, uint32 [C(k)]; bin c of a folded row counts k-mer
+    canonical_bins(k)[c] and its reverse complement.  Host only (dvs_canonical_bins); ValueError for k outside 1 .. 16"""
+    L = _lib.load()
+    n = C.c_uint64()
+    _lib.raise_for(L.dvs_canonical_bins(int(k), None, C.byref(n)), None)
+    reps = np.zeros(n.value, dtype=np.uint32)
+    _lib.raise_for(L.dvs_canonical_bins(int(k), _lib.ptr(reps, C.c_uint32), C.byref(n)), None)
+    return reps
+
+
+def _folded(m: "CountMatrix", canonical: bool) -> "CountMatrix":
+    """m, or with `canonical` its canonical fold, the plain matrix closed (the fold has waited for m's build)"""
+    if not canonical:
+        return m
+    try:
+        return m.canonical()
+    finally:
+        m.close()
+
+
 _live_contexts = weakref.WeakSet()
 
 
@@ -123,31 +145,32 @@ class Context:
         return {"name": name.value.decode(), "n_cu": ncu.value, "hbm_bytes": mem.value}
 
     # ---- matrices -----------------------------------------------------------
-    def build_matrix(self, seqs, k: int, num_states: int = 4) -> "CountMatrix":
-        """k-mer count matrix of host sequences (list of uint8 arrays / bytes)"""
+    def build_matrix(self, seqs, k: int, num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
+        """k-mer count matrix of host sequences (list of uint8 arrays / bytes); canonical (here and in the other
+        builds): the matrix is built, folded onto the canonical bins (`CountMatrix.canonical`) and the plain one closed"""
         data, offsets = concat(seqs)
-        return self.build_matrix_concat(data, offsets, k, num_states)
+        return self.build_matrix_concat(data, offsets, k, num_states, canonical=canonical)
 
     def build_matrix_concat(self, data: np.ndarray, offsets: np.ndarray, k: int,
-                            num_states: int = 4) -> "CountMatrix":
+                            num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
         h = C.c_void_p()
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.check(self._L.dvs_matrix_build(self._h, data.ctypes.data_as(C.c_void_p), 0,
                                             _lib.ptr(offsets, C.c_uint64), offsets.size - 1, k,
                                             num_states, C.byref(h)))
-        return CountMatrix(self, h, k, num_states)
+        return _folded(CountMatrix(self, h, k, num_states), canonical)
 
     def build_matrix_device(self, dev_ptr: int, offsets: np.ndarray, k: int,
-                            num_states: int = 4) -> "CountMatrix":
+                            num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
         """sequences already resident in HBM (e.g. a torch uint8 tensor's data_ptr()).  The call
         does not wait for its kernels: keep the buffer alive and unmodified until the matrix is
-        first used from the host side (a selection, counts(), ctx.sync())"""
+        first used from the host side (a selection, counts(), ctx.sync(); a canonical build waits itself)"""
         h = C.c_void_p()
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.check(self._L.dvs_matrix_build(self._h, C.c_void_p(dev_ptr), 1,
                                             _lib.ptr(offsets, C.c_uint64), offsets.size - 1, k,
                                             num_states, C.byref(h)))
-        return CountMatrix(self, h, k, num_states)
+        return _folded(CountMatrix(self, h, k, num_states), canonical)
 
     # ---- packed sequences (3 bits per base in HBM: csrc/pack.hip) ------------------
     def pack_device(self, dev_ptr: int, nbases: int) -> "Packed":
@@ -165,7 +188,8 @@ class Context:
                                               data.size, C.byref(h)))
         return Packed(self, h)
 
-    def build_matrix_packed(self, packed: "Packed", offsets: np.ndarray, k: int) -> "CountMatrix":
+    def build_matrix_packed(self, packed: "Packed", offsets: np.ndarray, k: int, *,
+                            canonical: bool = False) -> "CountMatrix":
         """k-mer count matrix of a packed batch (the histogram kernel reads the packed words as they are)"""
         h = C.c_void_p()
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -173,7 +197,7 @@ class Context:
                                                    k, C.byref(h)))
         m = CountMatrix(self, h, k, 4)
         m._source = packed  # (the build is not waited for: the planes must outlive its kernels)
-        return m
+        return _folded(m, canonical)
 
     # ---- ingest ---------------------------------------------------------------
     def encode_fasta(self, raw, join_records: bool = False, moltype: str = "dna",
@@ -334,13 +358,13 @@ class SeqBatch:
         view._batch = self  # (a view of this batch's planes: the batch lives as long as the view)
         return view
 
-    def build_matrix(self, k: int, num_states: int = 4) -> "CountMatrix":
+    def build_matrix(self, k: int, num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
         """k-mer count matrix straight from the encoded bases in HBM (no host round trip)"""
         h = C.c_void_p()
         self.ctx.check(self.ctx._L.dvs_matrix_build_from_seqbatch(self.ctx._h, self._h, k, num_states, C.byref(h)))
         m = CountMatrix(self.ctx, h, k, num_states)
         m._source = self  # (the build is not waited for: the batch must outlive its kernels)
-        return m
+        return _folded(m, canonical)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -402,6 +426,21 @@ class CountMatrix:
 
     def dev_counts(self) -> int:
         return int(self.ctx._L.dvs_matrix_dev_counts(self._h) or 0)
+
+    @property
+    def is_canonical(self) -> bool:
+        """the rows are folded onto the canonical bins of k (`canonical`)"""
+        return bool(self.ctx._L.dvs_matrix_is_canonical(self._h))
+
+    def canonical(self) -> "CountMatrix":
+        """a new matrix of these count rows folded onto the canonical k-mer bins, out[c] = in[rep_c] + in[rc(rep_c)]
+        (`canonical_bins(k)`; dvs_matrix_fold_canonical): C(k) bins, the same count width, totals unchanged, entropies
+        of the folded rows.  A sequence and its reverse complement get the same row, so every selection and every jsd /
+        euclidean distance over the result is strand-independent.  This matrix is left as it is.  ValueError for
+        frequency rows, for an alphabet that has not four states and for a matrix that is already canonical."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._L.dvs_matrix_fold_canonical(self.ctx._h, self._h, C.byref(h)))
+        return CountMatrix(self.ctx, h, self.k, self.num_states)
 
     @property
     def count_bytes(self) -> int:

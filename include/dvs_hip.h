@@ -115,6 +115,35 @@ int dvs_kmer_counts(dvs_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets,
                     uint32_t nseq, uint32_t k, uint32_t num_states,
                     uint32_t *counts_out, uint32_t *totals_out, double *entropy_out);
 
+/* ---- canonical k-mer count rows (strand-independent selection and distances) ---------------------- *
+ * A sequence and its reverse complement have different count rows, so every count-based operation tells the two
+ * strands apart.  Folding a k-mer's bin with its reverse complement's removes that.  (No counterpart in the reference:
+ * its only canonical form is the mash sketch's, src/distance.rs:17-19,65-87.)  Four states only, in the project's
+ * alphabet order T0 C1 A2 G3 (RNA: U C A G):
+ *   complement      of a digit d is d ^ 2: (base + 2) % 4 of src/distance.rs:18
+ *   rc(idx)         of a k-mer index (first base most significant, src/record.rs:18-29): its k base-4 digits
+ *                   reversed, each complemented
+ *   representative  min(idx, rc(idx)): the lexicographic choice hash_kmer makes (src/distance.rs:65-87)
+ *   canonical bins  the representatives in ascending order, C(k) of them: 4^k / 2 for odd k, (4^k + 4^(k/2)) / 2 for
+ *                   even k (2, 10, 32, 136, 512, 2 080, 8 192, 32 896 for k = 1 .. 8)
+ *   folded row      out[c] = in[rep_c] + in[rc(rep_c)]; for a palindrome (rc(rep_c) == rep_c, even k only) in[rep_c]
+ *                   alone.  The total is the source row's; the entropy is the Shannon entropy (bits) of out / total,
+ *                   0.0 for a row of total 0, which stays an all-zero row
+ * dvs_canonical_bins (host only, no context): *n_out = C(k) and, unless reps_out is NULL, reps_out[C(k)] the
+ * representatives.  DVS_ERR_VALUE: k outside 1 .. 16, both outputs NULL.
+ * dvs_matrix_fold_canonical makes a new count matrix of m's rows x C(k) bins with m's element width (16-bit rows stay
+ * 16-bit: a folded count is at most the row's total), k and num_states, flagged canonical (dvs_matrix_is_canonical).  It is
+ * a count matrix like any other for every selection, accessor and jsd / euclidean entry; m is left as it is.  The fold
+ * is enqueued on the context's stream behind m's build -- the call waits for that build if it is still in flight -- and
+ * returns when the folded rows are written.
+ *   DVS_ERR_VALUE, before any device work: a NULL argument; a frequency matrix (it has no k); num_states != 4; a matrix
+ *                  that is already canonical
+ *   DVS_ERR_NOMEM: the folded matrix does not fit
+ * A matrix without rows gives an empty folded matrix. */
+int dvs_canonical_bins(uint32_t k, uint32_t *reps_out, uint64_t *n_out);
+int dvs_matrix_fold_canonical(dvs_ctx *ctx, const dvs_matrix *m, dvs_matrix **out);
+uint32_t dvs_matrix_is_canonical(const dvs_matrix *m);
+
 /* ---- packed sequences ------------------------------------------------------ *
  * Four-state sequences at 3 bits per base instead of the reference's one byte per base
  * (src/record.rs:205-209, diverse_seq/util.py:32-45): the form the histogram (count_kmers,
