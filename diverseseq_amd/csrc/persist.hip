@@ -2638,11 +2638,12 @@ __global__ __launch_bounds__(P_THREADS, 2) void persist_nmost_kernel(SelDev d, c
         }
         // ================= leave-one-out (get_lowest_record_index, records.rs:220-252, with
         // updated_mean_freqs :276-286) as (n + 1) * K jobs over the workgroups.  A job's two sums
-        // (entropy terms, mean-vector total) are added to its member's accumulators as 2^-56
-        // fixed-point integers: integer addition is associative, so the totals do not depend on the
-        // order the K workgroups of a member arrive in, and partial sums of this magnitude
-        // (>= 2^-3) convert without rounding.  (Every term is >= 0: the clamps of the reference
-        // leave no negative bin here, so there is no NaN to carry.)
+        // (entropy terms, mean-vector total) are added to its member's accumulators as 2^-50
+        // fixed-point integers (p_acc_word: the sum times 2^50, rounded to nearest): integer addition
+        // is associative, so the totals do not depend on the order the K workgroups of a member
+        // arrive in.  Each conversion is off by at most 2^-51, a total of K <= 32 of them by at most
+        // K * 2^-51 <= 1.5e-14.  (Every term is >= 0: the clamps of the reference leave no negative
+        // bin here, so there is no NaN to carry.)
         P_PROBE_END(12);
         P_PROBE_BEGIN(13);  // 13: the job loop and wave 0's wait for the totals
         const double rdiv = 1.0 / (dn - 1.0);

@@ -10,6 +10,7 @@ import pytest
 import oracle
 from conftest import synth_seqs
 from gpu_synth import synth_device
+from test_bands_host import COARSE_BAND_K6, FAST_BAND, MULTS, _band_stream
 from test_gpu_parity import RTOL, _assert_selection
 
 pytestmark = pytest.mark.gpu
@@ -190,62 +191,7 @@ def test_count_rows_in_both_widths(ctx, u32, monkeypatch):
 
 
 # ---------------------------------------------------------------- candidates inside the bands
-COARSE_BAND_K6 = 1.25 * 2.0**-24 * (9.0 * 12 + 7.4)  # select_dev.h coarse_band(4096)
-FAST_BAND = 4e-7                                       # select_dev.h
-
-
-def _craft(oset, start, target, k, rng, tol):
-    """substitutions of `start` (one to three bases at a time) until the oracle's score of the
-    sequence against `oset` sits at threshold + target (records.rs:70-92) within tol.  Equal-length
-    sequences give the score a grain of ~1e-8, so tol is a few of those (0.08 of the band), not zero."""
-    seq = start.copy()
-    thr = oset.total_jsd
-
-    def margin(s):
-        f, h = oracle.to_kfreqs(s, 4, k)
-        return oset.delta_jsd(f, h) - thr
-
-    cur = margin(seq)
-    for _ in range(60_000):
-        if abs(cur - target) <= tol:
-            return seq, cur
-        m = int(rng.integers(1, 4))
-        pos = rng.integers(0, seq.size, size=m)
-        old = seq[pos].copy()
-        seq[pos] = (old + rng.integers(1, 4, size=m)) % 4
-        d = margin(seq)
-        if abs(d - target) < abs(cur - target):
-            cur = d
-        else:
-            seq[pos] = old
-    raise AssertionError(f"no sequence found at margin {target}: stuck at {cur}")
-
-
-def _band_stream(k, n, length, nprefix, targets, seed):
-    """a random prefix, then for every target margin a near-copy of the set's lowest member whose exact
-    score is threshold + margin (each followed by a few ordinary rows), the oracle tracking the set"""
-    rng = np.random.default_rng(seed)
-    seqs = synth_seqs(nprefix, length, seed)
-    oset = oracle.nmost(seqs, n, k, 4)
-    margins = []
-    for t in targets:
-        labels = oset.members()[0]
-        low = seqs[int(labels[oset.lowest_index])]
-        cand, got = _craft(oset, low, t, k, rng, tol=0.08 * (FAST_BAND if abs(t) < 1e-6 else COARSE_BAND_K6))
-        f, h = oracle.to_kfreqs(cand, 4, k)
-        if oset.increases_jsd(f, h, len(seqs)):
-            oset.replace_lowest(f, h, len(seqs))
-        seqs.append(cand)
-        margins.append(got)
-        for s in synth_seqs(3, length, int(rng.integers(1 << 30))):
-            f, h = oracle.to_kfreqs(s, 4, k)
-            if oset.increases_jsd(f, h, len(seqs)):
-                oset.replace_lowest(f, h, len(seqs))
-            seqs.append(s)
-    return seqs, oset, margins
-
-
-MULTS = (-1.1, -0.9, -0.5, -0.1, 0.1, 0.5, 0.9, 1.1)
+# (the crafting and the bands live in tests/test_bands_host.py, with the general form of both)
 
 
 @pytest.fixture(scope="module")

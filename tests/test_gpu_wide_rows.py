@@ -24,7 +24,7 @@ import pytest
 
 import oracle
 from test_distance_truth_host import distance_cases
-from test_gpu_configs import FAST_BAND, _band_stream
+from test_bands_host import FAST_BAND, _band_stream
 from test_gpu_parity import _assert_selection
 from test_maxmin_host import same_bits
 from test_readback_host import assert_scores

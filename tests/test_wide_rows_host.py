@@ -85,7 +85,7 @@ STEPWISE_CASE = NMOST_CASES[0]
 TIE_STREAMS = (Stream(4, 8, 60, 5000, 8701), Stream(5, 7, 60, 5000, 8702))
 TIE_NMOST_N = 6
 TIE_MAX = (4, 12, "stdev")
-# ---- 8. candidates inside FAST_BAND: arguments of test_gpu_configs._band_stream (k, n, length, nprefix, targets / FAST_BAND, seed)
+# ---- 8. candidates inside FAST_BAND: arguments of test_bands_host._band_stream (k, n, length, nprefix, targets / FAST_BAND, seed)
 BAND_CASE = dict(k=8, n=8, length=20_000, nprefix=150, mults=(-0.5, 0.5), seed=8801)
 # ---- 9. score read-back: queries against the finished set of the first nmost case
 READBACK_CASE = NMOST_CASES[0]
