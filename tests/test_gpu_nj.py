@@ -22,8 +22,11 @@ def ctx():
     c.close()
 
 
-# 63 .. 65: the wave; 257: more rows than a scan workgroup's waves and a join's first pass; 1025: the join workgroup;
-# every n > 8 repacks (first at r < n / 2), 2049 ten times
+# 63 .. 65: the wave; 257: more rows than a scan workgroup's waves and a join's first pass; 1025: more list positions
+# than the join workgroup has threads (the second trip of its list compaction; its update loop, which covers 4096
+# positions a trip, still takes one); 2049: 513 scan workgroups and a third trip of the compaction; every n > 8 repacks (first
+# at r < n / 2), 2049 ten times.  The regimes beyond -- a second trip of the update loop and of the candidate reduction
+# (r > 4096), a second pass of the scan over its capped grid (r > 8192) -- are in test_gpu_second_trips.py
 EXACT = [(n, shape) for n in (3, 4, 5, 63, 64, 65, 257) for shape in ("random", "caterpillar", "balanced")]
 EXACT += [(1025, "random"), (2049, "random")]
 
