@@ -55,7 +55,12 @@ EXPORTS = (
     "dvs_nj", "dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj", "dvs_nj_patristic",
     "dvs_maxmin", "dvs_sketches_maxmin", "dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin",
     "dvs_canonical_bins", "dvs_matrix_fold_canonical", "dvs_matrix_is_canonical",
+    "dvs_jsd_within", "dvs_euclidean_within", "dvs_sketches_within", "dvs_within",
+    "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get",
+    "dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters", "dvs_sketches_threshold_clusters",
+    "dvs_threshold_clusters",
 )
+WITHIN_SKIP_SELF = 1
 
 
 class SelectParams(C.Structure):
@@ -261,6 +266,20 @@ def load() -> C.CDLL:
         L.dvs_matrix_fold_canonical.argtypes = [vp, vp, C.POINTER(vp)]
         L.dvs_matrix_is_canonical.argtypes = [vp]
         L.dvs_matrix_is_canonical.restype = C.c_uint32
+        within = [C.c_double, u32, C.c_uint64, C.POINTER(vp)]  # radius, flags, max_pairs, the dvs_pairs
+        for n in ("dvs_jsd_within", "dvs_euclidean_within"):
+            getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, *within]
+        L.dvs_sketches_within.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, *within]
+        L.dvs_within.argtypes = [vp, vp, C.c_int, u32, *within]
+        L.dvs_pairs_destroy.argtypes = [vp]
+        L.dvs_pairs_destroy.restype = None
+        L.dvs_pairs_info.argtypes = [vp, u32p, u64p]
+        L.dvs_pairs_get.argtypes = [vp, u64p, u32p, f64p]
+        components = [C.c_double, u32p, u32p]  # radius, labels, n_clusters
+        for n in ("dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters"):
+            getattr(L, n).argtypes = [vp, vp, u32p, u32, *components]
+        L.dvs_sketches_threshold_clusters.argtypes = [vp, vp, u32p, u32, u32, u32, *components]
+        L.dvs_threshold_clusters.argtypes = [vp, vp, C.c_int, u32, *components]
         if L.dvs_abi_version() != 3:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -41,7 +41,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -398,6 +398,34 @@ class dvs_clusters(_DistanceApp):
         for name, c in zip(names, sc.labels.tolist()):
             clusters[c].append(name)
         return {"tree": newick, "clusters": clusters,
+                "medoids": {c: names[i] for c, i in enumerate(sc.medoids.tolist()) if i >= 0},
+                "silhouette": {name: float(v) for name, v in zip(names, sc.silhouette)},
+                "mean_silhouette": sc.mean_silhouette}
+
+
+@_define_app
+class dvs_dereplicate(_DistanceApp):
+    """The groups of sequences joined by distances of `radius` or less, with one representative per group (beyond the
+    reference, which has no such app): the connected components of "distance <= radius" -- the clusters `dvs_clusters`
+    gives for single linkage and height=radius -- found without the N x N matrix and without a tree.  `main(seqs)`
+    returns what `dvs_clusters` returns, {"tree": None, "clusters": {label: [names]}, "medoids": {label: name},
+    "silhouette": {name: float}, "mean_silhouette": float}: labels count from 0 in the order the groups first appear
+    among the names; a medoid, the group's representative, is the member with the least summed distance to the rest."""
+
+    def __init__(self, radius: float, distance_mode: str = "mash", *, k: int = 12, sketch_size: int | None = 3_000,
+                 moltype: str = "dna", mash_canonical_kmers: bool | None = None, canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
+        self._radius = _distance.check_radius(radius)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
+
+    def main(self, seqs):
+        names, arrays = _as_arrays(seqs, self._moltype)
+        _, _, sc = _cluster.dereplicate(dict(zip(names, arrays)), self._radius, **self._mode_kwargs())
+        clusters: dict = {c: [] for c in range(sc.sizes.size)}
+        for name, c in zip(names, sc.labels.tolist()):
+            clusters[c].append(name)
+        return {"tree": None, "clusters": clusters,
                 "medoids": {c: names[i] for c, i in enumerate(sc.medoids.tolist()) if i >= 0},
                 "silhouette": {name: float(v) for name, v in zip(names, sc.silhouette)},
                 "mean_silhouette": sc.mean_silhouette}

@@ -15,7 +15,9 @@ silhouettes, medoids) and both behind one call (`ctree_clusters`); how well a tr
 scipy's cophenet, the correlation reduced on the GPU by csrc/crossdist.hip's cophenet_kernel; `ctree_cophenet`,
 `compare_linkages`); and the tree of additive distances, neighbour joining (`neighbor_joining`, csrc/nj.hip: an unrooted
 tree with branch lengths and no molecular clock; `nj_to_newick`, `patristic`, `nj_tree`); and farthest-first selection
-of representatives over a caller's own distance matrix (`maxmin`, csrc/maxmin.hip).
+of representatives over a caller's own distance matrix (`maxmin`, csrc/maxmin.hip); and the pairs of a caller's matrix
+within a radius (`within`), the groups they make (`threshold_clusters`: the single-linkage clusters at that height
+without the tree) and, over sequences, those groups with one representative each (`dereplicate`).
 """
 
 from __future__ import annotations
@@ -292,6 +294,58 @@ def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float
     args = distance.check_maxmin_args(n, n_select, seeds, min_distance)
     wait()
     return distance._run_maxmin(ctx, "dvs_maxmin", n, *args, src, on_device)
+
+
+def within(dist, radius, *, skip_self: bool = True, max_pairs: int | None = None,
+           ctx: engine.Context | None = None) -> "distance.Neighbours":
+    """for every row of a caller's n x n distance matrix the columns with dist[i, j] <= radius (`distance.Neighbours`:
+    ascending columns, the matrix's own bits), compacted on the GPU a strip of rows at a time.  skip_self (the default):
+    the diagonal is left out and never read.  A NaN entry is never listed; the matrix need not be symmetric.
+
+    `dist`: as `cluster_scores` takes it, only READ.  The radius and max_pairs are checked before any device work."""
+    radius = distance.check_radius(radius)
+    limit = distance.check_max_pairs(max_pairs)
+    src, on_device, n, wait = _caller_matrix(dist)
+    if not n:
+        return distance._no_neighbours(0)
+    wait()
+    return distance._run_within(ctx, "dvs_within", src, on_device, n, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
+
+
+def threshold_clusters(dist, radius, *, ctx: engine.Context | None = None) -> "distance.ThresholdClusters":
+    """the groups that "dist[i, j] <= radius" makes of the rows of a caller's n x n distance matrix
+    (`distance.ThresholdClusters`): connected components, the labels of `cut_tree(linkage(dist, "single"), height=radius)`
+    without the tree.  Only the entries above the diagonal are read, a strip of rows at a time; a NaN entry joins nothing.
+
+    `dist`: as `cluster_scores` takes it, only READ.  The radius is checked before any device work."""
+    radius = distance.check_radius(radius)
+    src, on_device, n, wait = _caller_matrix(dist)
+    if n:
+        wait()
+    return distance._run_threshold_clusters(ctx, "dvs_threshold_clusters", n, src, on_device, n, radius)
+
+
+def dereplicate(seqs: dict, radius, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
+                mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False):
+    """sequences {name: uint8 codes} -> (None, None, distance.ClusterScores): the groups of sequences joined by
+    distances <= radius (`distance.threshold_clusters`: "cluster at mash distance 0.05") and their scores, whose
+    `.medoids` name one representative per group -- the member with the least summed distance to the rest of it.  The
+    shape is `ctree_clusters`', with None for the tree and its linkage matrix, which are not built: neither is the
+    N x N matrix.  Argument checks as `ctree` and the radius, before any device work.
+
+    The sketches (mash) or the count matrix (euclidean, jsd) are made once and stay in HBM; the groups and the scores
+    each compute the distances strip by strip (the same cells bit for bit)."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    radius = distance.check_radius(radius)
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
+    names = list(seqs)
+    if not names:
+        raise ValueError("no sequences")
+    with distance.device_side([seqs[n] for n in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
+        return None, None, dev.cluster_scores(dev.threshold_clusters(radius).labels)
 
 
 def ctree_clusters(seqs: dict, *, n_clusters: int | None = None, height: float | None = None, k: int = 12,

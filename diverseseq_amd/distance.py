@@ -13,7 +13,11 @@ with the cophenetic distances of a tree (cophenet: scipy's cophenet(Z, Y)[0]; no
 the neighbour-joining tree of each distance mode (mash_nj, euclidean_nj, jsd_nj: csrc/nj.hip, an unrooted tree with
 branch lengths, the matrix left in HBM as for the linkage trees; no counterpart in the reference); and farthest-first
 (max-min) selection of representatives by any of these distances (maxmin, matrix_maxmin, Sketches.maxmin:
-csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterpart in the reference).  `DeviceSide`
+csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterpart in the reference); and the sparse
+product over the same strips: the pairs within a radius (within, neighbours, matrix_within -> `Neighbours`) and the
+groups they make (threshold_clusters, matrix_threshold_clusters -> `ThresholdClusters`: connected components, the
+single-linkage clusters at that height), each strip compacted on the device (csrc/crossdist.hip) so that only the listed
+pairs cross to the host; no counterpart in the reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
 matrix_* functions and the Sketches methods are a few lines over it."""
 
@@ -280,6 +284,21 @@ class Sketches:
         per pick (dvs_sketches_maxmin); ZeroDivisionError where a pair the traversal visits has two empty sketches"""
         return DeviceSide(self, "mash").maxmin(n_select, seeds=seeds, min_distance=min_distance)
 
+    def within(self, other: "Sketches", radius, rows=None, other_rows=None, *, skip_self: bool = False,
+               max_pairs: int | None = None) -> "Neighbours":
+        """for each of this set's sketches `rows` the sketches of `other` at a mash distance <= radius (`Neighbours`:
+        the cells of `cross_distances`, compacted on the device; dvs_sketches_within); ZeroDivisionError as
+        `cross_distances`"""
+        check_radius(radius)
+        return DeviceSide(self, "mash").within(DeviceSide(other, "mash"), radius, rows, other_rows, skip_self=skip_self,
+                                               max_pairs=max_pairs)
+
+    def threshold_clusters(self, radius, rows=None) -> "ThresholdClusters":
+        """the groups that "mash distance <= radius" makes of this set's sketches `rows` (`ThresholdClusters`;
+        dvs_sketches_threshold_clusters); ZeroDivisionError as `cluster_scores`"""
+        check_radius(radius)
+        return DeviceSide(self, "mash").threshold_clusters(radius, rows)
+
 
 class DeviceSide:
     """What a distance mode keeps in HBM of one batch -- its `Sketches` (mash) or its count matrix (euclidean, jsd) --
@@ -302,6 +321,12 @@ class DeviceSide:
         "cluster_scores": ("dvs_sketches_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_jsd_cluster_scores"),
         "cophenet": ("dvs_sketches_cophenet", "dvs_euclidean_cophenet", "dvs_jsd_cophenet"),
         "maxmin": ("dvs_sketches_maxmin", "dvs_matrix_euclidean_maxmin", "dvs_matrix_jsd_maxmin"),
+    }
+    # the same for the operations whose result is sparse: the pairs within a radius, and the groups they make
+    SPARSE_ENTRIES = {
+        "within": ("dvs_sketches_within", "dvs_euclidean_within", "dvs_jsd_within"),
+        "threshold_clusters": ("dvs_sketches_threshold_clusters", "dvs_euclidean_threshold_clusters",
+                               "dvs_jsd_threshold_clusters"),
     }
 
     def __init__(self, handle, mode: str, *, owns: bool = False):
@@ -332,7 +357,8 @@ class DeviceSide:
     def _entry(self, op: str, *sides):
         """(the name of the mode's entry for `op`, its arguments behind the context up to the operation's own)"""
         mode_args = (self.handle.k, self.handle.sketch_size_u32) if self.mode == "mash" else ()
-        return self.ENTRIES[op][self.MODE_NAMES.index(self.mode)], (*sides, *mode_args)
+        table = self.ENTRIES if op in self.ENTRIES else self.SPARSE_ENTRIES
+        return table[op][self.MODE_NAMES.index(self.mode)], (*sides, *mode_args)
 
     def _against(self, other: "DeviceSide"):
         if other.mode != self.mode:
@@ -408,6 +434,27 @@ class DeviceSide:
         args = check_maxmin_args(self.n, n_select, seeds, min_distance)
         entry, front = self._entry("maxmin", self.handle._h)
         return _run_maxmin(self.ctx, entry, self.n, *args, *front)
+
+    def within(self, other: "DeviceSide", radius, rows=None, other_rows=None, *, skip_self: bool = False,
+               max_pairs: int | None = None) -> "Neighbours":
+        """for each of this side's `rows` (None: all) the rows of `other` (positions into other_rows, or rows) at a
+        distance <= radius, in ascending position; skip_self: row i against position i is left out (both sides list
+        the same rows); max_pairs: NotImplementedError once more pairs than that are found"""
+        radius = check_radius(radius)
+        limit = check_max_pairs(max_pairs)
+        self._against(other)
+        qr, nq = _row_list(rows, self.n)
+        rr, nr = _row_list(other_rows, other.n)
+        entry, front = self._entry("within", self.handle._h, _lib.ptr(qr, C.c_uint32), nq, other.handle._h,
+                                   _lib.ptr(rr, C.c_uint32), nr)
+        return _run_within(self.ctx, entry, *front, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
+
+    def threshold_clusters(self, radius, rows=None) -> "ThresholdClusters":
+        """the groups that "distance <= radius" makes of this side's `rows` (None: all): connected components"""
+        radius = check_radius(radius)
+        rr, n = _row_list(rows, self.n)
+        entry, front = self._entry("threshold_clusters", self.handle._h, _lib.ptr(rr, C.c_uint32), n)
+        return _run_threshold_clusters(self.ctx, entry, n, *front, radius)
 
 
 CANONICAL_MASH = "Canonical count rows should only be specified for the jsd and euclidean distances (mash: mash_canonical)."
@@ -990,3 +1037,151 @@ def maxmin(seqs, n_select: int | None = None, distance_mode: str = "mash", *, k:
     seqs = list(seqs)
     return _maxmin(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
                    n_select=n_select, seeds=seeds, min_distance=min_distance, ctx=ctx, canonical=canonical)
+
+
+# ---- the neighbours within a radius, and the groups they make (threshold clusters)
+
+class Neighbours(NamedTuple):
+    """For each of M queries the references within a radius (include/dvs_hip.h "neighbours within a radius"), as a CSR
+    list: row_start int64 [M + 1]; index int64, the positions in the reference list, ascending within a query; distance
+    float64, the cells of the mode's matrix bit for bit.  Query i owns the slots row_start[i] .. row_start[i + 1] - 1:
+    `of(i)`.  A cell equal to the radius is listed, a NaN cell never."""
+    row_start: np.ndarray
+    index: np.ndarray
+    distance: np.ndarray
+
+    def of(self, i: int):
+        """(the positions, the distances) of query i"""
+        lo, hi = int(self.row_start[i]), int(self.row_start[i + 1])
+        return self.index[lo:hi], self.distance[lo:hi]
+
+
+class ThresholdClusters(NamedTuple):
+    """The connected components of "distance <= radius" over n rows (include/dvs_hip.h "threshold clusters"): the flat
+    clusters of the single-linkage tree cut at that height.  labels int64 [n], numbered by first appearance in row
+    order (row 0 is in cluster 0), as cluster.cut_tree numbers them; n_clusters; sizes int64 [n_clusters]."""
+    labels: np.ndarray
+    n_clusters: int
+    sizes: np.ndarray
+
+
+def check_radius(radius) -> float:
+    """a radius as the dvs_*within and dvs_*threshold_clusters entries take it, checked before any handle is touched:
+    ValueError unless it is a real number that is not NaN (inclusive; negative: nothing lies within it; inf: all does)"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError(f"radius must be a real number, not {radius!r}")
+    r = float(radius)
+    if r != r:
+        raise ValueError("radius cannot be NaN")
+    return r
+
+
+def check_max_pairs(max_pairs) -> int:
+    """max_pairs as the dvs_*within entries take it (0: no limit): ValueError unless None or an integer of 1 or more"""
+    if max_pairs is None:
+        return 0
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or max_pairs < 1 or max_pairs >= 1 << 64:
+        raise ValueError(f"max_pairs must be None or an integer of 1 or more, not {max_pairs!r}")
+    return int(max_pairs)
+
+
+def _no_neighbours(m: int) -> Neighbours:
+    return Neighbours(np.zeros(m + 1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64))
+
+
+def _run_within(ctx, entry: str, *args) -> Neighbours:
+    """the dvs_*within call `entry`(ctx, *args, the dvs_pairs) -> Neighbours; the dvs_pairs is copied out and freed"""
+    ctx = ctx or engine.default_context()
+    L = ctx._L
+    h = C.c_void_p()
+    ctx.check(getattr(L, entry)(ctx._h, *args, C.byref(h)))
+    try:
+        rows, pairs = C.c_uint32(), C.c_uint64()
+        _lib.raise_for(L.dvs_pairs_info(h, C.byref(rows), C.byref(pairs)), None)
+        row_start = np.zeros(rows.value + 1, dtype=np.uint64)
+        col = np.zeros(pairs.value, dtype=np.uint32)
+        dist = np.zeros(pairs.value, dtype=np.float64)
+        _lib.raise_for(L.dvs_pairs_get(h, _lib.ptr(row_start, C.c_uint64), _lib.ptr(col, C.c_uint32),
+                                       _lib.ptr(dist, C.c_double)), None)
+    finally:
+        L.dvs_pairs_destroy(h)
+    return Neighbours(row_start.astype(np.int64), col.astype(np.int64), dist)
+
+
+def _run_threshold_clusters(ctx, entry: str, n: int, *args) -> ThresholdClusters:
+    """the dvs_*threshold_clusters call `entry`(ctx, *args, labels, n_clusters) over n rows -> ThresholdClusters"""
+    labels = np.zeros(n, dtype=np.uint32)
+    count = C.c_uint32(0)
+    if n:
+        ctx = ctx or engine.default_context()
+        ctx.check(getattr(ctx._L, entry)(ctx._h, *args, _lib.ptr(labels, C.c_uint32), C.byref(count)))
+    k = int(count.value)
+    return ThresholdClusters(labels.astype(np.int64), k, np.bincount(labels, minlength=k).astype(np.int64))
+
+
+def matrix_within(q: "engine.CountMatrix", r: "engine.CountMatrix", radius, mode: str = "jsd", q_rows=None, r_rows=None, *,
+                  skip_self: bool = False, max_pairs: int | None = None) -> Neighbours:
+    """for every row q_rows of q (None: all) the rows r_rows of r at a `mode` ("jsd", "euclidean") distance <= radius
+    (`Neighbours`): the cells of `matrix_cross_distances(q, r, mode, q_rows, r_rows)`, compacted on the device strip by
+    strip -- only the pairs listed cross to the host.  skip_self: row i against position i is left out (q_rows and
+    r_rows name the same rows of one matrix)."""
+    check_radius(radius)
+    return _count_side(q, mode).within(_count_side(r, mode), radius, q_rows, r_rows, skip_self=skip_self, max_pairs=max_pairs)
+
+
+def matrix_threshold_clusters(m: "engine.CountMatrix", radius, mode: str = "jsd", rows=None) -> ThresholdClusters:
+    """the groups that "`mode` distance <= radius" makes of rows `rows` of m (None: all): `ThresholdClusters`, the flat
+    clusters of their single-linkage tree cut at height radius, without the n x n matrix and without the tree"""
+    check_radius(radius)
+    return _count_side(m, mode).threshold_clusters(radius, rows)
+
+
+def within(queries, refs, radius, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+           num_states: int = 4, mash_canonical: bool = False, canonical: bool = False, max_pairs: int | None = None,
+           ctx: engine.Context | None = None) -> Neighbours:
+    """for every query sequence the reference sequences at a `distance_mode` distance <= radius (`Neighbours`: positions
+    in `refs`, ascending, and the cells `cross_distances` gives the same pairs, bit for bit).  The M x N matrix is never
+    held whole and never crosses to the host.  The radius, max_pairs and the arguments cluster.ctree checks are checked
+    before any device work; ZeroDivisionError and NaN cells as `cross_distances`; NotImplementedError once more than
+    max_pairs pairs are found."""
+    radius = check_radius(radius)
+    check_max_pairs(max_pairs)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    queries, refs = list(queries), list(refs)
+    if not queries or not refs:
+        return _no_neighbours(len(queries))
+    return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                      ctx, lambda q, r: q.within(r, radius, max_pairs=max_pairs), canonical)
+
+
+def neighbours(seqs, radius, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
+               mash_canonical: bool = False, canonical: bool = False, max_pairs: int | None = None,
+               ctx: engine.Context | None = None) -> Neighbours:
+    """`within` of a collection against itself, a sequence not listed as its own neighbour: every pair (i, j), i != j,
+    at a distance <= radius, from both of its ends"""
+    radius = check_radius(radius)
+    check_max_pairs(max_pairs)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    seqs = list(seqs)
+    if not seqs:
+        return _no_neighbours(0)
+    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
+                     canonical=canonical) as dev:
+        return dev.within(dev, radius, skip_self=True, max_pairs=max_pairs)
+
+
+def threshold_clusters(seqs, radius, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+                       num_states: int = 4, mash_canonical: bool = False, canonical: bool = False,
+                       ctx: engine.Context | None = None) -> ThresholdClusters:
+    """the groups that "`distance_mode` distance <= radius" makes of the sequences (`ThresholdClusters`): connected
+    components, i.e. the flat clusters of the single-linkage tree cut at height radius (dereplication: "cluster at mash
+    distance 0.05"), without the N x N matrix and without the tree.  Argument checks as `within`; ZeroDivisionError (mash)
+    as `cluster_scores`; a sequence without a valid k-mer (jsd, euclidean: NaN distances) is a cluster of its own."""
+    radius = check_radius(radius)
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    seqs = list(seqs)
+    if not seqs:
+        return _run_threshold_clusters(ctx, "", 0)
+    with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
+                     canonical=canonical) as dev:
+        return dev.threshold_clusters(radius)

@@ -551,6 +551,70 @@ int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uin
                        uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
                        uint32_t *medoids);
 
+/* ---- neighbours within a radius, and threshold clusters ------------------------------------------- *
+ * The sparse product of the cross entries above: for every query, the references whose cell is <= radius, the nq x nr
+ * matrix never existing whole and never leaving the device -- only the listed pairs come back.  (No counterpart in
+ * the reference.)  A cell is the bits of its mode's square entry for the same two rows, computed strip by strip as
+ * dvs_*_cross_distances computes it (same handles, row lists, strip bound and DVS_CROSS_STRIP_ROWS).  The result is a
+ * dvs_pairs: a CSR list on the host, row_start[nq + 1] (row_start[0] == 0, row_start[nq] == the number of pairs) and,
+ * for query i, col / dist [row_start[i], row_start[i + 1]): col is the position in the reference list 0 .. nr - 1 --
+ * not the matrix row --, dist that cell.  Within a query the entries are in ascending position.  radius is inclusive
+ * (a cell equal to it is listed); a NaN cell compares false and is never listed; -inf or any negative radius gives
+ * empty lists, +inf lists every non-NaN cell.  The same pairs in the same order on every run and for every strip
+ * height: no position depends on an atomic.  flags: DVS_WITHIN_SKIP_SELF drops cell (i, i), whatever it holds -- it is
+ * never read -- for a call whose two sides list the same positions (i against position i of the reference list).
+ * max_pairs (0: no limit): as soon as the pairs of the strips so far exceed it the call stops and fails; the context
+ * stays usable.  A dvs_pairs lives on the host and holds no reference to the context: it may outlive it, and is freed
+ * by dvs_pairs_destroy (NULL is fine).  dvs_within takes the caller's own n x n matrix as dvs_cluster_scores does and
+ * only reads it.  *out is NULL after an error.  Errors of the arguments, all before any device work:
+ *   DVS_OK with an empty list (nq rows, no pairs): nq == 0 or nr == 0 -- as for dvs_*_cross_distances, nothing else
+ *                  about the handles and the row lists is looked at then, so a bad row list passes unnoticed
+ *   DVS_ERR_VALUE: NULL arguments, NaN radius, unknown flag bits (checked first); a row index beyond its handle, handles of different
+ *                  contexts or devices, unequal nbins, a matrix that is not device memory where it is said to be
+ *   DVS_ERR_UNSUPPORTED: nr (n) beyond the row limit of the square entries
+ *   DVS_ERR_ZERODIV: (sketches) k == 0
+ * and those that show while the strips are walked:
+ *   DVS_ERR_UNSUPPORTED: more than max_pairs pairs (the message names both numbers)
+ *   DVS_ERR_NOMEM: the host lists do not fit
+ *   DVS_ERR_ZERODIV: (sketches) a visited pair has two empty sketches: exactly where dvs_sketches_cross_distances
+ *                  raises it */
+typedef struct dvs_pairs dvs_pairs;
+#define DVS_WITHIN_SKIP_SELF 1u /* drop cell (i, i): both sides list the same positions */
+int dvs_jsd_within(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
+                   const uint32_t *r_rows, uint32_t nr, double radius, uint32_t flags, uint64_t max_pairs, dvs_pairs **out);
+int dvs_euclidean_within(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
+                         const uint32_t *r_rows, uint32_t nr, double radius, uint32_t flags, uint64_t max_pairs,
+                         dvs_pairs **out);
+int dvs_sketches_within(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq, const dvs_sketches *r,
+                        const uint32_t *r_rows, uint32_t nr, uint32_t k, uint32_t sketch_size, double radius, uint32_t flags,
+                        uint64_t max_pairs, dvs_pairs **out);
+int dvs_within(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, double radius, uint32_t flags,
+               uint64_t max_pairs, dvs_pairs **out);
+void dvs_pairs_destroy(dvs_pairs *p);
+int dvs_pairs_info(const dvs_pairs *p, uint32_t *n_rows, uint64_t *n_pairs); /* either may be NULL */
+/* row_start[n_rows + 1], col[n_pairs], dist[n_pairs]: host arrays, any may be NULL */
+int dvs_pairs_get(const dvs_pairs *p, uint64_t *row_start, uint32_t *col, double *dist);
+/* Threshold clusters: the connected components of the graph that joins positions i and j when D(i, j) <= radius, over
+ * the n x n distances of a mode (queries = references = `rows` of the handle, NULL: rows 0 .. n - 1), computed strip by
+ * strip as above.  They are the flat clusters of the single-linkage tree cut at height radius -- dvs_linkage_cut with
+ * DVS_CUT_HEIGHT over dvs_linkage's DVS_LINKAGE_SINGLE tree -- without the n x n matrix and without the tree.  Only the
+ * cells above the diagonal (j > i) are read: a caller's matrix need not be symmetric, and its diagonal may hold
+ * anything.  A strip's edges go through a union-find on the host and are dropped before the next strip's arrive.
+ * labels[n]: the cluster of every position, in [0, *n_clusters), numbered by first appearance in position order
+ * (position 0 is in cluster 0), as dvs_linkage_cut numbers them.  A position whose every cell is NaN or beyond the
+ * radius is a cluster of its own; a negative radius joins nothing.  (No counterpart in the reference.)
+ *   DVS_OK with nothing written: n == 0.  n == 1: label 0, one cluster
+ *   DVS_ERR_VALUE, DVS_ERR_UNSUPPORTED, DVS_ERR_NOMEM: as above
+ *   DVS_ERR_ZERODIV: (sketches) exactly as dvs_sketches_cluster_scores */
+int dvs_jsd_threshold_clusters(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, double radius,
+                               uint32_t *labels, uint32_t *n_clusters);
+int dvs_euclidean_threshold_clusters(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, double radius,
+                                     uint32_t *labels, uint32_t *n_clusters);
+int dvs_sketches_threshold_clusters(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
+                                    uint32_t sketch_size, double radius, uint32_t *labels, uint32_t *n_clusters);
+int dvs_threshold_clusters(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, double radius,
+                           uint32_t *labels, uint32_t *n_clusters);
+
 /* ---- cophenetic distances of a tree, and their correlation with the distances it was built from ---- *
  * scipy.cluster.hierarchy.cophenet.  The cophenetic distance coph(i, j) of two leaves is the height of the merge at
  * which they first share a cluster.  Over dvs_linkage's outputs (pairs[2 (n - 1)], heights[n - 1], scipy's ids: leaves
