@@ -36,7 +36,7 @@ EXPORTS = (
     "dvs_select_destroy", "dvs_select_get_summary", "dvs_select_get_members",
     "dvs_select_gather_members",
     "dvs_select_delta_jsd", "dvs_select_step_pack",
-    "dvs_select_step_apply", "dvs_select_step_poll", "dvs_select_step_peek", "dvs_select_bench_scan", "dvs_selftest_fast_log2", "dvs_selftest_log2_acc", "dvs_selftest_log2_f32", "dvs_selftest_exact_div", "dvs_selftest_handover", "dvs_mash_sketch", "dvs_mash_distances", "dvs_euclidean_distances", "dvs_sketches_build", "dvs_sketches_destroy", "dvs_sketches_get", "dvs_sketches_dev", "dvs_sketches_dev_lens", "dvs_sketches_distances",
+    "dvs_select_step_apply", "dvs_select_step_poll", "dvs_select_step_peek", "dvs_select_bench_scan", "dvs_selftest_fast_log2", "dvs_selftest_log2_acc", "dvs_selftest_log2_f32", "dvs_selftest_exact_div", "dvs_selftest_handover", "dvs_mash_sketch", "dvs_mash_distances", "dvs_sketches_build", "dvs_sketches_destroy", "dvs_sketches_get", "dvs_sketches_dev", "dvs_sketches_dev_lens", "dvs_sketches_distances",
     "dvs_sketches_from_device", "dvs_sketches_copy_to_device", "dvs_sketches_distances_device",
     "dvs_default_alphabet_lut", "dvs_seqbatch_from_fasta", "dvs_seqbatch_destroy", "dvs_seqbatch_info",
     "dvs_seqbatch_offsets", "dvs_seqbatch_header_positions", "dvs_seqbatch_dev_codes", "dvs_seqbatch_get_codes",
@@ -44,23 +44,20 @@ EXPORTS = (
     "dvs_pack_sequences", "dvs_packed_destroy", "dvs_packed_info", "dvs_packed_dev_codes", "dvs_packed_dev_mask",
     "dvs_packed_get", "dvs_matrix_build_packed", "dvs_sketches_build_packed", "dvs_seqbatch_pack",
     "dvs_seqbatch_packed", "dvs_sketches_build_from_seqbatch",
-    "dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage",
-    "dvs_linkage", "dvs_sketches_linkage", "dvs_matrix_euclidean_linkage",
-    "dvs_jsd_distances", "dvs_matrix_jsd_linkage",
-    "dvs_jsd_cross_distances", "dvs_euclidean_cross_distances", "dvs_sketches_cross_distances",
-    "dvs_jsd_nearest", "dvs_euclidean_nearest", "dvs_sketches_nearest",
-    "dvs_linkage_cut", "dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_sketches_cluster_scores",
-    "dvs_cluster_scores",
-    "dvs_linkage_cophenet", "dvs_jsd_cophenet", "dvs_euclidean_cophenet", "dvs_sketches_cophenet", "dvs_cophenet",
-    "dvs_nj", "dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj", "dvs_nj_patristic",
-    "dvs_maxmin", "dvs_sketches_maxmin", "dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin",
     "dvs_canonical_bins", "dvs_matrix_fold_canonical", "dvs_matrix_is_canonical",
-    "dvs_jsd_within", "dvs_euclidean_within", "dvs_sketches_within", "dvs_within",
-    "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get",
-    "dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters", "dvs_sketches_threshold_clusters",
-    "dvs_threshold_clusters",
+    "dvs_linkage_cut", "dvs_linkage_cophenet", "dvs_nj_patristic", "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get",
+    # one entry per operation over the distances of a `Source`
+    "dvs_distances", "dvs_linkage", "dvs_nj", "dvs_maxmin", "dvs_cross_distances", "dvs_nearest", "dvs_within",
+    "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters",
 )
 WITHIN_SKIP_SELF = 1
+SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
+
+
+class Source(C.Structure):
+    """dvs_source: where an operation's distances come from"""
+    _fields_ = [("kind", C.c_uint32), ("handle", C.c_void_p), ("rows", C.POINTER(C.c_uint32)), ("n", C.c_uint32),
+                ("k", C.c_uint32), ("sketch_size", C.c_uint32), ("on_device", C.c_int)]
 
 
 class SelectParams(C.Structure):
@@ -185,7 +182,6 @@ def load() -> C.CDLL:
                                       C.c_uint32, C.c_int, u32p, u32p]
         L.dvs_mash_distances.argtypes = [vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, f64p]
-        L.dvs_euclidean_distances.argtypes = [vp, vp, f64p]
         L.dvs_sketches_build.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_int, C.POINTER(vp)]
         L.dvs_sketches_destroy.argtypes = [vp]
@@ -224,63 +220,32 @@ def load() -> C.CDLL:
         L.dvs_seqbatch_pack.argtypes = [vp, vp]
         L.dvs_sketches_build_from_seqbatch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                                        C.POINTER(vp)]
-        L.dvs_average_linkage.argtypes = [vp, vp, C.c_int, C.c_uint32, u32p, f64p, u32p]
-        L.dvs_sketches_average_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32, u32p, f64p, u32p]
-        L.dvs_matrix_euclidean_average_linkage.argtypes = [vp, vp, u32p, f64p, u32p]
-        L.dvs_linkage.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_int, u32p, f64p, u32p]
-        L.dvs_sketches_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, u32p, f64p, u32p]
-        L.dvs_matrix_euclidean_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
-        L.dvs_jsd_distances.argtypes = [vp, vp, f64p]
-        L.dvs_matrix_jsd_linkage.argtypes = [vp, vp, C.c_int, u32p, f64p, u32p]
-        u32 = C.c_uint32
-        for n in ("dvs_jsd_cross_distances", "dvs_euclidean_cross_distances"):
-            getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, f64p]
-        L.dvs_sketches_cross_distances.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, f64p]
-        for n in ("dvs_jsd_nearest", "dvs_euclidean_nearest"):
-            getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32p, f64p]
-        L.dvs_sketches_nearest.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, u32, u32p, f64p]
+        u32, srcp = C.c_uint32, C.POINTER(Source)
         L.dvs_linkage_cut.argtypes = [vp, u32, u32p, f64p, C.c_int, C.c_double, u32p, u32p]
-        scores = [u32p, u32, f64p, f64p, f64p, u32p, f64p, u32p]  # labels, n_clusters, the five per-row outputs, medoids
-        for n in ("dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores"):
-            getattr(L, n).argtypes = [vp, vp, u32p, u32, *scores]
-        L.dvs_sketches_cluster_scores.argtypes = [vp, vp, u32p, u32, u32, u32, *scores]
-        L.dvs_cluster_scores.argtypes = [vp, vp, C.c_int, u32, *scores]
         L.dvs_linkage_cophenet.argtypes = [vp, u32, u32p, f64p, f64p]
-        coph = [u32p, f64p, f64p, f64p, f64p]  # pairs, heights, the correlation, the row sums, the cophenetic matrix
-        for n in ("dvs_jsd_cophenet", "dvs_euclidean_cophenet"):
-            getattr(L, n).argtypes = [vp, vp, u32p, u32, *coph]
-        L.dvs_sketches_cophenet.argtypes = [vp, vp, u32p, u32, u32, u32, *coph]
-        L.dvs_cophenet.argtypes = [vp, vp, C.c_int, u32, *coph]
-        L.dvs_nj.argtypes = [vp, vp, C.c_int, u32, u32p, f64p]
-        L.dvs_sketches_nj.argtypes = [vp, vp, u32, u32, u32p, f64p]
-        for n in ("dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj"):
-            getattr(L, n).argtypes = [vp, vp, u32p, f64p]
         L.dvs_nj_patristic.argtypes = [vp, u32, u32p, f64p, f64p]
-        # n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover
-        maxmin = [u32, u32p, u32, u32, C.c_int, C.c_double, u32p, f64p, u32p, u32p, f64p, f64p]
-        L.dvs_maxmin.argtypes = [vp, vp, C.c_int, *maxmin]
-        L.dvs_sketches_maxmin.argtypes = [vp, vp, u32, u32, *maxmin]
-        for n in ("dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin"):
-            getattr(L, n).argtypes = [vp, vp, *maxmin]
         L.dvs_canonical_bins.argtypes = [u32, u32p, u64p]
         L.dvs_matrix_fold_canonical.argtypes = [vp, vp, C.POINTER(vp)]
         L.dvs_matrix_is_canonical.argtypes = [vp]
         L.dvs_matrix_is_canonical.restype = C.c_uint32
-        within = [C.c_double, u32, C.c_uint64, C.POINTER(vp)]  # radius, flags, max_pairs, the dvs_pairs
-        for n in ("dvs_jsd_within", "dvs_euclidean_within"):
-            getattr(L, n).argtypes = [vp, vp, u32p, u32, vp, u32p, u32, *within]
-        L.dvs_sketches_within.argtypes = [vp, vp, u32p, u32, vp, u32p, u32, u32, u32, *within]
-        L.dvs_within.argtypes = [vp, vp, C.c_int, u32, *within]
         L.dvs_pairs_destroy.argtypes = [vp]
         L.dvs_pairs_destroy.restype = None
         L.dvs_pairs_info.argtypes = [vp, u32p, u64p]
         L.dvs_pairs_get.argtypes = [vp, u64p, u32p, f64p]
-        components = [C.c_double, u32p, u32p]  # radius, labels, n_clusters
-        for n in ("dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters"):
-            getattr(L, n).argtypes = [vp, vp, u32p, u32, *components]
-        L.dvs_sketches_threshold_clusters.argtypes = [vp, vp, u32p, u32, u32, u32, *components]
-        L.dvs_threshold_clusters.argtypes = [vp, vp, C.c_int, u32, *components]
-        if L.dvs_abi_version() != 3:
+        # the operations over the distances of a source (or of two): the context, the source(s), the operation's own
+        L.dvs_distances.argtypes = [vp, srcp, f64p]
+        L.dvs_linkage.argtypes = [vp, srcp, C.c_int, u32p, f64p, u32p]  # method, pairs, heights, sizes
+        L.dvs_nj.argtypes = [vp, srcp, u32p, f64p]  # joins, lengths
+        # seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover
+        L.dvs_maxmin.argtypes = [vp, srcp, u32p, u32, u32, C.c_int, C.c_double, u32p, f64p, u32p, u32p, f64p, f64p]
+        L.dvs_cross_distances.argtypes = [vp, srcp, srcp, f64p]
+        L.dvs_nearest.argtypes = [vp, srcp, srcp, u32, u32p, f64p]  # kk, idx, dist
+        L.dvs_within.argtypes = [vp, srcp, srcp, C.c_double, u32, C.c_uint64, C.POINTER(vp)]  # radius, flags, max_pairs, the dvs_pairs
+        # labels, n_clusters, the five per-row outputs, medoids
+        L.dvs_cluster_scores.argtypes = [vp, srcp, u32p, u32, f64p, f64p, f64p, u32p, f64p, u32p]
+        L.dvs_cophenet.argtypes = [vp, srcp, u32p, f64p, f64p, f64p, f64p]  # pairs, heights, the correlation, the row sums, the matrix
+        L.dvs_threshold_clusters.argtypes = [vp, srcp, C.c_double, u32p, u32p]  # radius, labels, n_clusters
+        if L.dvs_abi_version() != 4:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L
         return _lib

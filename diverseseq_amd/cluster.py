@@ -54,19 +54,20 @@ def make_cluster_tree(seq_names: Sequence[str], pairwise_distances: np.ndarray) 
 
 def _caller_matrix(dist):
     """a caller's n x n distance matrix -- a square, contiguous float64 torch tensor on the GPU, or anything
-    np.asarray(dist, float64) takes -> (its pointer, whether that is device memory, n, wait); wait() returns once the
-    work torch has queued on the tensor's device's current stream is done (torch's stream -> the library's), at once
-    for host memory"""
+    np.asarray(dist, float64) takes -> (its `_lib.Source`, of kind GIVEN, which keeps the matrix alive; n; wait); wait()
+    returns once the work torch has queued on the tensor's device's current stream is done (torch's stream -> the
+    library's), at once for host memory"""
     torch = sys.modules.get("torch")
     if torch is not None and isinstance(dist, torch.Tensor) and dist.is_cuda:
         if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or not dist.is_contiguous():
             raise ValueError("a device distance matrix must be a square, contiguous float64 tensor")
         wait = lambda: torch.cuda.current_stream(dist.device).synchronize()  # noqa: E731
-        return C.c_void_p(dist.data_ptr()), 1, int(dist.shape[0]), wait
+        n = int(dist.shape[0])
+        return distance.make_source(_lib.SRC_GIVEN, dist.data_ptr(), n, on_device=1, keep=dist), n, wait
     d = np.ascontiguousarray(np.asarray(dist, dtype=np.float64))
     if d.ndim != 2 or d.shape[0] != d.shape[1]:
         raise ValueError(f"expected a square distance matrix, got shape {d.shape}")
-    return d.ctypes.data_as(C.c_void_p), 0, d.shape[0], lambda: None  # (the pointer keeps d alive)
+    return distance.make_source(_lib.SRC_GIVEN, d.ctypes.data, d.shape[0], keep=d), d.shape[0], lambda: None
 
 
 def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None) -> np.ndarray:
@@ -80,9 +81,9 @@ def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None)
     on the GPU, which is used as the working buffer and OVERWRITTEN.  Such a tensor must live on the context's
     device (ValueError otherwise); the call waits for the work torch has queued on that device's current stream."""
     code = distance.linkage_method_code(method)
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     wait()
-    return distance.run_linkage(ctx, n, "dvs_linkage", src, on_device, n, code,
+    return distance.run_linkage(ctx, n, src, code,
                                 too_few=f"Found array with {n} sample(s) while a minimum of 2 is required")
 
 
@@ -129,7 +130,7 @@ def ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_m
     sequence from its reverse complement; ValueError for mash, which has mash_canonical_kmers.
 
     tree="device": the distances and the tree both on the GPU, the N x N matrix never leaves HBM
-    (dvs_sketches_linkage / dvs_matrix_euclidean_linkage / dvs_matrix_jsd_linkage), the string from
+    (dvs_linkage over the mode's source), the string from
     `linkage_to_newick`; `linkage`: any method the module's `linkage` function builds.  tree="sklearn": the reference's path (the matrix copied to the host, sklearn, nested
     tuples; `make_cluster_tree`), average linkage only.  Both give the same string wherever the sklearn path
     returns one; the one intended difference is a tree deeper than Python's recursion limit (e.g. a caterpillar of
@@ -164,11 +165,11 @@ def neighbor_joining(dist, *, ctx: engine.Context | None = None) -> "distance.NJ
     `dist`: as `linkage` takes it -- anything np.asarray(dist, float64) takes (left as it is), or a square, contiguous
     float64 torch tensor on the context's device, which is the working buffer and OVERWRITTEN; the call waits for the
     work torch has queued on that device's current stream."""
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     if n < 3:
         raise ValueError(f"Found array with {n} sample(s) while a minimum of 3 is required for a neighbour-joining tree")
     wait()
-    return distance.run_nj(ctx, n, "dvs_nj", src, on_device, n)
+    return distance.run_nj(ctx, n, src)
 
 
 def nj_to_newick(names: Sequence, tree, *, lengths: bool = True) -> str:
@@ -224,7 +225,7 @@ def nj_tree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance
             mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False):
     """sequences {name: uint8 codes} -> (Newick string with branch lengths, distance.NJTree): the distances of
     `distance_mode` and their neighbour-joining tree both on the GPU, the N x N matrix never leaving HBM
-    (dvs_sketches_nj / dvs_matrix_euclidean_nj / dvs_matrix_jsd_nj); leaf i is the i-th name.  Argument checks as
+    (dvs_nj over the mode's source); leaf i is the i-th name.  Argument checks as
     `ctree`, and three sequences at least, before any device work."""
     if mash_canonical_kmers is None:
         mash_canonical_kmers = False
@@ -273,12 +274,11 @@ def cluster_scores(dist, labels, *, ctx: engine.Context | None = None) -> "dista
     `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
     as `linkage` handles it (it must live on the context's device) but only READ: it is the same afterwards.  The
     shapes and the labels are checked before any device work."""
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     lab = distance.check_labels(labels, n)
     if n:
         wait()
-    return distance._run_cluster_scores(ctx or (engine.default_context() if n else None), "dvs_cluster_scores", lab, src,
-                                        on_device, n)
+    return distance._run_cluster_scores(ctx or (engine.default_context() if n else None), lab, src)
 
 
 def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None,
@@ -290,10 +290,10 @@ def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float
 
     `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
     as `cluster_scores` handles it and only READ.  The arguments are checked before any device work."""
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     args = distance.check_maxmin_args(n, n_select, seeds, min_distance)
     wait()
-    return distance._run_maxmin(ctx, "dvs_maxmin", n, *args, src, on_device)
+    return distance._run_maxmin(ctx, n, *args, src)
 
 
 def within(dist, radius, *, skip_self: bool = True, max_pairs: int | None = None,
@@ -305,11 +305,11 @@ def within(dist, radius, *, skip_self: bool = True, max_pairs: int | None = None
     `dist`: as `cluster_scores` takes it, only READ.  The radius and max_pairs are checked before any device work."""
     radius = distance.check_radius(radius)
     limit = distance.check_max_pairs(max_pairs)
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     if not n:
         return distance._no_neighbours(0)
     wait()
-    return distance._run_within(ctx, "dvs_within", src, on_device, n, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
+    return distance._run_within(ctx, src, None, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
 
 
 def threshold_clusters(dist, radius, *, ctx: engine.Context | None = None) -> "distance.ThresholdClusters":
@@ -319,10 +319,10 @@ def threshold_clusters(dist, radius, *, ctx: engine.Context | None = None) -> "d
 
     `dist`: as `cluster_scores` takes it, only READ.  The radius is checked before any device work."""
     radius = distance.check_radius(radius)
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     if n:
         wait()
-    return distance._run_threshold_clusters(ctx, "dvs_threshold_clusters", n, src, on_device, n, radius)
+    return distance._run_threshold_clusters(ctx, n, src, radius)
 
 
 def dereplicate(seqs: dict, radius, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
@@ -393,14 +393,14 @@ def cophenet(Z, dist=None, *, matrix: bool = False, ctx: engine.Context | None =
         _lib.raise_for(_lib.load().dvs_linkage_cophenet(None, n, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
                                                         _lib.ptr(coph, C.c_double)), None)
         return coph
-    src, on_device, n, wait = _caller_matrix(dist)
+    src, n, wait = _caller_matrix(dist)
     if n == 0:  # nothing to compute: no device work either
         if np.asarray(Z).size:
             raise ValueError(f"a linkage matrix of 0 leaves is empty, not of shape {np.asarray(Z).shape}")
         return distance.CopheneticScores(float("nan"), np.zeros((5, 0)), np.zeros((0, 0)) if matrix else None)
     pairs, heights = distance.check_linkage_matrix(Z, n)
     wait()
-    return distance._run_cophenet(ctx or engine.default_context(), "dvs_cophenet", n, pairs, heights, matrix, src, on_device, n)
+    return distance._run_cophenet(ctx or engine.default_context(), n, pairs, heights, matrix, src)
 
 
 def ctree_cophenet(seqs: dict, *, linkage: str = "average", k: int = 12, sketch_size: int | None = 3000,

@@ -1125,134 +1125,58 @@ int dvs_cross_rows_check(dvs_ctx *ctx, const uint32_t *rows, uint32_t nrows, uin
     return DVS_OK;
 }
 
-extern "C" int dvs_jsd_cross_distances(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
-                                       const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, double *dist) {
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_host(ctx, jsd_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr), dist);
+// ---- the entries: a source or two (include/dvs_hip.h dvs_source), checked, as a stage of the drivers above
+
+// the sides checked by dvs_source_check: of one kind, GIVEN the caller's matrix against itself
+static dvs_cross_stage source_cross_stage(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r) {
+    switch (q->kind) {
+    case DVS_SRC_MASH:
+        return dvs_mash_cross_stage(ctx, dvs_src_sketches(q), q->rows, q->n, dvs_src_sketches(r), r->rows, r->n, q->k,
+                                    q->sketch_size);
+    case DVS_SRC_EUCLIDEAN:
+        return euclid_cross_stage(ctx, dvs_src_matrix(q), q->rows, q->n, dvs_src_matrix(r), r->rows, r->n);
+    case DVS_SRC_JSD:
+        return jsd_cross_stage(ctx, dvs_src_matrix(q), q->rows, q->n, dvs_src_matrix(r), r->rows, r->n);
+    default:
+        return matrix_rows_stage(ctx, static_cast<const double *>(q->handle), q->on_device, q->n);
+    }
 }
 
-extern "C" int dvs_euclidean_cross_distances(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
-                                             const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, double *dist) {
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_host(ctx, euclid_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr), dist);
+extern "C" int dvs_cross_distances(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, double *dist) {
+    if (int rc = dvs_source_check(ctx, q, r)) return rc;
+    if (q->kind == DVS_SRC_GIVEN) return dvs_source_refuse(ctx, "dvs_cross_distances", q, "the matrix");
+    return cross_to_host(ctx, source_cross_stage(ctx, q, r), dist);
 }
 
-extern "C" int dvs_sketches_cross_distances(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
-                                            const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
-                                            uint32_t sketch_size, double *dist) {
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_host(ctx, dvs_mash_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr, k, sketch_size), dist);
+extern "C" int dvs_nearest(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, uint32_t kk, uint32_t *idx,
+                           double *dist) {
+    if (int rc = dvs_source_check(ctx, q, r)) return rc;
+    if (q->kind == DVS_SRC_GIVEN) return dvs_source_refuse(ctx, "dvs_nearest", q, "the matrix");
+    return cross_to_topk(ctx, source_cross_stage(ctx, q, r), kk, idx, dist);
 }
 
-extern "C" int dvs_jsd_nearest(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                               const uint32_t *r_rows, uint32_t nr, uint32_t kk, uint32_t *idx, double *dist) {
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_topk(ctx, jsd_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr), kk, idx, dist);
+extern "C" int dvs_cluster_scores(dvs_ctx *ctx, const dvs_source *src, const uint32_t *labels, uint32_t n_clusters,
+                                  double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
+                                  uint32_t *medoids) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    return cross_to_cluster_scores(ctx, source_cross_stage(ctx, src, src), labels, n_clusters, within, a, b, neighbour,
+                                   silhouette, medoids);
 }
 
-extern "C" int dvs_euclidean_nearest(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
-                                     const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, uint32_t kk, uint32_t *idx,
-                                     double *dist) {
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_topk(ctx, euclid_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr), kk, idx, dist);
+extern "C" int dvs_cophenet(dvs_ctx *ctx, const dvs_source *src, const uint32_t *pairs, const double *heights, double *corr,
+                            double *row_sums, double *coph) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    return cross_to_cophenet(ctx, source_cross_stage(ctx, src, src), pairs, heights, corr, row_sums, coph);
 }
 
-extern "C" int dvs_sketches_nearest(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
-                                    const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
-                                    uint32_t sketch_size, uint32_t kk, uint32_t *idx, double *dist) {
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_topk(ctx, dvs_mash_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr, k, sketch_size), kk, idx, dist);
-}
-
-extern "C" int dvs_jsd_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
-                                      const uint32_t *labels, uint32_t n_clusters, double *within, double *a, double *b,
-                                      uint32_t *neighbour, double *silhouette, uint32_t *medoids) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cluster_scores(ctx, jsd_cross_stage(ctx, m, rows, n, m, rows, n), labels, n_clusters, within, a, b,
-                                   neighbour, silhouette, medoids);
-}
-
-extern "C" int dvs_euclidean_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
-                                            const uint32_t *labels, uint32_t n_clusters, double *within, double *a,
-                                            double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cluster_scores(ctx, euclid_cross_stage(ctx, m, rows, n, m, rows, n), labels, n_clusters, within, a, b,
-                                   neighbour, silhouette, medoids);
-}
-
-extern "C" int dvs_sketches_cluster_scores(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
-                                           uint32_t sketch_size, const uint32_t *labels, uint32_t n_clusters, double *within,
-                                           double *a, double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids) {
-    if (!ctx || !sk) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cluster_scores(ctx, dvs_mash_cross_stage(ctx, sk, rows, n, sk, rows, n, k, sketch_size), labels,
-                                   n_clusters, within, a, b, neighbour, silhouette, medoids);
-}
-
-extern "C" int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *labels,
-                                  uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour,
-                                  double *silhouette, uint32_t *medoids) {
-    if (!ctx || (!dist && n)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cluster_scores(ctx, matrix_rows_stage(ctx, dist, dist_on_device, n), labels, n_clusters, within, a, b,
-                                   neighbour, silhouette, medoids);
-}
-
-extern "C" int dvs_jsd_cophenet(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *pairs,
-                                const double *heights, double *corr, double *row_sums, double *coph) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cophenet(ctx, jsd_cross_stage(ctx, m, rows, n, m, rows, n), pairs, heights, corr, row_sums, coph);
-}
-
-extern "C" int dvs_euclidean_cophenet(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
-                                      const uint32_t *pairs, const double *heights, double *corr, double *row_sums,
-                                      double *coph) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cophenet(ctx, euclid_cross_stage(ctx, m, rows, n, m, rows, n), pairs, heights, corr, row_sums, coph);
-}
-
-extern "C" int dvs_sketches_cophenet(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
-                                     uint32_t sketch_size, const uint32_t *pairs, const double *heights, double *corr,
-                                     double *row_sums, double *coph) {
-    if (!ctx || !sk) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cophenet(ctx, dvs_mash_cross_stage(ctx, sk, rows, n, sk, rows, n, k, sketch_size), pairs, heights, corr,
-                             row_sums, coph);
-}
-
-extern "C" int dvs_cophenet(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *pairs,
-                            const double *heights, double *corr, double *row_sums, double *coph) {
-    if (!ctx || (!dist && n)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_cophenet(ctx, matrix_rows_stage(ctx, dist, dist_on_device, n), pairs, heights, corr, row_sums, coph);
-}
-
-extern "C" int dvs_jsd_within(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                              const uint32_t *r_rows, uint32_t nr, double radius, uint32_t flags, uint64_t max_pairs,
-                              dvs_pairs **out) {
-    if (out) *out = nullptr;
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_within(ctx, jsd_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr), radius, flags, max_pairs, out);
-}
-
-extern "C" int dvs_euclidean_within(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
-                                    const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, double radius, uint32_t flags,
-                                    uint64_t max_pairs, dvs_pairs **out) {
-    if (out) *out = nullptr;
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_within(ctx, euclid_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr), radius, flags, max_pairs, out);
-}
-
-extern "C" int dvs_sketches_within(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
-                                   const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
-                                   uint32_t sketch_size, double radius, uint32_t flags, uint64_t max_pairs, dvs_pairs **out) {
-    if (out) *out = nullptr;
-    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_within(ctx, dvs_mash_cross_stage(ctx, q, q_rows, nq, r, r_rows, nr, k, sketch_size), radius, flags,
-                           max_pairs, out);
-}
-
-extern "C" int dvs_within(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, double radius, uint32_t flags,
+extern "C" int dvs_within(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, double radius, uint32_t flags,
                           uint64_t max_pairs, dvs_pairs **out) {
     if (out) *out = nullptr;
-    if (!ctx || (!dist && n)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_within(ctx, matrix_rows_stage(ctx, dist, dist_on_device, n), radius, flags, max_pairs, out);
+    if (!r && q && q->kind == DVS_SRC_GIVEN) r = q;  // a caller's matrix is both sides
+    if (int rc = dvs_source_check(ctx, q, r)) return rc;
+    if (q->kind == DVS_SRC_GIVEN && (r->handle != q->handle || r->n != q->n || r->on_device != q->on_device))
+        return dvs_source_refuse(ctx, "dvs_within", q, "another matrix as the references");
+    return cross_to_within(ctx, source_cross_stage(ctx, q, r), radius, flags, max_pairs, out);
 }
 
 extern "C" void dvs_pairs_destroy(dvs_pairs *p) { delete p; }
@@ -1272,28 +1196,8 @@ extern "C" int dvs_pairs_get(const dvs_pairs *p, uint64_t *row_start, uint32_t *
     return DVS_OK;
 }
 
-extern "C" int dvs_jsd_threshold_clusters(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, double radius,
-                                          uint32_t *labels, uint32_t *n_clusters) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_threshold_clusters(ctx, jsd_cross_stage(ctx, m, rows, n, m, rows, n), radius, labels, n_clusters);
-}
-
-extern "C" int dvs_euclidean_threshold_clusters(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
-                                                double radius, uint32_t *labels, uint32_t *n_clusters) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_threshold_clusters(ctx, euclid_cross_stage(ctx, m, rows, n, m, rows, n), radius, labels, n_clusters);
-}
-
-extern "C" int dvs_sketches_threshold_clusters(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n,
-                                               uint32_t k, uint32_t sketch_size, double radius, uint32_t *labels,
-                                               uint32_t *n_clusters) {
-    if (!ctx || !sk) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_threshold_clusters(ctx, dvs_mash_cross_stage(ctx, sk, rows, n, sk, rows, n, k, sketch_size), radius, labels,
-                                       n_clusters);
-}
-
-extern "C" int dvs_threshold_clusters(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, double radius,
-                                      uint32_t *labels, uint32_t *n_clusters) {
-    if (!ctx || (!dist && n)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return cross_to_threshold_clusters(ctx, matrix_rows_stage(ctx, dist, dist_on_device, n), radius, labels, n_clusters);
+extern "C" int dvs_threshold_clusters(dvs_ctx *ctx, const dvs_source *src, double radius, uint32_t *labels,
+                                      uint32_t *n_clusters) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    return cross_to_threshold_clusters(ctx, source_cross_stage(ctx, src, src), radius, labels, n_clusters);
 }

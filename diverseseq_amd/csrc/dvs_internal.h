@@ -338,6 +338,23 @@ struct dvs_cross_lists {
     }
 };
 
+// ---- an operation's source (include/dvs_hip.h dvs_source): the tag in front of the stages above
+uint32_t dvs_sketches_nseq(const dvs_sketches *sk);  // mash.hip, whose struct it is
+inline const dvs_matrix *dvs_src_matrix(const dvs_source *s) { return static_cast<const dvs_matrix *>(s->handle); }
+inline const dvs_sketches *dvs_src_sketches(const dvs_source *s) { return static_cast<const dvs_sketches *>(s->handle); }
+// rowdist.hip.  What every entry checks before anything else, in place of what typed handles used to guarantee (r ==
+// q for an operation over one source): DVS_ERR_VALUE for a NULL context, source or handle, an unknown kind, a row
+// list with GIVEN, two sides of different kinds, two MASH sides of different k or sketch size
+int dvs_source_check(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r);
+// DVS_ERR_UNSUPPORTED, "<op>: <what> of a <kind> source": a combination no entry has served
+int dvs_source_refuse(dvs_ctx *ctx, const char *op, const dvs_source *src, const char *what);
+// ... for a row list, or n other than the handle's rows (the square drivers take a handle whole)
+int dvs_source_whole(dvs_ctx *ctx, const char *op, const dvs_source *src);
+// linkage.hip, nj.hip: the tree of a GIVEN matrix (host: uploaded; device: the working buffer), the method / n checked
+int dvs_linkage_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
+                      double *heights, uint32_t *sizes);
+int dvs_nj_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths);
+
 // f(typed row pointer) for the matrix's element type
 template <typename F>
 auto dvs_mat_dispatch(const dvs_matrix *m, F &&f) {

@@ -550,9 +550,8 @@ int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t 
     return DVS_OK;
 }
 
-extern "C" int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
-                           double *heights, uint32_t *sizes) {
-    if (!ctx || !dist || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+int dvs_linkage_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
+                      double *heights, uint32_t *sizes) {
     int rc = dvs_linkage_check_method(ctx, method);
     if (rc) return rc;
     if (n < 2)
@@ -581,11 +580,6 @@ extern "C" int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint3
         return dvs_hip_fail(ctx, e, "distance matrix upload");
     }
     return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, method, pairs, heights, sizes);
-}
-
-extern "C" int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
-                                   double *heights, uint32_t *sizes) {
-    return dvs_linkage(ctx, dist, dist_on_device, n, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
 }
 
 // The flat clusters of a cut (host only): the first m merges applied, m from the criterion; the merges name their

@@ -27,7 +27,6 @@
 #include <cmath>
 #include <type_traits>
 
-uint32_t dvs_sketches_nseq(const dvs_sketches *sk);  // mash.hip
 
 namespace {
 
@@ -439,14 +438,10 @@ MaxminMode stage_mode(dvs_ctx *ctx, const dvs_cross_stage &st, uint32_t n, bool 
     return mode;
 }
 
-}  // namespace
+// ---- the traversal over each kind of source: the arguments checked by maxmin_check
 
-extern "C" int dvs_maxmin(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *seeds,
-                          uint32_t n_seeds, uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks,
-                          double *radius, uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover) {
-    if (!ctx || (!dist && n)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    const MaxminArgs a{n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover};
-    if (int rc = maxmin_check(ctx, a)) return rc;
+int maxmin_given(dvs_ctx *ctx, const MaxminArgs &a, const double *dist, int dist_on_device) {
+    const uint32_t n = a.n;
     if (uint64_t(n) * n > (uint64_t(1) << 58))
         return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix does not fit in memory", n, n);
     DVS_HIP(ctx, hipSetDevice(ctx->device));
@@ -478,13 +473,8 @@ extern "C" int dvs_maxmin(dvs_ctx *ctx, const double *dist, int dist_on_device, 
     });
 }
 
-extern "C" int dvs_sketches_maxmin(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t n,
-                                   const uint32_t *seeds, uint32_t n_seeds, uint32_t n_select, int use_min_distance,
-                                   double min_distance, uint32_t *picks, double *radius, uint32_t *n_picked, uint32_t *owner,
-                                   double *dist_to_owner, double *cover) {
-    if (!ctx || !sk) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    const MaxminArgs a{n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover};
-    if (int rc = maxmin_check(ctx, a)) return rc;
+int maxmin_mash(dvs_ctx *ctx, const MaxminArgs &a, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size) {
+    const uint32_t n = a.n;
     if (n > dvs_sketches_nseq(sk))
         return dvs_set_error(ctx, DVS_ERR_VALUE, "%u rows of a handle that holds %u", n, dvs_sketches_nseq(sk));
     if (n == 1) return maxmin_single(a);
@@ -492,34 +482,24 @@ extern "C" int dvs_sketches_maxmin(dvs_ctx *ctx, const dvs_sketches *sk, uint32_
     if (!dvs_sketches_dev(sk)) return dvs_set_error(ctx, DVS_ERR_ZERODIV, "division by zero");  // every sketch empty
     DVS_HIP(ctx, hipSetDevice(ctx->device));
     return maxmin_run(ctx, a, [&](const MaxminState &S) {
-        return stage_mode(ctx, dvs_mash_cross_stage(ctx, sk, nullptr, n_select, sk, nullptr, n, k, sketch_size, S.picks), n, true);
+        return stage_mode(ctx, dvs_mash_cross_stage(ctx, sk, nullptr, a.n_select, sk, nullptr, n, k, sketch_size, S.picks), n, true);
     });
 }
 
-extern "C" int dvs_matrix_euclidean_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t n, const uint32_t *seeds,
-                                           uint32_t n_seeds, uint32_t n_select, int use_min_distance, double min_distance,
-                                           uint32_t *picks, double *radius, uint32_t *n_picked, uint32_t *owner,
-                                           double *dist_to_owner, double *cover) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    const MaxminArgs a{n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover};
-    if (int rc = maxmin_check(ctx, a)) return rc;
+int maxmin_euclidean(dvs_ctx *ctx, const MaxminArgs &a, const dvs_matrix *m) {
+    const uint32_t n = a.n;
     if (int rc = matrix_check(ctx, m, n)) return rc;
     if ((n + EUC_THREADS / 64 - 1) / (EUC_THREADS / 64) > 65535u)  // (euclid_cross_kernel's grid, a workgroup per 8 rows in y)
         return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%u rows: beyond the euclidean kernel's grid", n);
     if (n == 1) return maxmin_single(a);
     DVS_HIP(ctx, hipSetDevice(ctx->device));
     return maxmin_run(ctx, a, [&](const MaxminState &S) {
-        return stage_mode(ctx, dvs_euclid_cross_stage(ctx, m, nullptr, n_select, m, nullptr, n, S.picks), n, false);
+        return stage_mode(ctx, dvs_euclid_cross_stage(ctx, m, nullptr, a.n_select, m, nullptr, n, S.picks), n, false);
     });
 }
 
-extern "C" int dvs_matrix_jsd_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
-                                     uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks,
-                                     double *radius, uint32_t *n_picked, uint32_t *owner, double *dist_to_owner,
-                                     double *cover) {
-    if (!ctx || !m) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    const MaxminArgs a{n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover};
-    if (int rc = maxmin_check(ctx, a)) return rc;
+int maxmin_jsd(dvs_ctx *ctx, const MaxminArgs &a, const dvs_matrix *m) {
+    const uint32_t n = a.n, n_select = a.n_select;
     if (int rc = matrix_check(ctx, m, n)) return rc;
     if (n == 1) return maxmin_single(a);
     DVS_HIP(ctx, hipSetDevice(ctx->device));
@@ -557,4 +537,21 @@ extern "C" int dvs_matrix_jsd_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t
         };
         return mode;
     });
+}
+
+}  // namespace
+
+extern "C" int dvs_maxmin(dvs_ctx *ctx, const dvs_source *src, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_select,
+                          int use_min_distance, double min_distance, uint32_t *picks, double *radius, uint32_t *n_picked,
+                          uint32_t *owner, double *dist_to_owner, double *cover) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (src->rows) return dvs_source_refuse(ctx, "dvs_maxmin", src, "a row list");
+    const MaxminArgs a{src->n, seeds, n_seeds, n_select, use_min_distance, min_distance, picks, radius, n_picked, owner, dist_to_owner, cover};
+    if (int rc = maxmin_check(ctx, a)) return rc;
+    switch (src->kind) {
+    case DVS_SRC_MASH: return maxmin_mash(ctx, a, dvs_src_sketches(src), src->k, src->sketch_size);
+    case DVS_SRC_EUCLIDEAN: return maxmin_euclidean(ctx, a, dvs_src_matrix(src));
+    case DVS_SRC_JSD: return maxmin_jsd(ctx, a, dvs_src_matrix(src));
+    default: return maxmin_given(ctx, a, static_cast<const double *>(src->handle), src->on_device);
+    }
 }

@@ -389,8 +389,7 @@ int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_ze
     return DVS_OK;
 }
 
-extern "C" int dvs_nj(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths) {
-    if (!ctx || !dist || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+int dvs_nj_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths) {
     if (n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least three sequences for a neighbour-joining tree");
     DVS_HIP(ctx, hipSetDevice(ctx->device));
     if (dist_on_device) {

@@ -275,54 +275,69 @@ int stage_to_nj(dvs_ctx *ctx, const dvs_dist_stage &st, uint32_t *joins, double 
 
 int dvs_rows_check(dvs_ctx *ctx, uint32_t n) { return rows_check(ctx, n); }
 
-extern "C" int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
-    if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_host(ctx, euclid_stage(ctx, m), dist);
+// ---- a source (include/dvs_hip.h dvs_source): what every entry checks first, and the source as a stage
+
+static const char *const SRC_KIND[] = {"mash", "euclidean", "jsd", "given"};
+
+int dvs_source_check(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r) {
+    if (!ctx || !q || !r) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    for (const dvs_source *s : {q, r}) {
+        if (s->kind > DVS_SRC_GIVEN) return dvs_set_error(ctx, DVS_ERR_VALUE, "unknown source kind %u", s->kind);
+        if (!s->handle && !(s->kind == DVS_SRC_GIVEN && s->n == 0)) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+        if (s->kind == DVS_SRC_GIVEN && s->rows)
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "a caller's distance matrix takes no row list");
+    }
+    if (q->kind != r->kind)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "a %s source against a %s source", SRC_KIND[q->kind], SRC_KIND[r->kind]);
+    if (q->kind == DVS_SRC_MASH && (q->k != r->k || q->sketch_size != r->sketch_size))
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "sketches of k = %u, sketch size %u against k = %u, sketch size %u", q->k,
+                             q->sketch_size, r->k, r->sketch_size);
+    return DVS_OK;
 }
 
-extern "C" int dvs_jsd_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist) {
-    if (!ctx || !m || !dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_host(ctx, jsd_stage(ctx, m), dist);
+int dvs_source_refuse(dvs_ctx *ctx, const char *op, const dvs_source *src, const char *what) {
+    return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%s: %s of a %s source", op, what, SRC_KIND[src->kind]);
 }
 
-extern "C" int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, int method,
-                                    uint32_t *pairs, double *heights, uint32_t *sizes) {
-    if (!ctx || !sk || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_tree(ctx, dvs_mash_stage(ctx, sk, k, sketch_size), method, pairs, heights, sizes);
-}
-extern "C" int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
-                                            uint32_t *pairs, double *heights, uint32_t *sizes) {
-    return dvs_sketches_linkage(ctx, sk, k, sketch_size, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
+int dvs_source_whole(dvs_ctx *ctx, const char *op, const dvs_source *src) {
+    if (src->rows) return dvs_source_refuse(ctx, op, src, "a row list");
+    const uint32_t rows = src->kind == DVS_SRC_MASH ? dvs_sketches_nseq(dvs_src_sketches(src))
+                          : src->kind == DVS_SRC_GIVEN ? src->n : dvs_src_matrix(src)->nrows;
+    if (src->n != rows) return dvs_source_refuse(ctx, op, src, "some of the rows");
+    return DVS_OK;
 }
 
-extern "C" int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs,
-                                            double *heights, uint32_t *sizes) {
-    if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_tree(ctx, euclid_stage(ctx, m), method, pairs, heights, sizes);
-}
-extern "C" int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
-                                                    uint32_t *sizes) {
-    return dvs_matrix_euclidean_linkage(ctx, m, DVS_LINKAGE_AVERAGE, pairs, heights, sizes);
+// a MASH, EUCLIDEAN or JSD source, whole, as a stage of the drivers above
+static dvs_dist_stage source_stage(dvs_ctx *ctx, const dvs_source *src) {
+    if (src->kind == DVS_SRC_MASH) return dvs_mash_stage(ctx, dvs_src_sketches(src), src->k, src->sketch_size);
+    return src->kind == DVS_SRC_JSD ? jsd_stage(ctx, dvs_src_matrix(src)) : euclid_stage(ctx, dvs_src_matrix(src));
 }
 
-extern "C" int dvs_matrix_jsd_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
-                                      uint32_t *sizes) {
-    if (!ctx || !m || !pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_tree(ctx, jsd_stage(ctx, m), method, pairs, heights, sizes);
+extern "C" int dvs_distances(dvs_ctx *ctx, const dvs_source *src, double *dist) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (!dist) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (src->kind == DVS_SRC_GIVEN) return dvs_source_refuse(ctx, "dvs_distances", src, "the matrix");
+    if (int rc = dvs_source_whole(ctx, "dvs_distances", src)) return rc;
+    if (src->kind == DVS_SRC_MASH)  // (the pair kernel on the caller's diagonal, as Sketches.distances always ran it)
+        return dvs_sketches_distances(ctx, dvs_src_sketches(src), src->k, src->sketch_size, 0, 1, 1, dist);
+    return stage_to_host(ctx, source_stage(ctx, src), dist);
 }
 
-extern "C" int dvs_sketches_nj(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t *joins,
-                               double *lengths) {
-    if (!ctx || !sk || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_nj(ctx, dvs_mash_stage(ctx, sk, k, sketch_size), joins, lengths);
+extern "C" int dvs_linkage(dvs_ctx *ctx, const dvs_source *src, int method, uint32_t *pairs, double *heights,
+                           uint32_t *sizes) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (!pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (int rc = dvs_source_whole(ctx, "dvs_linkage", src)) return rc;
+    if (src->kind == DVS_SRC_GIVEN)
+        return dvs_linkage_given(ctx, static_cast<double *>(src->handle), src->on_device, src->n, method, pairs, heights, sizes);
+    return stage_to_tree(ctx, source_stage(ctx, src), method, pairs, heights, sizes);
 }
 
-extern "C" int dvs_matrix_euclidean_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths) {
-    if (!ctx || !m || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_nj(ctx, euclid_stage(ctx, m), joins, lengths);
-}
-
-extern "C" int dvs_matrix_jsd_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths) {
-    if (!ctx || !m || !joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    return stage_to_nj(ctx, jsd_stage(ctx, m), joins, lengths);
+extern "C" int dvs_nj(dvs_ctx *ctx, const dvs_source *src, uint32_t *joins, double *lengths) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (!joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (int rc = dvs_source_whole(ctx, "dvs_nj", src)) return rc;
+    if (src->kind == DVS_SRC_GIVEN)
+        return dvs_nj_given(ctx, static_cast<double *>(src->handle), src->on_device, src->n, joins, lengths);
+    return stage_to_nj(ctx, source_stage(ctx, src), joins, lengths);
 }

@@ -19,7 +19,8 @@ groups they make (threshold_clusters, matrix_threshold_clusters -> `ThresholdClu
 single-linkage clusters at that height), each strip compacted on the device (csrc/crossdist.hip) so that only the listed
 pairs cross to the host; no counterpart in the reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
-matrix_* functions and the Sketches methods are a few lines over it."""
+matrix_* functions and the Sketches methods are a few lines over it.  Every operation has one C entry, which takes a
+`_lib.Source` (dvs_source: the mode and its handle, or a caller's matrix): `make_source` fills one per call."""
 
 from __future__ import annotations
 
@@ -49,14 +50,14 @@ def linkage_method_code(method) -> int:
 
 
 def tree_outputs(n: int):
-    """host buffers of the dvs_*linkage calls for n leaves: pairs uint32 [2 (n - 1)], heights f64 [n - 1],
+    """host buffers of a dvs_linkage call for n leaves: pairs uint32 [2 (n - 1)], heights f64 [n - 1],
     sizes uint32 [n - 1]"""
     return (np.zeros(2 * (n - 1), dtype=np.uint32), np.zeros(n - 1, dtype=np.float64),
             np.zeros(n - 1, dtype=np.uint32))
 
 
 def linkage_matrix(pairs: np.ndarray, heights: np.ndarray, sizes: np.ndarray) -> np.ndarray:
-    """the outputs of a dvs_*linkage call -> scipy's linkage matrix Z, float64 [n - 1, 4]"""
+    """the outputs of a dvs_linkage call -> scipy's linkage matrix Z, float64 [n - 1, 4]"""
     z = np.empty((heights.size, 4), dtype=np.float64)
     z[:, 0] = pairs[0::2]
     z[:, 1] = pairs[1::2]
@@ -65,16 +66,26 @@ def linkage_matrix(pairs: np.ndarray, heights: np.ndarray, sizes: np.ndarray) ->
     return z
 
 
-def run_linkage(ctx: engine.Context | None, n: int, entry: str, *args,
+def make_source(kind: int, handle, n: int, rows: np.ndarray | None = None, *, k: int = 0, sketch_size: int = 0,
+                on_device: int = 0, keep=None) -> _lib.Source:
+    """the dvs_source of one call: `kind` (_lib.SRC_*), the handle or matrix pointer, the `n` rows taken and their
+    optional uint32 row list.  What its pointers refer to -- the row array, and `keep`, the owner of a caller's
+    matrix -- lives as long as the structure does"""
+    src = _lib.Source(kind, handle, _lib.ptr(rows, C.c_uint32), n, k, sketch_size, on_device)
+    src._keep = (handle, rows, keep)
+    return src
+
+
+def run_linkage(ctx: engine.Context | None, n: int, src: _lib.Source, code: int,
                 too_few: str = "need at least two sequences to build a tree") -> np.ndarray:
-    """the dvs_*linkage call `entry`(ctx, *args, pairs, heights, sizes) for n leaves -> Z; ValueError(too_few)
-    before any device work when n < 2"""
+    """dvs_linkage over `src` with the method `code` for n leaves -> Z; ValueError(too_few) before any device work
+    when n < 2"""
     if n < 2:
         raise ValueError(too_few)
     ctx = ctx or engine.default_context()
     pairs, heights, sizes = tree_outputs(n)
-    ctx.check(getattr(ctx._L, entry)(ctx._h, *args, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
-                                     _lib.ptr(sizes, C.c_uint32)))
+    ctx.check(ctx._L.dvs_linkage(ctx._h, src, code, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                 _lib.ptr(sizes, C.c_uint32)))
     return linkage_matrix(pairs, heights, sizes)
 
 
@@ -252,42 +263,42 @@ class Sketches:
 
     def linkage(self, method: str = "average") -> np.ndarray:
         """scipy's linkage matrix Z of `method` (LINKAGE_METHODS) over the mash distances of every pair: the N x N
-        matrix is written and read in HBM (dvs_sketches_linkage); ZeroDivisionError as `distances`"""
+        matrix is written and read in HBM (dvs_linkage); ZeroDivisionError as `distances`"""
         return DeviceSide(self, "mash").linkage(method)
 
     def cross_distances(self, other: "Sketches", rows=None, other_rows=None) -> np.ndarray:
         """the mash distances of this set's sketches `rows` (None: all) against `other`'s `other_rows`: float64 [M, N],
-        every cell the bits `distances` gives the same two sketches (dvs_sketches_cross_distances);
+        every cell the bits `distances` gives the same two sketches (dvs_cross_distances);
         ZeroDivisionError as `distances`"""
         return DeviceSide(self, "mash").cross_distances(DeviceSide(other, "mash"), rows, other_rows)
 
     def nearest(self, other: "Sketches", n_nearest: int = 1, rows=None, other_rows=None):
         """the n_nearest sketches of `other` (positions into other_rows, or rows) nearest to each of this set's, nearest
         first, a tie to the lower position: (int64 [M, n_nearest], -1 in a slot without a reference; float64 distances,
-        NaN there) (dvs_sketches_nearest)"""
+        NaN there) (dvs_nearest)"""
         return DeviceSide(self, "mash").nearest(DeviceSide(other, "mash"), n_nearest, rows, other_rows)
 
     def cluster_scores(self, labels, rows=None) -> "ClusterScores":
         """the scores of a labelling (`ClusterScores`) of this set's sketches `rows` (None: all; labels[i] belongs to
-        rows[i]) over their mash distances, computed strip by strip (dvs_sketches_cluster_scores); ZeroDivisionError
+        rows[i]) over their mash distances, computed strip by strip (dvs_cluster_scores); ZeroDivisionError
         as `distances`"""
         return DeviceSide(self, "mash").cluster_scores(labels, rows)
 
     def cophenet(self, Z, rows=None, matrix: bool = False) -> "CopheneticScores":
         """the cophenetic correlation (`CopheneticScores`) of the linkage matrix Z with the mash distances of this set's
-        sketches `rows` (None: all; leaf i of Z is rows[i]), computed strip by strip (dvs_sketches_cophenet);
+        sketches `rows` (None: all; leaf i of Z is rows[i]), computed strip by strip (dvs_cophenet);
         ZeroDivisionError as `cluster_scores`"""
         return DeviceSide(self, "mash").cophenet(Z, rows, matrix)
 
     def maxmin(self, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None) -> "MaxMin":
         """farthest-first selection (`MaxMin`) among this set's sketches by their mash distances, a row of distances
-        per pick (dvs_sketches_maxmin); ZeroDivisionError where a pair the traversal visits has two empty sketches"""
+        per pick (dvs_maxmin); ZeroDivisionError where a pair the traversal visits has two empty sketches"""
         return DeviceSide(self, "mash").maxmin(n_select, seeds=seeds, min_distance=min_distance)
 
     def within(self, other: "Sketches", radius, rows=None, other_rows=None, *, skip_self: bool = False,
                max_pairs: int | None = None) -> "Neighbours":
         """for each of this set's sketches `rows` the sketches of `other` at a mash distance <= radius (`Neighbours`:
-        the cells of `cross_distances`, compacted on the device; dvs_sketches_within); ZeroDivisionError as
+        the cells of `cross_distances`, compacted on the device; dvs_within); ZeroDivisionError as
         `cross_distances`"""
         check_radius(radius)
         return DeviceSide(self, "mash").within(DeviceSide(other, "mash"), radius, rows, other_rows, skip_self=skip_self,
@@ -295,7 +306,7 @@ class Sketches:
 
     def threshold_clusters(self, radius, rows=None) -> "ThresholdClusters":
         """the groups that "mash distance <= radius" makes of this set's sketches `rows` (`ThresholdClusters`;
-        dvs_sketches_threshold_clusters); ZeroDivisionError as `cluster_scores`"""
+        dvs_threshold_clusters); ZeroDivisionError as `cluster_scores`"""
         check_radius(radius)
         return DeviceSide(self, "mash").threshold_clusters(radius, rows)
 
@@ -305,29 +316,9 @@ class DeviceSide:
     together with the mode: every operation over "the distances of a collection", whatever the mode.  `device_side`
     makes one that owns its handle; DeviceSide(handle, mode) wraps a handle of the caller's, which close() then leaves
     alone.  Every method checks its arguments before it touches the handle; what the results hold is told where the
-    public functions of each operation are.  A new operation over distances is one row of ENTRIES and one method."""
+    public functions of each operation are.  A new operation over distances is one C entry and one method."""
 
-    MODE_NAMES = ("mash", "euclidean", "jsd")
-    # operation -> the C entry of each of MODE_NAMES.  Behind the context every entry takes its side or sides (a handle;
-    # or a handle, a row list and the number of rows; or two of those), then the mode's own arguments (k and the sketch
-    # size for mash, none for the count-matrix modes), then what the operation adds: `_entry` gives the first two in
-    # that order.  (mash's whole matrix is `Sketches.distances`, which also serves strided rows.)
-    ENTRIES = {
-        "distances": (None, "dvs_euclidean_distances", "dvs_jsd_distances"),
-        "linkage": ("dvs_sketches_linkage", "dvs_matrix_euclidean_linkage", "dvs_matrix_jsd_linkage"),
-        "nj": ("dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj"),
-        "cross_distances": ("dvs_sketches_cross_distances", "dvs_euclidean_cross_distances", "dvs_jsd_cross_distances"),
-        "nearest": ("dvs_sketches_nearest", "dvs_euclidean_nearest", "dvs_jsd_nearest"),
-        "cluster_scores": ("dvs_sketches_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_jsd_cluster_scores"),
-        "cophenet": ("dvs_sketches_cophenet", "dvs_euclidean_cophenet", "dvs_jsd_cophenet"),
-        "maxmin": ("dvs_sketches_maxmin", "dvs_matrix_euclidean_maxmin", "dvs_matrix_jsd_maxmin"),
-    }
-    # the same for the operations whose result is sparse: the pairs within a radius, and the groups they make
-    SPARSE_ENTRIES = {
-        "within": ("dvs_sketches_within", "dvs_euclidean_within", "dvs_jsd_within"),
-        "threshold_clusters": ("dvs_sketches_threshold_clusters", "dvs_euclidean_threshold_clusters",
-                               "dvs_jsd_threshold_clusters"),
-    }
+    MODE_NAMES = ("mash", "euclidean", "jsd")  # in the order of _lib.SRC_MASH, SRC_EUCLIDEAN, SRC_JSD
 
     def __init__(self, handle, mode: str, *, owns: bool = False):
         if mode not in self.MODE_NAMES:
@@ -354,11 +345,11 @@ class DeviceSide:
     def __exit__(self, *exc):
         self.close()
 
-    def _entry(self, op: str, *sides):
-        """(the name of the mode's entry for `op`, its arguments behind the context up to the operation's own)"""
-        mode_args = (self.handle.k, self.handle.sketch_size_u32) if self.mode == "mash" else ()
-        table = self.ENTRIES if op in self.ENTRIES else self.SPARSE_ENTRIES
-        return table[op][self.MODE_NAMES.index(self.mode)], (*sides, *mode_args)
+    def _source(self, listed=None) -> _lib.Source:
+        """this side as the C entries take it: the rows `listed` -- what `_row_list` made of a caller's list -- or all"""
+        rr, n = listed or (None, self.n)
+        mash = {"k": self.handle.k, "sketch_size": self.handle.sketch_size_u32} if self.mode == "mash" else {}
+        return make_source(self.MODE_NAMES.index(self.mode), self.handle._h, n, rr, **mash)
 
     def _against(self, other: "DeviceSide"):
         if other.mode != self.mode:
@@ -369,71 +360,57 @@ class DeviceSide:
 
     def distances(self) -> np.ndarray:
         """the symmetric n x n matrix of the distances, float64"""
-        if self.mode == "mash":
-            return self.handle.distances()
         dist = np.zeros((self.n, self.n), dtype=np.float64)
-        entry, front = self._entry("distances", self.handle._h)
-        self.ctx.check(getattr(self.ctx._L, entry)(self.ctx._h, *front, _lib.ptr(dist, C.c_double)))
+        self.ctx.check(self.ctx._L.dvs_distances(self.ctx._h, self._source(), _lib.ptr(dist, C.c_double)))
         return dist
 
     def linkage(self, method: str = "average") -> np.ndarray:
         """scipy's linkage matrix Z of `method` (LINKAGE_METHODS), the N x N matrix written and read in HBM"""
         code = linkage_method_code(method)
-        entry, front = self._entry("linkage", self.handle._h)
-        return run_linkage(self.ctx, self.n, entry, *front, code)
+        return run_linkage(self.ctx, self.n, self._source(), code)
 
     def nj(self) -> "NJTree":
         """the neighbour-joining tree, the N x N matrix left in HBM"""
-        entry, front = self._entry("nj", self.handle._h)
-        return run_nj(self.ctx, self.n, entry, *front)
+        return run_nj(self.ctx, self.n, self._source())
 
     def cross_distances(self, other: "DeviceSide", rows=None, other_rows=None) -> np.ndarray:
         """this side's `rows` (None: all) against `other`'s `other_rows`: float64 [M, N], the cells of `distances`"""
         self._against(other)
-        qr, nq = _row_list(rows, self.n)
-        rr, nr = _row_list(other_rows, other.n)
-        dist = np.zeros((nq, nr), dtype=np.float64)
-        entry, front = self._entry("cross_distances", self.handle._h, _lib.ptr(qr, C.c_uint32), nq, other.handle._h,
-                                   _lib.ptr(rr, C.c_uint32), nr)
-        self.ctx.check(getattr(self.ctx._L, entry)(self.ctx._h, *front, _lib.ptr(dist, C.c_double)))
+        q, r = _row_list(rows, self.n), _row_list(other_rows, other.n)
+        dist = np.zeros((q[1], r[1]), dtype=np.float64)
+        q, r = self._source(q), other._source(r)
+        self.ctx.check(self.ctx._L.dvs_cross_distances(self.ctx._h, q, r, _lib.ptr(dist, C.c_double)))
         return dist
 
     def nearest(self, other: "DeviceSide", n_nearest: int = 1, rows=None, other_rows=None):
         """the n_nearest rows of `other` nearest to each of this side's -> (int64 [M, n_nearest] positions into
         other_rows with -1 for an empty slot, float64 [M, n_nearest])"""
         self._against(other)
-        qr, nq = _row_list(rows, self.n)
-        rr, nr = _row_list(other_rows, other.n)
-        kk = check_n_nearest(n_nearest, nr)
-        idx = np.zeros((nq, kk), dtype=np.uint32)
-        dist = np.zeros((nq, kk), dtype=np.float64)
-        entry, front = self._entry("nearest", self.handle._h, _lib.ptr(qr, C.c_uint32), nq, other.handle._h,
-                                   _lib.ptr(rr, C.c_uint32), nr)
-        self.ctx.check(getattr(self.ctx._L, entry)(self.ctx._h, *front, kk, _lib.ptr(idx, C.c_uint32),
-                                                   _lib.ptr(dist, C.c_double)))
+        q, r = _row_list(rows, self.n), _row_list(other_rows, other.n)
+        kk = check_n_nearest(n_nearest, r[1])
+        idx = np.zeros((q[1], kk), dtype=np.uint32)
+        dist = np.zeros((q[1], kk), dtype=np.float64)
+        q, r = self._source(q), other._source(r)
+        self.ctx.check(self.ctx._L.dvs_nearest(self.ctx._h, q, r, kk, _lib.ptr(idx, C.c_uint32), _lib.ptr(dist, C.c_double)))
         out = idx.astype(np.int64)
         out[idx == _U32_MAX] = -1
         return out, dist
 
     def cluster_scores(self, labels, rows=None) -> "ClusterScores":
         """the scores of a labelling of this side's `rows` (None: all; labels[i] belongs to rows[i])"""
-        rr, n = _row_list(rows, self.n)
-        lab = check_labels(labels, n)
-        entry, front = self._entry("cluster_scores", self.handle._h, _lib.ptr(rr, C.c_uint32), n)
-        return _run_cluster_scores(self.ctx, entry, lab, *front)
+        listed = _row_list(rows, self.n)
+        return _run_cluster_scores(self.ctx, check_labels(labels, listed[1]), self._source(listed))
 
     def cophenet(self, Z, rows=None, matrix: bool = False) -> "CopheneticScores":
         """the cophenetic correlation of Z with the distances of this side's `rows` (None: all; leaf i is rows[i])"""
-        rr, n = _row_list(rows, self.n)
-        pairs, heights = check_linkage_matrix(Z, n)
-        entry, front = self._entry("cophenet", self.handle._h, _lib.ptr(rr, C.c_uint32), n)
-        return _run_cophenet(self.ctx, entry, n, pairs, heights, matrix, *front)
+        listed = _row_list(rows, self.n)
+        pairs, heights = check_linkage_matrix(Z, listed[1])
+        return _run_cophenet(self.ctx, listed[1], pairs, heights, matrix, self._source(listed))
 
     def maxmin(self, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None) -> "MaxMin":
         """farthest-first selection among this side's rows, a row of distances per pick"""
         args = check_maxmin_args(self.n, n_select, seeds, min_distance)
-        entry, front = self._entry("maxmin", self.handle._h)
-        return _run_maxmin(self.ctx, entry, self.n, *args, *front)
+        return _run_maxmin(self.ctx, self.n, *args, self._source())
 
     def within(self, other: "DeviceSide", radius, rows=None, other_rows=None, *, skip_self: bool = False,
                max_pairs: int | None = None) -> "Neighbours":
@@ -443,18 +420,14 @@ class DeviceSide:
         radius = check_radius(radius)
         limit = check_max_pairs(max_pairs)
         self._against(other)
-        qr, nq = _row_list(rows, self.n)
-        rr, nr = _row_list(other_rows, other.n)
-        entry, front = self._entry("within", self.handle._h, _lib.ptr(qr, C.c_uint32), nq, other.handle._h,
-                                   _lib.ptr(rr, C.c_uint32), nr)
-        return _run_within(self.ctx, entry, *front, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
+        q, r = _row_list(rows, self.n), _row_list(other_rows, other.n)
+        return _run_within(self.ctx, self._source(q), other._source(r), radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
 
     def threshold_clusters(self, radius, rows=None) -> "ThresholdClusters":
         """the groups that "distance <= radius" makes of this side's `rows` (None: all): connected components"""
         radius = check_radius(radius)
-        rr, n = _row_list(rows, self.n)
-        entry, front = self._entry("threshold_clusters", self.handle._h, _lib.ptr(rr, C.c_uint32), n)
-        return _run_threshold_clusters(self.ctx, entry, n, *front, radius)
+        listed = _row_list(rows, self.n)
+        return _run_threshold_clusters(self.ctx, listed[1], self._source(listed), radius)
 
 
 CANONICAL_MASH = "Canonical count rows should only be specified for the jsd and euclidean distances (mash: mash_canonical)."
@@ -558,12 +531,12 @@ class NJTree(NamedTuple):
 
 
 def nj_outputs(n: int):
-    """host buffers of the dvs_*nj calls for n leaves: joins uint32 [3 (n - 2)], lengths f64 [3 (n - 2)]"""
+    """host buffers of a dvs_nj call for n leaves: joins uint32 [3 (n - 2)], lengths f64 [3 (n - 2)]"""
     return np.zeros(3 * (n - 2), dtype=np.uint32), np.zeros(3 * (n - 2), dtype=np.float64)
 
 
 def nj_tree_of(joins: np.ndarray, lengths: np.ndarray) -> NJTree:
-    """the outputs of a dvs_*nj call -> NJTree"""
+    """the outputs of a dvs_nj call -> NJTree"""
     children = joins.reshape(-1, 3).astype(np.int64)
     children[children == _U32_MAX] = -1
     return NJTree(children, lengths.reshape(-1, 3).copy())
@@ -585,14 +558,13 @@ def nj_inputs(tree) -> tuple[int, np.ndarray, np.ndarray]:
     return n, np.ascontiguousarray(c, dtype=np.uint32).reshape(-1), np.ascontiguousarray(lengths).reshape(-1)
 
 
-def run_nj(ctx: engine.Context | None, n: int, entry: str, *args) -> NJTree:
-    """the dvs_*nj call `entry`(ctx, *args, joins, lengths) for n leaves -> NJTree; ValueError before any device work
-    when n < 3"""
+def run_nj(ctx: engine.Context | None, n: int, src: _lib.Source) -> NJTree:
+    """dvs_nj over `src` for n leaves -> NJTree; ValueError before any device work when n < 3"""
     if n < 3:
         raise ValueError("need at least three sequences for a neighbour-joining tree")
     ctx = ctx or engine.default_context()
     joins, lengths = nj_outputs(n)
-    ctx.check(getattr(ctx._L, entry)(ctx._h, *args, _lib.ptr(joins, C.c_uint32), _lib.ptr(lengths, C.c_double)))
+    ctx.check(ctx._L.dvs_nj(ctx._h, src, _lib.ptr(joins, C.c_uint32), _lib.ptr(lengths, C.c_double)))
     return nj_tree_of(joins, lengths)
 
 
@@ -643,7 +615,7 @@ N_NEAREST_MAX = 64  # include/dvs_hip.h: a caller who wants a full ranking takes
 
 
 def check_n_nearest(n_nearest, n_refs: int) -> int:
-    """n_nearest as the dvs_*_nearest entries take it, checked before any device work: ValueError unless it is an
+    """n_nearest as dvs_nearest takes it, checked before any device work: ValueError unless it is an
     integer in 1 .. n_refs, NotImplementedError beyond N_NEAREST_MAX"""
     if isinstance(n_nearest, bool) or not isinstance(n_nearest, (int, np.integer)):
         raise ValueError(f"n_nearest must be an integer, not {n_nearest!r}")
@@ -797,7 +769,7 @@ class ClusterScores(NamedTuple):
 
 
 def check_labels(labels, n: int) -> np.ndarray:
-    """a labelling of n rows as the dvs_*cluster_scores entries take it (uint32 [n]), checked before any device work:
+    """a labelling of n rows as dvs_cluster_scores takes it (uint32 [n]), checked before any device work:
     ValueError unless it is a one-dimensional sequence of n integers in 0 .. 2^32 - 2"""
     a = np.asarray(labels)
     if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
@@ -809,18 +781,18 @@ def check_labels(labels, n: int) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
-def _run_cluster_scores(ctx, entry: str, lab: np.ndarray, *front) -> ClusterScores:
-    """the dvs_*cluster_scores call `entry`(ctx, *front, labels, n_clusters, outputs...) -> ClusterScores; the means
-    per cluster and overall from the n silhouettes here"""
+def _run_cluster_scores(ctx, lab: np.ndarray, src: _lib.Source | None) -> ClusterScores:
+    """dvs_cluster_scores over `src` (not looked at for an empty labelling) -> ClusterScores; the means per cluster and
+    overall from the n silhouettes here"""
     n = lab.size
     k = int(lab.max()) + 1 if n else 0
     within, a, b, sil = (np.zeros(n, dtype=np.float64) for _ in range(4))
     nb = np.zeros(n, dtype=np.uint32)
     med = np.zeros(k, dtype=np.uint32)
     if n:
-        ctx.check(getattr(ctx._L, entry)(ctx._h, *front, _lib.ptr(lab, C.c_uint32), k, _lib.ptr(within, C.c_double),
-                                         _lib.ptr(a, C.c_double), _lib.ptr(b, C.c_double), _lib.ptr(nb, C.c_uint32),
-                                         _lib.ptr(sil, C.c_double), _lib.ptr(med, C.c_uint32)))
+        ctx.check(ctx._L.dvs_cluster_scores(ctx._h, src, _lib.ptr(lab, C.c_uint32), k, _lib.ptr(within, C.c_double),
+                                            _lib.ptr(a, C.c_double), _lib.ptr(b, C.c_double), _lib.ptr(nb, C.c_uint32),
+                                            _lib.ptr(sil, C.c_double), _lib.ptr(med, C.c_uint32)))
     neighbour, medoids = nb.astype(np.int64), med.astype(np.int64)
     neighbour[nb == _U32_MAX] = -1
     medoids[med == _U32_MAX] = -1
@@ -849,7 +821,7 @@ def cluster_scores(seqs, labels, distance_mode: str = "mash", *, k: int, sketch_
     seqs = list(seqs)
     lab = check_labels(labels, len(seqs))
     if not seqs:
-        return _run_cluster_scores(ctx, "", lab)
+        return _run_cluster_scores(ctx, lab, None)
     with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
                      canonical=canonical) as dev:
         return dev.cluster_scores(lab)
@@ -871,7 +843,7 @@ class CopheneticScores(NamedTuple):
 
 
 def check_linkage_matrix(Z, n: int | None = None):
-    """a linkage matrix in scipy's layout as the dvs_*cophenet entries take it, checked before any device work ->
+    """a linkage matrix in scipy's layout as dvs_cophenet takes it, checked before any device work ->
     (pairs uint32 [2 (n - 1)], heights float64 [n - 1]); ValueError unless its shape is (n - 1, 4) for n >= 2 leaves (n:
     the number of rows it must describe, None: taken from Z) and its first two columns are cluster ids.  (Which ids may
     meet in which merge is the C entry's check.)"""
@@ -887,13 +859,13 @@ def check_linkage_matrix(Z, n: int | None = None):
     return np.ascontiguousarray(kids, dtype=np.uint32).reshape(-1), np.ascontiguousarray(z[:, 2])
 
 
-def _run_cophenet(ctx, entry: str, n: int, pairs, heights, matrix: bool, *front) -> CopheneticScores:
-    """the dvs_*cophenet call `entry`(ctx, *front, pairs, heights, outputs...) -> CopheneticScores"""
+def _run_cophenet(ctx, n: int, pairs, heights, matrix: bool, src: _lib.Source) -> CopheneticScores:
+    """dvs_cophenet over the n rows of `src` -> CopheneticScores"""
     corr = C.c_double(float("nan"))
     sums = np.zeros((5, n), dtype=np.float64)
     coph = np.zeros((n, n), dtype=np.float64) if matrix else None
-    ctx.check(getattr(ctx._L, entry)(ctx._h, *front, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
-                                     C.byref(corr), _lib.ptr(sums, C.c_double), _lib.ptr(coph, C.c_double)))
+    ctx.check(ctx._L.dvs_cophenet(ctx._h, src, _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                  C.byref(corr), _lib.ptr(sums, C.c_double), _lib.ptr(coph, C.c_double)))
     return CopheneticScores(float(corr.value), sums, coph)
 
 
@@ -936,7 +908,7 @@ class MaxMin(NamedTuple):
 
 
 def check_maxmin_args(n: int, n_select, seeds, min_distance):
-    """the arguments of a farthest-first selection over n items as the dvs_*maxmin entries take them, checked before
+    """the arguments of a farthest-first selection over n items as dvs_maxmin takes them, checked before
     any device work -> (n_select, seeds uint32, use_min_distance, min_distance).  n_select None: n.  ValueError unless
     at least one of n_select and min_distance is given, the seeds are one or more distinct rows, n_seeds <= n_select <=
     n and min_distance is not NaN."""
@@ -963,18 +935,17 @@ def check_maxmin_args(n: int, n_select, seeds, min_distance):
     return int(n_select), np.ascontiguousarray(sd, dtype=np.uint32), int(min_distance is not None), md
 
 
-def _run_maxmin(ctx, entry: str, n: int, n_select: int, seeds: np.ndarray, use_min: int, min_distance: float, *front) -> MaxMin:
-    """the dvs_*maxmin call `entry`(ctx, *front, n, seeds, ..., outputs) -> MaxMin"""
+def _run_maxmin(ctx, n: int, n_select: int, seeds: np.ndarray, use_min: int, min_distance: float, src: _lib.Source) -> MaxMin:
+    """dvs_maxmin over rows 0 .. n - 1 of `src` -> MaxMin"""
     ctx = ctx or engine.default_context()
     picks = np.zeros(n_select, dtype=np.uint32)
     radius = np.zeros(n_select, dtype=np.float64)
     owner = np.zeros(n, dtype=np.uint32)
     dist = np.zeros(n, dtype=np.float64)
     count, cover = C.c_uint32(0), C.c_double(0.0)
-    ctx.check(getattr(ctx._L, entry)(ctx._h, *front, n, _lib.ptr(seeds, C.c_uint32), seeds.size, n_select, use_min,
-                                     min_distance, _lib.ptr(picks, C.c_uint32), _lib.ptr(radius, C.c_double),
-                                     C.byref(count), _lib.ptr(owner, C.c_uint32), _lib.ptr(dist, C.c_double),
-                                     C.byref(cover)))
+    ctx.check(ctx._L.dvs_maxmin(ctx._h, src, _lib.ptr(seeds, C.c_uint32), seeds.size, n_select, use_min, min_distance,
+                                _lib.ptr(picks, C.c_uint32), _lib.ptr(radius, C.c_double), C.byref(count),
+                                _lib.ptr(owner, C.c_uint32), _lib.ptr(dist, C.c_double), C.byref(cover)))
     own = owner.astype(np.int64)
     own[owner == _U32_MAX] = -1
     m = int(count.value)
@@ -1066,7 +1037,7 @@ class ThresholdClusters(NamedTuple):
 
 
 def check_radius(radius) -> float:
-    """a radius as the dvs_*within and dvs_*threshold_clusters entries take it, checked before any handle is touched:
+    """a radius as dvs_within and dvs_threshold_clusters take it, checked before any handle is touched:
     ValueError unless it is a real number that is not NaN (inclusive; negative: nothing lies within it; inf: all does)"""
     if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
         raise ValueError(f"radius must be a real number, not {radius!r}")
@@ -1077,7 +1048,7 @@ def check_radius(radius) -> float:
 
 
 def check_max_pairs(max_pairs) -> int:
-    """max_pairs as the dvs_*within entries take it (0: no limit): ValueError unless None or an integer of 1 or more"""
+    """max_pairs as dvs_within takes it (0: no limit): ValueError unless None or an integer of 1 or more"""
     if max_pairs is None:
         return 0
     if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or max_pairs < 1 or max_pairs >= 1 << 64:
@@ -1089,12 +1060,13 @@ def _no_neighbours(m: int) -> Neighbours:
     return Neighbours(np.zeros(m + 1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64))
 
 
-def _run_within(ctx, entry: str, *args) -> Neighbours:
-    """the dvs_*within call `entry`(ctx, *args, the dvs_pairs) -> Neighbours; the dvs_pairs is copied out and freed"""
+def _run_within(ctx, q: _lib.Source, r: _lib.Source | None, radius: float, flags: int, max_pairs: int) -> Neighbours:
+    """dvs_within of `q` against `r` (None: a caller's matrix against itself) -> Neighbours; the dvs_pairs is copied out
+    and freed"""
     ctx = ctx or engine.default_context()
     L = ctx._L
     h = C.c_void_p()
-    ctx.check(getattr(L, entry)(ctx._h, *args, C.byref(h)))
+    ctx.check(L.dvs_within(ctx._h, q, r, radius, flags, max_pairs, C.byref(h)))
     try:
         rows, pairs = C.c_uint32(), C.c_uint64()
         _lib.raise_for(L.dvs_pairs_info(h, C.byref(rows), C.byref(pairs)), None)
@@ -1108,13 +1080,13 @@ def _run_within(ctx, entry: str, *args) -> Neighbours:
     return Neighbours(row_start.astype(np.int64), col.astype(np.int64), dist)
 
 
-def _run_threshold_clusters(ctx, entry: str, n: int, *args) -> ThresholdClusters:
-    """the dvs_*threshold_clusters call `entry`(ctx, *args, labels, n_clusters) over n rows -> ThresholdClusters"""
+def _run_threshold_clusters(ctx, n: int, src: _lib.Source | None, radius: float) -> ThresholdClusters:
+    """dvs_threshold_clusters over the n rows of `src` (not looked at for n == 0) -> ThresholdClusters"""
     labels = np.zeros(n, dtype=np.uint32)
     count = C.c_uint32(0)
     if n:
         ctx = ctx or engine.default_context()
-        ctx.check(getattr(ctx._L, entry)(ctx._h, *args, _lib.ptr(labels, C.c_uint32), C.byref(count)))
+        ctx.check(ctx._L.dvs_threshold_clusters(ctx._h, src, radius, _lib.ptr(labels, C.c_uint32), C.byref(count)))
     k = int(count.value)
     return ThresholdClusters(labels.astype(np.int64), k, np.bincount(labels, minlength=k).astype(np.int64))
 
@@ -1181,7 +1153,7 @@ def threshold_clusters(seqs, radius, distance_mode: str = "mash", *, k: int, ske
     check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
     seqs = list(seqs)
     if not seqs:
-        return _run_threshold_clusters(ctx, "", 0)
+        return _run_threshold_clusters(ctx, 0, None, radius)
     with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
                      canonical=canonical) as dev:
         return dev.threshold_clusters(radius)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DVS_ABI_VERSION 3
+#define DVS_ABI_VERSION 4
 
 #define DVS_OK 0
 #define DVS_ERR_VALUE 1       /* the reference would panic -> python ValueError */
@@ -393,97 +393,98 @@ int dvs_sketches_copy_to_device(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t *
 int dvs_sketches_distances_device(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
                                   uint32_t row_start, uint32_t row_stride, int symmetric, double *d_dist,
                                   uint32_t *d_zerodiv);
-/* euclidean_distances (diverse_seq/distance.py:294-336): ||f_i - f_j||_2 over
- * the rows of m, full symmetric nrows x nrows matrix */
-int dvs_euclidean_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist);
 
-/* ---- average-linkage tree (the tree stage of ctree) ----------------------------- *
- * dvs_average_linkage replaces the clustering of make_cluster_tree (diverse_seq/cluster.py:216-230:
- * sklearn AgglomerativeClustering(metric="precomputed", linkage="average"), i.e. scipy's
- * linkage(X[triu_indices(n, 1)], "average") and its nearest-neighbour chain): the n - 1 merges of scipy's
- * linkage matrix Z bit for bit, row j = (pairs[2 j], pairs[2 j + 1], heights[j], sizes[j]), cluster ids
- * n, n + 1, ... in merge order.  `dist` is n x n, row-major float64; only D[i][j] with i < j counts (the
- * diagonal and the lower triangle are checked, not used).  A HOST matrix (dist_on_device == 0) is uploaded
- * into the context's scratch and left as it is; a DEVICE matrix (dist_on_device != 0) must live on the
- * context's device and is the working buffer: it is OVERWRITTEN.  Returns when the host outputs are written.
- * DVS_ERR_VALUE: n < 2, a NaN or +-inf entry anywhere (sklearn's check_array), a device matrix on another
- * device; DVS_ERR_NOMEM: the matrix does not fit in HBM. */
-int dvs_average_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *pairs,
-                        double *heights, uint32_t *sizes);
-/* ctree end to end with the N x N matrix left in HBM (it never crosses PCIe): the mash distances of
- * dvs_sketches_distances over every pair (DVS_ERR_ZERODIV as there when two sketches are empty), or the
- * euclidean distances of dvs_euclidean_distances over the rows of m (a row without valid k-mers gives NaN
- * distances, hence DVS_ERR_VALUE, as sklearn raises on that matrix), into the context's scratch; then the
- * tree above, same outputs. */
-int dvs_sketches_average_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size,
-                                 uint32_t *pairs, double *heights, uint32_t *sizes);
-int dvs_matrix_euclidean_average_linkage(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *pairs, double *heights,
-                                         uint32_t *sizes);
+/* ---- where an operation's distances come from ------------------------------------------------------ *
+ * Every operation below over "the distances of a collection" has ONE entry, which takes a dvs_source: the mode and
+ * what the mode keeps in HBM, or a caller's own matrix.  A source is a plain value the caller fills per call; the
+ * library keeps no pointer to it (or to `rows`) once the call has returned.
+ *   DVS_SRC_MASH       handle: a dvs_sketches; k and sketch_size as dvs_sketches_distances takes them
+ *   DVS_SRC_EUCLIDEAN  handle: a dvs_matrix (count rows of either width, or frequency rows)
+ *   DVS_SRC_JSD        handle: a dvs_matrix likewise
+ *   DVS_SRC_GIVEN      handle: the caller's n x n matrix, row-major float64; a HOST array, or with on_device != 0
+ *                      DEVICE memory on the context's device.  Only read, except by the two trees (dvs_linkage, dvs_nj),
+ *                      whose working buffer a device matrix is: they OVERWRITE it
+ * rows (host, optional; NULL: rows 0 .. n - 1 of the handle) and n say which rows of the handle take part, in which
+ * order; position i of a result is rows[i].
+ * Every entry checks its source or sources before anything else, DVS_ERR_VALUE for each of: a NULL source or handle
+ * (a GIVEN matrix of order 0 may be NULL); an unknown kind; a row list with DVS_SRC_GIVEN; two sides of different
+ * kinds; two MASH sides whose k or sketch_size differ.  A combination an operation does not serve is
+ * DVS_ERR_UNSUPPORTED with a message that names the operation and the kind; each operation lists its own below. */
+enum { DVS_SRC_MASH = 0, DVS_SRC_EUCLIDEAN = 1, DVS_SRC_JSD = 2, DVS_SRC_GIVEN = 3 };
+typedef struct dvs_source {
+    uint32_t kind;           /* DVS_SRC_* */
+    void *handle;            /* dvs_sketches* | dvs_matrix* | the n x n float64 matrix */
+    const uint32_t *rows;    /* optional host row list; NULL for DVS_SRC_GIVEN */
+    uint32_t n;              /* rows taken (GIVEN: the matrix's order) */
+    uint32_t k, sketch_size; /* MASH only */
+    int on_device;           /* GIVEN only */
+} dvs_source;
+/* The whole symmetric n x n matrix of a source into the host array dist.  MASH: exactly
+ * dvs_sketches_distances(sk, k, sketch_size, 0, 1, 1, dist) (mash_distances, diverse_seq/distance.py:119-175).
+ * EUCLIDEAN: ||f_i - f_j||_2 over the rows of the matrix (euclidean_distances, diverse_seq/distance.py:294-336).  JSD:
+ * "pairwise Jensen-Shannon divergence" below.  n == 0 writes nothing, n == 1 a zero.  DVS_ERR_UNSUPPORTED: a GIVEN
+ * source (the matrix is the caller's already); a row list, or n other than the handle's rows; (EUCLIDEAN, JSD) more
+ * than 524 280 rows, the row limit of the square entries.  DVS_ERR_ZERODIV: (MASH) as dvs_sketches_distances. */
+int dvs_distances(dvs_ctx *ctx, const dvs_source *src, double *dist);
 
-/* ---- linkage trees of the other methods ------------------------------------------------------- *
- * dvs_linkage is scipy.cluster.hierarchy.linkage(X[triu_indices(n, 1)], method) on the device: the same
- * linkage matrix bit for bit, the same outputs and the same host / device matrix handling as
- * dvs_average_linkage above.  `method` is scipy's _LINKAGE_METHODS code:
+/* ---- linkage trees (the tree stage of ctree) ----------------------------------------------------- *
+ * dvs_linkage is scipy.cluster.hierarchy.linkage(X[triu_indices(n, 1)], method) on the device over the n x n distances
+ * of a source; with DVS_LINKAGE_AVERAGE it replaces the clustering of make_cluster_tree (diverse_seq/cluster.py:216-230:
+ * sklearn AgglomerativeClustering(metric="precomputed", linkage="average")).  The n - 1 merges of scipy's linkage
+ * matrix Z bit for bit, row j = (pairs[2 j], pairs[2 j + 1], heights[j], sizes[j]), cluster ids n, n + 1, ... in merge
+ * order.  Only D[i][j] with i < j counts (the diagonal and the lower triangle are checked, not used).  Returns when
+ * the host outputs are written.  `method` is scipy's _LINKAGE_METHODS code:
  *   DVS_LINKAGE_SINGLE    restates scipy's _hierarchy.mst_single_linkage (Prim's minimum spanning tree)
  *   DVS_LINKAGE_COMPLETE, DVS_LINKAGE_AVERAGE, DVS_LINKAGE_WEIGHTED, DVS_LINKAGE_WARD
  *                         restate scipy's _hierarchy.nn_chain (nearest-neighbour chain) with the updates
  *                         of _hierarchy_distance_update.pxi
- * and both end in scipy's stable sort by height and `label` relabelling.  DVS_ERR_UNSUPPORTED: 3 (centroid)
- * and 4 (median), which scipy builds by _hierarchy.fast_linkage (not built here); DVS_ERR_VALUE: any other
- * code, the errors of dvs_average_linkage, and, for ward, a negative entry above the diagonal (scipy's
- * heights would be NaN).  dvs_linkage(..., DVS_LINKAGE_AVERAGE, ...) is dvs_average_linkage. */
+ * and both end in scipy's stable sort by height and `label` relabelling.
+ * The sources: MASH, EUCLIDEAN and JSD are ctree end to end with the N x N matrix left in HBM (it never crosses PCIe):
+ * the cells of dvs_distances for the source, written into the context's scratch, then the tree.  A GIVEN host matrix is
+ * uploaded into the context's scratch and left as it is; a GIVEN device matrix is the working buffer and is
+ * OVERWRITTEN.
+ *   DVS_ERR_UNSUPPORTED: 3 (centroid) and 4 (median), which scipy builds by _hierarchy.fast_linkage (not built here); a
+ *                  row list, or n other than the handle's rows
+ *   DVS_ERR_VALUE: any other method code; n < 2; a NaN or +-inf entry anywhere (sklearn's check_array; a row without
+ *                  valid k-mers gives NaN euclidean and jsd distances); for ward, a negative entry above the diagonal
+ *                  (scipy's heights would be NaN); a device matrix on another device
+ *   DVS_ERR_ZERODIV: (MASH) as dvs_sketches_distances, when two sketches are empty
+ *   DVS_ERR_NOMEM: the matrix does not fit in HBM
+ * The checks come in one order for every source: the method, n < 2, the source's own, the device, the fit in HBM. */
 #define DVS_LINKAGE_SINGLE 0
 #define DVS_LINKAGE_COMPLETE 1
 #define DVS_LINKAGE_AVERAGE 2
 #define DVS_LINKAGE_WARD 5
 #define DVS_LINKAGE_WEIGHTED 6
-int dvs_linkage(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
-                double *heights, uint32_t *sizes);
-/* the fused ctree entries above for any of those methods: the N x N mash / euclidean matrix stays in HBM */
-int dvs_sketches_linkage(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, int method,
-                         uint32_t *pairs, double *heights, uint32_t *sizes);
-int dvs_matrix_euclidean_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
-                                 uint32_t *sizes);
+int dvs_linkage(dvs_ctx *ctx, const dvs_source *src, int method, uint32_t *pairs, double *heights, uint32_t *sizes);
 
-/* ---- pairwise Jensen-Shannon divergence --------------------------------------------------------- *
- * D[i][j] = H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2 over the rows of m, f = counts / total, H in bits: the
+/* ---- pairwise Jensen-Shannon divergence: the cells of a DVS_SRC_JSD source ------------------------ *
+ * D[i][j] = H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2 over the rows of the matrix, f = counts / total, H in bits: the
  * total_jsd of the two-member set SummedRecords::new([i, j]) (src/records.rs:27-68), the measure of paper/paper.md
  * Table 1 (identical sequences 0.0, no k-mer in common 1.0); the divergence, not its square root.  Full symmetric
  * nrows x nrows float64 matrix, every cell in [0, 1], exactly 0 on the diagonal and between rows of equal
- * counts; a row without a valid k-mer has NaN off the diagonal.  Arguments, limits and errors as
- * dvs_euclidean_distances. */
-int dvs_jsd_distances(dvs_ctx *ctx, const dvs_matrix *m, double *dist);
-/* the fused ctree entry over those distances (src/records.rs:27-68 for the cells, then dvs_linkage's tree): the
- * N x N matrix, the same bits as dvs_jsd_distances writes, stays in HBM; arguments and errors as
- * dvs_matrix_euclidean_linkage (a row without a valid k-mer: NaN distances, DVS_ERR_VALUE) */
-int dvs_matrix_jsd_linkage(dvs_ctx *ctx, const dvs_matrix *m, int method, uint32_t *pairs, double *heights,
-                           uint32_t *sizes);
+ * counts; a row without a valid k-mer has NaN off the diagonal.  This is what a DVS_SRC_JSD source means to every
+ * operation: dvs_distances writes this matrix, dvs_linkage and dvs_nj build their trees over the same bits left in HBM. */
 
 /* ---- distances between two collections, and the k nearest references ------------------------------ *
  * The rectangular counterpart of the N x N entries above: cell (i, j) of an nq x nr float64 matrix is the distance
- * between query row q_rows[i] of q and reference row r_rows[j] of r (a NULL list: rows 0 .. n - 1 of its handle).
+ * between row q->rows[i] of source q and row r->rows[j] of source r (a NULL list: rows 0 .. n - 1 of its handle).
  * (No counterpart in the reference: its distance functions fill the square matrix of one collection,
  * diverse_seq/distance.py:119-175, 294-336.)  The two handles may be one and the same, so "every row against the
- * selected rows of the same matrix" copies nothing; for the jsd and euclidean entries they may differ in element
+ * selected rows of the same matrix" copies nothing; for the JSD and EUCLIDEAN kinds they may differ in element
  * type (16-bit counts, 32-bit counts, frequency rows, in any combination) but not in nbins.  A cell is the same bits
- * as the cell the square entry of its mode writes for the same two rows (dvs_jsd_distances: in [0, 1], exactly 0
+ * as the cell dvs_distances writes for the same two rows of a source of that kind (JSD: in [0, 1], exactly 0
  * between rows of equal counts, NaN where either row has no valid k-mer -- a rectangular matrix has no diagonal, so
- * also for such a row against itself; dvs_euclidean_distances; dvs_sketches_distances with its k and sketch_size).
+ * also for such a row against itself; MASH: with the sources' k and sketch_size).
  * The matrix is computed in strips of query rows whose device buffer is bounded (256 MiB, one tile row of 32 queries
  * at least; DVS_CROSS_STRIP_ROWS overrides the strip height), so nq is not limited by a grid dimension; dist is the
  * host array, nq x nr row-major.  Return when the host outputs are written.
  *   DVS_OK with nothing written: nq == 0 or nr == 0
  *   DVS_ERR_VALUE: a row index beyond its handle (or, with a NULL list, nq / nr beyond its rows), handles of
  *                  different contexts or devices, unequal nbins
- *   DVS_ERR_UNSUPPORTED: nr beyond the row limit of the square entries
- *   DVS_ERR_ZERODIV: (sketches) k == 0, or a visited pair has two empty sketches */
-int dvs_jsd_cross_distances(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                            const uint32_t *r_rows, uint32_t nr, double *dist);
-int dvs_euclidean_cross_distances(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq,
-                                  const dvs_matrix *r, const uint32_t *r_rows, uint32_t nr, double *dist);
-int dvs_sketches_cross_distances(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq,
-                                 const dvs_sketches *r, const uint32_t *r_rows, uint32_t nr, uint32_t k,
-                                 uint32_t sketch_size, double *dist);
+ *   DVS_ERR_UNSUPPORTED: nr beyond the row limit of the square entries; GIVEN sources (the matrix is the caller's)
+ *   DVS_ERR_ZERODIV: (MASH) k == 0, or a visited pair has two empty sketches */
+int dvs_cross_distances(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, double *dist);
 /* The kk nearest references of every query over those cells, the matrix never leaving the device: idx and dist are
  * host arrays nq x kk; row i lists the kk smallest cells of matrix row i in ascending order of (distance, position
  * in the reference list 0 .. nr - 1 -- not the matrix row): a tie goes to the lower position, so the result is unique
@@ -491,13 +492,7 @@ int dvs_sketches_cross_distances(dvs_ctx *ctx, const dvs_sketches *q, const uint
  * cells ends in slots of position 0xFFFFFFFF and distance NaN.  (No counterpart in the reference.)  Errors as above, and
  *   DVS_ERR_VALUE: kk == 0 or kk > nr (hence always for nr == 0)
  *   DVS_ERR_UNSUPPORTED: kk > 64 (a full ranking takes the matrix) */
-int dvs_jsd_nearest(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                    const uint32_t *r_rows, uint32_t nr, uint32_t kk, uint32_t *idx, double *dist);
-int dvs_euclidean_nearest(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                          const uint32_t *r_rows, uint32_t nr, uint32_t kk, uint32_t *idx, double *dist);
-int dvs_sketches_nearest(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq, const dvs_sketches *r,
-                         const uint32_t *r_rows, uint32_t nr, uint32_t k, uint32_t sketch_size, uint32_t kk,
-                         uint32_t *idx, double *dist);
+int dvs_nearest(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, uint32_t kk, uint32_t *idx, double *dist);
 
 /* ---- flat clusters of a tree: the cut, and the scores of a labelling ------------------------------- *
  * dvs_linkage_cut turns dvs_linkage's outputs (pairs[2 (n - 1)], heights[n - 1], as they are) into flat clusters on
@@ -516,9 +511,9 @@ int dvs_sketches_nearest(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_
 #define DVS_CUT_NCLUSTERS 1
 int dvs_linkage_cut(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, int criterion, double value,
                     uint32_t *labels_out, uint32_t *n_clusters_out);
-/* The scores of a labelling of n rows over the n x n distances D of a mode, computed strip by strip as the cross
- * entries above compute them (queries = references = `rows` of the handle, NULL: rows 0 .. n - 1; the same cells bit
- * for bit), the matrix never existing whole.  labels[n] in [0, n_clusters); a label nobody carries is an empty cluster
+/* The scores of a labelling of the n rows of a source over their n x n distances D, computed strip by strip as the
+ * cross entries above compute them (queries = references = the source; the same cells bit for bit), the matrix never
+ * existing whole.  labels[n] in [0, n_clusters); a label nobody carries is an empty cluster
  * and is skipped.  With n_c the size of cluster c, for every row i of cluster l:
  *   within[i]      sum of D(i, j) over the other members j of l.  Cell (i, i) is never read into a sum, whatever it holds
  *   a[i]           within[i] / (n_l - 1); 0 when i is alone in l
@@ -530,32 +525,21 @@ int dvs_linkage_cut(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const doubl
  * The order in which the terms of a sum are added depends on (n, labels) alone: the same bits on every run and for
  * every strip height (DVS_CROSS_STRIP_ROWS).  All outputs are host arrays ([n]; medoids [n_clusters]); any may be NULL
  * except within.  Return when they are written.  (No counterpart in the reference.)
- * dvs_cluster_scores takes the caller's own n x n matrix (row-major float64; host, or device memory on the context's
- * device when dist_on_device != 0) and only reads it, rows [q0, q0 + mq) at a time.
+ * A GIVEN matrix is only read, rows [q0, q0 + mq) at a time.
  *   DVS_OK with nothing written: n == 0
  *   DVS_ERR_VALUE: a label >= n_clusters (hence n_clusters == 0 with n > 0), a row index beyond the handle, a device
  *                  mismatch, a matrix that is not device memory where it is said to be
  *   DVS_ERR_UNSUPPORTED: n beyond the row limit of the square entries
- *   DVS_ERR_ZERODIV: (sketches) as dvs_sketches_cross_distances over the same rows on both sides: the strips hold every
+ *   DVS_ERR_ZERODIV: (MASH) as dvs_cross_distances over the same rows on both sides: the strips hold every
  *                  cell, a row against itself included, so one empty sketch among the rows is enough */
-int dvs_jsd_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *labels,
-                           uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour,
-                           double *silhouette, uint32_t *medoids);
-int dvs_euclidean_cluster_scores(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n,
-                                 const uint32_t *labels, uint32_t n_clusters, double *within, double *a, double *b,
-                                 uint32_t *neighbour, double *silhouette, uint32_t *medoids);
-int dvs_sketches_cluster_scores(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
-                                uint32_t sketch_size, const uint32_t *labels, uint32_t n_clusters, double *within,
-                                double *a, double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids);
-int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *labels,
-                       uint32_t n_clusters, double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
-                       uint32_t *medoids);
+int dvs_cluster_scores(dvs_ctx *ctx, const dvs_source *src, const uint32_t *labels, uint32_t n_clusters, double *within,
+                       double *a, double *b, uint32_t *neighbour, double *silhouette, uint32_t *medoids);
 
 /* ---- neighbours within a radius, and threshold clusters ------------------------------------------- *
  * The sparse product of the cross entries above: for every query, the references whose cell is <= radius, the nq x nr
  * matrix never existing whole and never leaving the device -- only the listed pairs come back.  (No counterpart in
- * the reference.)  A cell is the bits of its mode's square entry for the same two rows, computed strip by strip as
- * dvs_*_cross_distances computes it (same handles, row lists, strip bound and DVS_CROSS_STRIP_ROWS).  The result is a
+ * the reference.)  A cell is the bits dvs_distances gives the same two rows, computed strip by strip as
+ * dvs_cross_distances computes it (same sources, strip bound and DVS_CROSS_STRIP_ROWS).  The result is a
  * dvs_pairs: a CSR list on the host, row_start[nq + 1] (row_start[0] == 0, row_start[nq] == the number of pairs) and,
  * for query i, col / dist [row_start[i], row_start[i + 1]): col is the position in the reference list 0 .. nr - 1 --
  * not the matrix row --, dist that cell.  Within a query the entries are in ascending position.  radius is inclusive
@@ -565,55 +549,39 @@ int dvs_cluster_scores(dvs_ctx *ctx, const double *dist, int dist_on_device, uin
  * never read -- for a call whose two sides list the same positions (i against position i of the reference list).
  * max_pairs (0: no limit): as soon as the pairs of the strips so far exceed it the call stops and fails; the context
  * stays usable.  A dvs_pairs lives on the host and holds no reference to the context: it may outlive it, and is freed
- * by dvs_pairs_destroy (NULL is fine).  dvs_within takes the caller's own n x n matrix as dvs_cluster_scores does and
- * only reads it.  *out is NULL after an error.  Errors of the arguments, all before any device work:
- *   DVS_OK with an empty list (nq rows, no pairs): nq == 0 or nr == 0 -- as for dvs_*_cross_distances, nothing else
+ * by dvs_pairs_destroy (NULL is fine).  A GIVEN q is the caller's n x n matrix against itself, only read as
+ * dvs_cluster_scores reads it: r is then NULL or the same matrix (any other: DVS_ERR_UNSUPPORTED).  *out is NULL after
+ * an error.  Errors of the arguments, all before any device work:
+ *   DVS_OK with an empty list (nq rows, no pairs): nq == 0 or nr == 0 -- as for dvs_cross_distances, nothing else
  *                  about the handles and the row lists is looked at then, so a bad row list passes unnoticed
  *   DVS_ERR_VALUE: NULL arguments, NaN radius, unknown flag bits (checked first); a row index beyond its handle, handles of different
  *                  contexts or devices, unequal nbins, a matrix that is not device memory where it is said to be
  *   DVS_ERR_UNSUPPORTED: nr (n) beyond the row limit of the square entries
- *   DVS_ERR_ZERODIV: (sketches) k == 0
+ *   DVS_ERR_ZERODIV: (MASH) k == 0
  * and those that show while the strips are walked:
  *   DVS_ERR_UNSUPPORTED: more than max_pairs pairs (the message names both numbers)
  *   DVS_ERR_NOMEM: the host lists do not fit
- *   DVS_ERR_ZERODIV: (sketches) a visited pair has two empty sketches: exactly where dvs_sketches_cross_distances
- *                  raises it */
+ *   DVS_ERR_ZERODIV: (MASH) a visited pair has two empty sketches: exactly where dvs_cross_distances raises it */
 typedef struct dvs_pairs dvs_pairs;
 #define DVS_WITHIN_SKIP_SELF 1u /* drop cell (i, i): both sides list the same positions */
-int dvs_jsd_within(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                   const uint32_t *r_rows, uint32_t nr, double radius, uint32_t flags, uint64_t max_pairs, dvs_pairs **out);
-int dvs_euclidean_within(dvs_ctx *ctx, const dvs_matrix *q, const uint32_t *q_rows, uint32_t nq, const dvs_matrix *r,
-                         const uint32_t *r_rows, uint32_t nr, double radius, uint32_t flags, uint64_t max_pairs,
-                         dvs_pairs **out);
-int dvs_sketches_within(dvs_ctx *ctx, const dvs_sketches *q, const uint32_t *q_rows, uint32_t nq, const dvs_sketches *r,
-                        const uint32_t *r_rows, uint32_t nr, uint32_t k, uint32_t sketch_size, double radius, uint32_t flags,
-                        uint64_t max_pairs, dvs_pairs **out);
-int dvs_within(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, double radius, uint32_t flags,
-               uint64_t max_pairs, dvs_pairs **out);
+int dvs_within(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, double radius, uint32_t flags, uint64_t max_pairs,
+               dvs_pairs **out);
 void dvs_pairs_destroy(dvs_pairs *p);
 int dvs_pairs_info(const dvs_pairs *p, uint32_t *n_rows, uint64_t *n_pairs); /* either may be NULL */
 /* row_start[n_rows + 1], col[n_pairs], dist[n_pairs]: host arrays, any may be NULL */
 int dvs_pairs_get(const dvs_pairs *p, uint64_t *row_start, uint32_t *col, double *dist);
 /* Threshold clusters: the connected components of the graph that joins positions i and j when D(i, j) <= radius, over
- * the n x n distances of a mode (queries = references = `rows` of the handle, NULL: rows 0 .. n - 1), computed strip by
- * strip as above.  They are the flat clusters of the single-linkage tree cut at height radius -- dvs_linkage_cut with
- * DVS_CUT_HEIGHT over dvs_linkage's DVS_LINKAGE_SINGLE tree -- without the n x n matrix and without the tree.  Only the
- * cells above the diagonal (j > i) are read: a caller's matrix need not be symmetric, and its diagonal may hold
- * anything.  A strip's edges go through a union-find on the host and are dropped before the next strip's arrive.
+ * the n x n distances of a source (queries = references = its rows), computed strip by strip as above.  They are the
+ * flat clusters of the single-linkage tree cut at height radius -- dvs_linkage_cut with DVS_CUT_HEIGHT over
+ * dvs_linkage's DVS_LINKAGE_SINGLE tree -- without the n x n matrix and without the tree.  Only the cells above the
+ * diagonal (j > i) are read: a GIVEN matrix need not be symmetric, and its diagonal may hold anything.  A strip's edges go through a union-find on the host and are dropped before the next strip's arrive.
  * labels[n]: the cluster of every position, in [0, *n_clusters), numbered by first appearance in position order
  * (position 0 is in cluster 0), as dvs_linkage_cut numbers them.  A position whose every cell is NaN or beyond the
  * radius is a cluster of its own; a negative radius joins nothing.  (No counterpart in the reference.)
  *   DVS_OK with nothing written: n == 0.  n == 1: label 0, one cluster
  *   DVS_ERR_VALUE, DVS_ERR_UNSUPPORTED, DVS_ERR_NOMEM: as above
- *   DVS_ERR_ZERODIV: (sketches) exactly as dvs_sketches_cluster_scores */
-int dvs_jsd_threshold_clusters(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, double radius,
-                               uint32_t *labels, uint32_t *n_clusters);
-int dvs_euclidean_threshold_clusters(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, double radius,
-                                     uint32_t *labels, uint32_t *n_clusters);
-int dvs_sketches_threshold_clusters(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
-                                    uint32_t sketch_size, double radius, uint32_t *labels, uint32_t *n_clusters);
-int dvs_threshold_clusters(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, double radius,
-                           uint32_t *labels, uint32_t *n_clusters);
+ *   DVS_ERR_ZERODIV: (MASH) exactly as dvs_cluster_scores */
+int dvs_threshold_clusters(dvs_ctx *ctx, const dvs_source *src, double radius, uint32_t *labels, uint32_t *n_clusters);
 
 /* ---- cophenetic distances of a tree, and their correlation with the distances it was built from ---- *
  * scipy.cluster.hierarchy.cophenet.  The cophenetic distance coph(i, j) of two leaves is the height of the merge at
@@ -628,13 +596,12 @@ int dvs_threshold_clusters(dvs_ctx *ctx, const double *dist, int dist_on_device,
  * monotone (scipy's centroid and median trees are not), unlike dvs_linkage_cut.
  * dvs_linkage_cophenet is scipy's cophenet(Z) as the square matrix (squareform of its result, bit for bit): coph is a
  * host array n x n, zero on the diagonal; host only, ctx only takes the error text and may be NULL.
- * The other four are scipy's cophenet(Z, Y)[0], Pearson's r between D(i, j) and coph(i, j) over the n (n - 1) ordered
- * pairs i != j, with the n x n distances D of a mode computed strip by strip as for the cluster scores above (queries =
- * references = `rows` of the handle, NULL: rows 0 .. n - 1; leaf i of the tree is rows[i]); the matrix never exists
- * whole.  Cell (i, i) is never read.  Both variables are shifted by c_bar, the mean of all cophenetic distances (known
- * from the tree alone: a merge of clusters of sizes s_a and s_b at height h holds s_a s_b pairs at h), which leaves r
- * as it is and keeps the moments free of cancellation where the distances crowd near one value.  With x = D(i, j) -
- * c_bar and y = coph(i, j) - c_bar:
+ * dvs_cophenet is scipy's cophenet(Z, Y)[0], Pearson's r between D(i, j) and coph(i, j) over the n (n - 1) ordered
+ * pairs i != j, with the n x n distances D of a source computed strip by strip as for the cluster scores above (queries =
+ * references = the source; leaf i of the tree is rows[i]); the matrix never exists whole.  Cell (i, i) is never read.
+ * Both variables are shifted by c_bar, the mean of all cophenetic distances (known from the tree alone: a merge of
+ * clusters of sizes s_a and s_b at height h holds s_a s_b pairs at h), which leaves r as it is and keeps the moments
+ * free of cancellation where the distances crowd near one value.  With x = D(i, j) - c_bar and y = coph(i, j) - c_bar:
  *   row_sums  [5][n], optional: per row i the sums over j != i of x, y, x x, y y and x y.  The order in which a sum's
  *             terms are added depends on (n, the tree) alone: the same bits on every run and for every strip height
  *   *corr     r = Sxy / sqrt(Sxx Syy) from the 5 n sums in long double on the host (Sxy = sum xy - sum x sum y / M, M =
@@ -642,23 +609,16 @@ int dvs_threshold_clusters(dvs_ctx *ctx, const double *dist, int dist_on_device,
  *             gives -- zero meaning not above the rounding error of its own terms, 2 (n + 8) 2^-52 sum xx
  *   coph      n x n host array, optional: the cophenetic rows the kernel used, copied out strip by strip (N^2
  *             doubles over PCIe: ask for it only when it is wanted)
- * dvs_cophenet takes the caller's own n x n matrix as dvs_cluster_scores does and only reads it.
+ * A GIVEN matrix is only read, as dvs_cluster_scores reads it.
  *   DVS_OK with nothing written: n == 0
  *   DVS_ERR_VALUE: n == 1, a pair that names a cluster not yet made or already merged, a row index beyond the handle,
  *                  a device mismatch, a matrix that is not device memory where it is said to be
  *   DVS_ERR_UNSUPPORTED: n beyond the row limit of the square entries
- *   DVS_ERR_ZERODIV: (sketches) one empty sketch among the rows, as dvs_sketches_cluster_scores
+ *   DVS_ERR_ZERODIV: (MASH) one empty sketch among the rows, as dvs_cluster_scores
  * All argument checks come before any device work.  (No counterpart in the reference.) */
 int dvs_linkage_cophenet(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, double *coph);
-int dvs_jsd_cophenet(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *pairs,
-                     const double *heights, double *corr, double *row_sums, double *coph);
-int dvs_euclidean_cophenet(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t *rows, uint32_t n, const uint32_t *pairs,
-                           const double *heights, double *corr, double *row_sums, double *coph);
-int dvs_sketches_cophenet(dvs_ctx *ctx, const dvs_sketches *sk, const uint32_t *rows, uint32_t n, uint32_t k,
-                          uint32_t sketch_size, const uint32_t *pairs, const double *heights, double *corr,
-                          double *row_sums, double *coph);
-int dvs_cophenet(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *pairs,
-                 const double *heights, double *corr, double *row_sums, double *coph);
+int dvs_cophenet(dvs_ctx *ctx, const dvs_source *src, const uint32_t *pairs, const double *heights, double *corr,
+                 double *row_sums, double *coph);
 
 /* ---- neighbour-joining tree (the tree of additive distances) ------------------------------------- *
  * Canonical Saitou-Nei / Studier-Keppler neighbour joining of an n x n distance matrix, n >= 3, on the device.  As for
@@ -679,29 +639,26 @@ int dvs_cophenet(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t 
  *            record t makes n + t); the third child is 0xFFFFFFFF except in the last record
  *   lengths  double [3 (n - 2)]: the branch above each child (0.0 in an unused third slot); a negative length is
  *            neighbour joining's answer on distances that are not additive and is returned as it is
- * dvs_nj takes a host matrix (copied to the device, left unchanged) or, with dist_on_device, a device matrix, which is
- * the working buffer and is OVERWRITTEN.  The three fused entries compute the mode's distances into the context's
- * scratch, as the *_linkage entries do, and build the tree there: the matrix never leaves HBM.
+ * The sources as for dvs_linkage: a GIVEN host matrix is copied to the device and left unchanged, a GIVEN device matrix
+ * is the working buffer and is OVERWRITTEN; MASH, EUCLIDEAN and JSD compute their distances into the context's scratch
+ * and build the tree there: the matrix never leaves HBM.
  *   DVS_ERR_VALUE: n < 3, a NaN or +-inf entry anywhere, a device matrix on another device (and a row without a valid
- *                  k-mer in the euclidean and jsd modes: NaN distances); DVS_ERR_ZERODIV: (sketches) two empty
- *                  sketches; DVS_ERR_NOMEM: the matrix and the tree's scratch (a quarter of the matrix) do not fit
+ *                  k-mer, EUCLIDEAN and JSD: NaN distances); DVS_ERR_ZERODIV: (MASH) two empty sketches;
+ *                  DVS_ERR_NOMEM: the matrix and the tree's scratch (a quarter of the matrix) do not fit;
+ *                  DVS_ERR_UNSUPPORTED: a row list, or n other than the handle's rows
  * dvs_nj_patristic (host only, ctx may be NULL): out, n x n, the path length between every two leaves of such a tree;
  * O(n^2).  DVS_ERR_VALUE: n < 3, a record that names a node not yet made or already joined, a third child outside
  * the last record.  (No counterpart in the reference.) */
-int dvs_nj(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths);
-int dvs_sketches_nj(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t *joins,
-                    double *lengths);
-int dvs_matrix_euclidean_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths);
-int dvs_matrix_jsd_nj(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *joins, double *lengths);
+int dvs_nj(dvs_ctx *ctx, const dvs_source *src, uint32_t *joins, double *lengths);
 int dvs_nj_patristic(dvs_ctx *ctx, uint32_t n, const uint32_t *joins, const double *lengths, double *out);
 
 /* ---- farthest-first selection (max-min diversity, Gonzalez' greedy for k-center) ------------------- *
  * Representatives by distance: from one or more seeds on, the item whose distance to the nearest item already taken
  * is largest, until n_select items are taken or every item lies within min_distance of one.  A pick costs one row of
  * distances; the n x n matrix of a mode never exists.  (No counterpart in the reference.)  The algorithm:
- *   items and distances  items 0 .. n - 1; d(p, j) is the mode's cell for rows p and j (the bits of the square entry
- *       of the mode: dvs_jsd_distances, dvs_euclidean_distances, dvs_sketches_distances), on a caller's matrix
- *       dist[p * n + j]: a row is read as it stands, the diagonal never
+ *   items and distances  items 0 .. n - 1; d(p, j) is the source's cell for rows p and j (the bits dvs_distances
+ *       writes for a source of that kind), on a GIVEN matrix dist[p * n + j]: a row is read as it stands, the
+ *       diagonal never
  *   state per item  mind[j], +inf at first; owner[j], the position in the pick list of the nearest pick, NONE
  *       (0xFFFFFFFF) at first; a flag `taken`; a flag `out`
  *   take(p, r)  p is appended to the picks with radius r; mind[p] = 0, owner[p] = its own position; for every other j
@@ -718,30 +675,19 @@ int dvs_nj_patristic(dvs_ctx *ctx, uint32_t n, const uint32_t *joins, const doub
  * at +inf from every pick keeps owner NONE and is the next candidate.  Everything is a comparison or a copy of a cell,
  * so the result is exact and the same on every run and for every batch length (DVS_MAXMIN_BATCH: the steps enqueued
  * between two reads of the device's status word, 64 by default).
- * The three mode entries take rows 0 .. n - 1 of their handle (n <= its rows).  dvs_maxmin takes the caller's n x n
- * matrix (row-major float64; host: uploaded whole and left unchanged; dist_on_device != 0: device memory on the
- * context's device, only read).  picks and radius hold n_select entries, owner and dist_to_owner n; all are host
+ * MASH, EUCLIDEAN and JSD sources take rows 0 .. n - 1 of their handle (n <= its rows; a row list:
+ * DVS_ERR_UNSUPPORTED).  A GIVEN host matrix is uploaded whole and left unchanged, a GIVEN device matrix only read.  picks and radius hold n_select entries, owner and dist_to_owner n; all are host
  * arrays.  Return when they are written.
  *   DVS_ERR_VALUE, before any device work: no seed, a seed >= n, a repeated seed, n_select < n_seeds or > n, NaN
  *                  min_distance (with use_min_distance), n beyond the handle's rows; a device mismatch
- *   DVS_ERR_ZERODIV: (sketches) k == 0, or a pair the traversal visits -- (p, j) with p a pick and j neither taken nor
+ *   DVS_ERR_ZERODIV: (MASH) k == 0, or a pair the traversal visits -- (p, j) with p a pick and j neither taken nor
  *                  out at that point -- has two empty sketches, exactly where dvs_sketches_distances divides by zero
  *                  for the same pair.  A pick's own cell is not a pair: one empty sketch among the rows does not raise
- *   DVS_ERR_UNSUPPORTED: (euclidean) n beyond 524 280, the grid of the distance kernel
+ *   DVS_ERR_UNSUPPORTED: (EUCLIDEAN) n beyond 524 280, the grid of the distance kernel
  * The row limit of the square entries does not apply otherwise: nothing here is n x n but a caller's matrix. */
-int dvs_maxmin(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
-               uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks, double *radius,
-               uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover);
-int dvs_sketches_maxmin(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t k, uint32_t sketch_size, uint32_t n,
-                        const uint32_t *seeds, uint32_t n_seeds, uint32_t n_select, int use_min_distance,
-                        double min_distance, uint32_t *picks, double *radius, uint32_t *n_picked, uint32_t *owner,
-                        double *dist_to_owner, double *cover);
-int dvs_matrix_jsd_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
-                          uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks, double *radius,
-                          uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover);
-int dvs_matrix_euclidean_maxmin(dvs_ctx *ctx, const dvs_matrix *m, uint32_t n, const uint32_t *seeds, uint32_t n_seeds,
-                                uint32_t n_select, int use_min_distance, double min_distance, uint32_t *picks,
-                                double *radius, uint32_t *n_picked, uint32_t *owner, double *dist_to_owner, double *cover);
+int dvs_maxmin(dvs_ctx *ctx, const dvs_source *src, const uint32_t *seeds, uint32_t n_seeds, uint32_t n_select,
+               int use_min_distance, double min_distance, uint32_t *picks, double *radius, uint32_t *n_picked,
+               uint32_t *owner, double *dist_to_owner, double *cover);
 
 #ifdef __cplusplus
 }

@@ -86,7 +86,7 @@ def main():
         cluster.linkage(warm, method, ctx=ctx)
         distance.mash_linkage(warm_seqs, 12, 3000, method=method, ctx=ctx)
     if args.distance:
-        dist_entry = getattr(ctx._L, f"dvs_{args.distance}_distances")
+        dist_mode = distance.DeviceSide.MODE_NAMES.index(args.distance)  # the kind of the dvs_source
         dist_linkage = getattr(distance, f"{args.distance}_linkage")
         for method in methods:
             dist_linkage(uniform_seqs(64, 5000, 1), args.k, method=method, ctx=ctx)
@@ -122,7 +122,8 @@ def main():
                 useqs = uniform_seqs(n, 5000, n + 1)
                 m = ctx.build_matrix(useqs, args.k)
                 out = np.zeros((n, n))
-                run = lambda: ctx.check(dist_entry(ctx._h, m._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+                src = distance.make_source(dist_mode, m._h, n)
+                run = lambda: ctx.check(ctx._L.dvs_distances(ctx._h, src, out.ctypes.data_as(C.POINTER(C.c_double))))
                 run()
                 line[f"{args.distance}_matrix_ms"] = round(median_ms(run, args.reps), 3)
                 m.close()

@@ -26,7 +26,7 @@ KERNELS = ("jsd_pairs_kernel", "jsd_finish_kernel", "euclid_kernel")
 
 
 def run(sizes):
-    from diverseseq_amd import engine
+    from diverseseq_amd import _lib, distance, engine
 
     ctx = engine.Context(0)
     for n in sizes:
@@ -34,9 +34,10 @@ def run(sizes):
         m = ctx.build_matrix([rng.integers(0, 4, LENGTH, dtype=np.uint8) for _ in range(n)], K)
         out = np.zeros((n, n))
         p = out.ctypes.data_as(C.POINTER(C.c_double))
-        for entry in (ctx._L.dvs_jsd_distances, ctx._L.dvs_euclidean_distances):
+        for kind in (_lib.SRC_JSD, _lib.SRC_EUCLIDEAN):
+            src = distance.make_source(kind, m._h, n)
             for _ in range(4):
-                ctx.check(entry(ctx._h, m._h, p))
+                ctx.check(ctx._L.dvs_distances(ctx._h, src, p))
         m.close()
 
 

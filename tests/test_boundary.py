@@ -29,7 +29,33 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(str(_lib.LIB_PATH))
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in dvs_hip.h but not exported"
-    assert _lib.load().dvs_abi_version() == 3
+    assert _lib.load().dvs_abi_version() == 4
+
+
+# the operations over "the distances of a collection": one C entry each, which takes a dvs_source
+DISTANCE_OPERATIONS = ("distances", "linkage", "nj", "maxmin", "cross_distances", "nearest", "within", "cluster_scores",
+                       "cophenet", "threshold_clusters")
+
+
+def test_one_entry_per_distance_operation():
+    """each of the ten operations is declared exactly once in the header, with a dvs_source behind the context, and no
+    per-mode spelling of any of them is left -- neither declared nor exported by the library"""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "dvs_hip.h").read_text(), flags=re.S)
+    lib = ctypes.CDLL(str(_lib.LIB_PATH))
+    for op in DISTANCE_OPERATIONS:
+        found = re.findall(rf"\bint\s+dvs_{op}\s*\(([^)]*)\)\s*;", text)
+        assert len(found) == 1, (op, found)
+        assert re.match(r"\s*dvs_ctx\s*\*\s*ctx\s*,\s*const\s+dvs_source\s*\*", found[0]), (op, found[0])
+        assert f"dvs_{op}" in _lib.EXPORTS
+        per_mode = set(re.findall(rf"\bdvs_(?:jsd|euclidean|sketches|matrix)_(?:[a-z0-9]+_)*{op}\b", text))
+        stays = {"dvs_sketches_distances"}  # not an operation over a mode: strided rows, the symmetric flag
+        assert per_mode <= stays, (op, per_mode)
+        for head in ("jsd", "euclidean", "sketches", "matrix_jsd", "matrix_euclidean"):
+            if f"dvs_{head}_{op}" not in stays:
+                assert not hasattr(lib, f"dvs_{head}_{op}"), (head, op)
+    assert not re.search(r"\bdvs_\w*average_linkage\b", text)
+    for name in ("dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage"):
+        assert not hasattr(lib, name), name
 
 
 def test_product_never_imports_oracle():

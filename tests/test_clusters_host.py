@@ -37,13 +37,12 @@ def test_public_names_exist():
     assert callable(apps.dvs_clusters) and "dvs_clusters" in apps.__all__
     assert distance.ClusterScores._fields == ("labels", "within", "a", "b", "neighbour", "silhouette", "sizes", "medoids",
                                               "cluster_silhouette", "mean_silhouette")
-    new = {"dvs_linkage_cut", "dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores", "dvs_sketches_cluster_scores",
-           "dvs_cluster_scores"}
+    new = {"dvs_linkage_cut", "dvs_cluster_scores"}  # one entry for the scores: the mode travels in the dvs_source
     assert new <= set(_lib.EXPORTS)
     lib = _lib.load()
     for name in new:
         assert getattr(lib, name).argtypes is not None, name
-    assert lib.dvs_abi_version() == 3
+    assert lib.dvs_abi_version() == 4
 
 
 # ------------------------------------------------------------------ cut_tree against scipy

@@ -96,13 +96,12 @@ def test_public_names_exist():
     assert callable(apps.dvs_nearest) and "dvs_nearest" in apps.__all__
     assert set(distance.CROSS_MODES) == set(distance.MODES) == {"mash", "euclidean", "jsd"}
     assert len(distance.MODES["mash"]) == 2  # (left as it is: tests and apps index its pairs)
-    new = {"dvs_jsd_cross_distances", "dvs_euclidean_cross_distances", "dvs_sketches_cross_distances", "dvs_jsd_nearest",
-           "dvs_euclidean_nearest", "dvs_sketches_nearest"}
+    new = {"dvs_cross_distances", "dvs_nearest"}  # one entry per operation: the mode travels in the dvs_source
     assert new <= set(_lib.EXPORTS)
     lib = _lib.load()
     for name in new:
         assert getattr(lib, name).argtypes is not None, name
-    assert lib.dvs_abi_version() == 3
+    assert lib.dvs_abi_version() == 4
 
 
 # ------------------------------------------------------------------ argument errors come before any device work

@@ -374,8 +374,8 @@ def test_errors(ctx):
     within, med = np.zeros(65), np.zeros(2, np.uint32)
 
     def host(n, lab_, k, dist=D, on_device=0, within_=within):
-        return L.dvs_cluster_scores(ctx._h, dist.ctypes.data_as(C.c_void_p), on_device, n, u32(lab_), k, f64(within_), None,
-                                    None, None, None, u32(med))
+        given = distance.make_source(_lib.SRC_GIVEN, dist.ctypes.data, n, on_device=on_device)
+        return L.dvs_cluster_scores(ctx._h, given, u32(lab_), k, f64(within_), None, None, None, None, u32(med))
 
     assert host(65, labels, 2) == _lib.OK  # every output but `within` and the medoids left out
     t = truth_cluster_scores(D, lab)
@@ -393,13 +393,16 @@ def test_errors(ctx):
     try:
         l10 = np.zeros(10, np.uint32)
         w10 = np.zeros(11)
-        for entry in ("dvs_jsd_cluster_scores", "dvs_euclidean_cluster_scores"):
-            f = getattr(L, entry)
-            assert f(ctx._h, m._h, None, 10, u32(l10), 1, f64(w10), None, None, None, None, None) == _lib.OK
-            assert f(ctx._h, m._h, None, 11, u32(np.zeros(11, np.uint32)), 1, f64(w10), None, None, None, None, None) == _lib.ERR_VALUE
-            assert f(ctx._h, m._h, u32(np.array([0, 10], np.uint32)), 2, u32(l10), 1, f64(w10), None, None, None, None, None) == _lib.ERR_VALUE
-            assert f(ctx._h, m._h, None, 10, u32(l10 + 1), 1, f64(w10), None, None, None, None, None) == _lib.ERR_VALUE
-            assert f(ctx._h, m._h, None, 0, u32(l10), 0, f64(w10), None, None, None, None, None) == _lib.OK
+        for kind in (_lib.SRC_JSD, _lib.SRC_EUCLIDEAN):
+            def f(n, lab_, k, rows=None):
+                return L.dvs_cluster_scores(ctx._h, distance.make_source(kind, m._h, n, rows), u32(lab_), k, f64(w10), None, None,
+                                            None, None, None)
+
+            assert f(10, l10, 1) == _lib.OK
+            assert f(11, np.zeros(11, np.uint32), 1) == _lib.ERR_VALUE
+            assert f(2, l10, 1, np.array([0, 10], np.uint32)) == _lib.ERR_VALUE
+            assert f(10, l10 + 1, 1) == _lib.ERR_VALUE
+            assert f(0, l10, 0) == _lib.OK
         with pytest.raises(ValueError, match="row list"):
             distance.matrix_cluster_scores(m, [0, 0], "jsd", rows=[0, 10])
         with pytest.raises(ValueError, match="Unexpected distance"):

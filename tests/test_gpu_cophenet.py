@@ -291,7 +291,8 @@ def test_errors(ctx):
     corr = C.c_double(-2.0)
 
     def host(n, p=pairs, on_device=0, corr_=C.byref(corr)):
-        return L.dvs_cophenet(ctx._h, D.ctypes.data_as(C.c_void_p), on_device, n, u32(p), f64(heights), corr_, None, None)
+        given = distance.make_source(_lib.SRC_GIVEN, D.ctypes.data, n, on_device=on_device)
+        return L.dvs_cophenet(ctx._h, given, u32(p), f64(heights), corr_, None, None)
 
     assert host(65) == _lib.OK  # every output but the correlation left out
     assert abs(corr.value - truth_correlation(D, Z)) <= bound(65)
@@ -302,21 +303,21 @@ def test_errors(ctx):
     assert host(65, np.ascontiguousarray(twice[:, :2], dtype=np.uint32).reshape(-1)) == _lib.ERR_VALUE
     assert host(65, on_device=1) == _lib.ERR_VALUE    # a host array is not device memory
     big = 65535 * 8 + 1
-    assert L.dvs_cophenet(ctx._h, D.ctypes.data_as(C.c_void_p), 0, big, u32(np.zeros(2 * big, np.uint32)),
+    assert L.dvs_cophenet(ctx._h, distance.make_source(_lib.SRC_GIVEN, D.ctypes.data, big), u32(np.zeros(2 * big, np.uint32)),
                           f64(np.zeros(big)), C.byref(corr), None, None) == _lib.ERR_UNSUPPORTED
     seqs = _mode_seqs(25, 10)
     m = ctx.build_matrix(seqs, 3, 4)
     try:
         Z10 = scipy_linkage(condensed(case_matrix(10, "random")), "average")
         p10, h10 = np.ascontiguousarray(Z10[:, :2], dtype=np.uint32).reshape(-1), np.ascontiguousarray(Z10[:, 2])
-        for entry in ("dvs_jsd_cophenet", "dvs_euclidean_cophenet"):
-            f = getattr(L, entry)
-            assert f(ctx._h, m._h, None, 10, u32(p10), f64(h10), C.byref(corr), None, None) == _lib.OK
-            assert f(ctx._h, m._h, None, 11, u32(np.r_[p10, 0, 18].astype(np.uint32)), f64(np.r_[h10, 2.0]), C.byref(corr), None,
-                     None) == _lib.ERR_VALUE  # 11 rows of a handle that holds 10
-            assert f(ctx._h, m._h, u32(np.array([0, 10], np.uint32)), 2, u32(np.array([0, 1], np.uint32)), f64(h10),
-                     C.byref(corr), None, None) == _lib.ERR_VALUE
-            assert f(ctx._h, m._h, None, 0, u32(p10), f64(h10), C.byref(corr), None, None) == _lib.OK
+        for kind in (_lib.SRC_JSD, _lib.SRC_EUCLIDEAN):
+            def f(n, p, h, rows=None):
+                return L.dvs_cophenet(ctx._h, distance.make_source(kind, m._h, n, rows), u32(p), f64(h), C.byref(corr), None, None)
+
+            assert f(10, p10, h10) == _lib.OK
+            assert f(11, np.r_[p10, 0, 18].astype(np.uint32), np.r_[h10, 2.0]) == _lib.ERR_VALUE  # 11 rows of a handle that holds 10
+            assert f(2, np.array([0, 1], np.uint32), h10, np.array([0, 10], np.uint32)) == _lib.ERR_VALUE
+            assert f(0, p10, h10) == _lib.OK
         with pytest.raises(ValueError, match="row list"):
             distance.matrix_cophenet(m, Z10[:1], "jsd", rows=[0, 10])
         with pytest.raises(ValueError, match="Unexpected distance"):

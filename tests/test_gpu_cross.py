@@ -360,15 +360,15 @@ def test_nearest_errors(ctx):
     L, C = ctx._L, __import__("ctypes")
     idx, val = np.zeros((5, 70), np.uint32), np.zeros((5, 70), np.float64)
 
-    def raw(entry, q, r, nq, nr, kk, q_rows=None, r_rows=None):
+    def raw(kind, q, r, nq, nr, kk, q_rows=None, r_rows=None):
         from diverseseq_amd import _lib
 
-        return getattr(L, entry)(ctx._h, q._h, _lib.ptr(q_rows, C.c_uint32), nq, r._h, _lib.ptr(r_rows, C.c_uint32), nr, kk,
-                                 _lib.ptr(idx, C.c_uint32), _lib.ptr(val, C.c_double))
+        return L.dvs_nearest(ctx._h, distance.make_source(kind, q._h, nq, q_rows), distance.make_source(kind, r._h, nr, r_rows),
+                             kk, _lib.ptr(idx, C.c_uint32), _lib.ptr(val, C.c_double))
 
-    from diverseseq_amd._lib import ERR_UNSUPPORTED, ERR_VALUE, OK
+    from diverseseq_amd._lib import ERR_UNSUPPORTED, ERR_VALUE, OK, SRC_EUCLIDEAN, SRC_JSD
     try:
-        for entry in ("dvs_jsd_nearest", "dvs_euclidean_nearest"):
+        for entry in (SRC_JSD, SRC_EUCLIDEAN):
             assert raw(entry, mq, mr, 5, 70, 0) == ERR_VALUE       # kk == 0
             assert raw(entry, mq, mr, 5, 10, 11) == ERR_VALUE      # kk > N
             assert raw(entry, mq, mr, 5, 0, 1) == ERR_VALUE        # no references

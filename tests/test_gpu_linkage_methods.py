@@ -131,11 +131,11 @@ def test_unsupported_codes_at_the_c_boundary(ctx):
     d = np.random.default_rng(10).random((6, 6))
     pairs, heights, sizes = distance.tree_outputs(6)
     args = (_lib.ptr(pairs, ctypes.c_uint32), _lib.ptr(heights, ctypes.c_double), _lib.ptr(sizes, ctypes.c_uint32))
-    src = d.ctypes.data_as(ctypes.c_void_p)
+    src = distance.make_source(_lib.SRC_GIVEN, d.ctypes.data, 6)
     for code, rc in ((3, _lib.ERR_UNSUPPORTED), (4, _lib.ERR_UNSUPPORTED), (7, _lib.ERR_VALUE), (-1, _lib.ERR_VALUE)):
-        assert ctx._L.dvs_linkage(ctx._h, src, 0, 6, code, *args) == rc, code
+        assert ctx._L.dvs_linkage(ctx._h, src, code, *args) == rc, code
     for name, code in distance.LINKAGE_METHODS.items():
-        assert ctx._L.dvs_linkage(ctx._h, src, 0, 6, code, *args) == _lib.OK
+        assert ctx._L.dvs_linkage(ctx._h, src, code, *args) == _lib.OK
         assert np.array_equal(distance.linkage_matrix(pairs, heights, sizes), scipy_z(d, name)), name
 
 

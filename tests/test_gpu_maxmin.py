@@ -173,7 +173,8 @@ def test_c_entry_checks_its_arguments(ctx):
 
     def call(seeds, n_select, use_min=0, min_d=0.0):
         s = np.asarray(seeds, dtype=np.uint32)
-        return ctx._L.dvs_maxmin(ctx._h, d.ctypes.data_as(C.c_void_p), 0, 5, _lib.ptr(s, C.c_uint32), s.size, n_select, use_min,
+        given = distance.make_source(_lib.SRC_GIVEN, d.ctypes.data, 5)
+        return ctx._L.dvs_maxmin(ctx._h, given, _lib.ptr(s, C.c_uint32), s.size, n_select, use_min,
                                  min_d, _lib.ptr(out[0], C.c_uint32), _lib.ptr(out[1], C.c_double), C.byref(out[2]),
                                  _lib.ptr(out[3], C.c_uint32), _lib.ptr(out[4], C.c_double), C.byref(out[5]))
 

@@ -170,17 +170,23 @@ def test_c_boundary(ctx):
     joins = np.zeros(21, dtype=np.uint32)
     lens = np.full(21, -1.0)
     d = np.ascontiguousarray(A)
-    assert L.dvs_nj(ctx._h, d.ctypes.data_as(C.c_void_p), 0, 9, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.OK
+
+    def given(n, on_device=0, handle=d.ctypes.data):
+        return distance.make_source(_lib.SRC_GIVEN, handle, n, on_device=on_device)
+
+    assert L.dvs_nj(ctx._h, given(9), joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.OK
     j, l = joins.reshape(7, 3), lens.reshape(7, 3)
     assert (j[:6, 2] == 0xFFFFFFFF).all() and (l[:6, 2] == 0.0).all() and j[6, 2] != 0xFFFFFFFF
     assert sorted(j[j != 0xFFFFFFFF].tolist()) == list(range(15))
-    assert L.dvs_nj(ctx._h, d.ctypes.data_as(C.c_void_p), 0, 2, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    assert L.dvs_nj(ctx._h, given(2), joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
     assert b"three sequences" in L.dvs_last_error(ctx._h)
-    assert L.dvs_nj(ctx._h, None, 0, 9, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
-    assert L.dvs_nj(ctx._h, d.ctypes.data_as(C.c_void_p), 0, 9, None, lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
-    assert L.dvs_nj(ctx._h, d.ctypes.data_as(C.c_void_p), 0, 9, joins.ctypes.data_as(u32), None) == _lib.ERR_VALUE
-    assert L.dvs_sketches_nj(ctx._h, None, 8, 10, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
-    for name in ("dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj"):
-        assert getattr(L, name)(ctx._h, None, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    assert L.dvs_nj(ctx._h, given(9, handle=None), joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    assert L.dvs_nj(ctx._h, given(9), None, lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    assert L.dvs_nj(ctx._h, given(9), joins.ctypes.data_as(u32), None) == _lib.ERR_VALUE
+    null_sketches = distance.make_source(_lib.SRC_MASH, None, 9, k=8, sketch_size=10)
+    assert L.dvs_nj(ctx._h, null_sketches, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    for kind in (_lib.SRC_EUCLIDEAN, _lib.SRC_JSD):
+        null_matrix = distance.make_source(kind, None, 9)
+        assert L.dvs_nj(ctx._h, null_matrix, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
     # a host pointer said to be device memory
-    assert L.dvs_nj(ctx._h, d.ctypes.data_as(C.c_void_p), 1, 9, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    assert L.dvs_nj(ctx._h, given(9, 1), joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE

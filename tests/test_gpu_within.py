@@ -544,40 +544,46 @@ def test_c_entries_refuse_bad_arguments_and_leave_the_context_usable(ctx):
     lab, cnt = np.full(40, 7, np.uint32), C.c_uint32(99)
     big = 65535 * 8 + 1  # one row more than the square entries take (tests/test_gpu_clusters.py, test_gpu_cophenet.py)
 
-    def refused(entry, *args):
-        """the entry's code, with *out NULL afterwards whatever it held"""
+    S = distance.make_source
+
+    def given(n, on_device=0, handle=d.ctypes.data):
+        """the matrix d (or no matrix) as a caller's n x n matrix"""
+        return S(_lib.SRC_GIVEN, handle, n, on_device=on_device)
+
+    def refused(q, r, *args):
+        """dvs_within's code, with *out NULL afterwards whatever it held"""
         out.value = 0xDEAD
-        rc = getattr(L, entry)(ctx._h, *args, C.byref(out))
-        assert not out.value, (entry, rc)
+        rc = L.dvs_within(ctx._h, q, r, *args, C.byref(out))
+        assert not out.value, rc
         return rc
 
-    def clusters_refused(*args):
-        """the entry's code, with the labels and the count untouched"""
+    def clusters_refused(src, radius):
+        """dvs_threshold_clusters' code, with the labels and the count untouched"""
         lab[:], cnt.value = 7, 99
-        rc = L.dvs_threshold_clusters(ctx._h, *args, _lib.ptr(lab, C.c_uint32), C.byref(cnt))
+        rc = L.dvs_threshold_clusters(ctx._h, src, radius, _lib.ptr(lab, C.c_uint32), C.byref(cnt))
         assert (lab == 7).all() and cnt.value == 99, rc
         return rc
 
-    assert refused("dvs_within", p, 0, 40, float("nan"), 0, 0) == _lib.ERR_VALUE
-    assert refused("dvs_within", p, 0, 40, 0.1, 2, 0) == _lib.ERR_VALUE            # an unknown flag bit
-    assert refused("dvs_within", None, 0, 40, 0.1, 0, 0) == _lib.ERR_VALUE
-    assert refused("dvs_within", p, 1, 40, 0.1, 0, 0) == _lib.ERR_VALUE            # a host array is not device memory
-    assert refused("dvs_within", p, 0, big, 0.1, 0, 0) == _lib.ERR_UNSUPPORTED     # (refused before a cell is read)
-    assert L.dvs_within(ctx._h, p, 0, 40, 0.1, 0, 0, None) == _lib.ERR_VALUE
-    assert clusters_refused(p, 0, 40, float("nan")) == _lib.ERR_VALUE
-    assert clusters_refused(p, 1, 40, 0.1) == _lib.ERR_VALUE                       # a host array is not device memory
-    assert clusters_refused(p, 0, big, 0.1) == _lib.ERR_UNSUPPORTED
-    assert L.dvs_threshold_clusters(ctx._h, p, 0, 40, 0.1, None, C.byref(cnt)) == _lib.ERR_VALUE
-    assert L.dvs_threshold_clusters(ctx._h, p, 0, 40, 0.1, _lib.ptr(lab, C.c_uint32), None) == _lib.ERR_VALUE
+    assert refused(given(40), None, float("nan"), 0, 0) == _lib.ERR_VALUE
+    assert refused(given(40), None, 0.1, 2, 0) == _lib.ERR_VALUE            # an unknown flag bit
+    assert refused(given(40, handle=None), None, 0.1, 0, 0) == _lib.ERR_VALUE
+    assert refused(given(40, 1), None, 0.1, 0, 0) == _lib.ERR_VALUE         # a host array is not device memory
+    assert refused(given(big), None, 0.1, 0, 0) == _lib.ERR_UNSUPPORTED     # (refused before a cell is read)
+    assert L.dvs_within(ctx._h, given(40), None, 0.1, 0, 0, None) == _lib.ERR_VALUE
+    assert clusters_refused(given(40), float("nan")) == _lib.ERR_VALUE
+    assert clusters_refused(given(40, 1), 0.1) == _lib.ERR_VALUE            # a host array is not device memory
+    assert clusters_refused(given(big), 0.1) == _lib.ERR_UNSUPPORTED
+    assert L.dvs_threshold_clusters(ctx._h, given(40), 0.1, None, C.byref(cnt)) == _lib.ERR_VALUE
+    assert L.dvs_threshold_clusters(ctx._h, given(40), 0.1, _lib.ptr(lab, C.c_uint32), None) == _lib.ERR_VALUE
     assert (lab == 7).all() and cnt.value == 99
     with pytest.raises(NotImplementedError):  # the same through the Python layer: a matrix of `big` rows is never made,
-        distance._run_within(ctx, "dvs_within", p, 0, big, 0.1, 0, 0)                  # the entry refuses the number
+        distance._run_within(ctx, given(big), None, 0.1, 0, 0)                  # the entry refuses the number
     with pytest.raises(NotImplementedError):
-        distance._run_threshold_clusters(ctx, "dvs_threshold_clusters", big, p, 0, big, 0.1)
-    assert L.dvs_threshold_clusters(ctx._h, p, 0, 0, 0.1, None, None) == _lib.OK  # n == 0: nothing written
-    assert L.dvs_threshold_clusters(ctx._h, p, 0, 1, 0.1, _lib.ptr(lab, C.c_uint32), C.byref(cnt)) == _lib.OK
+        distance._run_threshold_clusters(ctx, big, given(big), 0.1)
+    assert L.dvs_threshold_clusters(ctx._h, given(0), 0.1, None, None) == _lib.OK  # n == 0: nothing written
+    assert L.dvs_threshold_clusters(ctx._h, given(1), 0.1, _lib.ptr(lab, C.c_uint32), C.byref(cnt)) == _lib.OK
     assert lab[0] == 0 and cnt.value == 1
-    assert L.dvs_within(ctx._h, p, 0, 0, 0.1, 0, 0, C.byref(out)) == _lib.OK and out.value  # an empty list
+    assert L.dvs_within(ctx._h, given(0), None, 0.1, 0, 0, C.byref(out)) == _lib.OK and out.value  # an empty list
     rows, pairs = C.c_uint32(9), C.c_uint64(9)
     assert L.dvs_pairs_info(out, C.byref(rows), C.byref(pairs)) == _lib.OK and (rows.value, pairs.value) == (0, 0)
     L.dvs_pairs_destroy(out)
@@ -588,18 +594,18 @@ def test_c_entries_refuse_bad_arguments_and_leave_the_context_usable(ctx):
             distance.matrix_within(m, other, 0.1)
         many = np.zeros(big, np.uint32)  # row 0, `big` times over: a reference list beyond the square entries' row limit
         u32 = lambda a: _lib.ptr(a, C.c_uint32)  # noqa: E731
-        for entry in ("dvs_jsd_within", "dvs_euclidean_within"):
-            assert refused(entry, m._h, None, 11, m._h, None, 10, 0.1, 0, 0) == _lib.ERR_VALUE  # more rows than the handle holds
-            assert refused(entry, m._h, u32(np.array([0, 10], np.uint32)), 2, m._h, None, 10, 0.1, 0, 0) == _lib.ERR_VALUE
-            assert refused(entry, m._h, None, 10, m._h, u32(many), big, 0.1, 0, 0) == _lib.ERR_UNSUPPORTED
-            assert refused(entry, m._h, None, 10, m._h, None, 10, float("nan"), 0, 0) == _lib.ERR_VALUE
-            assert refused(entry, m._h, None, 10, None, None, 10, 0.1, 0, 0) == _lib.ERR_VALUE
-        for entry in ("dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters"):
+        for kind in (_lib.SRC_JSD, _lib.SRC_EUCLIDEAN):
+            all10 = S(kind, m._h, 10)
+            assert refused(S(kind, m._h, 11), all10, 0.1, 0, 0) == _lib.ERR_VALUE  # more rows than the handle holds
+            assert refused(S(kind, m._h, 2, np.array([0, 10], np.uint32)), all10, 0.1, 0, 0) == _lib.ERR_VALUE
+            assert refused(all10, S(kind, m._h, big, many), 0.1, 0, 0) == _lib.ERR_UNSUPPORTED
+            assert refused(all10, all10, float("nan"), 0, 0) == _lib.ERR_VALUE
+            assert refused(all10, S(kind, None, 10), 0.1, 0, 0) == _lib.ERR_VALUE
             lab[:], cnt.value = 7, 99
-            f = getattr(L, entry)
-            assert f(ctx._h, m._h, u32(many), big, 0.1, u32(np.full(big, 7, np.uint32)), C.byref(cnt)) == _lib.ERR_UNSUPPORTED
-            assert f(ctx._h, m._h, None, 11, 0.1, u32(lab), C.byref(cnt)) == _lib.ERR_VALUE
-            assert f(ctx._h, m._h, None, 10, float("nan"), u32(lab), C.byref(cnt)) == _lib.ERR_VALUE
+            f = L.dvs_threshold_clusters
+            assert f(ctx._h, S(kind, m._h, big, many), 0.1, u32(np.full(big, 7, np.uint32)), C.byref(cnt)) == _lib.ERR_UNSUPPORTED
+            assert f(ctx._h, S(kind, m._h, 11), 0.1, u32(lab), C.byref(cnt)) == _lib.ERR_VALUE
+            assert f(ctx._h, all10, float("nan"), u32(lab), C.byref(cnt)) == _lib.ERR_VALUE
             assert (lab == 7).all() and cnt.value == 99
         with pytest.raises(NotImplementedError):
             distance.matrix_within(m, m, 0.1, "jsd", r_rows=many)
@@ -607,11 +613,13 @@ def test_c_entries_refuse_bad_arguments_and_leave_the_context_usable(ctx):
             distance.matrix_threshold_clusters(m, 0.1, "euclidean", rows=many)
         sk = distance.Sketches(_seqs(np.random.default_rng(2), 10), 8, 20, ctx=ctx)
         try:
-            assert refused("dvs_sketches_within", sk._h, None, 10, sk._h, u32(many), big, 8, 20, 0.1, 0, 0) == _lib.ERR_UNSUPPORTED
-            assert refused("dvs_sketches_within", sk._h, None, 11, sk._h, None, 10, 8, 20, 0.1, 0, 0) == _lib.ERR_VALUE
+            mash = {"k": 8, "sketch_size": 20}
+            all10 = S(_lib.SRC_MASH, sk._h, 10, **mash)
+            assert refused(all10, S(_lib.SRC_MASH, sk._h, big, many, **mash), 0.1, 0, 0) == _lib.ERR_UNSUPPORTED
+            assert refused(S(_lib.SRC_MASH, sk._h, 11, **mash), all10, 0.1, 0, 0) == _lib.ERR_VALUE
             lab[:], cnt.value = 7, 99
-            assert L.dvs_sketches_threshold_clusters(ctx._h, sk._h, u32(many), big, 8, 20, 0.1, u32(np.full(big, 7, np.uint32)),
-                                                     C.byref(cnt)) == _lib.ERR_UNSUPPORTED and cnt.value == 99
+            assert L.dvs_threshold_clusters(ctx._h, S(_lib.SRC_MASH, sk._h, big, many, **mash), 0.1,
+                                            u32(np.full(big, 7, np.uint32)), C.byref(cnt)) == _lib.ERR_UNSUPPORTED and cnt.value == 99
         finally:
             sk.close()
         nb = distance.matrix_within(m, m, float("inf"), "jsd", q_rows=[], r_rows=None)
@@ -623,3 +631,91 @@ def test_c_entries_refuse_bad_arguments_and_leave_the_context_usable(ctx):
         m.close()
         other.close()
     assert_within(cluster.within(d, 4 / 64, ctx=ctx), d, 4 / 64, True)
+
+
+def test_the_source_check_refuses_before_any_device_work(ctx):
+    """what every entry checks of its dvs_source before anything else (DVS_ERR_VALUE), and the combinations no entry
+    serves (DVS_ERR_UNSUPPORTED): the code, a message, and the context usable afterwards.  10 rows at k = 3; every output
+    is poisoned and must come back untouched -- nothing was launched, nothing written"""
+    L, S = ctx._L, distance.make_source
+    u32, f64 = (lambda a: _lib.ptr(a, C.c_uint32)), (lambda a: _lib.ptr(a, C.c_double))
+    seqs = _seqs(np.random.default_rng(5), 10)
+    m, sk = ctx.build_matrix(seqs, 3, 4), distance.Sketches(seqs, 3, 20, ctx=ctx)
+    d = tie_matrix(10, 3)
+    other = d.copy()
+    rows = np.array([0, 2, 4], np.uint32)
+    mash = {"k": 3, "sketch_size": 20}
+    jsd, euc, sketches, given = S(_lib.SRC_JSD, m._h, 10), S(_lib.SRC_EUCLIDEAN, m._h, 10), S(_lib.SRC_MASH, sk._h, 10, **mash), \
+        S(_lib.SRC_GIVEN, d.ctypes.data, 10)
+    dist, idx = np.full((10, 10), 7.0), np.full((10, 10), 7, np.uint32)
+    tree = (np.full(18, 7, np.uint32), np.full(9, 7.0), np.full(9, 7, np.uint32))
+    nj = (np.full(24, 7, np.uint32), np.full(24, 7.0))
+    seeds, cnt, cover = np.zeros(1, np.uint32), C.c_uint32(7), C.c_double(7.0)
+    mm = (np.full(10, 7, np.uint32), np.full(10, 7.0), np.full(10, 7, np.uint32), np.full(10, 7.0))
+    out = C.c_void_p()
+
+    ops = {  # every entry over one source, or over a (queries, references) pair
+        "distances": lambda s: L.dvs_distances(ctx._h, s, f64(dist)),
+        "linkage": lambda s: L.dvs_linkage(ctx._h, s, 2, u32(tree[0]), f64(tree[1]), u32(tree[2])),
+        "nj": lambda s: L.dvs_nj(ctx._h, s, u32(nj[0]), f64(nj[1])),
+        "maxmin": lambda s: L.dvs_maxmin(ctx._h, s, u32(seeds), 1, 3, 0, 0.0, u32(mm[0]), f64(mm[1]), C.byref(cnt), u32(mm[2]),
+                                         f64(mm[3]), C.byref(cover)),
+        "cluster_scores": lambda s: L.dvs_cluster_scores(ctx._h, s, u32(np.zeros(10, np.uint32)), 1, f64(dist), None, None, None,
+                                                         None, None),
+        "cophenet": lambda s: L.dvs_cophenet(ctx._h, s, u32(np.zeros(18, np.uint32)), f64(np.zeros(9)), C.byref(cover), None, None),
+        "threshold_clusters": lambda s: L.dvs_threshold_clusters(ctx._h, s, 0.1, u32(idx), C.byref(cnt)),
+    }
+    pair_ops = {
+        "cross_distances": lambda q, r: L.dvs_cross_distances(ctx._h, q, r, f64(dist)),
+        "nearest": lambda q, r: L.dvs_nearest(ctx._h, q, r, 1, u32(idx), f64(dist)),
+        "within": lambda q, r: L.dvs_within(ctx._h, q, r, 0.1, 0, 0, C.byref(out)),
+    }
+
+    def refused(rc, code, what):
+        assert rc == code, (what, rc)
+        assert L.dvs_last_error(ctx._h), what  # a message
+        assert (dist == 7.0).all() and (idx == 7).all() and cnt.value == 7 and cover.value == 7.0 and not out.value, what
+        assert all((a == 7).all() for a in (*tree, *nj, *mm)), what
+
+    try:
+        bad = {"an unknown kind": S(4, m._h, 10), "a null matrix": S(_lib.SRC_JSD, None, 10),
+               "null sketches": S(_lib.SRC_MASH, None, 10, **mash), "a null caller's matrix": S(_lib.SRC_GIVEN, None, 10),
+               "a caller's matrix with a row list": S(_lib.SRC_GIVEN, d.ctypes.data, 3, rows)}
+        for what, src in bad.items():
+            for op, call in ops.items():
+                refused(call(src), _lib.ERR_VALUE, (op, what))
+                refused(call(None), _lib.ERR_VALUE, (op, "no source"))
+            for op, call in pair_ops.items():
+                refused(call(src, src), _lib.ERR_VALUE, (op, what))
+                refused(call(jsd, src), _lib.ERR_VALUE, (op, what, "as the references"))
+                refused(call(jsd, None), _lib.ERR_VALUE, (op, "no references"))
+        for op, call in pair_ops.items():
+            refused(call(jsd, euc), _lib.ERR_VALUE, (op, "jsd against euclidean"))
+            refused(call(sketches, jsd), _lib.ERR_VALUE, (op, "mash against jsd"))
+            refused(call(given, jsd), _lib.ERR_VALUE, (op, "a caller's matrix against jsd"))
+            refused(call(sketches, S(_lib.SRC_MASH, sk._h, 10, k=4, sketch_size=20)), _lib.ERR_VALUE, (op, "another k"))
+            refused(call(sketches, S(_lib.SRC_MASH, sk._h, 10, k=3, sketch_size=21)), _lib.ERR_VALUE, (op, "another sketch size"))
+        # the combinations no entry has served
+        for op in ("distances", "cross_distances", "nearest"):
+            rc = ops[op](given) if op in ops else pair_ops[op](given, given)
+            refused(rc, _lib.ERR_UNSUPPORTED, (op, "a caller's matrix"))
+            assert f"dvs_{op}".encode() in L.dvs_last_error(ctx._h) and b"given" in L.dvs_last_error(ctx._h)
+        for kind, handle, extra in ((_lib.SRC_JSD, m._h, {}), (_lib.SRC_EUCLIDEAN, m._h, {}), (_lib.SRC_MASH, sk._h, mash)):
+            for op in ("distances", "linkage", "nj"):
+                refused(ops[op](S(kind, handle, 3, rows, **extra)), _lib.ERR_UNSUPPORTED, (op, kind, "a row list"))
+                refused(ops[op](S(kind, handle, 9, **extra)), _lib.ERR_UNSUPPORTED, (op, kind, "9 rows of 10"))
+                assert f"dvs_{op}".encode() in L.dvs_last_error(ctx._h)
+            refused(ops["maxmin"](S(kind, handle, 3, rows, **extra)), _lib.ERR_UNSUPPORTED, ("maxmin", kind, "a row list"))
+            assert b"dvs_maxmin" in L.dvs_last_error(ctx._h)
+        refused(pair_ops["within"](given, S(_lib.SRC_GIVEN, other.ctypes.data, 10)), _lib.ERR_UNSUPPORTED, "within: two matrices")
+        assert b"dvs_within" in L.dvs_last_error(ctx._h) and b"given" in L.dvs_last_error(ctx._h)
+        # the same context serves valid calls of every kind afterwards
+        assert_within(cluster.within(d, 4 / 64, ctx=ctx), d, 4 / 64, True)
+        assert pair_ops["within"](given, given) == _lib.OK and out.value  # the same matrix named twice is the matrix against itself
+        L.dvs_pairs_destroy(out)
+        assert same_bits(distance.matrix_cross_distances(m, m, "jsd"), distance.matrix_jsd_distances(m))  # (every row has k-mers)
+        assert np.array_equal(sk.distances(), distance.DeviceSide(sk, "mash").distances())
+        assert distance.matrix_maxmin(m, 3, mode="euclidean").picks.size == 3
+    finally:
+        m.close()
+        sk.close()

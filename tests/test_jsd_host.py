@@ -33,7 +33,7 @@ def oracle_jsd_matrix(seqs, k: int, num_states: int = 4) -> np.ndarray:
 def test_public_names_exist():
     assert callable(distance.jsd_distances) and callable(distance.jsd_linkage)
     assert callable(apps.dvs_dist) and "dvs_dist" in apps.__all__
-    assert {"dvs_jsd_distances", "dvs_matrix_jsd_linkage"} <= set(_lib.EXPORTS)
+    assert {"dvs_distances", "dvs_linkage"} <= set(_lib.EXPORTS) and _lib.SRC_JSD == 2  # the mode travels in the dvs_source
 
 
 def test_dvs_dist_constructor_checks():

@@ -148,12 +148,12 @@ def test_public_names_exist():
     assert distance.MaxMin._fields == ("picks", "radius", "owner", "dist", "cover")
     assert callable(distance.Sketches.maxmin) and callable(cluster.maxmin) and callable(engine.Selection.diversify)
     assert callable(apps.dvs_maxmin) and "dvs_maxmin" in apps.__all__
-    new = {"dvs_maxmin", "dvs_sketches_maxmin", "dvs_matrix_jsd_maxmin", "dvs_matrix_euclidean_maxmin"}
+    new = {"dvs_maxmin"}  # one entry: the mode, or the caller's matrix, travels in the dvs_source
     assert new <= set(_lib.EXPORTS)
     lib = _lib.load()
     for name in new:
         assert getattr(lib, name).argtypes is not None, name
-    assert lib.dvs_abi_version() == 3
+    assert lib.dvs_abi_version() == 4
 
 
 # ------------------------------------------------------------------ argument errors come before any device work

@@ -435,8 +435,8 @@ def test_argument_errors_need_no_device():
 
 def test_c_boundary_without_a_device():
     L = _lib.load()
-    assert L.dvs_abi_version() == 3
-    names = ("dvs_nj", "dvs_sketches_nj", "dvs_matrix_euclidean_nj", "dvs_matrix_jsd_nj", "dvs_nj_patristic")
+    assert L.dvs_abi_version() == 4
+    names = ("dvs_nj", "dvs_nj_patristic")  # one entry for the tree: the mode, or the caller's matrix, travels in the dvs_source
     lib = C.CDLL(str(_lib.LIB_PATH))
     for name in names:
         assert name in _lib.EXPORTS and hasattr(lib, name)
@@ -449,4 +449,5 @@ def test_c_boundary_without_a_device():
     assert L.dvs_nj_patristic(None, 2, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64), out.ctypes.data_as(f64)) == _lib.ERR_VALUE
     assert L.dvs_nj_patristic(None, 3, None, lens.ctypes.data_as(f64), out.ctypes.data_as(f64)) == _lib.ERR_VALUE
     # a null context is refused before anything else
-    assert L.dvs_nj(None, out.ctypes.data_as(C.c_void_p), 0, 3, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE
+    given = distance.make_source(_lib.SRC_GIVEN, out.ctypes.data, 3, keep=out)
+    assert L.dvs_nj(None, given, joins.ctypes.data_as(u32), lens.ctypes.data_as(f64)) == _lib.ERR_VALUE

@@ -22,9 +22,7 @@ from test_jsd_host import oracle_jsd_matrix
 # radius of the case is its middle
 FAMILY_WIDEST_GAP = (4.4e-3, 1.3e-1)
 
-NEW_EXPORTS = {"dvs_jsd_within", "dvs_euclidean_within", "dvs_sketches_within", "dvs_within", "dvs_pairs_destroy",
-               "dvs_pairs_info", "dvs_pairs_get", "dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters",
-               "dvs_sketches_threshold_clusters", "dvs_threshold_clusters"}
+NEW_EXPORTS = {"dvs_within", "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get", "dvs_threshold_clusters"}
 
 
 # ------------------------------------------------------------------ the yardsticks
@@ -105,14 +103,19 @@ def test_public_names_and_exports():
     lib = _lib.load()
     for name in NEW_EXPORTS:
         assert getattr(lib, name).argtypes is not None, name
-    assert lib.dvs_abi_version() == 3
+    assert lib.dvs_abi_version() == 4
     assert _lib.WITHIN_SKIP_SELF == 1
-    # the dense table is left as it is: the sparse operations have one of their own, and _entry reads both
-    assert set(distance.DeviceSide.ENTRIES) == {"distances", "linkage", "nj", "cross_distances", "nearest", "cluster_scores",
-                                                "cophenet", "maxmin"}
-    assert set(distance.DeviceSide.SPARSE_ENTRIES) == {"within", "threshold_clusters"}
-    for op, entries in distance.DeviceSide.SPARSE_ENTRIES.items():
-        assert len(entries) == 3 and set(entries) <= NEW_EXPORTS, op
+    # no table of entries per mode any more: every operation, dense or sparse, is a method of DeviceSide over ONE entry,
+    # which every mode reaches through the kind of its dvs_source
+    for op in ("distances", "linkage", "nj", "cross_distances", "nearest", "cluster_scores", "cophenet", "maxmin", "within",
+               "threshold_clusters"):
+        assert callable(getattr(distance.DeviceSide, op)), op
+        assert f"dvs_{op}" in _lib.EXPORTS and getattr(lib, f"dvs_{op}").argtypes[1] == C.POINTER(_lib.Source), op
+    for op in ("within", "threshold_clusters"):
+        assert not [name for name in _lib.EXPORTS if name.endswith("_" + op) and name != f"dvs_{op}"], op
+    assert [_lib.SRC_MASH, _lib.SRC_EUCLIDEAN, _lib.SRC_JSD] == [distance.DeviceSide.MODE_NAMES.index(m)
+                                                                 for m in ("mash", "euclidean", "jsd")]
+    assert _lib.SRC_GIVEN == 3
 
 
 # ------------------------------------------------------------------ argument errors come before any device work
@@ -218,16 +221,17 @@ def test_c_entries_refuse_their_arguments_before_any_device_work():
     out = C.c_void_p(0xDEAD)
     d = np.zeros((2, 2))
     lab, cnt = np.zeros(2, np.uint32), C.c_uint32()
-    assert lib.dvs_within(None, _lib.ptr(d, C.c_double), 0, 2, 0.5, 0, 0, C.byref(out)) == _lib.ERR_VALUE
+    given = distance.make_source(_lib.SRC_GIVEN, d.ctypes.data, 2, keep=d)
+    assert lib.dvs_within(None, given, None, 0.5, 0, 0, C.byref(out)) == _lib.ERR_VALUE
     assert not out.value  # *out is NULL after an error, whatever it held
-    assert lib.dvs_threshold_clusters(None, _lib.ptr(d, C.c_double), 0, 2, 0.5, _lib.ptr(lab, C.c_uint32),
-                                      C.byref(cnt)) == _lib.ERR_VALUE
-    for name in ("dvs_jsd_within", "dvs_euclidean_within"):
-        assert getattr(lib, name)(None, None, None, 0, None, None, 0, 0.5, 0, 0, C.byref(out)) == _lib.ERR_VALUE
-    assert lib.dvs_sketches_within(None, None, None, 0, None, None, 0, 3, 10, 0.5, 0, 0, C.byref(out)) == _lib.ERR_VALUE
-    for name in ("dvs_jsd_threshold_clusters", "dvs_euclidean_threshold_clusters"):
-        assert getattr(lib, name)(None, None, None, 0, 0.5, None, None) == _lib.ERR_VALUE
-    assert lib.dvs_sketches_threshold_clusters(None, None, None, 0, 3, 10, 0.5, None, None) == _lib.ERR_VALUE
+    assert lib.dvs_threshold_clusters(None, given, 0.5, _lib.ptr(lab, C.c_uint32), C.byref(cnt)) == _lib.ERR_VALUE
+    for kind, mash in ((_lib.SRC_JSD, {}), (_lib.SRC_EUCLIDEAN, {}), (_lib.SRC_MASH, {"k": 3, "sketch_size": 10})):
+        null = distance.make_source(kind, None, 0, **mash)  # a NULL handle, as the typed entries were handed
+        for q, r in ((null, null), (None, None)):
+            out = C.c_void_p(0xDEAD)
+            assert lib.dvs_within(None, q, r, 0.5, 0, 0, C.byref(out)) == _lib.ERR_VALUE
+            assert not out.value
+            assert lib.dvs_threshold_clusters(None, q, 0.5, None, None) == _lib.ERR_VALUE
     assert lib.dvs_pairs_info(None, None, None) == _lib.ERR_VALUE
     assert lib.dvs_pairs_get(None, None, None, None) == _lib.ERR_VALUE
     lib.dvs_pairs_destroy(None)
