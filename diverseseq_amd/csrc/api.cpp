@@ -1,6 +1,7 @@
 // Context, errors, matrix build / accessors of the C ABI (include/dvs_hip.h).
 #include "dvs_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -150,6 +151,10 @@ void dvs_knobs_from_env(dvs_knobs *k) {
     k->test_rowlog_ring = 0;
     if (const char *rr = tk ? strstr(tk, "rowlog_ring_") : nullptr) k->test_rowlog_ring = uint32_t(strtoul(rr + 12, nullptr, 10));
     k->test_poison_blocks = tk && strstr(tk, "poison_blocks") != nullptr;
+    if (const char *ic = tk ? strstr(tk, "ingest_chunk_") : nullptr)
+        k->test_ingest_chunk = uint32_t(std::min<unsigned long>(std::max<unsigned long>(strtoul(ic + 13, nullptr, 10), 1ul), 256ul));
+    if (const char *rc = tk ? strstr(tk, "ingest_reccap_") : nullptr)
+        k->test_ingest_reccap = std::max<uint64_t>(strtoull(rc + 14, nullptr, 10), 1ull);
 }
 
 extern "C" {

@@ -58,6 +58,13 @@ struct dvs_knobs {
     // bytes over its whole rounded size and the fill waited for; dvs_pinned_get fills its 4 KiB host block likewise.  A
     // read before the first write then sees NaN / all-ones instead of zeros or the last call's values
     bool test_poison_blocks = false;
+    // test-only (DVS_TEST_KNOBS=ingest_chunk_<n>): the streamed FASTA upload travels in chunks of n blocks of 128 KiB
+    // (clamped to 1 .. 256) instead of 256, so that files of three chunks and more -- the streaming threshold keeps
+    // its form -- are a few hundred KiB and every chunk seam can be reached with a small file (0: 256 blocks, 32 MiB)
+    uint32_t test_ingest_chunk = 0;
+    // test-only (DVS_TEST_KNOBS=ingest_reccap_<n>): the ingest's record arrays start with room for n >= 1 records
+    // instead of nbytes / 256 + 2^20, so that a file of a few records overflows them and the last pass is repeated
+    uint64_t test_ingest_reccap = 0;
 };
 void dvs_knobs_from_env(dvs_knobs *k);
 

@@ -376,7 +376,8 @@ extern "C" int dvs_seqbatch_from_fasta(dvs_ctx *ctx, const uint8_t *raw, int raw
     } while (0)
     // chunks: the whole file at once when it is already in HBM (or small), else 32 MiB pieces
     uint64_t chunk_blocks = nb ? nb : 1;
-    const uint64_t CH_BLOCKS = (32ull << 20) / ING_BLOCK;
+    // (test-only ingest_chunk_<n>: chunks of n blocks, so that the seams between chunks fall into small files)
+    const uint64_t CH_BLOCKS = ctx->knobs.test_ingest_chunk ? ctx->knobs.test_ingest_chunk : (32ull << 20) / ING_BLOCK;
     const bool streamed = !raw_on_device && nb >= 3 * CH_BLOCKS && !ctx->knobs.ingest_no_stream;
     constexpr int NSLOT = 4;
     if (raw_on_device) {
@@ -408,7 +409,8 @@ extern "C" int dvs_seqbatch_from_fasta(dvs_ctx *ctx, const uint8_t *raw, int raw
     // The number of records is known only at the end; the arrays are sized for records of >= 256 bytes on
     // average (+ 1 M) and the kernel raises a flag instead of writing beyond them -- then the last pass is
     // repeated over the whole file with arrays of the right size.
-    unsigned long long rec_cap = nbytes / 256 + (1ull << 20);
+    // (test-only ingest_reccap_<n>: room for n records, so that a small file takes the repeated pass)
+    unsigned long long rec_cap = ctx->knobs.test_ingest_reccap ? ctx->knobs.test_ingest_reccap : nbytes / 256 + (1ull << 20);
     ING_RC(dvs_dev_alloc(ctx, (void **)&d_rec, rec_cap * 8, "record starts"));
     ING_RC(dvs_dev_alloc(ctx, (void **)&d_hdr, rec_cap * 8, "header positions"));
     // the encoded bases: never more than the file's bytes
