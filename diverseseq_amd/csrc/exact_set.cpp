@@ -417,10 +417,10 @@ int dvs_select_arbitrate(dvs_ctx *ctx, dvs_select *s) {
             if (stepwise) {
                 const uint32_t at = a.replayed + i;
                 // (the whole log is on the host: dvs_select_step_poll drained the device ring before it called here)
-                if (uint64_t(at) >= s->rowlog_have)
+                if (uint64_t(at) >= s->fs.rowlog_have)
                     return dvs_set_error(ctx, DVS_ERR_RUNTIME, "tie arbitration in the stepwise mode: event %u is not in the "
-                                         "accepted rows' log (%llu rows)", at, (unsigned long long)s->rowlog_have);
-                rc = fetch_host_row(ctx, s, pos[i], s->h_rowlog.data() + uint64_t(at) * B, set, r);
+                                         "accepted rows' log (%llu rows)", at, (unsigned long long)s->fs.rowlog_have);
+                rc = fetch_host_row(ctx, s, pos[i], s->fs.h_rowlog.data() + uint64_t(at) * B, set, r);
             } else {
                 rc = fetch_row(ctx, s, pos[i], set, r);
             }

@@ -3248,7 +3248,7 @@ static const void *persist_fn(const dvs_select *s) {
     const bool cached = s->dev.B <= uint64_t(P_J) * P_THREADS;
     if (s->params.mode == DVS_MODE_MAX) return reinterpret_cast<const void *>(persist_nmost_kernel<T, true, true>);
     if constexpr (std::is_same_v<T, uint16_t>) {
-        if (s->persist_small) return reinterpret_cast<const void *>(persist_nmost_kernel<T, true, false, true>);
+        if (s->persist.small) return reinterpret_cast<const void *>(persist_nmost_kernel<T, true, false, true>);
     }
     return cached ? reinterpret_cast<const void *>(persist_nmost_kernel<T, true>)
                   : reinterpret_cast<const void *>(persist_nmost_kernel<T, false>);
@@ -3260,11 +3260,11 @@ static const void *persist_fn(const dvs_select *s) {
 // blocks (and a host image: the async upload may read it after this returns) of its own, so the
 // full-grid launch's can be made ready while the head phase is still running.
 static int persist_prepare(dvs_ctx *ctx, dvs_select *s, uint32_t head_stop, hipStream_t on) {
-    std::vector<unsigned char> &image = head_stop ? s->h_psync_head : s->h_psync;
+    std::vector<unsigned char> &image = head_stop ? s->persist.h_sync_head : s->persist.h_sync;
     image.assign(sizeof(PSync), 0);
     PSync &init = *reinterpret_cast<PSync *>(image.data());
     init.stop_at = head_stop;
-    init.seeded = s->persist_seeded ? 1u : 0u;  // (the first launch of a selection whose set-up kernels were skipped)
+    init.seeded = s->persist.seeded ? 1u : 0u;  // (the first launch of a selection whose set-up kernels were skipped)
     init.seed_list = static_cast<const unsigned long long *>(s->d_seed_list);
     for (int g = 0; g < 8; g++) init.rel[g].hint = ~0ull;  // (atomicMin targets; every other word starts as zero)
     // a row per workgroup while a window is at most this many rounds of the grid (default policy only)
@@ -3273,11 +3273,11 @@ static int persist_prepare(dvs_ctx *ctx, dvs_select *s, uint32_t head_stop, hipS
     if (ctx->knobs.persist_wg_rounds >= 0) init.wg_thresh = uint32_t(ctx->knobs.persist_wg_rounds);
     init.no_coarse = (ctx->knobs.persist_no_coarse ? 1u : 0u) | (ctx->knobs.persist_no_events ? 2u : 0u) |
                      0u;
-    init.small_rows = s->persist_small ? s->persist_small_rows : 0u;
-    init.lds_bytes = uint32_t(s->persist_lds);
+    init.small_rows = s->persist.small ? s->persist.small_rows : 0u;
+    init.lds_bytes = uint32_t(s->persist.lds);
     init.wmax = uint32_t(std::min<uint64_t>(s->npos, 0xFFFFFFFFull));
-    DVS_HIP(ctx, hipMemcpyAsync(head_stop ? s->psync_head : s->psync, &init, sizeof init, hipMemcpyHostToDevice, on));
-    DVS_HIP(ctx, hipMemsetAsync(head_stop ? s->ppart_head : s->ppart, 0, p_acc_bytes(s->persist_maxn), on));
+    DVS_HIP(ctx, hipMemcpyAsync(head_stop ? s->persist.sync_head : s->persist.sync, &init, sizeof init, hipMemcpyHostToDevice, on));
+    DVS_HIP(ctx, hipMemsetAsync(head_stop ? s->persist.part_head : s->persist.part, 0, p_acc_bytes(s->persist.maxn), on));
     return DVS_OK;
 }
 
@@ -3287,19 +3287,19 @@ template <typename T>
 static int persist_launch(dvs_ctx *ctx, dvs_select *s, const T *mat, uint32_t grid, uint32_t head_stop,
                           hipStream_t on) {
     const SelDev &d = s->dev;
-    if (head_stop ? !s->head_prepared : !s->persist_prepared) {
+    if (head_stop ? !s->persist.head_prepared : !s->persist.prepared) {
         int prc = persist_prepare(ctx, s, head_stop, on);
         if (prc) return prc;
     }
-    if (head_stop) s->head_prepared = false;
-    else s->persist_prepared = false;
-    s->persist_seeded = false;  // (only the first launch of a selection starts from the seeds)
+    if (head_stop) s->persist.head_prepared = false;
+    else s->persist.prepared = false;
+    s->persist.seeded = false;  // (only the first launch of a selection starts from the seeds)
     const hipEvent_t e1 = dvs_scan_timing_start(ctx, s, on);
     const void *fn = persist_fn<T>(s);
     SelDev d_arg = d;
     const T *mat_arg = mat;
-    PSync *sync_arg = static_cast<PSync *>(head_stop ? s->psync_head : s->psync);
-    unsigned long long *part_arg = static_cast<unsigned long long *>(head_stop ? s->ppart_head : s->ppart);
+    PSync *sync_arg = static_cast<PSync *>(head_stop ? s->persist.sync_head : s->persist.sync);
+    unsigned long long *part_arg = static_cast<unsigned long long *>(head_stop ? s->persist.part_head : s->persist.part);
     uint32_t g_arg = grid;
     void *args[] = {&d_arg, &mat_arg, &sync_arg, &part_arg, &g_arg};
     // The grid barrier needs every workgroup resident: dvs_persist_setup checked that the device holds
@@ -3310,7 +3310,7 @@ static int persist_launch(dvs_ctx *ctx, dvs_select *s, const T *mat, uint32_t gr
     // check of the same arithmetic and no reservation, and costs ~0.2 ms per selection on this stack
     // (a step of 2.13 -> 1.91 ms without it: the launch itself starts 40 us later, the memset in front
     // of it and the copy behind it take 35 us longer each, and the kernel runs 3 % slower): it is not used.
-    hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(P_THREADS), args, s->persist_lds, on);
+    hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(P_THREADS), args, s->persist.lds, on);
     if (s->time_scan) (void)hipEventRecord(e1, on);
     if (le != hipSuccess) {
         (void)hipGetLastError();
@@ -3322,19 +3322,19 @@ static int persist_launch(dvs_ctx *ctx, dvs_select *s, const T *mat, uint32_t gr
 
 int dvs_persist_setup(dvs_ctx *ctx, dvs_select *s) {
     const uint64_t B = s->dev.B;
-    s->persist = false;
+    s->persist.on = false;
     if (ctx->knobs.no_persist || ctx->persist_timeouts >= 3) return DVS_OK;
     // a process-wide CU mask hides CUs the device still reports: the grid below could never be resident
     if (ctx->knobs.cu_mask_set) return DVS_OK;
     const bool maxm = s->params.mode == DVS_MODE_MAX;
     if ((s->params.mode != DVS_MODE_NMOST && !maxm) || !s->h_order.empty() || !s->h_labels.empty()) return DVS_OK;
     if (s->npos >= P_POS_NONE) return DVS_OK;  // (window words hold 37-bit positions)
-    s->persist_grid = uint32_t(std::min(ctx->n_cu, int(P_MAXG)));  // one 512-thread workgroup per CU: all resident
+    s->persist.grid = uint32_t(std::min(ctx->n_cu, int(P_MAXG)));  // one 512-thread workgroup per CU: all resident
     const bool cached = B <= uint64_t(P_J) * P_THREADS;
     if (maxm && !cached) return DVS_OK;  // (the growth phase wants the candidate in registers and S in LDS)
     // SMALL sets (see the kernel): nmost, 16-bit rows of 4096 bins, every member's row in LDS
-    s->persist_small_rows = s->params.n_seed;
-    s->persist_small = !maxm && s->params.mode == DVS_MODE_NMOST && s->mat_kind == 2 && B == 4096 &&
+    s->persist.small_rows = s->params.n_seed;
+    s->persist.small = !maxm && s->params.mode == DVS_MODE_NMOST && s->mat_kind == 2 && B == 4096 &&
                        s->params.n_seed >= 2 && s->params.n_seed <= P_SMALL_ROWS && !ctx->knobs.persist_no_small;
     auto lds_for = [&](uint32_t maxn_) {
         return ((B + 1) & ~1ull) * 8 + (cached && s->mat_kind != 1 ? ((B + 3) & ~3ull) * 4 : 0) +
@@ -3344,21 +3344,21 @@ int dvs_persist_setup(dvs_ctx *ctx, dvs_select *s) {
                (maxm ? p_batch_lds() : 0);
     };
     size_t lds = lds_for(p_maxn(cached, maxm));
-    if (s->persist_small) {
-        const size_t lds_small = lds_for(P_SMALLN) + size_t(s->persist_small_rows) * B * 2 + 16;
+    if (s->persist.small) {
+        const size_t lds_small = lds_for(P_SMALLN) + size_t(s->persist.small_rows) * B * 2 + 16;
         if (lds_small <= ctx->lds_per_block) lds = lds_small;
-        else s->persist_small = false;
+        else s->persist.small = false;
     }
     // OWN (see the kernel): nmost over count rows in the register cache beyond SMALL -- the slot map and this
     // workgroup's own member's counts
-    if (cached && !maxm && s->mat_kind != 1 && !s->persist_small)
+    if (cached && !maxm && s->mat_kind != 1 && !s->persist.small)
         lds += size_t(p_maxn(cached, maxm)) * 4 + size_t(P_J) * P_THREADS * (s->mat_kind == 2 ? 2 : 4);
-    s->persist_maxn = s->persist_small ? P_SMALLN : p_maxn(cached, maxm);
-    s->persist_maxjobs = s->persist_small ? P_SMALLN + 1 : p_maxjobs(cached, maxm);
+    s->persist.maxn = s->persist.small ? P_SMALLN : p_maxn(cached, maxm);
+    s->persist.maxjobs = s->persist.small ? P_SMALLN + 1 : p_maxjobs(cached, maxm);
     // (MODE_MAX: max_size may be the whole stream; the kernel hands over when its LDS replica is full)
-    if (!maxm && s->cap > s->persist_maxn) return DVS_OK;
+    if (!maxm && s->cap > s->persist.maxn) return DVS_OK;
     if (lds > ctx->lds_per_block) return DVS_OK;
-    s->persist_lds = lds;
+    s->persist.lds = lds;
     const void *fn = dvs_mat_dispatch(s->mat, [&](auto *mp) -> const void * {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(mp)>>;
         return persist_fn<T>(s);
@@ -3377,11 +3377,11 @@ int dvs_persist_setup(dvs_ctx *ctx, dvs_select *s) {
         }
         if (!hit->second) return DVS_OK;
     }
-    rc = dvs_dev_alloc(ctx, &s->psync, sizeof(PSync), "persistent sync block");
-    if (!rc) rc = dvs_dev_alloc(ctx, &s->ppart, p_acc_bytes(s->persist_maxn) + (maxm ? 2 * p_batch_bytes() : 0),
+    rc = dvs_dev_alloc(ctx, &s->persist.sync, sizeof(PSync), "persistent sync block");
+    if (!rc) rc = dvs_dev_alloc(ctx, &s->persist.part, p_acc_bytes(s->persist.maxn) + (maxm ? 2 * p_batch_bytes() : 0),
                                 "leave-one-out accumulators");  // (MODE_MAX: + the results of a batch's jobs)
     if (rc) return rc;
-    s->persist = true;
+    s->persist.on = true;
     return DVS_OK;
 }
 
@@ -3451,9 +3451,9 @@ static void persist_trace_report(const void *blk, uint32_t G) {
 // DVS_PERSIST_DEBUG, at every poll of a selection on the persistent engine: what its launches left in their sync blocks
 // (the head phase's launch first, then the full grid's) on stderr -- scripts/stamps_to_json.py parses these lines
 void dvs_persist_debug_report(dvs_ctx *ctx, const dvs_select *s) {
-    for (int which = 0; which < 2 && s->persist; which++) {
+    for (int which = 0; which < 2 && s->persist.on; which++) {
         unsigned long long dbg[32];  // dbg2[16] then dbg[16]
-        const void *blk = which ? s->psync : s->psync_head;
+        const void *blk = which ? s->persist.sync : s->persist.sync_head;
         if (!blk || hipMemcpy(dbg, static_cast<const char *>(blk) + offsetof(PSync, dbg2), sizeof dbg, hipMemcpyDeviceToHost) != hipSuccess)
             continue;
         fprintf(stderr, "[dvs persist] %s launch\n", which ? "full-grid" : "head-phase");
@@ -3472,7 +3472,7 @@ void dvs_persist_debug_report(dvs_ctx *ctx, const dvs_select *s) {
                     dbg[6 + 16 * w] / 100.0, dbg[7 + 16 * w] / 100.0, dbg[8 + 16 * w] / 100.0,
                     dbg[5 + 16 * w] / 100.0);
 #ifdef DVS_PERSIST_STAMPS
-        persist_trace_report(blk, which ? s->persist_grid : uint32_t(ctx->head_cus));
+        persist_trace_report(blk, which ? s->persist.grid : uint32_t(ctx->head_cus));
 #endif
         if (dbg[15] + dbg[14])
             fprintf(stderr, "[dvs persist block 0] accepts for which its leave-one-out job was ready when the release came: %llu (the candidate's frequencies: %llu)\n", dbg[15], dbg[14]);
@@ -3493,14 +3493,21 @@ void dvs_persist_debug_done(const SelCtl &c) {
             c.why[4], c.why[5], c.why[6], c.why[7]);
 }
 
+void dvs_persist_free(dvs_select *s) {
+    dvs_dev_free(s->ctx, s->persist.sync);
+    dvs_dev_free(s->ctx, s->persist.part);
+    dvs_dev_free(s->ctx, s->persist.sync_head);
+    dvs_dev_free(s->ctx, s->persist.part_head);
+}
+
 int dvs_persist_launch(dvs_ctx *ctx, dvs_select *s) {
-    return dvs_mat_dispatch(s->mat, [&](auto *mp) { return persist_launch(ctx, s, mp, s->persist_grid, 0u, ctx->stream); });
+    return dvs_mat_dispatch(s->mat, [&](auto *mp) { return persist_launch(ctx, s, mp, s->persist.grid, 0u, ctx->stream); });
 }
 
 static int persist_head_blocks(dvs_ctx *ctx, dvs_select *s) {
-    if (s->psync_head) return DVS_OK;
-    int rc = dvs_dev_alloc(ctx, &s->psync_head, sizeof(PSync), "head phase sync block");
-    if (!rc) rc = dvs_dev_alloc(ctx, &s->ppart_head, p_acc_bytes(s->persist_maxn), "head phase accumulators");
+    if (s->persist.sync_head) return DVS_OK;
+    int rc = dvs_dev_alloc(ctx, &s->persist.sync_head, sizeof(PSync), "head phase sync block");
+    if (!rc) rc = dvs_dev_alloc(ctx, &s->persist.part_head, p_acc_bytes(s->persist.maxn), "head phase accumulators");
     return rc;
 }
 
@@ -3514,14 +3521,14 @@ int dvs_persist_launch_head(dvs_ctx *ctx, dvs_select *s, uint32_t grid, uint32_t
 int dvs_persist_prepare_head(dvs_ctx *ctx, dvs_select *s, uint32_t stop_at, hipStream_t on) {
     int rc = persist_head_blocks(ctx, s);
     if (!rc) rc = persist_prepare(ctx, s, stop_at, on);
-    if (!rc) s->head_prepared = true;
+    if (!rc) s->persist.head_prepared = true;
     return rc;
 }
 
 // the full-grid launch's blocks, made ready on the context's stream ahead of the launch itself
 int dvs_persist_prepare_main(dvs_ctx *ctx, dvs_select *s) {
     int rc = persist_prepare(ctx, s, 0u, ctx->stream);
-    if (!rc) s->persist_prepared = true;
+    if (!rc) s->persist.prepared = true;
     return rc;
 }
 

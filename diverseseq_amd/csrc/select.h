@@ -1,4 +1,5 @@
-// Shared between select.hip (device engine) and exact_set.cpp (host tie arbiter).
+// Shared between the selection's translation units (select.hip, stepwise.hip, maxbatch.hip, persist.hip) and
+// exact_set.cpp (host tie arbiter).
 #pragma once
 
 #include "dvs_internal.h"
@@ -78,7 +79,7 @@ struct SelDev {
     const double *gather_all = nullptr;
     uint32_t gather_world = 0;
     // ... and the frequency row of every accepted event, in event-log order, as a RING of rowlog_cap rows that the
-    // host drains at every poll (dvs_select::h_rowlog holds the whole log): what the
+    // host drains at every poll (dvs_select::fs.h_rowlog holds the whole log): what the
     // tie arbiter replays from when the rows themselves live on other ranks
     double *rowlog = nullptr;
     uint32_t rowlog_cap = 0;
@@ -105,23 +106,28 @@ struct dvs_select {
     bool base_in_lds = true;
     bool scan_hot = false;
     // persistent single-launch engine (persist.hip)
-    bool persist = false;
-    uint32_t persist_grid = 0, persist_maxn = 0, persist_maxjobs = 0;
-    bool persist_small = false;       // the SMALL instantiation: member count rows in every workgroup's LDS
-    uint32_t persist_small_rows = 0;  // ... that many of them
-    size_t persist_lds = 0;
-    void *psync = nullptr;
-    std::vector<unsigned char> h_psync;  // host image of the sync block (source of its upload)
-    std::vector<unsigned char> h_psync_head;  // ... and the head phase's
-    void *ppart = nullptr;
-    double *d_mbres = nullptr;  // MODE_MAX batches (select.hip: max_batch_*): the jobs' results, 3 x MB_ROWS x mb_jw
-    uint32_t mb_jw = 0;
-    uint32_t mb_launched = 0;   // batch pairs launched (summary / tests)
-    void *psync_head = nullptr, *ppart_head = nullptr;  // the head phase's own blocks
-    bool persist_seeded = false;    // the next persistent launch starts from the seed positions (no set-up kernels ran)
-    bool seeded_start = false;      // ... this selection began that way (sel_run_loop: a launch may hand the set-up back)
-    bool head_prepared = false;     // ... and psync_head / ppart_head for the head phase
-    bool persist_prepared = false;  // psync / ppart already hold a fresh image for the next full-grid launch
+    struct {
+        bool on = false;
+        uint32_t grid = 0, maxn = 0, maxjobs = 0;
+        bool small = false;       // the SMALL instantiation: member count rows in every workgroup's LDS
+        uint32_t small_rows = 0;  // ... that many of them
+        size_t lds = 0;
+        void *sync = nullptr;
+        std::vector<unsigned char> h_sync;  // host image of the sync block (source of its upload)
+        std::vector<unsigned char> h_sync_head;  // ... and the head phase's
+        void *part = nullptr;
+        void *sync_head = nullptr, *part_head = nullptr;  // the head phase's own blocks
+        bool seeded = false;         // the next persistent launch starts from the seed positions (no set-up kernels ran)
+        bool head_prepared = false;  // sync_head / part_head hold a fresh image for the head phase
+        bool prepared = false;       // sync / part already hold a fresh image for the next full-grid launch
+    } persist;
+    // MODE_MAX batches (maxbatch.hip)
+    struct {
+        double *d_res = nullptr;  // the jobs' results, 3 x MB_ROWS x jw
+        uint32_t jw = 0;
+        uint32_t launched = 0;    // batch pairs launched (summary / tests)
+    } mb;
+    bool seeded_start = false;      // this selection began with a seeded persistent launch (sel_run_loop: a launch may hand the set-up back)
     bool used_side_streams = false;   // work of this selection was queued on ctx->stream_head / stream2 (sel_free waits)
     hipEvent_t ev_side_done = nullptr;  // the set-up kernels on the context's second stream have run
     void *d_seed_list = nullptr;  // the seed positions on the device (kept until the selection goes: two streams read it)
@@ -139,22 +145,25 @@ struct dvs_select {
     uint64_t scan_launches = 0;
     uint32_t n_arbitrated = 0;
     double arbiter_ms = 0.0;    // host wall clock inside dvs_select_arbitrate
-    // stepwise selections, MODE_NMOST without labels: the fast step (select.hip fs_jobs_kernel / fs_step_kernel)
-    bool fast_step = false;
-    bool fs_need_scan = false;   // the next dvs_select_step_pack must scan first (selection start, behind an arbitration)
-    unsigned long long *h_fshist = nullptr;  // pinned: the status word of every apply launch (FS_HIST of them, dvs_select_step_peek; every fast step has it)
-    unsigned long long fs_launches = 0;      // apply launches of the fast step so far
-    unsigned long long fs_peek_floor = 0;    // ... of them, those enqueued before the last dvs_select_step_poll
-    double *fs_slot = nullptr;   // the caller's slot of the last dvs_select_step_pack (the next step's kernel packs into it)
-    double *fs_packed = nullptr; // ... and the slot the last fs_step_kernel launch packed (nullptr: none)
-    double *d_jobres = nullptr;  // the leave-one-out jobs' sums of the current step
-    void *d_fsync = nullptr;     // FsSync
-    uint32_t fs_K = 1, fs_jobs = 0, fs_grid = 0;
-    size_t fs_lds = 0;
-    // stepwise selections: the accepted rows' log on the host (drained from the device ring by dvs_select_step_poll)
-    std::vector<double> h_rowlog;
-    uint64_t rowlog_have = 0;       // rows of it that are on the host
-    uint32_t steps_since_poll = 0;  // dvs_select_step_apply calls since the last poll (bounded by the ring)
+    // stepwise selections (stepwise.hip)
+    struct {
+        // MODE_NMOST without labels: the fast step (fs_jobs_kernel / fs_step_kernel)
+        bool on = false;
+        bool need_scan = false;   // the next dvs_select_step_pack must scan first (selection start, behind an arbitration)
+        unsigned long long *h_hist = nullptr;  // pinned: the status word of every apply launch (FS_HIST of them, dvs_select_step_peek; every fast step has it)
+        unsigned long long launches = 0;      // apply launches of the fast step so far
+        unsigned long long peek_floor = 0;    // ... of them, those enqueued before the last dvs_select_step_poll
+        double *slot = nullptr;   // the caller's slot of the last dvs_select_step_pack (the next step's kernel packs into it)
+        double *packed = nullptr; // ... and the slot the last fs_step_kernel launch packed (nullptr: none)
+        double *d_jobres = nullptr;  // the leave-one-out jobs' sums of the current step
+        void *d_sync = nullptr;      // FsSync
+        uint32_t K = 1, jobs = 0, grid = 0;
+        size_t lds = 0;
+        // the accepted rows' log on the host (drained from the device ring by dvs_select_step_poll)
+        std::vector<double> h_rowlog;
+        uint64_t rowlog_have = 0;       // rows of it that are on the host
+        uint32_t steps_since_poll = 0;  // dvs_select_step_apply calls since the last poll (bounded by the ring)
+    } fs;
     void *arbiter = nullptr;  // ExactSet*, created on first use
 };
 
@@ -165,6 +174,7 @@ void dvs_select_arbiter_free(dvs_select *s);
 
 // persist.hip
 int dvs_persist_setup(dvs_ctx *ctx, dvs_select *s);
+void dvs_persist_free(dvs_select *s);  // its blocks back to the context's pool (sel_free; so the two *_free below)
 int dvs_persist_launch(dvs_ctx *ctx, dvs_select *s);
 int dvs_persist_launch_head(dvs_ctx *ctx, dvs_select *s, uint32_t grid, uint32_t stop_at, hipStream_t on);
 int dvs_persist_prepare_main(dvs_ctx *ctx, dvs_select *s);
@@ -175,3 +185,23 @@ void dvs_persist_debug_done(const SelCtl &c);                        // ... and 
 // select.hip: s->time_scan -- the next (start, stop) pair of the selection's event pool, the start recorded on `on`;
 // returns the stop, which the caller records behind its launch (the next poll adds the pair up)
 hipEvent_t dvs_scan_timing_start(dvs_ctx *ctx, dvs_select *s, hipStream_t on);
+// ... what the stepwise entries share with the run-to-completion driver, enqueued on the context's stream: one scan
+// launch (`hot` picks the instantiation) / the launches of one iteration from `stage` on (0 scan, 1 resolve, 2 loo) /
+// the control block into h_ctl, waited for / the host arbiter's verdict on the decision h_ctl stopped at and the
+// launches that carry on from it
+void dvs_select_launch_scan(dvs_ctx *ctx, dvs_select *s, bool hot);
+void dvs_select_launch_iteration(dvs_ctx *ctx, dvs_select *s, int stage);
+int dvs_select_poll(dvs_ctx *ctx, dvs_select *s);
+int dvs_select_arbitrate_resume(dvs_ctx *ctx, dvs_select *s);
+
+// stepwise.hip (the dvs_select_step_* entries of include/dvs_hip.h live there too)
+int dvs_stepwise_alloc(dvs_ctx *ctx, dvs_select *s, const uint32_t *labels);  // sel_alloc, DVS_SELECT_STEPWISE: the row ring, the fast step's blocks
+void dvs_stepwise_wait(dvs_select *s);  // sel_free: the fast step's queued launches, before h_ctl goes back to the pinned cache
+void dvs_stepwise_free(dvs_select *s);
+#ifdef DVS_FS_TRACE
+void dvs_stepwise_trace_report(const dvs_select *s);
+#endif
+
+// maxbatch.hip: one batch pair on the context's stream (size_bound: no set this launch can meet is larger)
+int dvs_max_batch_launch(dvs_ctx *ctx, dvs_select *s, uint32_t size_bound);
+void dvs_max_batch_free(dvs_select *s);

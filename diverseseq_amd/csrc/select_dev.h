@@ -1,9 +1,12 @@
-// Device helpers shared by the selection kernels (select.hip, persist.hip).
+// Device helpers shared by the selection kernels (select.hip, stepwise.hip, maxbatch.hip, persist.hip).
 #pragma once
 
 #include "select.h"
 
 namespace {
+
+constexpr int WIDE_THREADS = 1024;  // single-block state kernels
+constexpr int LOO_THREADS = 256;
 
 // sum_{x>0} -x log2 x over the bins a thread owns, plus what the reference's
 // entropy() (src/record.rs:86-106) is sensitive to: a negative bin (log2 -> NaN)

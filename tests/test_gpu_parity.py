@@ -555,7 +555,7 @@ def test_max_mode_batches_of_consecutive_events(ctx, k, min_size, max_size, stat
     m = ctx.build_matrix(seqs, k, 4)
     sel = m.max_divergent(min_size, mx, stat)
     s = _assert_selection(sel, oracle.max_divergent(seqs, min_size, mx, k, 4, stat))
-    # 4^7 bins: not the persistent engine's -- the multi-launch kernels' own batches (select.hip: max_batch_*)
+    # 4^7 bins: not the persistent engine's -- the multi-launch kernels' own batches (maxbatch.hip: max_batch_*)
     assert s.engine == (1 if k <= 6 else 0)
     if max_size is None and stat == "stdev":  # (under cov nearly every push of this stream is kept: nothing to batch)
         assert s.n_events > 300 and s.n_windows * 4 < s.n_events, (s.n_windows, s.n_events)  # (batches were formed)
