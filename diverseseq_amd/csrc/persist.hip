@@ -28,30 +28,10 @@
 // inside the rounding band stops the kernel with SEL_ARBITER; the host arbitrates and
 // runs that one event through the multi-launch kernels, then relaunches this one.
 //
-// Inter-workgroup protocol (MI355X: 8 XCDs, private L2s; written down in DESIGN.md 4.3c).  Nothing a
-// workgroup stores with plain stores is read by another workgroup during the launch: the matrix, totals
-// and row entropies are read-only (a member's frequency row is re-derived from its matrix row, whose
-// position every workgroup keeps in LDS) and the set state is replicated.  What crosses workgroups are
-// single 64-bit words, read and written with relaxed agent-scope atomics, and every one of them carries
-// in itself what a reader needs to know that it is the word it is waiting for -- no word's meaning depends
-// on the order in which stores to two different addresses become visible:
-//   * WINDOW words carry the window's number in their top bits (p_word).  A workgroup that has scanned its
-//     share stores ONE arrival record (its first event, how many near-threshold candidates it listed); the
-//     mirror block, which scans nothing, polls the records, and when all carry the window's number stores
-//     the release word (the window's first event) to eight copies that the others poll.  Events found
-//     early also go, by atomicMin, to a hint word beside the release word so that waves can stop scanning
-//     rows behind them; a newer window's tag is SMALLER, so a straggler of an older window never wins, and
-//     nothing is ever cleared.  The outcome never depends on a hint: a wave only skips rows behind a hint
-//     of the current window, and whoever posted that hint has the same event in its record.
-//   * LEAVE-ONE-OUT sums are added to monotonic accumulators (fixed point + a contribution count in the low
-//     bits, p_acc_word) that are never cleared: every workgroup remembers the totals it read at the previous
-//     use (LDS) and takes the difference; the count's difference says when the K contributions are in.
-// The counter barrier below (grid_barrier) is a pure rendezvous for the few places that still want one (the
-// seeded start, `max` batches): two-level monotonic arrival counters (per group of blockIdx % 8, then one
-// top counter) and a generation word per group, all on their own cache lines, zeroed by the host before
-// every launch; every spin is bounded (a grid that is not fully resident ends with SEL_ERROR instead of
-// hanging).
-#include "select_dev.h"
+// What crosses workgroups, and how: persist_dev.h.  The scan tiers: persist_scan.h.  The macros of the measurement and
+// stress builds: persist_probe.h.  What DVS_PERSIST_DEBUG prints: persist_report.hip.
+#include "persist_scan.h"
+#include "persist_probe.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -61,795 +41,9 @@
 
 namespace {
 
-constexpr int P_THREADS = 512;
-constexpr int P_J = 8;                      // bins per thread kept in registers (B <= 4096)
-constexpr int P_CH = 16;                    // row chunks requested per burst (4096 bins)
-constexpr uint32_t P_MAXN = 512;            // members the LDS replica holds when 4^k <= 4096 ...
-constexpr uint32_t P_MAXN_BIG = 256;        // ... and beyond (k = 7: 128 KB of LDS go to the set state)
-constexpr uint32_t P_MAXN_MAX = 896;        // ... `max` with 4^k <= 4096 (sets grow; what 160 KB of LDS hold beside S, sl and the batches)
-constexpr uint32_t p_maxn(bool cached, bool maxm = false) { return cached ? (maxm ? P_MAXN_MAX : P_MAXN) : P_MAXN_BIG; }
-// SMALL sets (nmost over 16-bit count rows of 4096 bins): the members' count rows live in every
-// workgroup's LDS (see the kernel)
-constexpr uint32_t P_SMALLN = 16;      // members the replica arrays of a SMALL launch hold ...
-constexpr uint32_t P_SMALL_ROWS = 13;  // ... and rows (8 KB each) that fit beside the state in 160 KB of LDS
-// leave-one-out jobs per event: (n + 1) * K <= max(G - 1, n + 1) <= maxn + 1 (G <= maxn + 2 is checked)
-constexpr uint32_t p_maxjobs(bool cached, bool maxm = false) { return p_maxn(cached, maxm) + 1; }
-// leave-one-out accumulators: 8 group replicas x (maxn + 1) members x 2 words, zeroed by the host before the
-// launch and never cleared again.  A word = (2^-50 fixed-point sum << 6) + number of contributions, added to
-// by every job of every use; a reader keeps the totals it read at the previous use (LDS, p_prev) and works
-// with the DIFFERENCE: its low six bits are the contributions of this use -- complete at K -- and the rest
-// is their sum (two's complement: wrap-around cancels in the difference; |sum| < 64 per use and K <= 32
-// keep one use inside the word).  Integer addition is associative, so the totals do not depend on the order
-// the jobs arrive in; nothing is ever reset, so there is no clear that a late add could race with, and an
-// add can never be mistaken for one of an earlier use: the earlier use was complete, in every replica,
-// when it was read (each job adds the same word to all eight replicas).
-constexpr size_t p_acc_bytes(uint32_t maxn) { return size_t(8) * (maxn + 1) * 2 * sizeof(unsigned long long); }
-__device__ __forceinline__ unsigned long long p_acc_word(double v) {
-    return ((unsigned long long)__double2ll_rn(v * 0x1p50) << 6) + 1ull;
-}
-__device__ __forceinline__ double p_acc_value(unsigned long long w) { return double((long long)w >> 6) * 0x1p-50; }
-// A job's two words added to an accumulator pair (non-returning adds: the readers wait for the counts)
-__device__ __forceinline__ void p_acc_add(unsigned long long *dst, double th, double ts) {
-    atomicAdd(dst, p_acc_word(th));
-    atomicAdd(dst + 1, p_acc_word(ts));
-}
-__device__ __forceinline__ uint32_t p_acc_count(unsigned long long w) { return uint32_t(w & 63ull); }
-// this use's share of an accumulator word once all K contributions are in: (total now) - (total at the previous
-// use, *prev, which is brought up to date).  Bounded spin: ok = false on a time-out (an error and the
-// multi-launch kernels, never a wrong total).
-__device__ __forceinline__ unsigned long long p_acc_complete(const unsigned long long *w, unsigned long long *prev,
-                                                             uint32_t K, bool &ok) {
-    const unsigned long long before = *prev;
-    unsigned long long v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t spins = 0;
-    while (uint32_t((v - before) & 63ull) != K) {
-        if (++spins > (1u << 20)) {
-            ok = false;
-            break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        v = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    *prev = v;
-    return v - before;
-}
-constexpr uint32_t P_SPIN_LIMIT = 1u << 22;  // ~0.5 s of polling
-constexpr uint32_t P_MAXG = 256;             // workgroups a launch may have (one arrival record each)
-constexpr uint32_t P_FLAT_GRID = 64;         // counter barrier: grids of up to this many workgroups use one counter
-constexpr uint32_t P_WINWORDS = 64;          // LDS words of a window's bookkeeping (s_win)
-constexpr uint32_t P_LIST = 2;               // near-threshold candidates a workgroup lists per window (more become plain events)
-// MODE_MAX, growth phase: consecutive rows evaluated against the same set in one go (see the kernel)
-constexpr uint32_t P_BATCH = 32;             // rows per batch at most
-constexpr uint32_t P_BATCH_MEMBERS = 256;    // set size + 2 up to which batches are formed (4 members per lane)
-constexpr size_t p_batch_bytes() { return size_t(P_BATCH) * (P_BATCH_MEMBERS + 2) * 4 * sizeof(double); }
-constexpr size_t p_batch_lds() { return size_t(P_BATCH) * (2 + 12 + 24) * sizeof(double); }
-
-struct PLine {  // a polled word on a cache line of its own (256 B apart)
-    uint32_t v;
-    uint32_t pad[63];
-};
-struct PRel {  // what a waiting workgroup polls with ONE 16-byte load, on a cache line of its own
-    unsigned long long rel;   // the release word of the current window: its first event (window word, below)
-    unsigned long long hint;  // events posted so far (atomicMin of window words; starts as all ones)
-    unsigned long long pad[30];
-};
-
-struct PSync {
-    uint32_t count;  // counter barrier: top-level arrivals (one per group and barrier), monotonic over the launch
-    uint32_t pad0[63];
-    PLine gcount[8];  // ... arrivals of group g = blockIdx % 8 (workgroups are dealt round-robin to the 8 XCDs)
-    PLine ggen[8];    // ... completed barriers, one copy per group so 32 pollers share a line, not 256
-    uint32_t timeout;
-    uint32_t wg_thresh;  // windows of up to wg_thresh rows per workgroup are scanned a row per WORKGROUP (0: never)
-    float wg_scale;      // ... and are cursor * wg_scale / size rows long (rounded up to whole rounds)
-    uint32_t no_coarse;  // measurement aid: skip the COARSE tier
-    uint32_t stop_at;    // head phase: leave at this stream position with status RUN (0: walk the whole stream)
-    uint32_t seeded;     // the set is still only its seed positions: the launch works the initial state out itself
-    const unsigned long long *seed_list;  // ... those positions (ctl->size of them)
-    uint32_t small_rows;  // SMALL instantiation: member rows the LDS replica has room for
-    uint32_t lds_bytes;   // the launch's dynamic LDS (a -DDVS_PERSIST_STAMPS build keeps its ticks in the last 128 bytes)
-    uint32_t wmax;        // longest window of this engine (the control block's cap is the multi-launch scan's)
-    uint32_t pad2[53];
-    PRel rel[8];                            // one copy per group g = blockIdx % 8
-    // Two sets of arrival records and listed candidates, taking turns by the window's parity: a workgroup that is
-    // still walking window e's listed candidates reads the others' records and entries of window e, while a quick
-    // one may already have scanned window e + 1 and stored its record for it.  Window e + 2's words (the same set as
-    // e's) cannot be written before every workgroup has stored its record for e + 1, i.e. has left window e.
-    unsigned long long wrec[2][P_MAXG];          // arrival record of every workgroup (a window word)
-    unsigned long long soft[2][P_MAXG][P_LIST];  // the candidates a workgroup listed in the window (window words)
-#ifdef DVS_PERSIST_STAMPS
-    // four traced windows (epochs 12, 24, 36, 48): 100 MHz ticks per workgroup at the window's top, at its arrival record,
-    // when it saw the release; [3] = the gathering block's own: gather begun, last record seen, release stored
-    // [4..6]: the accept behind the window: this workgroup's job published (or nothing to publish), its totals read, its
-    // rebuild of sl done
-    unsigned long long trace[4][8][P_MAXG];  // ([7]: the speculative job's sums handed to the accumulators, or that point passed)
-#endif
-    unsigned long long dbg2[16];   // block 0 (owns a job): phase ticks
-    unsigned long long dbg[16];    // mirror block: 100 MHz ticks per phase (scan, bar1, resolve, loo, bar2, finalize)
-};
-
-struct PState {  // replicated scalars (identical in every workgroup)
-    uint64_t cursor, npos;
-    uint32_t window, wmin, wmax;
-    uint32_t n, li;
-    double sumH, total_jsd, thr, band, wscale;
-    uint32_t n_windows, n_events, n_accepts;
-    // MODE_MAX: the set grows while it is below max_size (tentative pushes, records.rs:427-451)
-    uint32_t max_size, stat;
-    double mean_d, std_d, cov_d;  // statistics of the current set's delta_jsd
-};
-
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-// ---- window words.  [63:40] tag = P_TAG0 - window number (a NEWER window has the SMALLER tag: an atomicMin
-// prefers it and a straggler of an older window can never replace it; all ones -- the hint words' initial
-// value -- and zero -- everything else's -- are no window's tag), [39:3] stream position (all ones: none),
-// [2:1] candidates listed (arrival record: how many this workgroup listed; release word: non-zero if anybody
-// did), [0] set when the event is not a sure one (its exact score decides).
-constexpr uint32_t P_TAG0 = 0xFFFFFEu;
-constexpr uint32_t P_EPOCH_MAX = 0xFFFFF0u;  // windows a launch may walk (it leaves with status RUN there)
-constexpr unsigned long long P_POS_NONE = (1ull << 37) - 1;
-__device__ __forceinline__ unsigned long long p_word(uint32_t epoch, uint64_t pos, bool sure) {
-    return ((unsigned long long)(P_TAG0 - epoch) << 40) | ((pos == SEL_NONE ? P_POS_NONE : pos) << 3) | (sure ? 0ull : 1ull);
-}
-__device__ __forceinline__ bool p_word_is(unsigned long long w, uint32_t epoch) { return uint32_t(w >> 40) == P_TAG0 - epoch; }
-// the position a word of window `epoch` names (SEL_NONE: none, or a word of another window)
-__device__ __forceinline__ uint64_t p_word_pos(unsigned long long w, uint32_t epoch) {
-    const unsigned long long pos = (w >> 3) & P_POS_NONE;
-    return (!p_word_is(w, epoch) || pos == P_POS_NONE) ? SEL_NONE : uint64_t(pos);
-}
-__device__ __forceinline__ bool p_word_sure(unsigned long long w) { return (w & 1ull) == 0; }
-__device__ __forceinline__ uint32_t p_word_listed(unsigned long long w) { return uint32_t(w >> 1) & 3u; }
-
-// returns false on timeout (every thread of the block gets the same answer).
-// Two levels: a workgroup arrives on its group's counter, the last of a group arrives on the top
-// counter, the last group publishes the generation to all eight group words.  Measured on MI355X
-// (scripts/micro/barrier_bench.hip, 256 workgroups): 1.9 us against 3.7 us for one counter + one
-// word -- the 256 same-address atomics serialise at ~11 ns each.
-// The barrier is a pure rendezvous: no fences.  What is handed across it are atomic words whose readers
-// can tell that they are complete (the accumulators' contribution counts) or whose writer consumed the
-// result of the exchange that put them there (the `max` batches' results); the matrix is read-only for the
-// whole launch, and what the mirror block stores to global memory is read by nobody before the kernel
-// ends.  (An agent-scope release + acquire pair around the barrier -- L2 write-back and invalidate on
-// every XCD -- cost another 4 us per barrier.)
-__device__ bool grid_barrier(PSync *sync, uint32_t G, uint32_t &gen, int *s_ok) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t target = gen + 1;
-        const uint32_t x = blockIdx.x & 7u, ng = G < 8u ? G : 8u;
-        const uint32_t gsz = (G - x + 7u) >> 3;  // workgroups with blockIdx % 8 == x
-        int ok = 1;
-        bool released = false;
-        const bool last = G <= P_FLAT_GRID
-                              ? __hip_atomic_fetch_add(&sync->count, 1u, RLX_AGENT) == G * target - 1
-                              : (__hip_atomic_fetch_add(&sync->gcount[x].v, 1u, RLX_AGENT) == gsz * target - 1 &&
-                                 __hip_atomic_fetch_add(&sync->count, 1u, RLX_AGENT) == ng * target - 1);
-        if (last) {
-            for (uint32_t g = 0; g < ng; g++) __hip_atomic_store(&sync->ggen[g].v, target, RLX_AGENT);
-            released = true;
-        }
-        if (!released) {
-            uint32_t spins = 0;
-            while (__hip_atomic_load(&sync->ggen[x].v, RLX_AGENT) < target) {
-                if ((++spins & 255u) == 0 &&
-                    (spins > P_SPIN_LIMIT || __hip_atomic_load(&sync->timeout, RLX_AGENT))) {
-                    __hip_atomic_store(&sync->timeout, 1u, RLX_AGENT);
-                    ok = 0;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        *s_ok = ok;
-    }
-    __syncthreads();
-    gen++;
-    return *s_ok != 0;
-}
-
-// 16 bytes in one agent-scope load (one request for a PRel's two words; each word validates itself)
-__device__ __forceinline__ uint4 p_load16_agent(const void *ptr) {
-    uint4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(ptr) : "memory");
-    return v;
-}
-
-// What a scanning wave needs of the window it is in (uniform values).
-struct PWin {
-    uint32_t epoch;               // the window's number
-    const unsigned long long *hintp;  // this group's hint word
-    PRel *rel;                    // the eight group copies (hints are posted to all of them)
-    unsigned long long *wgev;     // LDS: this workgroup's first event so far (becomes its arrival record)
-    uint32_t *nlist;              // LDS: candidates this workgroup has listed in this window
-    unsigned long long *mysoft;   // this workgroup's list entries (sync->soft[epoch & 1][blockIdx.x])
-};
-// the first event posted so far in this window, as far as this group's hint word knows
-__device__ __forceinline__ uint64_t p_hint_pos(const PWin &w) {
-    return p_word_pos(__hip_atomic_load(w.hintp, RLX_AGENT), w.epoch);
-}
-// An event found by a wave (called by its lanes 0..7 at least): into the workgroup's record (LDS) and, as a
-// hint for the waves still scanning, into every group's hint word -- fire and forget, nothing waits for it.
-__device__ __forceinline__ void p_post_event_wave(const PWin &w, uint64_t p, bool sure, uint32_t lane) {
-    const unsigned long long word = p_word(w.epoch, p, sure);
-    if (lane == 0) atomicMin(w.wgev, word);
-    if (lane < 8) atomicMin(&w.rel[lane].hint, word);
-}
-__device__ __forceinline__ void p_post_event_thread(const PWin &w, uint64_t p, bool sure) {
-    const unsigned long long word = p_word(w.epoch, p, sure);
-    atomicMin(w.wgev, word);
-    for (uint32_t g = 0; g < 8; g++) atomicMin(&w.rel[g].hint, word);
-}
-// A candidate whose fast score is within FAST_BAND of the threshold: listed, not an event -- the scan goes on
-// and the workgroups settle it in f64 after the rendezvous.  A workgroup's list holds P_LIST entries per
-// window (window words: a reader knows which window an entry belongs to); the count travels in its arrival
-// record.  A full list makes the candidate a plain (unsure) event.  One thread.
-__device__ __forceinline__ void p_list_candidate(const PWin &w, uint64_t p) {
-    const uint32_t idx = atomicAdd(w.nlist, 1u);
-    if (idx < P_LIST) __hip_atomic_store(w.mysoft + idx, p_word(w.epoch, p, false), RLX_AGENT);
-    else p_post_event_thread(w, p, false);
-}
-// wave-wide minimum of 64-bit words by DPP (register cross-lane moves, as dvs_wave_sum_dpp): every lane gets it
-template <int CTRL>
-__device__ __forceinline__ unsigned long long p_dpp_mov_u64(unsigned long long v) {
-    int lo = int(uint32_t(v)), hi = int(uint32_t(v >> 32));
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return ((unsigned long long)uint32_t(hi) << 32) | uint32_t(lo);
-}
-__device__ __forceinline__ unsigned long long p_wave_min_u64(unsigned long long v) {
-    auto mn = [](unsigned long long a, unsigned long long b) { return b < a ? b : a; };
-    v = mn(v, p_dpp_mov_u64<0xB1>(v));   // quad_perm [1,0,3,2]
-    v = mn(v, p_dpp_mov_u64<0x4E>(v));   // quad_perm [2,3,0,1]
-    v = mn(v, p_dpp_mov_u64<0x141>(v));  // row_half_mirror
-    v = mn(v, p_dpp_mov_u64<0x140>(v));  // row_mirror: every lane holds the minimum of its row of 16
-    const int lo = int(uint32_t(v)), hi = int(uint32_t(v >> 32));
-    auto row = [&](int l) {
-        return ((unsigned long long)uint32_t(__builtin_amdgcn_readlane(hi, l)) << 32) | uint32_t(__builtin_amdgcn_readlane(lo, l));
-    };
-    return mn(mn(row(0), row(16)), mn(row(32), row(48)));
-}
-
-// The gathering block's part of a window's rendezvous, by ONE wave: lane l waits for the arrival records of
-// workgroups l, l + 64, l + 128, l + 192 (four loads in flight per look; records of other windows are not looked
-// at twice), the minimum is taken by DPP, lanes 0..7 store the release word -- no LDS, no barrier between the last
-// record's arrival and the release.  `own`: the gathering block's own record.  Returns the release word; ok = false
-// on a time-out (the launch is then given up: sync->timeout).  seen_all / stored: 100 MHz ticks (stamps builds).
-__device__ __forceinline__ unsigned long long p_gather(PSync *sync, uint32_t G, uint32_t epoch, unsigned long long own,
-                                                       uint32_t lane, bool &ok, unsigned long long *seen_all = nullptr,
-                                                       unsigned long long *stored = nullptr) {
-    constexpr uint32_t Q = P_MAXG / 64;
-    unsigned long long w[Q];
-    bool have[Q];
-#pragma unroll
-    for (uint32_t q = 0; q < Q; q++) {
-        w[q] = ~0ull;
-        have[q] = lane + 64 * q >= G - 1;  // (this workgroup's own record is `own`)
-    }
-    uint32_t spins = 0;
-    ok = true;
-    for (;;) {
-        unsigned long long got[Q];
-#pragma unroll
-        for (uint32_t q = 0; q < Q; q++)
-            got[q] = have[q] ? 0ull : __hip_atomic_load(&sync->wrec[epoch & 1u][lane + 64 * q], RLX_AGENT);
-        bool all = true;
-#pragma unroll
-        for (uint32_t q = 0; q < Q; q++) {
-            if (!have[q] && p_word_is(got[q], epoch)) {
-                w[q] = got[q];
-                have[q] = true;
-            }
-            all = all && have[q];
-        }
-        if (__ballot(!all) == 0ull) break;
-        if ((++spins & 255u) == 0 && (spins > P_SPIN_LIMIT || __hip_atomic_load(&sync->timeout, RLX_AGENT))) {
-            ok = false;
-            break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    if (seen_all) *seen_all = __builtin_amdgcn_s_memrealtime();
-    unsigned long long m = own & ~6ull, fl = own & 6ull;
-#pragma unroll
-    for (uint32_t q = 0; q < Q; q++)
-        if (lane + 64 * q < G - 1 && have[q]) {
-            m = (w[q] & ~6ull) < m ? (w[q] & ~6ull) : m;
-            fl |= w[q] & 6ull;
-        }
-    m = p_wave_min_u64(m);
-    const bool anyl = __ballot(fl != 0ull) != 0ull;
-    const unsigned long long relw = m | (anyl ? 2ull : 0ull);
-    if (ok && lane < 8) __hip_atomic_store(&sync->rel[lane].rel, relw, RLX_AGENT);
-    if (!ok && lane == 0) __hip_atomic_store(&sync->timeout, 1u, RLX_AGENT);
-    if (stored) *stored = __builtin_amdgcn_s_memrealtime();
-    return relw;
-}
-
-// One wave's share of the window, as scan_rows_hot but against the unscaled vector sl:
-// x = (sl_i + c_i / T) / n  computed as  fma(c, 1/T, sl) * (1/n).
-template <typename T, bool COARSE>
-__device__ __forceinline__ void p_scan_rows(const T *__restrict__ mat,
-                                            const uint32_t *__restrict__ totals,
-                                            const double *__restrict__ rowH, const double *sl,
-                                            const float *slf, uint64_t B, const PState &st, double he_base,
-                                            const PWin &win,
-                                            uint64_t first, uint64_t stride, uint64_t nrows,
-                                            uint32_t lane, uint32_t &nread,
-                                            uint32_t &nprecise, uint32_t &nmid, bool coarse_on,
-                                            bool burst_drop = true) {
-    const double dn = double(st.n), rn = 1.0 / dn;
-    const double thr_lo = st.thr - st.band;
-    const double thr_fast = thr_lo - FAST_BAND, thr_sure = st.thr + st.band + FAST_BAND;
-    (void)thr_lo;
-    const bool vec = (B & 255) == 0;
-    const double cband = coarse_band(B);
-    const double thr_c_lo = st.thr - st.band - cband, thr_c_hi = st.thr + st.band + cband;
-    for (uint64_t r = first; r < nrows; r += stride) {
-        const uint64_t p = st.cursor + r;
-        const T *rp = mat + p * B;
-        const uint64_t ev = p_hint_pos(win);
-        const uint32_t tot = totals[p];
-        const double hrow = rowH[p];
-        if (ev < p) break;
-        if (tot == 0) continue;
-        const double rt = 1.0 / double(tot);
-        const double mean_entropy = (he_base + hrow) / dn;
-        nread++;
-        if constexpr (COARSE) {
-            if (vec && coarse_on) {  // COARSE tier: decides every row farther than cband from the threshold
-                const float rtn = float(rt * rn);
-                const dvs_f2 r2 = {rtn, rtn};
-                double c0 = 0.0, c1 = 0.0;
-                bool done16 = false;
-                if constexpr (sizeof(T) == 2) {
-                    // 16-bit rows of 4096 bins: eight 16-byte loads per lane (lane l owns bins
-                    // 512 j + 8 l .. + 7), the whole 8 KiB row requested at once.  (Requesting it beside the
-                    // look at the event word instead of behind it -- all of it, half, a quarter -- measured
-                    // the same step and event-free pass, and half again as much traffic for rows dropped.)
-                    if (B == 4096) {
-                        uint4 raw8[8];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) raw8[j] = *reinterpret_cast<const uint4 *>(rp + j * 512 + lane * 8);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            asm volatile("" : "+v"(raw8[j].x), "+v"(raw8[j].y), "+v"(raw8[j].z), "+v"(raw8[j].w));
-                            coarse8(raw8[j], slf + j * 512 + lane * 8, r2, c0, c1);
-                        }
-                        done16 = true;
-                    }
-                }
-                if (!done16) {
-                // Bursts of C_CH chunks: 4 KiB of a row requested at a time keep the memory pipe as full
-                // as 16 KiB do (scripts/micro/stream_read.hip), and a row that an earlier event has made
-                // pointless is dropped at the next burst with its other bytes never requested.
-                constexpr int C_CH = sizeof(T) == 2 ? 16 : 8;  // (16-bit rows: the same bytes per burst)
-                const uint64_t full = B - B % (256 * C_CH);
-                uint64_t i0 = 0;
-                bool dropped = false;
-                for (; i0 < full; i0 += 256 * C_CH) {
-                    if (i0 && burst_drop && p_hint_pos(win) < p) {
-                        dropped = true;
-                        break;
-                    }
-                    Raw4<T> raw[C_CH];
-#pragma unroll
-                    for (int j = 0; j < C_CH; j++) raw[j].load(rp + i0 + uint64_t(j) * 256 + lane * 4);
-                    // (the scheduler would otherwise sink each load to its use: one 1 KiB request in
-                    // flight per wave instead of four)
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int j = 0; j < C_CH; j += 2) {
-                        const uint64_t i = i0 + uint64_t(j) * 256 + lane * 4;
-                        raw[j].pin();  // nothing of chunk j is consumed (converted) above this point
-                        raw[j + 1].pin();
-                        c0 += double(coarse4(raw[j].c, *reinterpret_cast<const float4 *>(slf + i), r2));
-                        c1 += double(coarse4(raw[j + 1].c, *reinterpret_cast<const float4 *>(slf + i + 256), r2));
-                    }
-                }
-                if (dropped) {  // (an earlier event exists: this wave's later rows are pointless too)
-                    nread--;    // not a row scored: it does not count towards the algorithmic bytes
-                    break;
-                }
-                for (; i0 < B; i0 += 256) {
-                    const uint64_t i = i0 + lane * 4;
-                    Raw4<T> raw;
-                    raw.load(rp + i);
-                    c0 += double(coarse4(raw.c, *reinterpret_cast<const float4 *>(slf + i), r2));
-                }
-                }  // !done16
-                const double jf0 = -dvs_wave_sum_dpp(c0 + c1) - mean_entropy;
-                if (!(jf0 > thr_c_lo)) continue;  // (NaN: a negative bin, rejected as the reference does)
-                if (jf0 > thr_c_hi) {
-                    p_post_event_wave(win, p, true, lane);
-                    continue;
-                }
-                nmid++;
-            }
-        }
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, xmin = 0.0;
-        if (vec) {
-            // (behind the COARSE tier this pass sees a few dozen rows per selection: half the burst, half the registers)
-            constexpr int F_CH = COARSE ? P_CH / 2 : P_CH;
-            const uint64_t full = B - B % (256 * F_CH);
-            uint64_t i0 = 0;
-            for (; i0 < full; i0 += 256 * F_CH) {  // F_CH chunks of 1 KiB per wave instruction per burst
-                Raw4<T> raw[F_CH];
-#pragma unroll
-                for (int j = 0; j < F_CH; j++) raw[j].load(rp + i0 + uint64_t(j) * 256 + lane * 4);
-#pragma unroll
-                for (int j = 0; j < F_CH; j++) {
-                    const uint64_t i = i0 + uint64_t(j) * 256 + lane * 4;
-                    const double2 b01 = *reinterpret_cast<const double2 *>(sl + i);
-                    const double2 b23 = *reinterpret_cast<const double2 *>(sl + i + 2);
-                    double v0, v1, v2, v3;
-                    raw[j].get(v0, v1, v2, v3);
-                    const double x0 = fma(v0, rt, b01.x) * rn, x1 = fma(v1, rt, b01.y) * rn;
-                    const double x2 = fma(v2, rt, b23.x) * rn, x3 = fma(v3, rt, b23.y) * rn;
-                    a0 += fast_neg_xlog2x(x0);
-                    a1 += fast_neg_xlog2x(x1);
-                    a2 += fast_neg_xlog2x(x2);
-                    a3 += fast_neg_xlog2x(x3);
-                    xmin = fmin(fmin(xmin, fmin(x0, x1)), fmin(x2, x3));
-                }
-            }
-            for (; i0 < B; i0 += 256) {
-                const uint64_t i = i0 + lane * 4;
-                double v0, v1, v2, v3;
-                load4(rp, i, v0, v1, v2, v3);
-                const double2 b01 = *reinterpret_cast<const double2 *>(sl + i);
-                const double2 b23 = *reinterpret_cast<const double2 *>(sl + i + 2);
-                const double x0 = fma(v0, rt, b01.x) * rn, x1 = fma(v1, rt, b01.y) * rn;
-                const double x2 = fma(v2, rt, b23.x) * rn, x3 = fma(v3, rt, b23.y) * rn;
-                a0 += fast_neg_xlog2x(x0);
-                a1 += fast_neg_xlog2x(x1);
-                a2 += fast_neg_xlog2x(x2);
-                a3 += fast_neg_xlog2x(x3);
-                xmin = fmin(fmin(xmin, fmin(x0, x1)), fmin(x2, x3));
-            }
-        } else {
-            for (uint64_t i = lane; i < B; i += 64) {
-                const double x = fma(row_value(rp, i), rt, sl[i]) * rn;
-                a0 += fast_neg_xlog2x(x);
-                xmin = fmin(xmin, x);
-            }
-        }
-        const double hf = dvs_wave_sum((a0 + a1) + (a2 + a3));
-        const double mn = dvs_wave_min(xmin);
-        const double jf = hf - mean_entropy;
-        if (!(mn < 0.0) && jf > thr_sure) {
-            // above the threshold by more than every error bound: no f64 re-evaluation needed
-            p_post_event_wave(win, p, true, lane);
-        } else if (!(mn < 0.0) && jf > thr_fast && lane == 0) {
-            {
-                // within FAST_BAND of the threshold: listed, not an event -- the scan goes on and
-                // the workgroups settle it in f64 after the rendezvous (a wave doing that alone
-                // would hold the whole grid at the barrier for 4^k f64 logarithms)
-                nprecise++;
-                p_list_candidate(win, p);
-            }
-        }
-    }
-}
-
-// The same scores with one row per WORKGROUP (8 waves x 512 bins at k=6): a row takes an eighth of
-// the time a lone wave needs for it, so a short window -- early in the stream an accept comes every
-// few hundred rows and the scan is pure latency -- ends that much sooner, and the rows in flight
-// when an event is found are 255, not 2040.  One barrier per row: the waves' partial sums alternate
-// between two sets of LDS slots.  Lane l of wave w owns bins 4 (512 c + 64 w + l) .. + 3 of every
-// 2048-bin chunk c.  red: 2 x 24 doubles.
-template <typename T, bool COARSE>
-__device__ __forceinline__ void p_scan_rows_wg(const T *__restrict__ mat, const uint32_t *__restrict__ totals,
-                                               const double *__restrict__ rowH, const double *sl,
-                                               const float *slf, uint64_t B,
-                                               const PState &st, double he_base, const PWin &win,
-                                               uint64_t first, uint64_t stride,
-                                               uint64_t nrows, double *red, uint32_t &nread,
-                                               uint32_t &nprecise, uint32_t &nmid, bool coarse_on,
-                                            bool burst_drop = true) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double dn = double(st.n), rn = 1.0 / dn;
-    const double thr_fast = st.thr - st.band - FAST_BAND, thr_sure = st.thr + st.band + FAST_BAND;
-    const bool vec = (B & 2047) == 0;
-    const double cband = coarse_band(B);
-    const double thr_c_lo = st.thr - st.band - cband, thr_c_hi = st.thr + st.band + cband;
-    uint32_t par = 0;
-    for (uint64_t r = first; r < nrows; r += stride, par ^= 1) {
-        const uint64_t p = st.cursor + r;
-        const T *rp = mat + p * B;
-        const uint64_t ev = wave == 0 ? p_hint_pos(win) : 0ull;
-        const uint32_t tot = totals[p];
-        const double hrow = rowH[p];
-        const double rt = tot ? 1.0 / double(tot) : 0.0;
-        if constexpr (COARSE) {
-            if (vec && B <= 4 * 2048 && coarse_on) {  // COARSE tier first (select_dev.h); its sums use red[48..]
-                const float rtn = float(rt * rn);
-                const dvs_f2 r2 = {rtn, rtn};
-                double c0 = 0.0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const uint64_t i = uint64_t(j) * 2048 + tid * 4;
-                    if (i < B) {
-                        Raw4<T> raw;
-                        raw.load(rp + i);
-                        c0 += double(coarse4(raw.c, *reinterpret_cast<const float4 *>(slf + i), r2));
-                    }
-                }
-                c0 = dvs_wave_sum_dpp(c0);
-                double *cslot = red + 48 + par * 16;
-                if (lane == 0) {
-                    cslot[wave] = c0;
-                    if (wave == 0) cslot[8] = __longlong_as_double((long long)ev);
-                }
-                __syncthreads();
-                if ((unsigned long long)__double_as_longlong(cslot[8]) < p) break;
-                if (tot == 0) continue;
-                double hc = 0.0;
-#pragma unroll
-                for (int w = 0; w < P_THREADS / 64; w++) hc += cslot[w];
-                const double jf0 = -hc - (he_base + hrow) / dn;
-                if (tid == 0) nread++;
-                if (!(jf0 > thr_c_lo)) continue;
-                if (jf0 > thr_c_hi) {
-                    if (tid < 8) p_post_event_wave(win, p, true, tid);  // (eight lanes, one instruction: every thread knows the score)
-                    continue;
-                }
-                if (tid == 0) {
-                    nmid++;
-                    nread--;  // counted again below
-                }
-            }
-        }
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, xmin = 0.0;
-        if (vec) {
-            for (uint64_t i0 = 0; i0 < B; i0 += 4 * 2048) {  // up to four chunks requested at once
-                Raw4<T> raw[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (i0 + uint64_t(j) * 2048 < B) raw[j].load(rp + i0 + uint64_t(j) * 2048 + tid * 4);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const uint64_t i = i0 + uint64_t(j) * 2048 + tid * 4;
-                    if (i < B) {
-                        const double2 b01 = *reinterpret_cast<const double2 *>(sl + i);
-                        const double2 b23 = *reinterpret_cast<const double2 *>(sl + i + 2);
-                        double v0, v1, v2, v3;
-                        raw[j].get(v0, v1, v2, v3);
-                        const double x0 = fma(v0, rt, b01.x) * rn, x1 = fma(v1, rt, b01.y) * rn;
-                        const double x2 = fma(v2, rt, b23.x) * rn, x3 = fma(v3, rt, b23.y) * rn;
-                        a0 += fast_neg_xlog2x(x0);
-                        a1 += fast_neg_xlog2x(x1);
-                        a2 += fast_neg_xlog2x(x2);
-                        a3 += fast_neg_xlog2x(x3);
-                        xmin = fmin(fmin(xmin, fmin(x0, x1)), fmin(x2, x3));
-                    }
-                }
-            }
-        } else {
-            for (uint64_t i = tid; i < B; i += P_THREADS) {
-                const double x = fma(row_value(rp, i), rt, sl[i]) * rn;
-                a0 += fast_neg_xlog2x(x);
-                xmin = fmin(xmin, x);
-            }
-        }
-        const double hw = dvs_wave_sum((a0 + a1) + (a2 + a3));
-        const bool negw = __ballot(xmin < 0.0) != 0ull;
-        double *slot = red + par * 24;
-        if (lane == 0) {
-            slot[wave] = hw;
-            slot[8 + wave] = negw ? 1.0 : 0.0;
-            if (wave == 0) slot[16] = __longlong_as_double((long long)ev);
-        }
-        __syncthreads();
-        // every thread takes the same decisions from the same LDS words
-        if ((unsigned long long)__double_as_longlong(slot[16]) < p) break;
-        if (tot == 0) continue;
-        double hf = 0.0, neg = 0.0;
-#pragma unroll
-        for (int w = 0; w < P_THREADS / 64; w++) {
-            hf += slot[w];
-            neg += slot[8 + w];
-        }
-        const double jf = hf - (he_base + hrow) / dn;
-        // (a sure event goes out from eight lanes in one instruction: every thread knows the score)
-        if (tid < 8 && neg == 0.0 && jf > thr_fast && jf > thr_sure) p_post_event_wave(win, p, true, tid);
-        if (tid == 0) {
-            nread++;
-            if (neg == 0.0 && jf > thr_fast) {
-                if (jf > thr_sure) {
-                } else {
-                    nprecise++;
-                    p_list_candidate(win, p);
-                }
-            }
-        }
-    }
-}
-
-// The row-per-workgroup scan as a stream (4^k = 4096 bins, COARSE tier): every thread keeps the
-// two 16-byte requests of each of the next D rows of its workgroup in flight, so the grid streams
-// rows at memory speed while an event still leaves only ~one row per workgroup to drain.  A row the
-// COARSE tier cannot decide is scored again by p_scan_rows_wg (FAST tier) as a one-row window.
-// red: the 128-double scratch area minus its first 32 (slots [48..80) are this function's).
-template <typename T>
-__device__ __forceinline__ void p_scan_rows_wg_stream(const T *__restrict__ mat,
-                                                      const uint32_t *__restrict__ totals,
-                                                      const double *__restrict__ rowH, const double *sl,
-                                                      const float *slf, const PState &st, double he_base,
-                                                      const PWin &win, uint64_t first,
-                                                      uint64_t stride, uint64_t nrows, double *red,
-                                                      uint32_t &nread, uint32_t &nprecise, uint32_t &nmid,
-                                                      bool no_first_poll = true) {
-    constexpr uint64_t B = 4096;
-    constexpr int D = 4;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double dn = double(st.n), rn = 1.0 / dn;
-    const double cband = coarse_band(B);
-    const double thr_c_lo = st.thr - st.band - cband, thr_c_hi = st.thr + st.band + cband;
-    constexpr bool W16 = sizeof(T) == 2;  // 16-bit rows: ONE 16-byte load per thread (bins 8 tid .. + 7)
-    struct Row {
-        Raw4<T> r0, r1;
-        uint4 q;
-        uint32_t tot;
-        double hrow;
-        unsigned long long ev;
-    };
-    // poll: also look at the event word (a device-scope round trip, longer than an L2 hit on the row).  The
-    // window's first rows go without it -- the window has only just begun, and a row scored for nothing
-    // changes no answer -- so the first score waits for its row alone.
-    auto issue = [&](Row &w, uint64_t r, bool poll) {
-        const uint64_t p = st.cursor + r;
-        const T *rp = mat + p * B;
-        if constexpr (W16) {
-            w.q = *reinterpret_cast<const uint4 *>(rp + tid * 8);
-        } else {
-            w.r0.load(rp + tid * 4);
-            w.r1.load(rp + 2048 + tid * 4);
-        }
-        w.tot = totals[p];
-        if (wave == 0) {  // the row's entropy and the event word travel through LDS with the partial sums
-            w.hrow = rowH[p];
-            w.ev = poll ? p_hint_pos(win) : SEL_NONE;
-        }
-    };
-    uint32_t par = 0;
-    auto process = [&](Row &w, uint64_t r) -> bool {  // false: an earlier event exists, the workgroup is done
-        const uint64_t p = st.cursor + r;
-        const float rtn = w.tot ? float(rn / double(w.tot)) : 0.0f;
-        const dvs_f2 r2 = {rtn, rtn};
-        double c;
-        if constexpr (W16) {
-            asm volatile("" : "+v"(w.q.x), "+v"(w.q.y), "+v"(w.q.z), "+v"(w.q.w));
-            double ca = 0.0, cb = 0.0;
-            coarse8(w.q, slf + tid * 8, r2, ca, cb);
-            c = ca + cb;
-        } else {
-            w.r0.pin();
-            w.r1.pin();
-            c = double(coarse4(w.r0.c, *reinterpret_cast<const float4 *>(slf + tid * 4), r2)) +
-                double(coarse4(w.r1.c, *reinterpret_cast<const float4 *>(slf + 2048 + tid * 4), r2));
-        }
-        const double cs = dvs_wave_sum_dpp(c);
-        double *slot = red + 48 + par * 16;
-        par ^= 1;
-        if (lane == 0) {
-            slot[wave] = cs;
-            if (wave == 0) {
-                slot[8] = __longlong_as_double((long long)w.ev);
-                slot[9] = w.hrow;
-            }
-        }
-        __syncthreads();
-        if ((unsigned long long)__double_as_longlong(slot[8]) < p) return false;
-        if (w.tot == 0) return true;
-        double hc = 0.0;
-#pragma unroll
-        for (int q = 0; q < P_THREADS / 64; q++) hc += slot[q];
-        const double jf0 = -hc - (he_base + slot[9]) / dn;
-        if (tid == 0) nread++;
-        if (!(jf0 > thr_c_lo)) return true;  // (NaN: a negative bin, rejected as the reference does)
-        if (jf0 > thr_c_hi) {
-            if (tid < 8) p_post_event_wave(win, p, true, tid);  // (eight lanes, one instruction: every thread knows the score)
-            return true;
-        }
-        if (tid == 0) {
-            nmid++;
-            nread--;  // counted again by the FAST pass
-        }
-        uint32_t nm = 0;
-        p_scan_rows_wg<T, false>(mat, totals, rowH, sl, slf, B, st, he_base, win, r, nrows, nrows, red,
-                                 nread, nprecise, nm, false);
-        return true;
-    };
-    Row w[D];
-#pragma unroll
-    for (int d = 0; d < D; d++)
-        if (first + uint64_t(d) * stride < nrows) issue(w[d], first + uint64_t(d) * stride, no_first_poll ? d >= 2 : true);
-    for (uint64_t base = first; base < nrows; base += uint64_t(D) * stride) {
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            const uint64_t r = base + uint64_t(d) * stride;
-            if (r >= nrows) return;
-            if (!process(w[d], r)) return;
-            if (r + uint64_t(D) * stride < nrows) issue(w[d], r + uint64_t(D) * stride, true);
-        }
-    }
-}
-
-// Window policy of the persistent engine.  Short windows run a row per workgroup (p_scan_rows_wg) and
-// are whole rounds of the scanning workgroups long; the scale aims at ~3 in 4 windows ending in an
-// accept (the accept probability at stream position i is ~ size / i).
-__device__ __forceinline__ uint32_t p_next_window(const PState &st, uint32_t nwg, uint32_t wg_thresh,
-                                                  double wg_scale, bool &wgmode) {
-    if (wg_thresh) {
-        uint64_t w = uint64_t(double(st.cursor) * wg_scale / double(st.n ? st.n : 1u));
-        w = (w + nwg - 1) / nwg * nwg;
-        if (w < nwg) w = nwg;
-        if (w <= uint64_t(wg_thresh) * nwg) {
-            wgmode = true;
-            return uint32_t(w);
-        }
-    }
-    wgmode = false;
-    return sel_next_window(st.cursor, st.n, st.wmin, st.wmax, st.wscale);
-}
-
-// argmin (strict '<' from 1e6, first index), runner-up, mean and standard deviation of the
-// members' delta_jsd by ONE wave: lane l owns members l, l + 64, ... (Q per lane; re-read from LDS
-// in every pass when Q > 1 -- registers are the scan loop's).
-// scratch[100..105] = min, index, second, mean, sd, any-risky.
-template <uint32_t Q>
-__device__ __forceinline__ void p_argmin(const double *s_dl, const double *s_ds, uint32_t n, uint64_t B,
-                                         uint32_t lane, double *scratch) {
-    const double v0 = lane < n ? s_dl[lane] : 1e6;
-    auto val = [&](uint32_t q) { return (Q == 1 || q == 0) ? v0 : s_dl[lane + 64 * q]; };
-    double best = 1e6, acc = 0.0;
-    bool rk = false;
-#pragma unroll
-    for (uint32_t q = 0; q < Q; q++) {
-        const uint32_t r = lane + 64 * q;
-        if (r < n) {
-            const double v = val(q);
-            rk |= sum_risky(s_ds[r], B);
-            acc += v;
-            if (v < best) best = v;
-        }
-    }
-    const double dn = double(n);
-    const double mnv = dvs_wave_min(best);
-    double fi = 4294967295.0;
-#pragma unroll
-    for (uint32_t q = 0; q < Q; q++)
-        if (mnv < 1e6 && lane + 64 * q < n && val(q) == mnv) fi = fmin(fi, double(lane + 64 * q));
-    const double first = dvs_wave_min(fi);
-    const uint32_t lw = (first < 4294967295.0) ? uint32_t(first) : 0u;
-    const double mu = dvs_wave_sum(acc) / dn;
-    double sec = 1e6, tv = 0.0;
-#pragma unroll
-    for (uint32_t q = 0; q < Q; q++) {
-        const uint32_t r = lane + 64 * q;
-        if (r < n) {
-            const double v = val(q);
-            if (r != lw && v < sec) sec = v;
-            const double t = v - mu;
-            tv += t * t;
-        }
-    }
-    sec = dvs_wave_min(sec);
-    const double var = dvs_wave_sum(tv);
-    const unsigned long long anyr = __ballot(rk);
-    if (lane == 0) {
-        scratch[100] = mnv;
-        scratch[101] = double(lw);
-        scratch[102] = sec;
-        scratch[103] = mu;
-        scratch[104] = sqrt(var / (dn - 1.0));
-        scratch[105] = anyr ? 1.0 : 0.0;
-    }
-}
-
 // LDS: [sl B f64][scratch 128 f64][s_mH, s_tot, s_rt, s_dl, s_ds maxn f64][s_pos maxn u64]
-//      [s_slot maxn u32][s_win P_WINWORDS u64][flags][log2 table][s_prev (maxn + 1) x 2 u64]
+//      [s_slot maxn u32][s_win P_WINWORDS u64][flags][log2 table][s_prev (maxn + 1) x 2 u64][s_tail]
+// (the host asks for it with p_lds_bytes, persist_dev.h, which names every term: a member added here goes there too)
 // maxn = p_maxn(CACHED): compile-time offsets (runtime ones cost registers the scan loop needs),
 // smaller beyond 4096 bins so that 4^7 bins (128 KB of sl) still fit.
 // CACHED: B <= P_J * 512, so a thread's share of the candidate row stays in registers
@@ -1201,7 +395,6 @@ __global__ __launch_bounds__(P_THREADS, 2) void persist_nmost_kernel(SelDev d, c
                     const double nv = Sreg[j] - count_freq_x(lv[j], ltot, lrt);
                     sl[i] = nv;
                     if (COARSE) slf[i] = coarse_sl(nv, rn0);
-                    (void)dn0;
                 }
             }
         }
@@ -1297,84 +490,6 @@ __global__ __launch_bounds__(P_THREADS, 2) void persist_nmost_kernel(SelDev d, c
     if (tid < 16) s_dbg[tid] = 0ull;
     __syncthreads();
     unsigned long long t_prev = __builtin_amdgcn_s_memrealtime();
-#ifdef DVS_PROBE
-// ONE interval per build (-DDVS_PERSIST_STAMPS -DDVS_PROBE=k, scripts/probe.sh): thread 0 of block 0 (it owns a leave-one-out
-// job) and of the last scanning block (it owns none) take two clock reads per pass -- everything else is switched off, so
-// what is measured is not the stamps.  [0] the ticks, [1] the passes.
-#define P_PROBE_BEGIN(id)                                                                          \
-    do {                                                                                           \
-        if ((id) == DVS_PROBE && (blockIdx.x == 0 || blockIdx.x == n_work - 1) && tid == 0)        \
-            t_prev = __builtin_amdgcn_s_memrealtime();                                             \
-    } while (0)
-#define P_PROBE_END(id)                                                                            \
-    do {                                                                                           \
-        if ((id) == DVS_PROBE && (blockIdx.x == 0 || blockIdx.x == n_work - 1) && tid == 0) {      \
-            s_dbg[0] += __builtin_amdgcn_s_memrealtime() - t_prev;                                 \
-            s_dbg[1] += 1;                                                                         \
-        }                                                                                          \
-    } while (0)
-#define P_STAMP(k) do { } while (0)
-#define P_STAMP_B0(k) do { } while (0)
-#define P_TRACE(which) do { } while (0)
-#define P_TRACE_G(slot) do { } while (0)
-#else
-#define P_PROBE_BEGIN(id) do { } while (0)
-#define P_PROBE_END(id) do { } while (0)
-#define P_STAMP(k)                                                         \
-    do {                                                                   \
-        if ((lead || blockIdx.x == 0) && tid == 0) {                       \
-            const unsigned long long t_now = __builtin_amdgcn_s_memrealtime(); \
-            s_dbg[k] += t_now - t_prev;                                    \
-            t_prev = t_now;                                                \
-        }                                                                  \
-    } while (0)
-// (block 0 only: finer stamps inside a phase -- slots 9..14 are the mirror block's window statistics)
-#define P_STAMP_B0(k)                                                      \
-    do {                                                                   \
-        if (blockIdx.x == 0 && !lead && tid == 0) {                        \
-            const unsigned long long t_now = __builtin_amdgcn_s_memrealtime(); \
-            s_dbg[k] += t_now - t_prev;                                    \
-            t_prev = t_now;                                                \
-        }                                                                  \
-    } while (0)
-// one window's timeline across the grid (DVS_PERSIST_DEBUG prints it): slot `which` of the traced window
-#define P_TRACE(which)                                                                             \
-    do {                                                                                           \
-        if (tid == 0 && (epoch == 12 || epoch == 24 || epoch == 36 || epoch == 48))               \
-            sync->trace[epoch / 12 - 1][which][blockIdx.x] = __builtin_amdgcn_s_memrealtime();     \
-    } while (0)
-#define P_TRACE_G(slot)                                                                            \
-    do {                                                                                           \
-        if (tid == 0 && (epoch == 12 || epoch == 24 || epoch == 36 || epoch == 48))               \
-            sync->trace[epoch / 12 - 1][3][slot] = __builtin_amdgcn_s_memrealtime();               \
-    } while (0)
-#endif  // DVS_PROBE
-#else
-#define P_STAMP(k) do { } while (0)
-#define P_STAMP_B0(k) do { } while (0)
-#define P_TRACE(which) do { } while (0)
-#define P_TRACE_G(slot) do { } while (0)
-#define P_PROBE_BEGIN(id) do { } while (0)
-#define P_PROBE_END(id) do { } while (0)
-#endif
-// A -DDVS_PERSIST_CHAOS build holds pseudo-randomly chosen workgroups back (one in sixteen up to ~10 us, one in four
-// thousand for ~60 us) at the points where they are about to write or read a word another workgroup reads or
-// writes: the answers must not change
-// (scripts/chaos.sh runs the parity suite and the repeat script against such a build).
-#ifdef DVS_PERSIST_CHAOS
-#define P_CHAOS(k)                                                                                         \
-    do {                                                                                                   \
-        uint32_t h_ = (epoch * 0x9E3779B1u) ^ ((blockIdx.x + 1u) * 0x85EBCA77u) ^ (uint32_t(k) * 0xC2B2AE3Du); \
-        h_ ^= h_ >> 15;                                                                                    \
-        h_ *= 0x27D4EB2Fu;                                                                                 \
-        h_ ^= h_ >> 13;                                                                                    \
-        if ((h_ & 15u) == 0u)                                                                              \
-            for (uint32_t z_ = (h_ >> 8) & 31u; z_ > 0; z_--) __builtin_amdgcn_s_sleep(12);               \
-        if ((h_ & 0xFFF0u) == 0x1230u) /* now and then for the length of several windows (~60 us) */      \
-            for (uint32_t z_ = 0; z_ < 160; z_++) __builtin_amdgcn_s_sleep(14);                            \
-    } while (0)
-#else
-#define P_CHAOS(k) do { } while (0)
 #endif
     for (;;) {
         // The loop body's view of the bin count and the thread index goes through an empty asm:
@@ -3271,8 +2386,7 @@ static int persist_prepare(dvs_ctx *ctx, dvs_select *s, uint32_t head_stop, hipS
     init.wg_thresh = s->params.window ? 0u : 4u;
     init.wg_scale = 1.5f;
     if (ctx->knobs.persist_wg_rounds >= 0) init.wg_thresh = uint32_t(ctx->knobs.persist_wg_rounds);
-    init.no_coarse = (ctx->knobs.persist_no_coarse ? 1u : 0u) | (ctx->knobs.persist_no_events ? 2u : 0u) |
-                     0u;
+    init.no_coarse = (ctx->knobs.persist_no_coarse ? 1u : 0u) | (ctx->knobs.persist_no_events ? 2u : 0u);
     init.small_rows = s->persist.small ? s->persist.small_rows : 0u;
     init.lds_bytes = uint32_t(s->persist.lds);
     init.wmax = uint32_t(std::min<uint64_t>(s->npos, 0xFFFFFFFFull));
@@ -3336,23 +2450,13 @@ int dvs_persist_setup(dvs_ctx *ctx, dvs_select *s) {
     s->persist.small_rows = s->params.n_seed;
     s->persist.small = !maxm && s->params.mode == DVS_MODE_NMOST && s->mat_kind == 2 && B == 4096 &&
                        s->params.n_seed >= 2 && s->params.n_seed <= P_SMALL_ROWS && !ctx->knobs.persist_no_small;
-    auto lds_for = [&](uint32_t maxn_) {
-        return ((B + 1) & ~1ull) * 8 + (cached && s->mat_kind != 1 ? ((B + 3) & ~3ull) * 4 : 0) +
-               (maxm ? ((B + 1) & ~1ull) * 8 : 0) + 128 * 8 + size_t(maxn_) * 52 + 8 + P_WINWORDS * 8 + 64 +
-               128 * 16 + 128 +  // (+ log2_tab's table, + the stamps of a -DDVS_PERSIST_STAMPS build)
-               size_t(maxn_ + 1) * 16 +  // (the accumulators' previous totals)
-               (maxm ? p_batch_lds() : 0);
-    };
-    size_t lds = lds_for(p_maxn(cached, maxm));
+    // the launch's LDS (p_lds_bytes, persist_dev.h): OWN's (see the kernel) wherever SMALL does not serve or fit
+    size_t lds = p_lds_bytes(B, s->mat_kind, cached, maxm, 0u);
     if (s->persist.small) {
-        const size_t lds_small = lds_for(P_SMALLN) + size_t(s->persist.small_rows) * B * 2 + 16;
+        const size_t lds_small = p_lds_bytes(B, s->mat_kind, cached, maxm, s->persist.small_rows);
         if (lds_small <= ctx->lds_per_block) lds = lds_small;
         else s->persist.small = false;
     }
-    // OWN (see the kernel): nmost over count rows in the register cache beyond SMALL -- the slot map and this
-    // workgroup's own member's counts
-    if (cached && !maxm && s->mat_kind != 1 && !s->persist.small)
-        lds += size_t(p_maxn(cached, maxm)) * 4 + size_t(P_J) * P_THREADS * (s->mat_kind == 2 ? 2 : 4);
     s->persist.maxn = s->persist.small ? P_SMALLN : p_maxn(cached, maxm);
     s->persist.maxjobs = s->persist.small ? P_SMALLN + 1 : p_maxjobs(cached, maxm);
     // (MODE_MAX: max_size may be the whole stream; the kernel hands over when its LDS replica is full)
@@ -3383,114 +2487,6 @@ int dvs_persist_setup(dvs_ctx *ctx, dvs_select *s) {
     if (rc) return rc;
     s->persist.on = true;
     return DVS_OK;
-}
-
-#ifdef DVS_PERSIST_STAMPS
-// four windows' timelines across the grid of `G` workgroups (PSync::trace of the launch's sync block `blk`)
-static void persist_trace_report(const void *blk, uint32_t G) {
-    std::vector<unsigned long long> tr(4 * 8 * 256);
-    if (hipMemcpy(tr.data(), static_cast<const char *>(blk) + offsetof(PSync, trace), tr.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-    for (int w_ = 0; w_ < 4; w_++) {
-        const unsigned long long *t0 = &tr[(w_ * 8 + 0) * 256], *t1 = &tr[(w_ * 8 + 1) * 256], *t2 = &tr[(w_ * 8 + 2) * 256], *tg = &tr[(w_ * 8 + 3) * 256];
-        const unsigned long long *t4 = &tr[(w_ * 8 + 4) * 256], *t5 = &tr[(w_ * 8 + 5) * 256], *t6 = &tr[(w_ * 8 + 6) * 256], *t7 = &tr[(w_ * 8 + 7) * 256];
-        if (!tg[2] || G < 4) continue;
-        std::vector<double> top, arr, seen, pub, tot, end_;
-        unsigned long long first_top = ~0ull;
-        for (uint32_t b = 0; b + 2 < G; b++) if (t0[b]) first_top = std::min(first_top, t0[b]);
-        for (uint32_t b = 0; b + 2 < G; b++) {
-            if (!t0[b] || !t1[b] || !t2[b]) continue;
-            top.push_back((t0[b] - first_top) / 100.0);
-            arr.push_back((t1[b] - first_top) / 100.0);
-            seen.push_back((double(t2[b]) - double(tg[2])) / 100.0);
-            if (t4[b] > tg[2] && t5[b] > tg[2] && t6[b] > tg[2]) {  // (the window ended in an accept)
-                pub.push_back((double(t4[b]) - double(tg[2])) / 100.0);
-                tot.push_back((double(t5[b]) - double(tg[2])) / 100.0);
-                end_.push_back((double(t6[b]) - double(tg[2])) / 100.0);
-            }
-        }
-        if (arr.empty()) continue;
-        auto srt = [](std::vector<double> &v) { std::sort(v.begin(), v.end()); };
-        srt(top); srt(arr); srt(seen);
-        auto q_ = [](const std::vector<double> &v, double f) { return v[size_t(f * (v.size() - 1))]; };
-        fprintf(stderr, "[dvs persist trace] window %d: tops 0 / %.2f / %.2f (min/median/max us), records stored %.2f / %.2f / %.2f / %.2f (min/median/90%%/max), "
-                "gather begun %.2f, last record seen %.2f, release stored %.2f, release seen +%.2f / +%.2f / +%.2f (min/median/max after it was stored)\n",
-                w_ * 12 + 12, q_(top, 0.5), top.back(), arr.front(), q_(arr, 0.5), q_(arr, 0.9), arr.back(),
-                (double(tg[0]) - double(first_top)) / 100.0, (double(tg[1]) - double(first_top)) / 100.0, (double(tg[2]) - double(first_top)) / 100.0,
-                seen.front(), q_(seen, 0.5), seen.back());
-        if (pub.empty()) continue;
-        {   // the five workgroups that published last: when each arrived, saw the release, published
-            std::vector<std::pair<double, uint32_t>> late;
-            for (uint32_t b = 0; b + 2 < G; b++)
-                if (t4[b] > tg[2]) late.emplace_back((double(t4[b]) - double(tg[2])) / 100.0, b);
-            std::sort(late.rbegin(), late.rend());
-            for (size_t i = 0; i < late.size() && i < 5; i++) {
-                const uint32_t b = late[i].second;
-                fprintf(stderr, "[dvs persist trace] window %d: workgroup %u arrived %.2f before the release was stored, saw it +%.2f, handed its speculative job over +%.2f, was through the job loop +%.2f\n",
-                        w_ * 12 + 12, b, (double(tg[2]) - double(t1[b])) / 100.0, (double(t2[b]) - double(tg[2])) / 100.0,
-                        (double(t7[b]) - double(tg[2])) / 100.0, late[i].first);
-            }
-        }
-        {   // when the speculative jobs were handed over (mailboxes: stored), relative to the release
-            std::vector<double> sp;
-            for (uint32_t b = 0; b + 2 < G; b++)
-                if (t7[b] && t4[b] > tg[2]) sp.push_back((double(t7[b]) - double(tg[2])) / 100.0);
-            if (!sp.empty()) {
-                srt(sp);
-                fprintf(stderr, "[dvs persist trace] window %d: speculative jobs handed over %.2f / %.2f / %.2f / %.2f us after the release was stored "
-                        "(min/median/90%%/max over %zu workgroups; negative: before)\n", w_ * 12 + 12, sp.front(), q_(sp, 0.5), q_(sp, 0.9), sp.back(), sp.size());
-            }
-        }
-        srt(pub); srt(tot); srt(end_);
-        fprintf(stderr, "[dvs persist trace] window %d, its accept (us after the release was stored; min/median/max): job published %.2f / %.2f / %.2f, "
-                "totals read %.2f / %.2f / %.2f, rebuild done %.2f / %.2f / %.2f\n", w_ * 12 + 12, pub.front(), q_(pub, 0.5), pub.back(),
-                tot.front(), q_(tot, 0.5), tot.back(), end_.front(), q_(end_, 0.5), end_.back());
-    }
-}
-#endif
-
-// DVS_PERSIST_DEBUG, at every poll of a selection on the persistent engine: what its launches left in their sync blocks
-// (the head phase's launch first, then the full grid's) on stderr -- scripts/stamps_to_json.py parses these lines
-void dvs_persist_debug_report(dvs_ctx *ctx, const dvs_select *s) {
-    for (int which = 0; which < 2 && s->persist.on; which++) {
-        unsigned long long dbg[32];  // dbg2[16] then dbg[16]
-        const void *blk = which ? s->persist.sync : s->persist.sync_head;
-        if (!blk || hipMemcpy(dbg, static_cast<const char *>(blk) + offsetof(PSync, dbg2), sizeof dbg, hipMemcpyDeviceToHost) != hipSuccess)
-            continue;
-        fprintf(stderr, "[dvs persist] %s launch\n", which ? "full-grid" : "head-phase");
-#if defined(DVS_PERSIST_STAMPS) && defined(DVS_PROBE)
-        if (DVS_PROBE) {  // (a one-interval build: [0] ticks, [1] passes; block 0 then the last scanning block)
-            fprintf(stderr, "[dvs persist probe %d] block 0 (owns a job): %.3f us x %llu; the last scanning block (no job): %.3f us x %llu\n",
-                    int(DVS_PROBE), dbg[1] ? dbg[0] / 100.0 / double(dbg[1]) : 0.0, dbg[1],
-                    dbg[17] ? dbg[16] / 100.0 / double(dbg[17]) : 0.0, dbg[17]);
-            continue;
-        }
-#endif
-        for (int w = 0; w < 2; w++)
-            fprintf(stderr, "[dvs persist %s] us: scan %.1f bar1 %.1f resolve %.1f loo %.1f bar2 %.1f | partials %.1f combine %.1f lowest-row fetch %.1f rebuild %.1f\n",
-                    w ? "mirror block" : "block 0", dbg[0 + 16 * w] / 100.0, dbg[1 + 16 * w] / 100.0,
-                    dbg[2 + 16 * w] / 100.0, dbg[3 + 16 * w] / 100.0, dbg[4 + 16 * w] / 100.0,
-                    dbg[6 + 16 * w] / 100.0, dbg[7 + 16 * w] / 100.0, dbg[8 + 16 * w] / 100.0,
-                    dbg[5 + 16 * w] / 100.0);
-#ifdef DVS_PERSIST_STAMPS
-        persist_trace_report(blk, which ? s->persist.grid : uint32_t(ctx->head_cus));
-#endif
-        if (dbg[15] + dbg[14])
-            fprintf(stderr, "[dvs persist block 0] accepts for which its leave-one-out job was ready when the release came: %llu (the candidate's frequencies: %llu)\n", dbg[15], dbg[14]);
-        if (dbg[9] + dbg[10] + dbg[11] + dbg[12])
-            fprintf(stderr, "[dvs persist block 0] us inside the phases: window top %.1f own rows scanned %.1f hint look + record %.1f (then: scan = the rest) | behind the rebuild %.1f\n",
-                    dbg[9] / 100.0, dbg[10] / 100.0, dbg[11] / 100.0, dbg[12] / 100.0);
-        if (dbg[16 + 10] + dbg[16 + 12])
-            fprintf(stderr, "[dvs persist] scan + rendezvous: row-per-workgroup windows %llu (%.1f us, %llu rows), "
-                    "row-per-wave windows %llu (%.1f us, %llu rows)\n", dbg[16 + 10], dbg[16 + 9] / 100.0,
-                    dbg[16 + 13], dbg[16 + 12], dbg[16 + 11] / 100.0, dbg[16 + 14]);
-    }
-}
-
-// DVS_PERSIST_DEBUG, when a selection is done: why its persistent launches ended early (SelCtl::why)
-void dvs_persist_debug_done(const SelCtl &c) {
-    fprintf(stderr, "[dvs persist] launches ended early: replica full %u, sum check %u, push argmin %u, stat comparison %u, "
-            "candidate in band %u, replace argmin %u, state not taken %u / %u\n", c.why[0], c.why[1], c.why[2], c.why[3],
-            c.why[4], c.why[5], c.why[6], c.why[7]);
 }
 
 void dvs_persist_free(dvs_select *s) {

@@ -1,4 +1,4 @@
-// Shared between the selection's translation units (select.hip, stepwise.hip, maxbatch.hip, persist.hip) and
+// Shared between the selection's translation units (select.hip, stepwise.hip, maxbatch.hip, persist.hip, persist_report.hip) and
 // exact_set.cpp (host tie arbiter).
 #pragma once
 
@@ -179,6 +179,7 @@ int dvs_persist_launch(dvs_ctx *ctx, dvs_select *s);
 int dvs_persist_launch_head(dvs_ctx *ctx, dvs_select *s, uint32_t grid, uint32_t stop_at, hipStream_t on);
 int dvs_persist_prepare_main(dvs_ctx *ctx, dvs_select *s);
 int dvs_persist_prepare_head(dvs_ctx *ctx, dvs_select *s, uint32_t stop_at, hipStream_t on);
+// persist_report.hip
 void dvs_persist_debug_report(dvs_ctx *ctx, const dvs_select *s);  // DVS_PERSIST_DEBUG: the launches' phase times
 void dvs_persist_debug_done(const SelCtl &c);                        // ... and why they ended early
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The persistent engine with pseudo-randomly delayed workgroups (a -DDVS_PERSIST_CHAOS build: persist.hip P_CHAOS), in ONE
+# The persistent engine with pseudo-randomly delayed workgroups (a -DDVS_PERSIST_CHAOS build: P_CHAOS of persist_probe.h, placed by persist.hip), in ONE
 # gpurun call:   gpurun -- scripts/chaos.sh <tag> [repetitions per case]
 # runs the selection tests of the parity suite and scripts/repeat_selections.py against it, then rebuilds the plain library.
 set -u

@@ -1,6 +1,6 @@
 """the C4 share's selection (12 500 x 5 kb, k=7, nmost n=100; or: reps k nseq n) many times over the same
 sequences: are the counters and the members the same every time?  (This is how the lost leave-one-out
-partials of persist.hip's grid_barrier comment were found.)"""
+partials of persist_dev.h's grid_barrier comment were found.)"""
 import os, sys, collections
 import numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))

@@ -12,7 +12,7 @@ for k in $ids; do
   ev=$(echo $e | tr ',' ' '); [ "$e" = "-" ] && ev=""
   [ "$envs" != "-" ] && echo "-- env: $e" >> gpurun_out/${tag}_probe.txt
   if [ "$e" = "$(echo $envs | cut -d' ' -f1)" ]; then
-   rm -f diverseseq_amd/csrc/build/persist.hip.o diverseseq_amd/csrc/build/select.hip.o   # (the two units that see the switch)
+   rm -f diverseseq_amd/csrc/build/persist.hip.o diverseseq_amd/csrc/build/persist_report.hip.o diverseseq_amd/csrc/build/select.hip.o   # (the units that see the switch: PSync changes with it)
    make -C diverseseq_amd/csrc -j8 EXTRA="-DDVS_PERSIST_STAMPS -DDVS_PROBE=$k" > gpurun_out/${tag}_probe_build.log 2>&1 || { tail -5 gpurun_out/${tag}_probe_build.log; exit 1; }
   fi
   if [ -z "$grp" ]; then
@@ -25,6 +25,6 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('probe $k: scan_m
   grep "dvs persist probe\|\] .* launch" gpurun_out/${tag}_probe_$k.err | tail -4 >> gpurun_out/${tag}_probe.txt
  done
 done
-rm -f diverseseq_amd/csrc/build/persist.hip.o diverseseq_amd/csrc/build/select.hip.o
+rm -f diverseseq_amd/csrc/build/persist.hip.o diverseseq_amd/csrc/build/persist_report.hip.o diverseseq_amd/csrc/build/select.hip.o
 make -C diverseseq_amd/csrc -j8 > /dev/null 2>&1
 cat gpurun_out/${tag}_probe.txt

@@ -461,7 +461,7 @@ class Case(NamedTuple):
 
 
 NMOST = ("nmost",)
-# P_SMALL_ROWS = 13 (persist.hip): nmost 13 is the SMALL instantiation's last set size, 14 the first of OWN
+# P_SMALL_ROWS = 13 (persist_dev.h): nmost 13 is the SMALL instantiation's last set size, 14 the first of OWN
 SMALL13 = Case("small13", 4, 6, NMOST, 13, 5000, 300, 9101, 2, True, reaches="SMALL's last size")
 OWN14 = Case("own14", 4, 6, NMOST, 14, 5000, 300, 9102, 2, True, reaches="OWN's first size")
 OWN65 = Case("own65", 4, 6, NMOST, 65, 5000, 400, 9103, 2, True, reaches="OWN, a set beyond one wave's argmin")
@@ -604,7 +604,7 @@ def test_every_case_of_the_table_is_there():
 @pytest.mark.parametrize("case", ALL_CASES, ids=_ids)
 def test_shapes_take_the_intended_branch(case):
     B = case.nbins
-    cached = B <= 4096                                  # persist.hip: P_J * P_THREADS bins in the register cache
+    cached = B <= 4096                                  # persist_dev.h: P_J * P_THREADS bins in the register cache
     u16 = B <= 4096 and B % 4 == 0 and not case.env     # kmer_hist.hip: 16-bit rows (DVS_COUNTS_U32 keeps 32)
     if case.count_bytes != 8:
         assert case.count_bytes == (2 if u16 else 4)
