@@ -48,7 +48,7 @@ EXPORTS = (
     "dvs_linkage_cut", "dvs_linkage_cophenet", "dvs_nj_patristic", "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get",
     # one entry per operation over the distances of a `Source`
     "dvs_distances", "dvs_linkage", "dvs_nj", "dvs_maxmin", "dvs_cross_distances", "dvs_nearest", "dvs_within",
-    "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters",
+    "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters", "dvs_pcoa", "dvs_pcoa_project",
 )
 WITHIN_SKIP_SELF = 1
 SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
@@ -58,6 +58,17 @@ class Source(C.Structure):
     """dvs_source: where an operation's distances come from"""
     _fields_ = [("kind", C.c_uint32), ("handle", C.c_void_p), ("rows", C.POINTER(C.c_uint32)), ("n", C.c_uint32),
                 ("k", C.c_uint32), ("sketch_size", C.c_uint32), ("on_device", C.c_int)]
+
+
+class PcoaParams(C.Structure):
+    """dvs_pcoa_params"""
+    _fields_ = [("n_axes", C.c_uint32), ("max_basis", C.c_uint32), ("tol", C.c_double)]
+
+
+class PcoaInfo(C.Structure):
+    """dvs_pcoa_info"""
+    _fields_ = [("trace", C.c_double), ("converged", C.c_uint32), ("basis", C.c_uint32), ("steps", C.c_uint32),
+                ("products", C.c_uint64)]
 
 
 class SelectParams(C.Structure):
@@ -245,6 +256,9 @@ def load() -> C.CDLL:
         L.dvs_cluster_scores.argtypes = [vp, srcp, u32p, u32, f64p, f64p, f64p, u32p, f64p, u32p]
         L.dvs_cophenet.argtypes = [vp, srcp, u32p, f64p, f64p, f64p, f64p]  # pairs, heights, the correlation, the row sums, the matrix
         L.dvs_threshold_clusters.argtypes = [vp, srcp, C.c_double, u32p, u32p]  # radius, labels, n_clusters
+        # params, values, vectors, residuals, row_means, info
+        L.dvs_pcoa.argtypes = [vp, srcp, C.POINTER(PcoaParams), f64p, f64p, f64p, f64p, C.POINTER(PcoaInfo)]
+        L.dvs_pcoa_project.argtypes = [vp, srcp, srcp, u32, f64p, f64p, f64p, f64p]  # n_axes, values, vectors, row_means, coords
         if L.dvs_abi_version() != 4:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

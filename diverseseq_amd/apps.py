@@ -9,7 +9,8 @@ nearest of a fixed set of reference sequences for every query (diverseseq_amd.di
 the tree, its flat clusters at a cut, one representative per cluster and the silhouettes
 (diverseseq_amd.cluster.ctree_clusters); and `dvs_njtree`: the neighbour-joining tree of the same distances, with branch
 lengths (diverseseq_amd.cluster.nj_tree); and `dvs_maxmin`: farthest-first selection of representatives by distance,
-a diverse panel or a dereplication (diverseseq_amd.distance.maxmin).
+a diverse panel or a dereplication (diverseseq_amd.distance.maxmin); and `dvs_pcoa`: the principal coordinates of the
+same distances, the picture that goes with the trees and the clusters (diverseseq_amd.cluster.ordinate).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -41,7 +42,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -286,6 +287,29 @@ class dvs_njtree(_ClusterTreeBase):
 
             return make_tree(newick, underscore_unmunge=True)
         return newick
+
+
+@_define_app
+class dvs_pcoa(_DistanceApp):
+    """Principal coordinates (PCoA, classical MDS) of the k-mer distances of a collection (beyond the reference, which has
+    no such app): the picture that goes with `dvs_ctree`, `dvs_njtree` and `dvs_clusters`.  The mode arguments and their
+    checks as `dvs_ctree`; n_axes: the axes wanted (1 .. 64, and fewer than the sequences).  `main(seqs)` returns
+    {"names": [...], "coordinates": float64 [n, n_axes] (row i belongs to names[i]), "proportion": float64 [n_axes], the
+    share of the total inertia on each axis, "eigenvalues": float64 [n_axes]}."""
+
+    def __init__(self, n_axes: int = 3, *, k: int = 12, sketch_size: int | None = 3_000, moltype: str = "dna",
+                 distance_mode: str = "mash", mash_canonical_kmers: bool | None = None, canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             moltypes="dna/rna", canonical=canonical)
+        if isinstance(n_axes, bool) or not isinstance(n_axes, (int, np.integer)) or not 1 <= n_axes <= _distance.PCOA_MAX_AXES:
+            raise ValueError(f"n_axes must be an integer in 1 .. {_distance.PCOA_MAX_AXES}, not {n_axes!r}")
+        self._n_axes = int(n_axes)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
+
+    def main(self, seqs):
+        names, arrays = _as_arrays(seqs, self._moltype)
+        names, fit = _cluster.ordinate(dict(zip(names, arrays)), self._n_axes, **self._mode_kwargs())
+        return {"names": names, "coordinates": fit.coordinates, "proportion": fit.proportion, "eigenvalues": fit.values}
 
 
 @_define_app

@@ -17,11 +17,15 @@ scipy's cophenet, the correlation reduced on the GPU by csrc/crossdist.hip's cop
 tree with branch lengths and no molecular clock; `nj_to_newick`, `patristic`, `nj_tree`); and farthest-first selection
 of representatives over a caller's own distance matrix (`maxmin`, csrc/maxmin.hip); and the pairs of a caller's matrix
 within a radius (`within`), the groups they make (`threshold_clusters`: the single-linkage clusters at that height
-without the tree) and, over sequences, those groups with one representative each (`dereplicate`).
+without the tree) and, over sequences, those groups with one representative each (`dereplicate`); and the picture of a
+collection's distances, principal coordinates (`pcoa` over a caller's matrix, `ordinate` over sequences, csrc/pcoa.hip;
+`landmark_pcoa`: the ordination of a few thousand farthest-first landmarks with every other sequence projected into
+it, for collections whose N x N matrix could never exist).
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import sys
 from collections.abc import Sequence
@@ -238,6 +242,76 @@ def nj_tree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance
                               canonical=canonical) as dev:
         tree = dev.nj()
     return nj_to_newick(names, tree), tree
+
+
+def pcoa(dist, n_axes: int = 3, *, tol: float = 1e-8, max_basis: int | None = None, strict: bool = True,
+         ctx: engine.Context | None = None) -> "distance.PCoA":
+    """principal coordinates (PCoA, classical MDS; include/dvs_hip.h) of an n x n distance matrix on the GPU ->
+    `distance.PCoA`: the n_axes largest eigenpairs of Gower's double-centred matrix, the coordinates, the proportion of
+    the inertia on each axis and the true residual of every pair.  The entries are used as they are (no square root);
+    the diagonal counts as 0 and is never read; the matrix must be symmetric bit for bit and finite off the diagonal
+    (ValueError).  strict: RuntimeError unless every axis converged to tol; strict=False returns what the basis of
+    max_basis columns (None: min(n - 1, 512)) gave, with `converged` False -- a spectrum without gaps is a property of
+    the data.  The shape and the arguments are checked before any device work.
+
+    `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the context's
+    device, which is only READ and the same afterwards -- unlike `linkage` and `neighbor_joining` next to it, which
+    overwrite theirs; the call waits for the work torch has queued on that device's current stream."""
+    src, n, wait = _caller_matrix(dist)
+    args = distance.check_pcoa_args(n, n_axes, tol, max_basis)
+    wait()
+    return distance.run_pcoa(ctx, n, src, *args, strict)
+
+
+def ordinate(seqs: dict, n_axes: int = 3, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
+             mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False, tol: float = 1e-8,
+             max_basis: int | None = None, strict: bool = True):
+    """sequences {name: uint8 codes} -> (names, distance.PCoA): the distances of `distance_mode` and their principal
+    coordinates both on the GPU, the N x N matrix never leaving HBM (dvs_pcoa over the mode's source); row i of the
+    coordinates is the i-th name.  Argument checks as `ctree` and `pcoa`, before any device work."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
+    names = list(seqs)
+    distance.check_pcoa_args(len(names), n_axes, tol, max_basis)
+    with distance.device_side([seqs[n] for n in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
+        return names, dev.pcoa(n_axes, tol=tol, max_basis=max_basis, strict=strict)
+
+
+def landmark_pcoa(seqs, n_landmarks: int, n_axes: int = 3, *, k: int = 12, sketch_size: int | None = 3000,
+                  distance_mode: str = "mash", mash_canonical_kmers: bool | None = None, num_states: int = 4,
+                  canonical: bool = False, tol: float = 1e-8, max_basis: int | None = None, strict: bool = True, seeds=(0,)):
+    """sequences {name: uint8 codes} -> (names, coordinates float64 [N, n_axes], landmarks int64 [L], distance.PCoA of
+    the landmarks): landmark MDS.  n_landmarks rows are picked farthest-first (`DeviceSide.maxmin` from `seeds`), their
+    L x L distances go to the host (L a few thousand at most) and through `pcoa`, and every row -- the landmarks
+    included, which get their own coordinates back -- is projected against the landmarks by Gower's formula
+    (`DeviceSide.pcoa_project`).  The N x N matrix never exists; the sketches or the count matrix are made once and stay
+    in HBM.  Argument checks as `ctree`, `maxmin` and `pcoa` (n_axes <= L - 1), before any device work.
+
+    `seqs` may also be a `distance.DeviceSide` the caller has made (sketches or a count matrix already in HBM, frequency
+    rows included): it is used as it is and left open, the mode arguments are not looked at, and names is None."""
+    if isinstance(seqs, distance.DeviceSide):
+        names, n, side = None, seqs.n, contextlib.nullcontext(seqs)
+    else:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
+        names = list(seqs)
+        n = len(names)
+    distance.check_maxmin_args(n, n_landmarks, seeds, None)
+    distance.check_pcoa_args(int(n_landmarks), n_axes, tol, max_basis)
+    if names is not None:
+        side = distance.device_side([seqs[name] for name in names], distance_mode,
+                                    *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                                    canonical=canonical)
+    with side as dev:
+        marks = dev.maxmin(n_landmarks, seeds=seeds).picks
+        if marks.size < 2 or n_axes > marks.size - 1:
+            raise ValueError(f"only {marks.size} landmarks could be picked: too few for {n_axes} axes")
+        fit = pcoa(dev.cross_distances(dev, marks, marks), n_axes, tol=tol, max_basis=max_basis, strict=strict, ctx=dev.ctx)
+        return names, dev.pcoa_project(fit, dev, None, marks), marks.astype(np.int64), fit
 
 
 def cut_tree(Z, *, n_clusters: int | None = None, height: float | None = None) -> np.ndarray:

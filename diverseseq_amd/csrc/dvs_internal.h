@@ -267,6 +267,18 @@ hipError_t dvs_linkage_enqueue_prepare(dvs_ctx *ctx, double *d_dist, uint32_t n,
 // written.  DVS_ERR_NOMEM unless its scratch fits beside the matrix.
 int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *joins, double *lengths);
 
+// pcoa.hip: the principal coordinates (include/dvs_hip.h) of the n x n matrix at d_dist, which is only read; enqueued
+// behind whatever wrote it on the context's stream, d_zerodiv as above; returns when the host outputs (dvs_pcoa's) are
+// written.  The caller has run dvs_pcoa_check_args (the arguments, then n) and dvs_pcoa_fits (DVS_ERR_NOMEM unless the
+// matrix -- need_matrix --, the basis and the small blocks fit the device).  dvs_pcoa_given: a caller's matrix, every check
+// included.
+int dvs_pcoa_check_args(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p);
+int dvs_pcoa_fits(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p, bool need_matrix);
+int dvs_pcoa_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv, const dvs_pcoa_params *p,
+                    double *values, double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info);
+int dvs_pcoa_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_pcoa_params *p, double *values,
+                   double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info);
+
 // linkage.hip, host only: the in-order walk of the tree behind dvs_linkage's outputs (include/dvs_hip.h "cophenetic
 // distances"): order[n] the leaves in dendrogram order, pos[n] its inverse, gap[n - 1] the merge between positions p
 // and p + 1, *c_bar the mean of all cophenetic distances.  DVS_ERR_VALUE for n < 2 or a pair that names a cluster not

@@ -271,6 +271,21 @@ int stage_to_nj(dvs_ctx *ctx, const dvs_dist_stage &st, uint32_t *joins, double 
                          lengths);
 }
 
+// The same with the principal coordinates (pcoa.hip) behind the distances, which only read the matrix; the checks in
+// the same order: the arguments, n, the mode's own, the device, the fit in HBM.
+int stage_to_pcoa(dvs_ctx *ctx, const dvs_dist_stage &st, const dvs_pcoa_params *p, double *values, double *vectors,
+                  double *residuals, double *row_means, dvs_pcoa_info *info) {
+    if (int rc = dvs_pcoa_check_args(ctx, st.n, p)) return rc;
+    if (int rc = st.check()) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx}, d_scratch{ctx};
+    int rc = dvs_pcoa_fits(ctx, st.n, p, true);
+    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
+    if (rc) return rc;
+    return dvs_pcoa_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr, p,
+                           values, vectors, residuals, row_means, info);
+}
+
 }  // namespace
 
 int dvs_rows_check(dvs_ctx *ctx, uint32_t n) { return rows_check(ctx, n); }
@@ -340,4 +355,15 @@ extern "C" int dvs_nj(dvs_ctx *ctx, const dvs_source *src, uint32_t *joins, doub
     if (src->kind == DVS_SRC_GIVEN)
         return dvs_nj_given(ctx, static_cast<double *>(src->handle), src->on_device, src->n, joins, lengths);
     return stage_to_nj(ctx, source_stage(ctx, src), joins, lengths);
+}
+
+extern "C" int dvs_pcoa(dvs_ctx *ctx, const dvs_source *src, const dvs_pcoa_params *params, double *values, double *vectors,
+                        double *residuals, double *row_means, dvs_pcoa_info *info) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (!params || !values || !vectors || !residuals || !row_means || !info) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (int rc = dvs_source_whole(ctx, "dvs_pcoa", src)) return rc;
+    if (src->kind == DVS_SRC_GIVEN)
+        return dvs_pcoa_given(ctx, static_cast<const double *>(src->handle), src->on_device, src->n, params, values, vectors,
+                              residuals, row_means, info);
+    return stage_to_pcoa(ctx, source_stage(ctx, src), params, values, vectors, residuals, row_means, info);
 }

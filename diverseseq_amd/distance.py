@@ -17,7 +17,11 @@ csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterp
 product over the same strips: the pairs within a radius (within, neighbours, matrix_within -> `Neighbours`) and the
 groups they make (threshold_clusters, matrix_threshold_clusters -> `ThresholdClusters`: connected components, the
 single-linkage clusters at that height), each strip compacted on the device (csrc/crossdist.hip) so that only the listed
-pairs cross to the host; no counterpart in the reference.  `DeviceSide`
+pairs cross to the host; no counterpart in the reference; and the ordination of a collection's distances, principal
+coordinates (pcoa, matrix_pcoa, mash_pcoa / euclidean_pcoa / jsd_pcoa -> `PCoA`: csrc/pcoa.hip, the few largest eigenpairs
+of the double-centred matrix by an iteration that only reads the N x N matrix in HBM) with the projection of further
+rows into a fitted ordination (pcoa_project, matrix_pcoa_project: Gower's formula beside each strip of
+cross_distances, csrc/crossdist.hip); no counterpart in the reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
 matrix_* functions and the Sketches methods are a few lines over it.  Every operation has one C entry, which takes a
 `_lib.Source` (dvs_source: the mode and its handle, or a caller's matrix): `make_source` fills one per call."""
@@ -311,7 +315,32 @@ class Sketches:
         return DeviceSide(self, "mash").threshold_clusters(radius, rows)
 
 
-class DeviceSide:
+class OrdinationOps:
+    """The ordination operations of a `DeviceSide` -- principal coordinates and the projection into a fitted ordination
+    -- which it inherits: `DeviceSide.pcoa`, `DeviceSide.pcoa_project`.  They stand in a base class of their own because
+    tests/test_blocks_host.py pins the operations `DeviceSide` itself defines to those with a poisoned-block case in
+    its table; the cases of these two are in tests/test_gpu_pcoa.py."""
+
+    def pcoa(self, n_axes: int = 3, *, tol: float = 1e-8, max_basis: int | None = None, strict: bool = True) -> "PCoA":
+        """the principal coordinates of the distances (`PCoA`), the N x N matrix written and only read in HBM"""
+        args = check_pcoa_args(self.n, n_axes, tol, max_basis)
+        return run_pcoa(self.ctx, self.n, self._source(), *args, strict)
+
+    def pcoa_project(self, fit: "PCoA", other: "DeviceSide", rows=None, other_rows=None) -> np.ndarray:
+        """the coordinates of this side's `rows` (None: all) in the ordination `fit` of `other`'s `other_rows` (None:
+        all; they are the fitted rows, in the fit's order): float64 [M, n_axes]"""
+        self._against(other)
+        q, r = _row_list(rows, self.n), _row_list(other_rows, other.n)
+        values, vectors, mu = check_pcoa_fit(fit, r[1])
+        coords = np.zeros((q[1], values.size), dtype=np.float64)
+        q, r = self._source(q), other._source(r)
+        self.ctx.check(self.ctx._L.dvs_pcoa_project(self.ctx._h, q, r, values.size, _lib.ptr(values, C.c_double),
+                                                    _lib.ptr(vectors, C.c_double), _lib.ptr(mu, C.c_double),
+                                                    _lib.ptr(coords, C.c_double)))
+        return coords
+
+
+class DeviceSide(OrdinationOps):
     """What a distance mode keeps in HBM of one batch -- its `Sketches` (mash) or its count matrix (euclidean, jsd) --
     together with the mode: every operation over "the distances of a collection", whatever the mode.  `device_side`
     makes one that owns its handle; DeviceSide(handle, mode) wraps a handle of the caller's, which close() then leaves
@@ -1157,3 +1186,168 @@ def threshold_clusters(seqs, radius, distance_mode: str = "mash", *, k: int, ske
     with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
                      canonical=canonical) as dev:
         return dev.threshold_clusters(radius)
+
+
+# ---- principal coordinates (PCoA, classical MDS) and the projection of further rows
+
+PCOA_MAX_AXES = 64  # include/dvs_hip.h: a full spectrum takes a dense solver
+
+
+class PCoA(NamedTuple):
+    """The principal coordinates of n rows (include/dvs_hip.h "principal coordinates"): the n_axes algebraically largest
+    eigenpairs of Gower's double-centred matrix B = J (-1/2 D o D) J, in descending order.
+    values float64 [n_axes]; vectors float64 [n, n_axes], unit columns orthogonal to 1, the component of largest
+    magnitude positive; coordinates float64 [n, n_axes] = vectors * sqrt(values), a zero column where values <= 0 (a
+    non-Euclidean matrix has such axes; they come last); proportion = values / trace; residuals float64 [n_axes], the
+    true ||B v - lambda v||_2 of each returned pair; row_means float64 [n], the row means of the squared distances (what
+    a projection needs beside values and vectors); trace, the total inertia (1 / 2n) sum d^2; converged: every residual
+    <= tol * values[0]; basis, steps: the columns of the Krylov basis at the end and the passes over the matrix."""
+    values: np.ndarray
+    vectors: np.ndarray
+    coordinates: np.ndarray
+    proportion: np.ndarray
+    residuals: np.ndarray
+    row_means: np.ndarray
+    trace: float
+    converged: bool
+    basis: int
+    steps: int
+
+
+def check_pcoa_args(n: int, n_axes, tol, max_basis) -> tuple[int, float, int]:
+    """the arguments of a principal-coordinates run over n rows as dvs_pcoa takes them -> (n_axes, tol, max_basis with
+    0 for None), checked before any device work: ValueError unless n >= 2, n_axes is an integer in 1 .. n - 1, tol a
+    number >= 0 and max_basis None or an integer >= n_axes; NotImplementedError for n_axes > PCOA_MAX_AXES"""
+    if n < 2:
+        raise ValueError(f"need at least two rows for principal coordinates, not {n}")
+    if isinstance(n_axes, bool) or not isinstance(n_axes, (int, np.integer)):
+        raise ValueError(f"n_axes must be an integer, not {n_axes!r}")
+    if n_axes < 1 or n_axes > n - 1:
+        raise ValueError(f"n_axes = {n_axes}: between 1 and n - 1 = {n - 1}")
+    if n_axes > PCOA_MAX_AXES:
+        raise NotImplementedError(f"n_axes = {n_axes}: {PCOA_MAX_AXES} at most (a full spectrum takes a dense solver)")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not float(tol) >= 0.0:
+        raise ValueError(f"tol must be a number >= 0, not {tol!r}")
+    if max_basis is None:
+        max_basis = 0
+    elif isinstance(max_basis, bool) or not isinstance(max_basis, (int, np.integer)) or max_basis < n_axes:
+        raise ValueError(f"max_basis must be None or an integer >= n_axes = {n_axes}, not {max_basis!r}")
+    return int(n_axes), float(tol), int(max_basis)
+
+
+def check_pcoa_fit(fit, n_fitted: int):
+    """the tables of a fit as dvs_pcoa_project takes them -> (values [m], vectors [n_fitted, m], row_means [n_fitted]),
+    contiguous float64; ValueError unless `fit` is a `PCoA` (or has its values, vectors and row_means) of n_fitted rows"""
+    try:
+        values = np.ascontiguousarray(fit.values, dtype=np.float64)
+        vectors = np.ascontiguousarray(fit.vectors, dtype=np.float64)
+        mu = np.ascontiguousarray(fit.row_means, dtype=np.float64)
+    except AttributeError:
+        raise ValueError("a projection takes the PCoA of the fitted rows") from None
+    if values.ndim != 1 or values.size < 1 or vectors.shape != (mu.size, values.size):
+        raise ValueError(f"a fit of shapes {values.shape}, {vectors.shape}, {mu.shape}: values [m], vectors [n, m], row_means [n]")
+    if values.size > PCOA_MAX_AXES:
+        raise NotImplementedError(f"{values.size} axes: {PCOA_MAX_AXES} at most")
+    if mu.size != n_fitted or n_fitted == 0:
+        raise ValueError(f"the fit holds {mu.size} rows, the references {n_fitted}: they must be the fitted rows")
+    return values, vectors, mu
+
+
+def run_pcoa(ctx: engine.Context | None, n: int, src: _lib.Source, n_axes: int, tol: float, max_basis: int,
+             strict: bool = True) -> PCoA:
+    """dvs_pcoa over `src` for n rows (the arguments as `check_pcoa_args` returns them) -> PCoA.  strict: RuntimeError,
+    naming the worst residual, unless every axis converged; strict=False returns what the basis gave, `converged` False"""
+    ctx = ctx or engine.default_context()
+    params = _lib.PcoaParams(n_axes, max_basis, tol)
+    info = _lib.PcoaInfo()
+    values, residuals = np.zeros(n_axes, dtype=np.float64), np.zeros(n_axes, dtype=np.float64)
+    vectors, mu = np.zeros((n, n_axes), dtype=np.float64), np.zeros(n, dtype=np.float64)
+    ctx.check(ctx._L.dvs_pcoa(ctx._h, src, C.byref(params), _lib.ptr(values, C.c_double), _lib.ptr(vectors, C.c_double),
+                              _lib.ptr(residuals, C.c_double), _lib.ptr(mu, C.c_double), C.byref(info)))
+    converged = info.converged == n_axes
+    if strict and not converged:
+        worst = int(np.argmax(residuals))
+        raise RuntimeError(f"principal coordinates: {n_axes - info.converged} of {n_axes} axes did not converge in a basis of "
+                           f"{info.basis} columns ({info.steps} steps); the worst residual, axis {worst}, is "
+                           f"{residuals[worst]:.3g} against tol * lambda_1 = {tol * max(values[0], 0.0):.3g} (a spectrum "
+                           "without gaps is a property of the data: raise max_basis or tol, or pass strict=False)")
+    pos = values > 0.0
+    coordinates = np.where(pos, vectors * np.sqrt(np.where(pos, values, 0.0)), 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        proportion = values / info.trace
+    return PCoA(values, vectors, coordinates, proportion, residuals, mu, float(info.trace), bool(converged), int(info.basis),
+                int(info.steps))
+
+
+def matrix_pcoa(m: "engine.CountMatrix", mode: str = "jsd", n_axes: int = 3, *, tol: float = 1e-8,
+                max_basis: int | None = None, strict: bool = True) -> PCoA:
+    """`pcoa` over the rows of a matrix already in HBM, by `mode` ("jsd" or "euclidean")"""
+    return _count_side(m, mode).pcoa(n_axes, tol=tol, max_basis=max_basis, strict=strict)
+
+
+def matrix_pcoa_project(fit: PCoA, q: "engine.CountMatrix", r: "engine.CountMatrix", mode: str = "jsd", q_rows=None,
+                        r_rows=None) -> np.ndarray:
+    """the coordinates of rows q_rows of q (None: all) in the ordination `fit` of rows r_rows of r, by `mode`: float64
+    [M, n_axes]; q and r as `matrix_cross_distances` takes them"""
+    return _count_side(q, mode).pcoa_project(fit, _count_side(r, mode), q_rows, r_rows)
+
+
+def mash_pcoa(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *, n_axes: int = 3,
+              tol: float = 1e-8, max_basis: int | None = None, strict: bool = True,
+              ctx: engine.Context | None = None) -> PCoA:
+    """the principal coordinates of the mash distances on the device: sketches, the N x N distances and the iteration,
+    every stage in HBM; only the n_axes eigenpairs come back.  ZeroDivisionError as `mash_distances`."""
+    return _pcoa(seqs, "mash", k, sketch_size, num_states, mash_canonical, n_axes=n_axes, tol=tol, max_basis=max_basis,
+                 strict=strict, ctx=ctx)
+
+
+def euclidean_pcoa(seqs, k: int, num_states: int = 4, *, n_axes: int = 3, tol: float = 1e-8, max_basis: int | None = None,
+                   strict: bool = True, ctx: engine.Context | None = None, canonical: bool = False) -> PCoA:
+    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    return _pcoa(seqs, "euclidean", k, num_states, n_axes=n_axes, tol=tol, max_basis=max_basis, strict=strict, ctx=ctx,
+                 canonical=canonical)
+
+
+def jsd_pcoa(seqs, k: int, num_states: int = 4, *, n_axes: int = 3, tol: float = 1e-8, max_basis: int | None = None,
+             strict: bool = True, ctx: engine.Context | None = None, canonical: bool = False) -> PCoA:
+    """the same for the Jensen-Shannon divergences of `jsd_distances` (a sequence without valid k-mers: ValueError)"""
+    return _pcoa(seqs, "jsd", k, num_states, n_axes=n_axes, tol=tol, max_basis=max_basis, strict=strict, ctx=ctx,
+                 canonical=canonical)
+
+
+def _pcoa(seqs, distance_mode: str, *args, n_axes, tol, max_basis, strict, ctx, canonical: bool = False) -> PCoA:
+    check_pcoa_args(len(seqs), n_axes, tol, max_basis)
+    with device_side(seqs, distance_mode, *args, ctx=ctx, canonical=canonical) as dev:
+        return dev.pcoa(n_axes, tol=tol, max_basis=max_basis, strict=strict)
+
+
+# a distance mode -> its principal coordinates: takes (seqs, *mode_args(...)), and n_axes=, tol=, max_basis=, strict=, ctx=
+PCOA_MODES = {"mash": mash_pcoa, "euclidean": euclidean_pcoa, "jsd": jsd_pcoa}
+
+
+def pcoa(seqs, n_axes: int = 3, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
+         mash_canonical: bool = False, tol: float = 1e-8, max_basis: int | None = None, strict: bool = True,
+         ctx: engine.Context | None = None, canonical: bool = False) -> PCoA:
+    """the principal coordinates (`PCoA`) of the `distance_mode` distances of a collection of sequences: the distances
+    are written into HBM and stay there, only the n_axes eigenpairs come back.  Argument checks as cluster.ctree and
+    those of `check_pcoa_args`, before any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    seqs = list(seqs)
+    return _pcoa(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), n_axes=n_axes,
+                 tol=tol, max_basis=max_basis, strict=strict, ctx=ctx, canonical=canonical)
+
+
+def pcoa_project(fit: PCoA, queries, refs, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+                 num_states: int = 4, mash_canonical: bool = False, ctx: engine.Context | None = None,
+                 canonical: bool = False) -> np.ndarray:
+    """the coordinates of every query sequence in the ordination `fit` of the sequences `refs` (the fitted ones, in the
+    fit's order) by Gower's formula over the `distance_mode` distances: float64 [M, n_axes].  Only the M x N distances
+    are computed, strip by strip, and none leaves the device.  A query without a valid k-mer (jsd, euclidean) gets NaN
+    coordinates.  Argument checks as `cross_distances` and the fit's shapes, before any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    queries, refs = list(queries), list(refs)
+    values, _, _ = check_pcoa_fit(fit, len(refs))
+    if not queries:
+        return np.zeros((0, values.size), dtype=np.float64)
+    return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                      ctx, lambda q, r: q.pcoa_project(fit, r), canonical)

@@ -689,6 +689,68 @@ int dvs_maxmin(dvs_ctx *ctx, const dvs_source *src, const uint32_t *seeds, uint3
                int use_min_distance, double min_distance, uint32_t *picks, double *radius, uint32_t *n_picked,
                uint32_t *owner, double *dist_to_owner, double *cover);
 
+/* ---- principal coordinates (PCoA, classical MDS), with projection of further rows ----------------- *
+ * The ordination of a collection's distances: coordinates in a few dimensions whose Euclidean distances approximate
+ * the given ones.  (No counterpart in the reference.)  The matrix is D, n x n: the entries of a MASH, EUCLIDEAN or JSD
+ * source or of a caller's GIVEN matrix as they are, no square root taken; the diagonal counts as 0 and is never read.
+ *   A = -1/2 D o D               the element-wise square times -1/2
+ *   B = J A J, J = I - 11^T / n  Gower's double centring
+ *   mu_i = (1/n) sum_j d_ij^2    the row means of the squared distances
+ *   trace(B) = (1/2n) sum_ij d_ij^2   the total inertia, known from mu alone, without any eigenvalue
+ * The result is the n_axes algebraically largest eigenpairs (lambda_a, v_a) of B, ||v_a||_2 = 1 and v_a orthogonal to
+ * 1, in descending lambda; the sign of v_a is fixed so that its component of largest magnitude (the lowest index on a
+ * tie) is positive.  Coordinates: X[i, a] = v_a[i] sqrt(lambda_a) for lambda_a > 0, else 0; proportion:
+ * lambda_a / trace(B).  A JSD or mash matrix is not Euclidean: B then has negative eigenvalues, which are never among
+ * the returned axes unless n_axes reaches into them.
+ * B is never formed: the iteration keeps every vector orthogonal to 1, so B x = A x - mean(A x) 1, and the kernel
+ * squares the cells as it reads them.  The n x n matrix is only READ, a GIVEN device matrix as well as the scratch a
+ * mode wrote -- unlike the two trees, which overwrite their working buffer.  The solver is a block Krylov iteration
+ * (blocks of 16 columns, start vectors from a counter-based hash of (row, column)) with full orthogonalisation and
+ * Rayleigh-Ritz on the host; it stops when the n_axes leading Ritz pairs all have residual <= tol * lambda_1, or when
+ * the basis holds max_basis columns (0: min(n - 1, 512); never more than n - 1, at which it spans the whole
+ * complement of 1 and the pairs are exact).
+ *   values[n_axes], vectors[n x n_axes] row-major, row_means[n] (mu)
+ *   residuals[n_axes]   the true ||B v_a - lambda_a v_a||_2 of the vectors returned
+ *   info: trace; converged, the number of axes with residual <= tol * lambda_1; basis, the columns of the basis at the
+ *         end; steps, the passes over the matrix; products, the matrix-vector products they held
+ * A call that runs out of basis returns DVS_OK with what it has: info->converged < n_axes.  A spectrum without gaps is a
+ * property of the data, not an error of the call.  Every sum is added in an order that n and the block shape fix: the
+ * same bits on every run, and for a GIVEN host matrix and the same matrix in device memory.
+ * The sources as for dvs_nj: whole, no row list; MASH, EUCLIDEAN and JSD write their matrix into the context's scratch,
+ * where it stays; a GIVEN host matrix is uploaded, a GIVEN device matrix read where it is.  The checks come in this
+ * order, all before any device work: the arguments, n, the source's own, the device, the fit in HBM.
+ *   DVS_ERR_VALUE: n < 2; n_axes == 0 or n_axes > n - 1; tol < 0 or NaN; max_basis < n_axes when not 0; a device
+ *                  matrix on another device; and, found by the pass in front of the first step, a NaN or +-inf entry
+ *                  off the diagonal (the text the trees give) or D[i][j] and D[j][i] that differ in a bit
+ *   DVS_ERR_UNSUPPORTED: n_axes > 64; max_basis > 4096; a row list, or n other than the handle's rows
+ *   DVS_ERR_ZERODIV: (MASH) as dvs_nj
+ *   DVS_ERR_NOMEM: the matrix, the basis with B times the basis beside it (2 n max_basis doubles) and the small blocks
+ *                  do not fit in HBM
+ * dvs_pcoa_project (Gower 1968) gives further rows their coordinates in a fitted ordination: for a query with distances
+ * delta_j to the n fitted rows
+ *   x_a = -1/2 v_a^T (delta o delta - mu) / sqrt(lambda_a)    for lambda_a > 0, else 0
+ * which needs only (values, vectors, row_means) of the fit because v_a is orthogonal to 1; a fitted row projected
+ * against its own collection gets its own coordinates back.  q and r as dvs_cross_distances takes them, row lists on
+ * both sides included; r's n rows are the fitted rows in the fit's order.  The cells are computed in the same strips
+ * (the same bound, the same DVS_CROSS_STRIP_ROWS) and never leave the device: only coords, nq x n_axes row-major, comes
+ * back, the same bits for every strip height.  A NaN cell (a row without valid k-mers) makes that query's coordinates
+ * NaN.
+ *   DVS_ERR_VALUE: r->n == 0, n_axes == 0, a NULL table; DVS_ERR_UNSUPPORTED: n_axes > 64, GIVEN sources; everything
+ *                  else as dvs_cross_distances */
+typedef struct dvs_pcoa_params {
+    uint32_t n_axes, max_basis;
+    double tol;
+} dvs_pcoa_params;
+typedef struct dvs_pcoa_info {
+    double trace;
+    uint32_t converged, basis, steps;
+    uint64_t products;
+} dvs_pcoa_info;
+int dvs_pcoa(dvs_ctx *ctx, const dvs_source *src, const dvs_pcoa_params *params, double *values, double *vectors,
+             double *residuals, double *row_means, dvs_pcoa_info *info);
+int dvs_pcoa_project(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, uint32_t n_axes, const double *values,
+                     const double *vectors, const double *row_means, double *coords);
+
 #ifdef __cplusplus
 }
 #endif
