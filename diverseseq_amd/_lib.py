@@ -48,7 +48,7 @@ EXPORTS = (
     "dvs_linkage_cut", "dvs_linkage_cophenet", "dvs_nj_patristic", "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get",
     # one entry per operation over the distances of a `Source`
     "dvs_distances", "dvs_linkage", "dvs_nj", "dvs_maxmin", "dvs_cross_distances", "dvs_nearest", "dvs_within",
-    "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters", "dvs_pcoa", "dvs_pcoa_project",
+    "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters", "dvs_pcoa", "dvs_pcoa_project", "dvs_kmedoids",
 )
 WITHIN_SKIP_SELF = 1
 SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
@@ -69,6 +69,20 @@ class PcoaInfo(C.Structure):
     """dvs_pcoa_info"""
     _fields_ = [("trace", C.c_double), ("converged", C.c_uint32), ("basis", C.c_uint32), ("steps", C.c_uint32),
                 ("products", C.c_uint64)]
+
+
+class KmedoidsParams(C.Structure):
+    """dvs_kmedoids_params"""
+    _fields_ = [("k", C.c_uint32), ("init", C.c_uint32), ("max_swaps", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KmedoidsInfo(C.Structure):
+    """dvs_kmedoids_info"""
+    _fields_ = [("td_init", C.c_double), ("td", C.c_double), ("n_swaps", C.c_uint32), ("stop", C.c_uint32),
+                ("passes", C.c_uint32)]
+
+
+KMEDOIDS_INIT_BUILD, KMEDOIDS_INIT_GIVEN = 0, 1
 
 
 class SelectParams(C.Structure):
@@ -259,6 +273,9 @@ def load() -> C.CDLL:
         # params, values, vectors, residuals, row_means, info
         L.dvs_pcoa.argtypes = [vp, srcp, C.POINTER(PcoaParams), f64p, f64p, f64p, f64p, C.POINTER(PcoaInfo)]
         L.dvs_pcoa_project.argtypes = [vp, srcp, srcp, u32, f64p, f64p, f64p, f64p]  # n_axes, values, vectors, row_means, coords
+        # params, medoids, labels, dist, second, swaps, td, info
+        L.dvs_kmedoids.argtypes = [vp, srcp, C.POINTER(KmedoidsParams), u32p, u32p, f64p, f64p, u32p, f64p,
+                                   C.POINTER(KmedoidsInfo)]
         if L.dvs_abi_version() != 4:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -10,7 +10,9 @@ the tree, its flat clusters at a cut, one representative per cluster and the sil
 (diverseseq_amd.cluster.ctree_clusters); and `dvs_njtree`: the neighbour-joining tree of the same distances, with branch
 lengths (diverseseq_amd.cluster.nj_tree); and `dvs_maxmin`: farthest-first selection of representatives by distance,
 a diverse panel or a dereplication (diverseseq_amd.distance.maxmin); and `dvs_pcoa`: the principal coordinates of the
-same distances, the picture that goes with the trees and the clusters (diverseseq_amd.cluster.ordinate).
+same distances, the picture that goes with the trees and the clusters (diverseseq_amd.cluster.ordinate); and
+`dvs_kmedoids`: the n sequences that represent a collection best, k-medoids over the same distances
+(diverseseq_amd.cluster.representatives).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -42,7 +44,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa", "dvs_kmedoids"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -310,6 +312,42 @@ class dvs_pcoa(_DistanceApp):
         names, arrays = _as_arrays(seqs, self._moltype)
         names, fit = _cluster.ordinate(dict(zip(names, arrays)), self._n_axes, **self._mode_kwargs())
         return {"names": names, "coordinates": fit.coordinates, "proportion": fit.proportion, "eigenvalues": fit.values}
+
+
+@_define_app
+class dvs_kmedoids(_DistanceApp):
+    """The n sequences that represent a collection best (beyond the reference, which has no such app): k-medoids, the
+    set whose members lie closest, in total, to everything else, by any distance of `dvs_dist`.  The mode arguments and
+    their checks as `dvs_maxmin`; init: "build" (PAM's BUILD) or "maxmin" (farthest-first picks as the start);
+    max_swaps: the most exchanges made (0: the initial set as it is).  `main(seqs)` returns {"representatives": [names,
+    slot order], "sizes": [the size of each one's cluster], "representative": {name: its representative's name},
+    "distance": {name: float}, "total_distance": float, "converged": bool}."""
+
+    def __init__(self, n: int, distance_mode: str = "mash", *, k: int = 12, sketch_size: int | None = 3_000,
+                 moltype: str = "dna", mash_canonical_kmers: bool | None = None, init: str = "build", max_swaps: int = 300,
+                 canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= _distance.KMEDOIDS_MAX_K:
+            raise ValueError(f"n must be an integer in 1 .. {_distance.KMEDOIDS_MAX_K}, not {n!r}")
+        if init not in ("build", "maxmin"):
+            raise ValueError(f"init must be 'build' or 'maxmin', not {init!r}")
+        if (isinstance(max_swaps, bool) or not isinstance(max_swaps, (int, np.integer))
+                or not 0 <= max_swaps <= _distance.KMEDOIDS_MAX_SWAPS):
+            raise ValueError(f"max_swaps must be an integer in 0 .. {_distance.KMEDOIDS_MAX_SWAPS}, not {max_swaps!r}")
+        self._n, self._init, self._max_swaps = int(n), init, int(max_swaps)
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
+
+    def main(self, seqs):
+        names, arrays = _as_arrays(seqs, self._moltype)
+        if not names:
+            raise ValueError("no sequences")
+        reps, sizes, labels, fit = _cluster.representatives(dict(zip(names, arrays)), self._n, init=self._init,
+                                                            max_swaps=self._max_swaps, **self._mode_kwargs())
+        return {"representatives": reps, "sizes": [int(v) for v in sizes],
+                "representative": {name: reps[l] for name, l in zip(names, labels.tolist())},
+                "distance": {name: float(d) for name, d in zip(names, fit.dist)},
+                "total_distance": float(fit.td[-1]), "converged": bool(fit.stop)}
 
 
 @_define_app

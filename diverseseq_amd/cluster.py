@@ -20,7 +20,10 @@ within a radius (`within`), the groups they make (`threshold_clusters`: the sing
 without the tree) and, over sequences, those groups with one representative each (`dereplicate`); and the picture of a
 collection's distances, principal coordinates (`pcoa` over a caller's matrix, `ordinate` over sequences, csrc/pcoa.hip;
 `landmark_pcoa`: the ordination of a few thousand farthest-first landmarks with every other sequence projected into
-it, for collections whose N x N matrix could never exist).
+it, for collections whose N x N matrix could never exist); and the representatives that lie closest, in total, to
+everything else, k-medoids (`kmedoids` over a caller's matrix, `representatives` over sequences, csrc/kmedoids.hip;
+`sampled_kmedoids`: k-medoids of farthest-first landmarks with every sequence assigned to its nearest medoid, for
+collections whose N x N matrix could never exist).
 """
 
 from __future__ import annotations
@@ -368,6 +371,83 @@ def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float
     args = distance.check_maxmin_args(n, n_select, seeds, min_distance)
     wait()
     return distance._run_maxmin(ctx, n, *args, src)
+
+
+def kmedoids(dist, n_medoids: int, *, init="build", max_swaps: int = 300,
+             ctx: engine.Context | None = None) -> "distance.KMedoids":
+    """k-medoids (PAM; include/dvs_hip.h "k-medoids") over a caller's n x n dissimilarity matrix on the GPU ->
+    `distance.KMedoids`: the n_medoids rows that minimise the total distance of every row to its nearest one, with the
+    partition they make.  d(x, o) is dist[x, o]: a row is read as it stands (the matrix need not be symmetric), the
+    diagonal never; every other entry must be finite and >= 0 (ValueError).  init: "build" (PAM's BUILD), "maxmin"
+    (the first n_medoids picks of `maxmin` from row 0) or the initial medoids as rows; max_swaps = 0 scores a set as it
+    is -- the picks of `nmost` or `maxmin` as representatives, say.
+
+    `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
+    as `cluster_scores` handles it and only READ.  The arguments are checked before any device work."""
+    src, n, wait = _caller_matrix(dist)
+    k, kind, rows, max_swaps = distance.check_kmedoids_args(n, n_medoids, init, max_swaps)
+    wait()
+    if kind == "maxmin":
+        rows = distance._run_maxmin(ctx, n, *distance.check_maxmin_args(n, k, (0,), None), src).picks.astype(np.uint32)
+        if rows.size != k:
+            raise ValueError(f"farthest-first selection found only {rows.size} of {k} initial medoids")
+    return distance.run_kmedoids(ctx, n, src, k, rows, max_swaps)
+
+
+def representatives(seqs: dict, n: int, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
+                    mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False, init="build",
+                    max_swaps: int = 300):
+    """sequences {name: uint8 codes} -> (the names of the n representatives, int64 [n] the size of each one's cluster,
+    int64 [N] labels: the position among the representatives of every sequence's nearest one, in the order of seqs;
+    the `distance.KMedoids`): the distances of `distance_mode` and k-medoids over them both on the GPU, the N x N
+    matrix never leaving HBM.  Argument checks as `ctree` and `kmedoids`, before any device work."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
+    names = list(seqs)
+    distance.check_kmedoids_args(len(names), n, init, max_swaps)
+    with distance.device_side([seqs[name] for name in names], distance_mode,
+                              *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                              canonical=canonical) as dev:
+        fit = dev.kmedoids(n, init=init, max_swaps=max_swaps)
+    return [names[i] for i in fit.medoids.tolist()], np.bincount(fit.labels, minlength=n).astype(np.int64), fit.labels, fit
+
+
+def sampled_kmedoids(seqs, n_medoids: int, n_sample: int, *, k: int = 12, sketch_size: int | None = 3000,
+                     distance_mode: str = "mash", mash_canonical_kmers: bool | None = None, num_states: int = 4,
+                     canonical: bool = False, init="build", max_swaps: int = 300, seeds=(0,)):
+    """sequences {name: uint8 codes} -> (names, medoids int64 [n_medoids] as rows of the collection, labels int64 [N],
+    dist float64 [N], landmarks int64 [L], distance.KMedoids of the landmarks): k-medoids of a collection whose N x N
+    matrix cannot exist.  n_sample rows are picked farthest-first (`DeviceSide.maxmin` from `seeds`), their L x L
+    distances go to the host and through `kmedoids`, and every row is given its nearest medoid
+    (`DeviceSide.nearest(..., 1)`: labels, the position among the medoids; dist, the distance to it).  The sketches or
+    the count matrix are made once and stay in HBM.  Argument checks as `ctree`, `maxmin` and `kmedoids` (n_medoids <=
+    n_sample), before any device work.
+
+    `seqs` may also be a `distance.DeviceSide` the caller has made: it is used as it is and left open, the mode
+    arguments are not looked at, and names is None."""
+    if isinstance(seqs, distance.DeviceSide):
+        names, n, side = None, seqs.n, contextlib.nullcontext(seqs)
+    else:
+        if mash_canonical_kmers is None:
+            mash_canonical_kmers = False
+        distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
+        names = list(seqs)
+        n = len(names)
+    distance.check_maxmin_args(n, n_sample, seeds, None)
+    distance.check_kmedoids_args(int(n_sample), n_medoids, init, max_swaps)
+    if names is not None:
+        side = distance.device_side([seqs[name] for name in names], distance_mode,
+                                    *distance.mode_args(distance_mode, k, sketch_size, num_states, mash_canonical_kmers),
+                                    canonical=canonical)
+    with side as dev:
+        marks = dev.maxmin(n_sample, seeds=seeds).picks
+        if marks.size < n_medoids:
+            raise ValueError(f"only {marks.size} landmarks could be picked: too few for {n_medoids} medoids")
+        fit = kmedoids(dev.cross_distances(dev, marks, marks), n_medoids, init=init, max_swaps=max_swaps, ctx=dev.ctx)
+        medoids = marks[fit.medoids]
+        labels, dist = dev.nearest(dev, 1, None, medoids)
+        return names, medoids.astype(np.int64), labels[:, 0], dist[:, 0], marks.astype(np.int64), fit
 
 
 def within(dist, radius, *, skip_self: bool = True, max_pairs: int | None = None,

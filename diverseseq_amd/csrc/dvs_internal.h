@@ -43,6 +43,7 @@ struct dvs_knobs {
     uint32_t cross_strip_rows = 0;    // DVS_CROSS_STRIP_ROWS: query rows per strip of the rectangular drivers (0: from the strip's byte bound)
     // farthest-first selection (maxmin.hip)
     uint32_t maxmin_batch = 0;        // DVS_MAXMIN_BATCH: steps enqueued between two reads of the status word (0: 64)
+    uint32_t kmedoids_batch = 0;      // DVS_KMEDOIDS_BATCH: swap rounds enqueued between two reads of the status word (0: 8)
     bool maxmin_jsd_cross = false;    // DVS_MAXMIN_JSD_CROSS: the jsd traversal runs jsd_cross_kernel on one query row (the A/B of DESIGN.md 4.13)
     // ingest
     bool ingest_no_stream = false;    // DVS_INGEST_NO_STREAM: host files are uploaded whole before they are parsed
@@ -278,6 +279,25 @@ int dvs_pcoa_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32
                     double *values, double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info);
 int dvs_pcoa_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_pcoa_params *p, double *values,
                    double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info);
+
+// kmedoids.hip: k-medoids (include/dvs_hip.h) over the n x n matrix at d_dist, which is only read; enqueued behind
+// whatever wrote it on the context's stream, d_zerodiv as above; returns when the host outputs (dvs_kmedoids's) are
+// written.  The caller has run dvs_kmedoids_check_args (the arguments, then n) and dvs_kmedoids_fits (DVS_ERR_NOMEM
+// unless the matrix -- need_matrix -- and the state fit the device).  dvs_kmedoids_given: a caller's matrix, every
+// check included.
+struct dvs_kmedoids_out {
+    uint32_t *medoids, *labels;
+    double *dist, *second;
+    uint32_t *swaps;
+    double *td;
+    dvs_kmedoids_info *info;
+};
+int dvs_kmedoids_check_args(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, const uint32_t *medoids);
+int dvs_kmedoids_fits(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, bool need_matrix);
+int dvs_kmedoids_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv,
+                        const dvs_kmedoids_params *p, const dvs_kmedoids_out &out);
+int dvs_kmedoids_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_kmedoids_params *p,
+                       const dvs_kmedoids_out &out);
 
 // linkage.hip, host only: the in-order walk of the tree behind dvs_linkage's outputs (include/dvs_hip.h "cophenetic
 // distances"): order[n] the leaves in dendrogram order, pos[n] its inverse, gap[n - 1] the merge between positions p

@@ -286,6 +286,27 @@ int stage_to_pcoa(dvs_ctx *ctx, const dvs_dist_stage &st, const dvs_pcoa_params 
                            values, vectors, residuals, row_means, info);
 }
 
+// The same with k-medoids (kmedoids.hip) behind the distances, which only read the matrix; the checks in the same
+// order: the arguments, n, the mode's own, the device, the fit in HBM.
+int stage_to_kmedoids(dvs_ctx *ctx, const dvs_dist_stage &st, const dvs_kmedoids_params *p, const dvs_kmedoids_out &out) {
+    if (int rc = dvs_kmedoids_check_args(ctx, st.n, p, out.medoids)) return rc;
+    if (st.n == 1) {  // the one item its own medoid: there is no cell to compute or to check
+        out.medoids[0] = out.labels[0] = 0;
+        out.dist[0] = 0.0;
+        if (out.second) out.second[0] = HUGE_VAL;
+        if (out.td) out.td[0] = 0.0;
+        *out.info = dvs_kmedoids_info{0.0, 0.0, 0, 1, 1};
+        return DVS_OK;
+    }
+    if (int rc = st.check()) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    PooledBuf d_dist{ctx}, d_scratch{ctx};
+    int rc = dvs_kmedoids_fits(ctx, st.n, p, true);
+    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
+    if (rc) return rc;
+    return dvs_kmedoids_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr, p, out);
+}
+
 }  // namespace
 
 int dvs_rows_check(dvs_ctx *ctx, uint32_t n) { return rows_check(ctx, n); }
@@ -366,4 +387,16 @@ extern "C" int dvs_pcoa(dvs_ctx *ctx, const dvs_source *src, const dvs_pcoa_para
         return dvs_pcoa_given(ctx, static_cast<const double *>(src->handle), src->on_device, src->n, params, values, vectors,
                               residuals, row_means, info);
     return stage_to_pcoa(ctx, source_stage(ctx, src), params, values, vectors, residuals, row_means, info);
+}
+
+extern "C" int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src, const dvs_kmedoids_params *params, uint32_t *medoids,
+                            uint32_t *labels, double *dist, double *second, uint32_t *swaps, double *td, dvs_kmedoids_info *info) {
+    if (!ctx || !src) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: null argument");
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (!params || !medoids || !labels || !dist || !info) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: null argument");
+    if (int rc = dvs_source_whole(ctx, "dvs_kmedoids", src)) return rc;
+    const dvs_kmedoids_out out{medoids, labels, dist, second, swaps, td, info};
+    if (src->kind == DVS_SRC_GIVEN)
+        return dvs_kmedoids_given(ctx, static_cast<const double *>(src->handle), src->on_device, src->n, params, out);
+    return stage_to_kmedoids(ctx, source_stage(ctx, src), params, out);
 }

@@ -21,7 +21,10 @@ pairs cross to the host; no counterpart in the reference; and the ordination of 
 coordinates (pcoa, matrix_pcoa, mash_pcoa / euclidean_pcoa / jsd_pcoa -> `PCoA`: csrc/pcoa.hip, the few largest eigenpairs
 of the double-centred matrix by an iteration that only reads the N x N matrix in HBM) with the projection of further
 rows into a fitted ordination (pcoa_project, matrix_pcoa_project: Gower's formula beside each strip of
-cross_distances, csrc/crossdist.hip); no counterpart in the reference.  `DeviceSide`
+cross_distances, csrc/crossdist.hip); no counterpart in the reference; and the representatives that lie closest, in
+total, to everything else, k-medoids (kmedoids, matrix_kmedoids, mash_kmedoids / euclidean_kmedoids / jsd_kmedoids ->
+`KMedoids`: csrc/kmedoids.hip, PAM's BUILD and FastPAM1's swaps over the N x N matrix in HBM); no counterpart in the
+reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
 matrix_* functions and the Sketches methods are a few lines over it.  Every operation has one C entry, which takes a
 `_lib.Source` (dvs_source: the mode and its handle, or a caller's matrix): `make_source` fills one per call."""
@@ -299,6 +302,11 @@ class Sketches:
         per pick (dvs_maxmin); ZeroDivisionError where a pair the traversal visits has two empty sketches"""
         return DeviceSide(self, "mash").maxmin(n_select, seeds=seeds, min_distance=min_distance)
 
+    def kmedoids(self, n_medoids: int, *, init="build", max_swaps: int = 300) -> "KMedoids":
+        """k-medoids (`KMedoids`) of this set's sketches over their mash distances, the N x N matrix written and only
+        read in HBM (dvs_kmedoids); ZeroDivisionError as `distances`"""
+        return DeviceSide(self, "mash").kmedoids(n_medoids, init=init, max_swaps=max_swaps)
+
     def within(self, other: "Sketches", radius, rows=None, other_rows=None, *, skip_self: bool = False,
                max_pairs: int | None = None) -> "Neighbours":
         """for each of this set's sketches `rows` the sketches of `other` at a mash distance <= radius (`Neighbours`:
@@ -340,7 +348,23 @@ class OrdinationOps:
         return coords
 
 
-class DeviceSide(OrdinationOps):
+class MedoidOps:
+    """k-medoids as an operation of a `DeviceSide`, which inherits it: `DeviceSide.kmedoids`.  In a base class of its
+    own for the reason `OrdinationOps` gives; its poisoned-block cases are in tests/test_gpu_kmedoids.py."""
+
+    def kmedoids(self, n_medoids: int, *, init="build", max_swaps: int = 300) -> "KMedoids":
+        """k-medoids of the distances (`KMedoids`), the N x N matrix written and only read in HBM.  init: "build"
+        (PAM's BUILD), "maxmin" (the first n_medoids farthest-first picks from row 0, `maxmin`, as the initial
+        medoids) or the initial medoids themselves, n_medoids distinct rows"""
+        k, kind, rows, max_swaps = check_kmedoids_args(self.n, n_medoids, init, max_swaps)
+        if kind == "maxmin":
+            rows = self.maxmin(k, seeds=(0,)).picks.astype(np.uint32)
+            if rows.size != k:
+                raise ValueError(f"farthest-first selection found only {rows.size} of {k} initial medoids")
+        return run_kmedoids(self.ctx, self.n, self._source(), k, rows, max_swaps)
+
+
+class DeviceSide(OrdinationOps, MedoidOps):
     """What a distance mode keeps in HBM of one batch -- its `Sketches` (mash) or its count matrix (euclidean, jsd) --
     together with the mode: every operation over "the distances of a collection", whatever the mode.  `device_side`
     makes one that owns its handle; DeviceSide(handle, mode) wraps a handle of the caller's, which close() then leaves
@@ -1351,3 +1375,135 @@ def pcoa_project(fit: PCoA, queries, refs, distance_mode: str = "mash", *, k: in
         return np.zeros((0, values.size), dtype=np.float64)
     return _two_sides(queries, refs, distance_mode, mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
                       ctx, lambda q, r: q.pcoa_project(fit, r), canonical)
+
+
+# ---- k-medoids (PAM): the representatives that minimise the total distance
+
+KMEDOIDS_MAX_K = 1024        # include/dvs_hip.h: the accumulators of a candidate live in LDS
+KMEDOIDS_MAX_SWAPS = 65_535
+
+
+class KMedoids(NamedTuple):
+    """A k-medoids clustering of n items (include/dvs_hip.h "k-medoids").  medoids int64 [k]: the representatives, slot
+    order part of the result; labels int64 [n]: the slot of every item's nearest medoid, equal distances to the lowest
+    slot, a medoid in its own; dist float64 [n]: the distance to that medoid (0.0 for a medoid); second float64 [n]:
+    the least distance to a medoid of any other slot (+inf when k = 1); swaps int64 [m, 2]: the exchanges in order, (the
+    row that came in, the slot it took); td float64 [m + 1]: the total distance after the initialisation and after
+    every exchange, td[-1] the final one; stop: 1 when no exchange lowers td any more, 0 when max_swaps exchanges were
+    made; passes: the reads of the whole matrix."""
+    medoids: np.ndarray
+    labels: np.ndarray
+    dist: np.ndarray
+    second: np.ndarray
+    swaps: np.ndarray
+    td: np.ndarray
+    stop: int
+    passes: int
+
+
+def check_kmedoids_args(n: int, n_medoids, init, max_swaps):
+    """the arguments of a k-medoids run over n items, checked before any device work -> (k, kind, rows, max_swaps):
+    kind "build", "maxmin" or "given", rows the initial medoids as uint32 [k] for "given", else None.  ValueError unless
+    n >= 1, n_medoids is an integer in 1 .. n, max_swaps an integer >= 0 and init is "build", "maxmin" or n_medoids
+    distinct rows; NotImplementedError for n_medoids > KMEDOIDS_MAX_K or max_swaps > KMEDOIDS_MAX_SWAPS"""
+    if n < 1:
+        raise ValueError("need at least one row for k-medoids")
+    if isinstance(n_medoids, bool) or not isinstance(n_medoids, (int, np.integer)):
+        raise ValueError(f"n_medoids must be an integer, not {n_medoids!r}")
+    if n_medoids < 1 or n_medoids > n:
+        raise ValueError(f"n_medoids = {n_medoids}: between 1 and the number of rows ({n})")
+    if n_medoids > KMEDOIDS_MAX_K:
+        raise NotImplementedError(f"n_medoids = {n_medoids}: {KMEDOIDS_MAX_K} at most")
+    if isinstance(max_swaps, bool) or not isinstance(max_swaps, (int, np.integer)) or max_swaps < 0:
+        raise ValueError(f"max_swaps must be an integer >= 0, not {max_swaps!r}")
+    if max_swaps > KMEDOIDS_MAX_SWAPS:
+        raise NotImplementedError(f"max_swaps = {max_swaps}: {KMEDOIDS_MAX_SWAPS} at most")
+    if isinstance(init, str):
+        if init not in ("build", "maxmin"):
+            raise ValueError(f"init must be 'build', 'maxmin' or the initial medoids, not {init!r}")
+        return int(n_medoids), init, None, int(max_swaps)
+    try:
+        rows = np.asarray(list(init) if not isinstance(init, np.ndarray) else init)
+    except TypeError:
+        raise ValueError(f"init must be 'build', 'maxmin' or the initial medoids, not {init!r}") from None
+    if rows.ndim != 1 or rows.size == 0 or rows.dtype.kind not in "iu":
+        raise ValueError("init: the initial medoids as row indices")
+    if rows.size != n_medoids:
+        raise ValueError(f"init names {rows.size} initial medoids, n_medoids is {n_medoids}")
+    if int(rows.min()) < 0 or int(rows.max()) >= n:
+        raise ValueError(f"initial medoid outside 0 .. {n - 1}")
+    if np.unique(rows).size != rows.size:
+        raise ValueError("a row is an initial medoid more than once")
+    return int(n_medoids), "given", np.ascontiguousarray(rows, dtype=np.uint32), int(max_swaps)
+
+
+def run_kmedoids(ctx: engine.Context | None, n: int, src: _lib.Source, k: int, rows: np.ndarray | None,
+                 max_swaps: int) -> KMedoids:
+    """dvs_kmedoids over `src` for n rows -> KMedoids; rows: the initial medoids (uint32 [k]), None for BUILD"""
+    ctx = ctx or engine.default_context()
+    params = _lib.KmedoidsParams(k, _lib.KMEDOIDS_INIT_BUILD if rows is None else _lib.KMEDOIDS_INIT_GIVEN, max_swaps, 0)
+    info = _lib.KmedoidsInfo()
+    medoids = np.zeros(k, dtype=np.uint32) if rows is None else np.array(rows, dtype=np.uint32)
+    labels = np.zeros(n, dtype=np.uint32)
+    dist, second = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+    swaps = np.zeros((max(max_swaps, 1), 2), dtype=np.uint32)
+    td = np.zeros(max_swaps + 1, dtype=np.float64)
+    ctx.check(ctx._L.dvs_kmedoids(ctx._h, src, C.byref(params), _lib.ptr(medoids, C.c_uint32), _lib.ptr(labels, C.c_uint32),
+                                  _lib.ptr(dist, C.c_double), _lib.ptr(second, C.c_double), _lib.ptr(swaps, C.c_uint32),
+                                  _lib.ptr(td, C.c_double), C.byref(info)))
+    m = int(info.n_swaps)
+    return KMedoids(medoids.astype(np.int64), labels.astype(np.int64), dist, second, swaps[:m].astype(np.int64),
+                    td[:m + 1].copy(), int(info.stop), int(info.passes))
+
+
+def matrix_kmedoids(m: "engine.CountMatrix", n_medoids: int, *, mode: str = "jsd", init="build",
+                    max_swaps: int = 300) -> KMedoids:
+    """`kmedoids` over the rows of a matrix already in HBM, by `mode` ("jsd" or "euclidean")"""
+    return _count_side(m, mode).kmedoids(n_medoids, init=init, max_swaps=max_swaps)
+
+
+def mash_kmedoids(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *, n_medoids: int,
+                  init="build", max_swaps: int = 300, ctx: engine.Context | None = None) -> KMedoids:
+    """k-medoids of the mash distances on the device: sketches, the N x N distances and the search, every stage in HBM.
+    ZeroDivisionError as `mash_distances`."""
+    return _kmedoids(seqs, "mash", k, sketch_size, num_states, mash_canonical, n_medoids=n_medoids, init=init,
+                     max_swaps=max_swaps, ctx=ctx)
+
+
+def euclidean_kmedoids(seqs, k: int, num_states: int = 4, *, n_medoids: int, init="build", max_swaps: int = 300,
+                       ctx: engine.Context | None = None, canonical: bool = False) -> KMedoids:
+    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    return _kmedoids(seqs, "euclidean", k, num_states, n_medoids=n_medoids, init=init, max_swaps=max_swaps, ctx=ctx,
+                     canonical=canonical)
+
+
+def jsd_kmedoids(seqs, k: int, num_states: int = 4, *, n_medoids: int, init="build", max_swaps: int = 300,
+                 ctx: engine.Context | None = None, canonical: bool = False) -> KMedoids:
+    """the same for the Jensen-Shannon divergences of `jsd_distances` (a sequence without valid k-mers: ValueError)"""
+    return _kmedoids(seqs, "jsd", k, num_states, n_medoids=n_medoids, init=init, max_swaps=max_swaps, ctx=ctx,
+                     canonical=canonical)
+
+
+def _kmedoids(seqs, distance_mode: str, *args, n_medoids, init, max_swaps, ctx, canonical: bool = False) -> KMedoids:
+    check_kmedoids_args(len(seqs), n_medoids, init, max_swaps)
+    with device_side(seqs, distance_mode, *args, ctx=ctx, canonical=canonical) as dev:
+        return dev.kmedoids(n_medoids, init=init, max_swaps=max_swaps)
+
+
+# a distance mode -> its k-medoids: takes (seqs, *mode_args(...)), and n_medoids=, init=, max_swaps=, ctx=
+KMEDOIDS_MODES = {"mash": mash_kmedoids, "euclidean": euclidean_kmedoids, "jsd": jsd_kmedoids}
+
+
+def kmedoids(seqs, n_medoids: int, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None,
+             num_states: int = 4, mash_canonical: bool = False, init="build", max_swaps: int = 300,
+             ctx: engine.Context | None = None, canonical: bool = False) -> KMedoids:
+    """k-medoids (`KMedoids`) of a collection of sequences by `distance_mode`: the n_medoids sequences that lie closest,
+    in total, to everything else, with the partition they make -- representation, where `maxmin` gives coverage of the
+    worst case and `nmost` diversity.  The distances are written into HBM and stay there.  init: "build" (PAM's BUILD),
+    "maxmin" (the farthest-first picks as the start: cheaper, usually a higher td) or the initial medoids as rows;
+    max_swaps = 0 scores a set as it is.  Argument checks as cluster.ctree and those of `check_kmedoids_args`, before
+    any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    seqs = list(seqs)
+    return _kmedoids(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                     n_medoids=n_medoids, init=init, max_swaps=max_swaps, ctx=ctx, canonical=canonical)

@@ -751,6 +751,68 @@ int dvs_pcoa(dvs_ctx *ctx, const dvs_source *src, const dvs_pcoa_params *params,
 int dvs_pcoa_project(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r, uint32_t n_axes, const double *values,
                      const double *vectors, const double *row_means, double *coords);
 
+/* ---- k-medoids (PAM): the k items that lie closest, in total, to everything else ------------------- *
+ * Representatives that minimise the total distance TD = sum_o d(o, nearest medoid), with the partition they make.  (No
+ * counterpart in the reference.)  Items are 0 .. n - 1, D is the n x n matrix of the source: the distance between a
+ * medoid or candidate x and an item o is D[x][o] -- a row is read as it stands, so the matrix need not be symmetric;
+ * the diagonal counts as 0 and is never read.  Every off-diagonal entry must be finite and >= 0 (DVS_ERR_VALUE; for NaN
+ * or +-inf with the text the trees give), so a row without valid k-mers raises as it does for dvs_nj.
+ *   state    med[0 .. k), distinct items; slot order is part of the result.  Per item o: near[o], the slot of its
+ *       nearest medoid, equal distances to the lowest slot; dn[o], that distance; ds[o], the least distance to a medoid
+ *       in any OTHER slot, +inf when k = 1.  A medoid, taken as an item, has near = its own slot and dn = 0 whatever the
+ *       other medoids' distances; its ds is the least distance over the other slots.  near, dn and ds are comparisons
+ *       and copies of cells, hence exact.  td = sum_o dn[o].
+ *   init     DVS_KMEDOIDS_INIT_GIVEN: the caller's k distinct items in their order.  DVS_KMEDOIDS_INIT_BUILD, PAM's
+ *       BUILD: slot 0 takes the x with the least sum_{o != x} D[x][o], ties to the lowest x; each following slot takes
+ *       the non-medoid x with the largest gain sum_o max(dn[o] - D[x][o], 0), the term for o = x being dn[x], ties to
+ *       the lowest x -- a gain of 0 everywhere still takes the lowest non-medoid.
+ *   swap     steepest-descent PAM SWAP with FastPAM1's shared evaluation (Schubert & Rousseeuw 2021), at most
+ *       max_swaps rounds.  A round scores every non-medoid x with d = D[x][o], d = 0 for o = x.  For k >= 2:
+ *         R[l]     = sum_{near[o] = l} (ds[o] - dn[o])     the loss of removing slot l, once per round
+ *         shared_x = sum_o min(d - dn[o], 0)
+ *         C_x[l]   = sum_{near[o] = l} c(o),  c(o) = dn[o] - ds[o] if d < dn[o], else d - ds[o] if d < ds[o], else 0
+ *         Delta_x[l] = (R[l] + C_x[l]) + shared_x
+ *       for k = 1: Delta_x[0] = sum_o (d - dn[o]); no infinity enters a sum.  The round's exchange is the (x, l) of the
+ *       least Delta, ties to the lowest x, then to the lowest l.  If that Delta is not < -noise the search has
+ *       converged and stops (stop = 1); else med[l] = x, the state is rebuilt from the k medoid rows, td summed afresh
+ *       and the exchange recorded.  noise = 4 (n + 8) 2^-52 n d_max, d_max the largest entry off the diagonal (as a
+ *       float64 product in that order): what a float64 Delta may be off by -- three sums of <= n terms each <= d_max
+ *       and two additions.  A Delta within the noise of 0 lowers td by nothing that can be told from rounding, and
+ *       taking it lets the search cycle: a symmetric matrix has exchanges of Delta = 0 by its structure (the two
+ *       members of a cluster of two), which evaluate to -1e-17 as easily as to 0.  An accepted Delta is truly < 0, td
+ *       truly falls with every exchange, and no set of medoids comes twice.  k == n: no candidate, converged at once (stop = 1, whatever max_swaps).  max_swaps rounds
+ *       done, each with an exchange: stop = 0 -- max_swaps == 0 evaluates a set as it is.
+ * Each sum (R, C, shared, the gains, the row sums, td) is added in an order that (n, k) and the state fix, without
+ * floating-point atomics: the same bits on every run, for every batch length (DVS_KMEDOIDS_BATCH: the rounds enqueued
+ * between two reads of the device's status word, 8 by default) and for a host matrix and the same matrix in device
+ * memory.
+ *   medoids[k]  in (INIT_GIVEN) and out; labels[n] near; dist[n] dn; second[n] ds (optional: NULL)
+ *   swaps[2 max_swaps]  (x, slot) per exchange, optional; td[max_swaps + 1]  td after init and after every exchange,
+ *       optional; both filled up to info->n_swaps, the rest left as it was
+ *   info: td_init, td; n_swaps; stop (0: max_swaps reached, 1: no exchange lowers td); passes, the reads of the whole
+ *       matrix: the entry check (which holds slot 0's row sums), one per further BUILD slot, one per scored round
+ * The sources as for dvs_pcoa: whole, no row list; MASH, EUCLIDEAN and JSD write their matrix into the context's
+ * scratch, where it stays; a GIVEN host matrix is uploaded and left as it is, a GIVEN device matrix only read.  The
+ * checks come in dvs_pcoa's order: the arguments, n, the source's own, the device, the fit in HBM; the arguments and n
+ * before any device work.
+ *   DVS_ERR_VALUE: a NULL argument; k == 0 or k > n; n == 0; an unknown init; non-zero flags; an initial medoid >= n or
+ *                  repeated; a non-finite or negative entry off the diagonal
+ *   DVS_ERR_UNSUPPORTED: k > 1024 (the per-candidate accumulators live in LDS); max_swaps > 65 535; a row list, or n
+ *                  other than the handle's rows
+ *   DVS_ERR_ZERODIV: (MASH) as dvs_nj
+ *   DVS_ERR_NOMEM: the matrix and the state do not fit in HBM */
+#define DVS_KMEDOIDS_INIT_BUILD 0
+#define DVS_KMEDOIDS_INIT_GIVEN 1
+typedef struct dvs_kmedoids_params {
+    uint32_t k, init, max_swaps, flags /* 0 */;
+} dvs_kmedoids_params;
+typedef struct dvs_kmedoids_info {
+    double td_init, td;
+    uint32_t n_swaps, stop, passes;
+} dvs_kmedoids_info;
+int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src, const dvs_kmedoids_params *params, uint32_t *medoids,
+                 uint32_t *labels, double *dist, double *second, uint32_t *swaps, double *td, dvs_kmedoids_info *info);
+
 #ifdef __cplusplus
 }
 #endif
