@@ -692,16 +692,8 @@ dvs_cross_stage euclid_cross_stage(dvs_ctx *ctx, const dvs_matrix *q, const uint
 dvs_cross_stage matrix_rows_stage(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n) {
     dvs_cross_stage st{"distance matrix rows", n, n};
     st.check = [=] {
-        if (dist_on_device) {
-            hipPointerAttribute_t attr;
-            if (hipPointerGetAttributes(&attr, dist) != hipSuccess) {
-                (void)hipGetLastError();
-                return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
-            }
-            if (attr.device != ctx->device)
-                return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
-                                     attr.device, ctx->device);
-        }
+        if (dist_on_device)
+            if (int rc = dvs_given_on_device(ctx, nullptr, dist)) return rc;
         return dvs_rows_check(ctx, n);
     };
     st.scratch_bytes = 0;

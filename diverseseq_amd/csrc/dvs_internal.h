@@ -248,56 +248,11 @@ int dvs_packed_fill_from_device(dvs_ctx *ctx, dvs_packed *p, const uint8_t *d_se
 int dvs_packed_fill_from_host(dvs_ctx *ctx, dvs_packed *p, const uint8_t *seqs);             // host threads pack, chunks cross PCIe packed
 bool dvs_packed_upload_wanted(const dvs_ctx *ctx, uint32_t num_states, uint64_t nbytes);
 
-// linkage.hip: DVS_ERR_NOMEM unless an n x n f64 matrix and the tree's scratch fit the device; DVS_ERR_UNSUPPORTED /
-// DVS_ERR_VALUE unless `method` (scipy's code) is one the device builds; the tree of that method over the n x n
-// matrix at d_dist (a working buffer, overwritten), enqueued behind whatever wrote it on the context's stream
-// (d_zerodiv, may be NULL: a flag the distance kernel set, reported as DVS_ERR_ZERODIV first); returns when the host
-// outputs (dvs_linkage's) are written
-int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n);
-int dvs_linkage_check_method(dvs_ctx *ctx, int method);
-int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
-                       double *heights, uint32_t *sizes);
 // linkage.hip's prepare pass on its own, enqueued on the context's stream: every entry of the n x n matrix checked and
 // the upper triangle copied over the lower one; the bits below are OR-ed into the device word *d_status (`sign`: a
 // negative entry above the diagonal is flagged too)
 constexpr uint32_t DVS_LNK_NONFINITE = 1, DVS_LNK_NEGATIVE = 4;
 hipError_t dvs_linkage_enqueue_prepare(dvs_ctx *ctx, double *d_dist, uint32_t n, bool sign, uint32_t *d_status);
-
-// nj.hip: the neighbour-joining tree of the n x n matrix at d_dist (n >= 3; a working buffer, overwritten), enqueued
-// behind whatever wrote it on the context's stream, d_zerodiv as above; returns when the host outputs (dvs_nj's) are
-// written.  DVS_ERR_NOMEM unless its scratch fits beside the matrix.
-int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *joins, double *lengths);
-
-// pcoa.hip: the principal coordinates (include/dvs_hip.h) of the n x n matrix at d_dist, which is only read; enqueued
-// behind whatever wrote it on the context's stream, d_zerodiv as above; returns when the host outputs (dvs_pcoa's) are
-// written.  The caller has run dvs_pcoa_check_args (the arguments, then n) and dvs_pcoa_fits (DVS_ERR_NOMEM unless the
-// matrix -- need_matrix --, the basis and the small blocks fit the device).  dvs_pcoa_given: a caller's matrix, every check
-// included.
-int dvs_pcoa_check_args(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p);
-int dvs_pcoa_fits(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p, bool need_matrix);
-int dvs_pcoa_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv, const dvs_pcoa_params *p,
-                    double *values, double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info);
-int dvs_pcoa_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_pcoa_params *p, double *values,
-                   double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info);
-
-// kmedoids.hip: k-medoids (include/dvs_hip.h) over the n x n matrix at d_dist, which is only read; enqueued behind
-// whatever wrote it on the context's stream, d_zerodiv as above; returns when the host outputs (dvs_kmedoids's) are
-// written.  The caller has run dvs_kmedoids_check_args (the arguments, then n) and dvs_kmedoids_fits (DVS_ERR_NOMEM
-// unless the matrix -- need_matrix -- and the state fit the device).  dvs_kmedoids_given: a caller's matrix, every
-// check included.
-struct dvs_kmedoids_out {
-    uint32_t *medoids, *labels;
-    double *dist, *second;
-    uint32_t *swaps;
-    double *td;
-    dvs_kmedoids_info *info;
-};
-int dvs_kmedoids_check_args(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, const uint32_t *medoids);
-int dvs_kmedoids_fits(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, bool need_matrix);
-int dvs_kmedoids_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv,
-                        const dvs_kmedoids_params *p, const dvs_kmedoids_out &out);
-int dvs_kmedoids_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_kmedoids_params *p,
-                       const dvs_kmedoids_out &out);
 
 // linkage.hip, host only: the in-order walk of the tree behind dvs_linkage's outputs (include/dvs_hip.h "cophenetic
 // distances"): order[n] the leaves in dendrogram order, pos[n] its inverse, gap[n - 1] the merge between positions p
@@ -305,6 +260,58 @@ int dvs_kmedoids_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uin
 // yet made or already merged; the heights need not be monotone.
 int dvs_cophenet_walk(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const double *heights, uint32_t *order,
                       uint32_t *pos, uint32_t *gap, double *c_bar);
+
+// One consumer of a whole n x n f64 distance matrix in HBM, as the square driver of rowdist.hip takes it: what differs
+// between the linkage tree, the neighbour-joining tree, the principal coordinates and k-medoids.  The driver brings the
+// matrix -- a MASH, EUCLIDEAN or JSD source's kernels enqueued, a caller's host matrix uploaded, a caller's device
+// matrix where it is -- and calls run.  On entry to run: check has passed, the context's device is set, the matrix and
+// extra_bytes() beside it have been found to fit, and the matrix is resident or enqueued on the context's stream.  run
+// enqueues behind it, returns once the host outputs are written, and may return an error with work still queued: the
+// driver drains the stream before the matrix goes back to the block cache.
+struct dvs_square_consumer {
+    const char *name;                     // the entry, in front of the driver's own messages: "dvs_kmedoids"
+    std::function<int()> check;           // the arguments, then n: DVS_OK, or the error it set
+    std::function<bool()> early;          // optional, staged sources only: true when it has answered with no cell computed
+    std::function<size_t()> extra_bytes;  // what run allocates beside the matrix (asked once check has passed) ...
+    char extra_what[48];                  // ... and its noun phrase in the DVS_ERR_NOMEM message: "its tree"
+    bool writes_matrix;                   // run overwrites the matrix (a caller's device matrix is used in place either way)
+    // d_zerodiv (may be NULL): a word the distance kernels set where the reference divides by zero, reported as
+    // DVS_ERR_ZERODIV before anything else
+    std::function<int(double *d_dist, const uint32_t *d_zerodiv)> run;
+};
+// the consumers, built by their entries (n: the source's; given: a DVS_SRC_GIVEN source, where the wording or the
+// early answer differs)
+struct dvs_kmedoids_out {
+    uint32_t *medoids, *labels;
+    double *dist, *second;
+    uint32_t *swaps;
+    double *td;
+    dvs_kmedoids_info *info;
+};
+dvs_square_consumer dvs_linkage_consumer(dvs_ctx *ctx, uint32_t n, bool given, int method, uint32_t *pairs, double *heights,
+                                         uint32_t *sizes);                                                     // linkage.hip
+dvs_square_consumer dvs_nj_consumer(dvs_ctx *ctx, uint32_t n, uint32_t *joins, double *lengths);                // nj.hip
+dvs_square_consumer dvs_pcoa_consumer(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p, double *values, double *vectors,
+                                      double *residuals, double *row_means, dvs_pcoa_info *info);              // pcoa.hip
+dvs_square_consumer dvs_kmedoids_consumer(dvs_ctx *ctx, uint32_t n, bool given, const dvs_kmedoids_params *p,
+                                          const dvs_kmedoids_out &out);                                        // kmedoids.hip
+// A run's status words: `bytes` of them zeroed on the context's stream, then the distance kernels' zero-division word
+// (d_zerodiv, may be NULL) copied into word `at`.
+inline hipError_t dvs_status_begin(dvs_ctx *ctx, uint32_t *d_status, size_t bytes, uint32_t at, const uint32_t *d_zerodiv) {
+    hipError_t e = hipMemsetAsync(d_status, 0, bytes, ctx->stream);
+    if (e == hipSuccess && d_zerodiv) e = hipMemcpyAsync(d_status + at, d_zerodiv, 4, hipMemcpyDeviceToDevice, ctx->stream);
+    return e;
+}
+
+// rowdist.hip, what every operation over a whole n x n matrix shares (op, may be NULL: the entry's name, put in front
+// of the message as "<op>: ").
+// DVS_ERR_NOMEM unless the matrix (need_matrix: it is still to be allocated) and extra_bytes beside it fit the device
+// with the context's cached blocks counted as free; extra_what: the noun phrase for what the extra bytes hold.
+int dvs_square_fits(dvs_ctx *ctx, const char *op, uint32_t n, bool need_matrix, size_t extra_bytes, const char *extra_what);
+// DVS_ERR_VALUE unless a caller's matrix that claims to be on the device is device memory of the context's device
+int dvs_given_on_device(dvs_ctx *ctx, const char *op, const void *dist);
+// a caller's n x n host matrix into a block of the cache, the copy enqueued on the context's stream (an error: drained)
+int dvs_given_upload(dvs_ctx *ctx, const double *dist, uint32_t n, PooledBuf *d_dist);
 
 // One distance mode of ctree, as the drivers of rowdist.hip take it: "fill this device n x n f64 matrix" on the
 // context's stream, with what differs from mode to mode beside it.
@@ -389,10 +396,6 @@ int dvs_source_check(dvs_ctx *ctx, const dvs_source *q, const dvs_source *r);
 int dvs_source_refuse(dvs_ctx *ctx, const char *op, const dvs_source *src, const char *what);
 // ... for a row list, or n other than the handle's rows (the square drivers take a handle whole)
 int dvs_source_whole(dvs_ctx *ctx, const char *op, const dvs_source *src);
-// linkage.hip, nj.hip: the tree of a GIVEN matrix (host: uploaded; device: the working buffer), the method / n checked
-int dvs_linkage_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
-                      double *heights, uint32_t *sizes);
-int dvs_nj_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths);
 
 // f(typed row pointer) for the matrix's element type
 template <typename F>

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmed_clear_kernel(uint32_t n, Kmed
     if (j < n) S.slot_of[j] = KM_NONE;
 }
 
-// INIT_GIVEN: the caller's medoids (distinct and < n: dvs_kmedoids_check_args) marked
+// INIT_GIVEN: the caller's medoids (distinct and < n: kmedoids_check_args) marked
 __global__ __launch_bounds__(KM_THREADS) void kmed_mark_kernel(uint32_t k, KmedState S) {
     const uint32_t l = blockIdx.x * KM_THREADS + threadIdx.x;
     if (l < k) S.slot_of[S.med[l]] = l;
@@ -429,7 +429,7 @@ uint32_t grid_of(uint32_t n, uint32_t per) { return (n + per - 1) / per; }
 }  // namespace
 
 // the arguments and n, before anything else is looked at
-int dvs_kmedoids_check_args(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, const uint32_t *medoids) {
+static int kmedoids_check_args(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, const uint32_t *medoids) {
     if (p->flags) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: flags = %u: no flag is defined", p->flags);
     if (p->init != DVS_KMEDOIDS_INIT_BUILD && p->init != DVS_KMEDOIDS_INIT_GIVEN)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: unknown init %u", p->init);
@@ -454,30 +454,15 @@ int dvs_kmedoids_check_args(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params 
     return DVS_OK;
 }
 
-// the matrix (need_matrix) and the state against the device's memory
-int dvs_kmedoids_fits(dvs_ctx *ctx, uint32_t n, const dvs_kmedoids_params *p, bool need_matrix) {
-    const uint64_t n2 = uint64_t(n) * n;
-    if (n2 > (uint64_t(1) << 58))
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "dvs_kmedoids: a %u x %u distance matrix does not fit in memory", n, n);
-    const size_t bytes = (need_matrix ? size_t(n2) * 8 : 0) + KmedLayout(n, p->k, p->max_swaps).bytes;
-    size_t free_b = 0, total_b = 0;
-    DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    if (bytes + (64u << 20) > free_b + ctx->pool_bytes)
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "dvs_kmedoids: a %u x %u distance matrix and the state of %u medoids need %zu "
-                             "bytes of HBM, %zu free", n, n, p->k, bytes, free_b);
-    return DVS_OK;
-}
-
-int dvs_kmedoids_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv,
+// A consumer's run (dvs_internal.h dvs_square_consumer): k-medoids over the n x n matrix at d_dist (only read), enqueued
+// on the context's stream behind whatever wrote the matrix.  Returns when the host outputs (dvs_kmedoids's) are written.
+static int kmedoids_run(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv,
                         const dvs_kmedoids_params *p, const dvs_kmedoids_out &out) {
     const uint32_t k = p->k, ms = p->max_swaps;
     const bool given = p->init == DVS_KMEDOIDS_INIT_GIVEN;
     const KmedLayout L(n, k, ms);
     PooledBuf d_state{ctx};
-    if (int rc = dvs_dev_alloc(ctx, &d_state.p, L.bytes, "k-medoids state")) {
-        (void)hipStreamSynchronize(ctx->stream);  // (the kernels that write the matrix)
-        return rc;
-    }
+    if (int rc = dvs_dev_alloc(ctx, &d_state.p, L.bytes, "k-medoids state")) return rc;
     char *base = d_state.as<char>();
     auto f64 = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
@@ -489,8 +474,7 @@ int dvs_kmedoids_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const ui
     const uint32_t n_r = k >= 2 ? k : 0;
 
     // ---- the entry check, the initial medoids and their state
-    hipError_t e = hipMemsetAsync(S.status, 0, 32, s);
-    if (e == hipSuccess && d_zerodiv) e = hipMemcpyAsync(S.status + KM_ST_ZERODIV, d_zerodiv, 4, hipMemcpyDeviceToDevice, s);
+    hipError_t e = dvs_status_begin(ctx, S.status, 32, KM_ST_ZERODIV, d_zerodiv);
     if (e == hipSuccess && given) e = hipMemcpyAsync(S.med, out.medoids, size_t(k) * 4, hipMemcpyHostToDevice, s);
     auto assign = [&] {
         hipLaunchKernelGGL(kmed_assign_kernel, items, thr, 0, s, d_dist, n, k, S);
@@ -565,31 +549,25 @@ int dvs_kmedoids_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const ui
     return DVS_OK;
 }
 
-// a caller's matrix: a device matrix is read where it is, a host matrix uploaded.  The checks in dvs_pcoa's order.
-int dvs_kmedoids_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_kmedoids_params *p,
-                       const dvs_kmedoids_out &out) {
-    if (int rc = dvs_kmedoids_check_args(ctx, n, p, out.medoids)) return rc;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    if (dist_on_device) {
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, dist);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: the distance matrix is not device memory");
-        }
-        if (attr.device != ctx->device)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: the distance matrix is on device %d, the context on device %d",
-                                 attr.device, ctx->device);
-        if (int rc = dvs_kmedoids_fits(ctx, n, p, false)) return rc;
-        return dvs_kmedoids_device(ctx, dist, n, nullptr, p, out);
-    }
-    if (int rc = dvs_kmedoids_fits(ctx, n, p, true)) return rc;
-    PooledBuf d_dist{ctx};
-    if (int rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix")) return rc;
-    const hipError_t e = hipMemcpyAsync(d_dist.p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, e, "distance matrix upload");
-    }
-    return dvs_kmedoids_device(ctx, d_dist.as<double>(), n, nullptr, p, out);
+// beside the matrix: the state.  A source of one row the library measures itself (not given) is answered at once: the
+// one item its own medoid, there is no cell to compute or to check.
+dvs_square_consumer dvs_kmedoids_consumer(dvs_ctx *ctx, uint32_t n, bool given, const dvs_kmedoids_params *p,
+                                          const dvs_kmedoids_out &out) {
+    dvs_square_consumer c{"dvs_kmedoids"};
+    c.check = [=] { return kmedoids_check_args(ctx, n, p, out.medoids); };
+    if (!given)
+        c.early = [=] {
+            if (n != 1) return false;
+            out.medoids[0] = out.labels[0] = 0;
+            out.dist[0] = 0.0;
+            if (out.second) out.second[0] = HUGE_VAL;
+            if (out.td) out.td[0] = 0.0;
+            *out.info = dvs_kmedoids_info{0.0, 0.0, 0, 1, 1};
+            return true;
+        };
+    c.extra_bytes = [=] { return KmedLayout(n, p->k, p->max_swaps).bytes; };
+    snprintf(c.extra_what, sizeof c.extra_what, "the state of %u medoids", p->k);
+    c.writes_matrix = false;
+    c.run = [=](double *d_dist, const uint32_t *d_zerodiv) { return kmedoids_run(ctx, d_dist, n, d_zerodiv, p, out); };
+    return c;
 }

@@ -471,22 +471,6 @@ void linkage_relabel(uint32_t n, const double *rec_h, const uint32_t *rec_pair, 
 
 }  // namespace
 
-// the matrix (need_matrix) and the loop's scratch against the device's memory: DVS_ERR_NOMEM when they cannot fit
-static int linkage_fits(dvs_ctx *ctx, uint32_t n, bool need_matrix) {
-    const uint64_t n2 = uint64_t(n) * n;
-    if (n2 > (uint64_t(1) << 58))
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix does not fit in memory", n, n);
-    const size_t bytes = (need_matrix ? size_t(n2) * 8 : 0) + LnkLayout(n).bytes;
-    size_t free_b = 0, total_b = 0;
-    DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    if (bytes + (64u << 20) > free_b + ctx->pool_bytes)
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix and its tree need %zu bytes of HBM, %zu free", n,
-                             n, bytes, free_b);
-    return DVS_OK;
-}
-
-int dvs_linkage_check_size(dvs_ctx *ctx, uint32_t n) { return linkage_fits(ctx, n, true); }
-
 // the prepare pass (check + mirror; `sign`: ward's, a negative entry above the diagonal flagged too) on the context's
 // stream; *d_status collects DVS_LNK_NONFINITE / DVS_LNK_NEGATIVE
 hipError_t dvs_linkage_enqueue_prepare(dvs_ctx *ctx, double *d_dist, uint32_t n, bool sign, uint32_t *d_status) {
@@ -498,7 +482,8 @@ hipError_t dvs_linkage_enqueue_prepare(dvs_ctx *ctx, double *d_dist, uint32_t n,
     return hipGetLastError();
 }
 
-int dvs_linkage_check_method(dvs_ctx *ctx, int method) {
+// DVS_ERR_UNSUPPORTED / DVS_ERR_VALUE unless `method` (scipy's code) is one the device builds
+static int linkage_check_method(dvs_ctx *ctx, int method) {
     if (method == LNK_CENTROID || method == LNK_MEDIAN)
         return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
                              "%s linkage is scipy's fast_linkage, not built on the device (single, complete, average, "
@@ -509,26 +494,19 @@ int dvs_linkage_check_method(dvs_ctx *ctx, int method) {
     return DVS_OK;
 }
 
-// The tree of the n x n matrix at d_dist (a working buffer: overwritten; single linkage only reads it once it is
-// mirrored).  Everything is enqueued on the context's stream behind whatever wrote the matrix; d_zerodiv (may be
-// NULL): a device word a distance kernel in front set where the reference divides by zero, reported first.  Returns
-// when the host outputs are written.
-int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
+// A consumer's run (dvs_internal.h dvs_square_consumer): the tree of the n x n matrix at d_dist (a working buffer:
+// overwritten; single linkage only reads it once it is mirrored), enqueued on the context's stream behind whatever
+// wrote the matrix.  Returns when the host outputs are written.
+static int linkage_run(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, int method, uint32_t *pairs,
                        double *heights, uint32_t *sizes) {
-    int rc = dvs_linkage_check_method(ctx, method);
-    if (!rc) rc = linkage_fits(ctx, n, false);
-    if (rc) return rc;
     const LnkLayout L(n);
     PooledBuf scratch{ctx};
-    rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "linkage scratch");
-    if (rc) return rc;
+    if (int rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "linkage scratch")) return rc;
     char *base = scratch.as<char>();
     uint32_t *d_status = reinterpret_cast<uint32_t *>(base + L.status);
     std::vector<uint64_t> host((L.out_bytes + 7) / 8);
     const char *what = lnk_name(method);
-    hipError_t e = hipMemsetAsync(d_status, 0, 16, ctx->stream);
-    if (e == hipSuccess && d_zerodiv)
-        e = hipMemcpyAsync(d_status + 1, d_zerodiv, 4, hipMemcpyDeviceToDevice, ctx->stream);
+    hipError_t e = dvs_status_begin(ctx, d_status, 16, 1, d_zerodiv);
     if (e == hipSuccess) e = dvs_linkage_enqueue_prepare(ctx, d_dist, n, method == LNK_WARD, d_status);
     if (e == hipSuccess) e = lnk_launch_tree(ctx, method, d_dist, n, base, L);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), base, L.out_bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -550,36 +528,23 @@ int dvs_linkage_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t 
     return DVS_OK;
 }
 
-int dvs_linkage_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, int method, uint32_t *pairs,
-                      double *heights, uint32_t *sizes) {
-    int rc = dvs_linkage_check_method(ctx, method);
-    if (rc) return rc;
-    if (n < 2)
-        return dvs_set_error(ctx, DVS_ERR_VALUE, "Found array with %u sample(s) while a minimum of 2 is required", n);
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    if (dist_on_device) {
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, dist);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
-        }
-        if (attr.device != ctx->device)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
-                                 attr.device, ctx->device);
-        return dvs_linkage_device(ctx, dist, n, nullptr, method, pairs, heights, sizes);
-    }
-    rc = linkage_fits(ctx, n, true);
-    if (rc) return rc;
-    PooledBuf d_dist{ctx};
-    rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix");
-    if (rc) return rc;
-    const hipError_t e = hipMemcpyAsync(d_dist.p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, e, "distance matrix upload");
-    }
-    return dvs_linkage_device(ctx, d_dist.as<double>(), n, nullptr, method, pairs, heights, sizes);
+// the method, then n: a caller's matrix is refused in sklearn's words (it checks every entry, as sklearn does)
+dvs_square_consumer dvs_linkage_consumer(dvs_ctx *ctx, uint32_t n, bool given, int method, uint32_t *pairs, double *heights,
+                                         uint32_t *sizes) {
+    dvs_square_consumer c{"dvs_linkage"};
+    c.check = [=] {
+        if (int rc = linkage_check_method(ctx, method)) return rc;
+        if (n >= 2) return int(DVS_OK);
+        if (given) return dvs_set_error(ctx, DVS_ERR_VALUE, "Found array with %u sample(s) while a minimum of 2 is required", n);
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
+    };
+    c.extra_bytes = [=] { return LnkLayout(n).bytes; };
+    snprintf(c.extra_what, sizeof c.extra_what, "its tree");
+    c.writes_matrix = true;
+    c.run = [=](double *d_dist, const uint32_t *d_zerodiv) {
+        return linkage_run(ctx, d_dist, n, d_zerodiv, method, pairs, heights, sizes);
+    };
+    return c;
 }
 
 // The flat clusters of a cut (host only): the first m merges applied, m from the criterion; the merges name their

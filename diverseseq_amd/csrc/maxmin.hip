@@ -330,32 +330,41 @@ hipError_t enqueue_update(dvs_ctx *ctx, const double *base, uint64_t ld, uint32_
     return hipGetLastError();
 }
 
+// byte offsets of the state, one block: what is copied back first (status, cover, radius, picks), then owner, mind,
+// then the rest
+struct MaxminLayout {
+    size_t cover, radius, picks, owner, mind, flag, cv, cj, row, bytes;
+    MaxminLayout(uint32_t n, uint32_t ns) {
+        auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
+        const uint32_t max_cand = (n + 63) / 64;
+        cover = 16, radius = cover + 8, picks = radius + size_t(ns) * 8, owner = up8(picks + size_t(ns) * 4);
+        mind = up8(owner + size_t(n) * 4), flag = mind + size_t(n) * 8;
+        cv = up8(flag + n), cj = cv + size_t(max_cand) * 8, row = up8(cj + size_t(max_cand) * 4);
+        bytes = row + size_t(n) * 8;
+    }
+};
+
 // The traversal over a mode (the arguments checked, the device set).  make(S) builds the mode around the device state:
 // its query list is S.picks.
 template <typename F>
 int maxmin_run(dvs_ctx *ctx, const MaxminArgs &a, F &&make) {
     const uint32_t n = a.n, ns = a.n_select;
-    auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
-    // one block: what is copied back first (status, cover, radius, picks), then owner, mind, then the rest
-    const size_t o_cover = 16, o_radius = o_cover + 8, o_picks = o_radius + size_t(ns) * 8, o_owner = up8(o_picks + size_t(ns) * 4);
-    const size_t o_mind = up8(o_owner + size_t(n) * 4), o_flag = o_mind + size_t(n) * 8;
-    const uint32_t max_cand = (n + 63) / 64;
-    const size_t o_cv = up8(o_flag + n), o_cj = o_cv + size_t(max_cand) * 8, o_row = up8(o_cj + size_t(max_cand) * 4);
+    const MaxminLayout L(n, ns);
     PooledBuf d_buf{ctx}, d_extra{ctx};
-    int rc = dvs_dev_alloc(ctx, &d_buf.p, o_row + size_t(n) * 8, "farthest-first state");
+    int rc = dvs_dev_alloc(ctx, &d_buf.p, L.bytes, "farthest-first state");
     if (rc) return rc;
     char *base = d_buf.as<char>();
     MaxminState S;
     S.status = reinterpret_cast<uint32_t *>(base);
-    S.cover = reinterpret_cast<double *>(base + o_cover);
-    S.radius = reinterpret_cast<double *>(base + o_radius);
-    S.picks = reinterpret_cast<uint32_t *>(base + o_picks);
-    S.owner = reinterpret_cast<uint32_t *>(base + o_owner);
-    S.mind = reinterpret_cast<double *>(base + o_mind);
-    S.flag = reinterpret_cast<uint8_t *>(base + o_flag);
-    S.cand_v = reinterpret_cast<double *>(base + o_cv);
-    S.cand_j = reinterpret_cast<uint32_t *>(base + o_cj);
-    double *d_row = reinterpret_cast<double *>(base + o_row);
+    S.cover = reinterpret_cast<double *>(base + L.cover);
+    S.radius = reinterpret_cast<double *>(base + L.radius);
+    S.picks = reinterpret_cast<uint32_t *>(base + L.picks);
+    S.owner = reinterpret_cast<uint32_t *>(base + L.owner);
+    S.mind = reinterpret_cast<double *>(base + L.mind);
+    S.flag = reinterpret_cast<uint8_t *>(base + L.flag);
+    S.cand_v = reinterpret_cast<double *>(base + L.cv);
+    S.cand_j = reinterpret_cast<uint32_t *>(base + L.cj);
+    double *d_row = reinterpret_cast<double *>(base + L.row);
     const MaxminMode mode = make(S);
     if (mode.extra) {
         rc = dvs_dev_alloc(ctx, &d_extra.p, mode.extra, mode.what);
@@ -387,17 +396,17 @@ int maxmin_run(dvs_ctx *ctx, const MaxminArgs &a, F &&make) {
     std::vector<uint64_t> head;
     if (e == hipSuccess && se == hipSuccess && !status[MM_ST_ZERODIV]) {
         const uint32_t np = std::min(status[MM_ST_NPICKED], ns);
-        head.resize(o_owner / 8);
-        e = hipMemcpyAsync(head.data(), base, o_owner, hipMemcpyDeviceToHost, ctx->stream);
+        head.resize(L.owner / 8);
+        e = hipMemcpyAsync(head.data(), base, L.owner, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(a.owner, S.owner, size_t(n) * 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(a.dist_to_owner, S.mind, size_t(n) * 8, hipMemcpyDeviceToHost, ctx->stream);
         se = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess && se == hipSuccess) {
             const char *hb = reinterpret_cast<const char *>(head.data());
             *a.n_picked = np;
-            *a.cover = *reinterpret_cast<const double *>(hb + o_cover);
-            std::copy_n(reinterpret_cast<const double *>(hb + o_radius), np, a.radius);
-            std::copy_n(reinterpret_cast<const uint32_t *>(hb + o_picks), np, a.picks);
+            *a.cover = *reinterpret_cast<const double *>(hb + L.cover);
+            std::copy_n(reinterpret_cast<const double *>(hb + L.radius), np, a.radius);
+            std::copy_n(reinterpret_cast<const uint32_t *>(hb + L.picks), np, a.picks);
         }
     } else if (se == hipSuccess) {
         se = hipStreamSynchronize(ctx->stream);  // (the blocks go back to the cache behind it)
@@ -442,29 +451,14 @@ MaxminMode stage_mode(dvs_ctx *ctx, const dvs_cross_stage &st, uint32_t n, bool 
 
 int maxmin_given(dvs_ctx *ctx, const MaxminArgs &a, const double *dist, int dist_on_device) {
     const uint32_t n = a.n;
-    if (uint64_t(n) * n > (uint64_t(1) << 58))
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix does not fit in memory", n, n);
     DVS_HIP(ctx, hipSetDevice(ctx->device));
     PooledBuf d_dist{ctx};
     const double *d_mat = dist;
-    if (dist_on_device) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, dist) != hipSuccess) {
-            (void)hipGetLastError();
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
-        }
-        if (attr.device != ctx->device)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
-                                 attr.device, ctx->device);
-    } else {
-        if (int rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix")) return rc;
-        const hipError_t e = hipMemcpyAsync(d_dist.p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return dvs_hip_fail(ctx, e, "distance matrix upload");
-        }
-        d_mat = d_dist.as<double>();
-    }
+    int rc = dist_on_device ? dvs_given_on_device(ctx, nullptr, dist) : DVS_OK;
+    if (!rc) rc = dvs_square_fits(ctx, nullptr, n, !dist_on_device, MaxminLayout(n, a.n_select).bytes, "the farthest-first state");
+    if (!rc && !dist_on_device) rc = dvs_given_upload(ctx, dist, n, &d_dist);
+    if (rc) return rc;
+    if (!dist_on_device) d_mat = d_dist.as<double>();
     return maxmin_run(ctx, a, [&](const MaxminState &) {
         MaxminMode mode{"farthest-first selection", 0, "", false, upd_blocks(n)};
         mode.prepare = [](void *, const MaxminState &) { return hipSuccess; };

@@ -299,32 +299,15 @@ size_t nj_pack_elems(uint32_t n) {
     return h * h + 1;
 }
 
-// the matrix (need_matrix), the second buffer and the loop's scratch against the device's memory
-int nj_fits(dvs_ctx *ctx, uint32_t n, bool need_matrix) {
-    const uint64_t n2 = uint64_t(n) * n;
-    if (n2 > (uint64_t(1) << 58))
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix does not fit in memory", n, n);
-    const size_t bytes = (need_matrix ? size_t(n2) * 8 : 0) + nj_pack_elems(n) * 8 + NjLayout(n).bytes;
-    size_t free_b = 0, total_b = 0;
-    DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    if (bytes + (64u << 20) > free_b + ctx->pool_bytes)
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix and its neighbour-joining tree need %zu bytes "
-                             "of HBM, %zu free", n, n, bytes, free_b);
-    return DVS_OK;
-}
-
 }  // namespace
 
-// The neighbour-joining tree of the n x n matrix at d_dist (a working buffer: overwritten), n >= 3.  Everything is
-// enqueued on the context's stream behind whatever wrote the matrix; d_zerodiv as dvs_linkage_device takes it.  Returns
+// A consumer's run (dvs_internal.h dvs_square_consumer): the neighbour-joining tree of the n x n matrix at d_dist (a
+// working buffer: overwritten), n >= 3, enqueued on the context's stream behind whatever wrote the matrix.  Returns
 // when the host outputs (dvs_nj's) are written.
-int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *joins, double *lengths) {
-    if (n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least three sequences for a neighbour-joining tree");
-    int rc = nj_fits(ctx, n, false);
-    if (rc) return rc;
+static int nj_run(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_zerodiv, uint32_t *joins, double *lengths) {
     const NjLayout L(n);
     PooledBuf scratch{ctx}, pack{ctx};
-    rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "neighbour-joining scratch");
+    int rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "neighbour-joining scratch");
     if (!rc) rc = dvs_dev_alloc(ctx, &pack.p, nj_pack_elems(n) * 8, "neighbour-joining repack buffer");
     if (rc) return rc;
     char *base = scratch.as<char>();
@@ -333,9 +316,7 @@ int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_ze
     uint32_t *d_status = u32(L.status);
     std::vector<uint64_t> host((L.out_bytes + 7) / 8);
     const char *what = "neighbour joining";
-    hipError_t e = hipMemsetAsync(d_status, 0, 16, ctx->stream);
-    if (e == hipSuccess && d_zerodiv)
-        e = hipMemcpyAsync(d_status + 1, d_zerodiv, 4, hipMemcpyDeviceToDevice, ctx->stream);
+    hipError_t e = dvs_status_begin(ctx, d_status, 16, 1, d_zerodiv);
     if (e == hipSuccess) e = dvs_linkage_enqueue_prepare(ctx, d_dist, n, false, d_status);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(nj_rowsum_kernel, dim3((n + NJ_SCAN_WAVES - 1) / NJ_SCAN_WAVES), dim3(NJ_SCAN_THREADS), 0,
@@ -389,32 +370,18 @@ int dvs_nj_device(dvs_ctx *ctx, double *d_dist, uint32_t n, const uint32_t *d_ze
     return DVS_OK;
 }
 
-int dvs_nj_given(dvs_ctx *ctx, double *dist, int dist_on_device, uint32_t n, uint32_t *joins, double *lengths) {
-    if (n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least three sequences for a neighbour-joining tree");
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    if (dist_on_device) {
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, dist);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
-        }
-        if (attr.device != ctx->device)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
-                                 attr.device, ctx->device);
-        return dvs_nj_device(ctx, dist, n, nullptr, joins, lengths);
-    }
-    int rc = nj_fits(ctx, n, true);
-    if (rc) return rc;
-    PooledBuf d_dist{ctx};
-    rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix");
-    if (rc) return rc;
-    const hipError_t e = hipMemcpyAsync(d_dist.p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, e, "distance matrix upload");
-    }
-    return dvs_nj_device(ctx, d_dist.as<double>(), n, nullptr, joins, lengths);
+// beside the matrix: the second buffer and the loop's scratch
+dvs_square_consumer dvs_nj_consumer(dvs_ctx *ctx, uint32_t n, uint32_t *joins, double *lengths) {
+    dvs_square_consumer c{"dvs_nj"};
+    c.check = [=] {
+        if (n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least three sequences for a neighbour-joining tree");
+        return int(DVS_OK);
+    };
+    c.extra_bytes = [=] { return nj_pack_elems(n) * 8 + NjLayout(n).bytes; };
+    snprintf(c.extra_what, sizeof c.extra_what, "its neighbour-joining tree");
+    c.writes_matrix = true;
+    c.run = [=](double *d_dist, const uint32_t *d_zerodiv) { return nj_run(ctx, d_dist, n, d_zerodiv, joins, lengths); };
+    return c;
 }
 
 // The path lengths between the leaves (host only).  A record's children were made before it, so rooted at the last

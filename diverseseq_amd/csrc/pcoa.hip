@@ -275,7 +275,7 @@ uint32_t basis_limit(uint32_t n, uint32_t max_basis) {
 }  // namespace
 
 // the arguments and n, before anything else is looked at
-int dvs_pcoa_check_args(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p) {
+static int pcoa_check_args(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p) {
     if (p->n_axes == 0) return dvs_set_error(ctx, DVS_ERR_VALUE, "principal coordinates: one axis at least");
     if (!(p->tol >= 0.0)) return dvs_set_error(ctx, DVS_ERR_VALUE, "tol must be a number >= 0");
     if (p->max_basis && p->max_basis < p->n_axes)
@@ -291,35 +291,17 @@ int dvs_pcoa_check_args(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p) {
     return DVS_OK;
 }
 
-// the matrix (need_matrix), the basis with B Q beside it and the small blocks against the device's memory
-int dvs_pcoa_fits(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p, bool need_matrix) {
-    const uint64_t n2 = uint64_t(n) * n;
-    if (n2 > (uint64_t(1) << 58))
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix does not fit in memory", n, n);
-    const uint32_t limit = basis_limit(n, p->max_basis);
-    const size_t bytes = (need_matrix ? size_t(n2) * 8 : 0) + 2 * size_t(n) * limit * 8 + PcoaLayout(n, limit, p->n_axes).bytes;
-    size_t free_b = 0, total_b = 0;
-    DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    if (bytes + (64u << 20) > free_b + ctx->pool_bytes)
-        return dvs_set_error(ctx, DVS_ERR_NOMEM, "a %u x %u distance matrix and a basis of %u columns need %zu bytes of HBM, "
-                             "%zu free", n, n, limit, bytes, free_b);
-    return DVS_OK;
-}
-
-// The principal coordinates of the n x n matrix at d_dist (only read), the arguments checked.  The prepare pass is
-// enqueued on the context's stream behind whatever wrote the matrix; d_zerodiv as dvs_nj_device takes it.  Returns when
-// the host outputs (dvs_pcoa's) are written.
-int dvs_pcoa_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv, const dvs_pcoa_params *p,
+// A consumer's run (dvs_internal.h dvs_square_consumer): the principal coordinates of the n x n matrix at d_dist (only
+// read).  The prepare pass is enqueued on the context's stream behind whatever wrote the matrix.  Returns when the host
+// outputs (dvs_pcoa's) are written.
+static int pcoa_run(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32_t *d_zerodiv, const dvs_pcoa_params *p,
                     double *values, double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info) {
     const uint32_t m = p->n_axes, limit = basis_limit(n, p->max_basis);
     const PcoaLayout L(n, limit, m);
     PooledBuf basis{ctx}, scratch{ctx};
     int rc = dvs_dev_alloc(ctx, &basis.p, 2 * size_t(n) * limit * 8, "principal-coordinates basis");
     if (!rc) rc = dvs_dev_alloc(ctx, &scratch.p, L.bytes, "principal-coordinates scratch");
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);  // (the kernels that write the matrix)
-        return rc;
-    }
+    if (rc) return rc;
     double *Q = basis.as<double>(), *BQ = Q + size_t(n) * limit;
     char *base = scratch.as<char>();
     auto f64 = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
@@ -331,8 +313,7 @@ int dvs_pcoa_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32
     // ---- the prepare pass
     uint32_t st[4] = {0, 0, 0, 0};
     std::vector<double> rowsum(n);
-    hipError_t e = hipMemsetAsync(d_status, 0, 16, s);
-    if (e == hipSuccess && d_zerodiv) e = hipMemcpyAsync(d_status + 1, d_zerodiv, 4, hipMemcpyDeviceToDevice, s);
+    hipError_t e = dvs_status_begin(ctx, d_status, 16, 1, d_zerodiv);
     if (e == hipSuccess) {
         const uint32_t tiles = (n + PCOA_TILE - 1) / PCOA_TILE;
         hipLaunchKernelGGL(pcoa_check_kernel, dim3(tiles, tiles), dim3(256), 0, s, d_dist, n, d_status, f64(L.partial));
@@ -502,31 +483,17 @@ int dvs_pcoa_device(dvs_ctx *ctx, const double *d_dist, uint32_t n, const uint32
     return DVS_OK;
 }
 
-// a caller's matrix: a device matrix is read where it is, a host matrix uploaded.  The checks in dvs_pcoa's order.
-int dvs_pcoa_given(dvs_ctx *ctx, const double *dist, int dist_on_device, uint32_t n, const dvs_pcoa_params *p, double *values,
-                   double *vectors, double *residuals, double *row_means, dvs_pcoa_info *info) {
-    if (int rc = dvs_pcoa_check_args(ctx, n, p)) return rc;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    if (dist_on_device) {
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, dist);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is not device memory");
-        }
-        if (attr.device != ctx->device)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "the distance matrix is on device %d, the context on device %d",
-                                 attr.device, ctx->device);
-        if (int rc = dvs_pcoa_fits(ctx, n, p, false)) return rc;
-        return dvs_pcoa_device(ctx, dist, n, nullptr, p, values, vectors, residuals, row_means, info);
-    }
-    if (int rc = dvs_pcoa_fits(ctx, n, p, true)) return rc;
-    PooledBuf d_dist{ctx};
-    if (int rc = dvs_dev_alloc(ctx, &d_dist.p, size_t(n) * n * 8, "distance matrix")) return rc;
-    const hipError_t e = hipMemcpyAsync(d_dist.p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return dvs_hip_fail(ctx, e, "distance matrix upload");
-    }
-    return dvs_pcoa_device(ctx, d_dist.as<double>(), n, nullptr, p, values, vectors, residuals, row_means, info);
+// beside the matrix: the basis with B Q beside it, and the small blocks
+dvs_square_consumer dvs_pcoa_consumer(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_params *p, double *values, double *vectors,
+                                      double *residuals, double *row_means, dvs_pcoa_info *info) {
+    dvs_square_consumer c{"dvs_pcoa"};
+    const uint32_t limit = basis_limit(n, p->max_basis);
+    c.check = [=] { return pcoa_check_args(ctx, n, p); };
+    c.extra_bytes = [=] { return 2 * size_t(n) * limit * 8 + PcoaLayout(n, limit, p->n_axes).bytes; };
+    snprintf(c.extra_what, sizeof c.extra_what, "a basis of %u columns", limit);
+    c.writes_matrix = false;
+    c.run = [=](double *d_dist, const uint32_t *d_zerodiv) {
+        return pcoa_run(ctx, d_dist, n, d_zerodiv, p, values, vectors, residuals, row_means, info);
+    };
+    return c;
 }

@@ -1,6 +1,7 @@
 // Pairwise distances between the rows of a k-mer matrix -- the Jensen-Shannon divergence and the euclidean distance
-// (diverse_seq/distance.py:294-336) -- and the two drivers every ctree distance mode goes through: rows of a matrix to
-// a host N x N array, and distances to linkage tree with the N x N matrix left in HBM.
+// (diverse_seq/distance.py:294-336) -- and the drivers every ctree distance mode goes through: rows of a matrix to a
+// host N x N array, and a whole source to a consumer of its N x N matrix (the linkage tree, the neighbour-joining tree,
+// the principal coordinates, k-medoids) with the matrix left in HBM.
 //
 // The Jensen-Shannon divergence:
 //   D[i][j] = H((f_i + f_j) / 2) - (H(f_i) + H(f_j)) / 2,   f = counts / total, H in bits,
@@ -205,7 +206,8 @@ dvs_dist_stage euclid_stage(dvs_ctx *ctx, const dvs_matrix *m) {
     return st;
 }
 
-// ---- the two drivers
+// ---- the drivers.  stage_enqueue: what both go through; stage_to_host: a mode's matrix to a host array; square_run
+// (behind the sources below, which it takes as they are): a whole matrix, left in HBM, to its consumer
 
 // The matrix and the mode's scratch from the context's cache, then the mode's kernels, behind a zeroed diagonal where
 // they leave it alone: DVS_OK with everything enqueued and nothing waited for, or the error (the stream drained, so
@@ -240,76 +242,48 @@ int stage_to_host(dvs_ctx *ctx, const dvs_dist_stage &st, double *dist) {
     return DVS_OK;
 }
 
-// ctree end to end on the device (diverse_seq/cluster.py:164-188, 216-233): the mode's N x N matrix is written into the
-// context's scratch and read there by the linkage tree (linkage.hip, which checks every entry, as sklearn does, and
-// returns once the stream is drained); it never crosses PCIe.  The checks come in one order for every mode: the
-// method, n < 2, the mode's own, the device, the fit in HBM.
-int stage_to_tree(dvs_ctx *ctx, const dvs_dist_stage &st, int method, uint32_t *pairs, double *heights, uint32_t *sizes) {
-    if (int rc = dvs_linkage_check_method(ctx, method)) return rc;
-    if (st.n < 2) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least two sequences to build a tree");
-    if (int rc = st.check()) return rc;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    PooledBuf d_dist{ctx}, d_scratch{ctx};
-    int rc = dvs_linkage_check_size(ctx, st.n);
-    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
-    if (rc) return rc;
-    return dvs_linkage_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr,
-                              method, pairs, heights, sizes);
-}
-
-// The same with the neighbour-joining tree (nj.hip) behind the distances; the checks in the same order: n < 3, the
-// mode's own, the device, the fit in HBM.
-int stage_to_nj(dvs_ctx *ctx, const dvs_dist_stage &st, uint32_t *joins, double *lengths) {
-    if (st.n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "need at least three sequences for a neighbour-joining tree");
-    if (int rc = st.check()) return rc;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    PooledBuf d_dist{ctx}, d_scratch{ctx};
-    int rc = dvs_linkage_check_size(ctx, st.n);
-    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
-    if (rc) return rc;
-    return dvs_nj_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr, joins,
-                         lengths);
-}
-
-// The same with the principal coordinates (pcoa.hip) behind the distances, which only read the matrix; the checks in
-// the same order: the arguments, n, the mode's own, the device, the fit in HBM.
-int stage_to_pcoa(dvs_ctx *ctx, const dvs_dist_stage &st, const dvs_pcoa_params *p, double *values, double *vectors,
-                  double *residuals, double *row_means, dvs_pcoa_info *info) {
-    if (int rc = dvs_pcoa_check_args(ctx, st.n, p)) return rc;
-    if (int rc = st.check()) return rc;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    PooledBuf d_dist{ctx}, d_scratch{ctx};
-    int rc = dvs_pcoa_fits(ctx, st.n, p, true);
-    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
-    if (rc) return rc;
-    return dvs_pcoa_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr, p,
-                           values, vectors, residuals, row_means, info);
-}
-
-// The same with k-medoids (kmedoids.hip) behind the distances, which only read the matrix; the checks in the same
-// order: the arguments, n, the mode's own, the device, the fit in HBM.
-int stage_to_kmedoids(dvs_ctx *ctx, const dvs_dist_stage &st, const dvs_kmedoids_params *p, const dvs_kmedoids_out &out) {
-    if (int rc = dvs_kmedoids_check_args(ctx, st.n, p, out.medoids)) return rc;
-    if (st.n == 1) {  // the one item its own medoid: there is no cell to compute or to check
-        out.medoids[0] = out.labels[0] = 0;
-        out.dist[0] = 0.0;
-        if (out.second) out.second[0] = HUGE_VAL;
-        if (out.td) out.td[0] = 0.0;
-        *out.info = dvs_kmedoids_info{0.0, 0.0, 0, 1, 1};
-        return DVS_OK;
-    }
-    if (int rc = st.check()) return rc;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    PooledBuf d_dist{ctx}, d_scratch{ctx};
-    int rc = dvs_kmedoids_fits(ctx, st.n, p, true);
-    if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
-    if (rc) return rc;
-    return dvs_kmedoids_device(ctx, d_dist.as<double>(), st.n, st.scratch_is_zerodiv ? d_scratch.as<uint32_t>() : nullptr, p, out);
-}
-
 }  // namespace
 
 int dvs_rows_check(dvs_ctx *ctx, uint32_t n) { return rows_check(ctx, n); }
+
+// ---- what every operation over a whole n x n matrix shares (dvs_internal.h)
+
+int dvs_square_fits(dvs_ctx *ctx, const char *op, uint32_t n, bool need_matrix, size_t extra_bytes, const char *extra_what) {
+    const char *sep = op ? ": " : "";
+    if (!op) op = "";
+    const uint64_t n2 = uint64_t(n) * n;
+    if (n2 > (uint64_t(1) << 58))
+        return dvs_set_error(ctx, DVS_ERR_NOMEM, "%s%sa %u x %u distance matrix does not fit in memory", op, sep, n, n);
+    const size_t bytes = (need_matrix ? size_t(n2) * 8 : 0) + extra_bytes;
+    size_t free_b = 0, total_b = 0;
+    DVS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (bytes + (64u << 20) > free_b + ctx->pool_bytes)
+        return dvs_set_error(ctx, DVS_ERR_NOMEM, "%s%sa %u x %u distance matrix and %s need %zu bytes of HBM, %zu free", op, sep,
+                             n, n, extra_what, bytes, free_b);
+    return DVS_OK;
+}
+
+int dvs_given_on_device(dvs_ctx *ctx, const char *op, const void *dist) {
+    const char *sep = op ? ": " : "";
+    if (!op) op = "";
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, dist) != hipSuccess) {
+        (void)hipGetLastError();  // clear the sticky error
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "%s%sthe distance matrix is not device memory", op, sep);
+    }
+    if (attr.device != ctx->device)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "%s%sthe distance matrix is on device %d, the context on device %d", op, sep,
+                             attr.device, ctx->device);
+    return DVS_OK;
+}
+
+int dvs_given_upload(dvs_ctx *ctx, const double *dist, uint32_t n, PooledBuf *d_dist) {
+    if (int rc = dvs_dev_alloc(ctx, &d_dist->p, size_t(n) * n * 8, "distance matrix")) return rc;
+    const hipError_t e = hipMemcpyAsync(d_dist->p, dist, size_t(n) * n * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) return DVS_OK;
+    (void)hipStreamSynchronize(ctx->stream);
+    return dvs_hip_fail(ctx, e, "distance matrix upload");
+}
 
 // ---- a source (include/dvs_hip.h dvs_source): what every entry checks first, and the source as a stage
 
@@ -359,23 +333,56 @@ extern "C" int dvs_distances(dvs_ctx *ctx, const dvs_source *src, double *dist) 
     return stage_to_host(ctx, source_stage(ctx, src), dist);
 }
 
+// The square driver: a whole source (checked by its entry) brought to the device as an n x n matrix, and a consumer
+// run over it (dvs_internal.h dvs_square_consumer: the linkage tree of ctree, diverse_seq/cluster.py:164-188, 216-233,
+// and what else reads a whole matrix).  A matrix the library measures never crosses PCIe: the mode's kernels write it
+// into a block of the cache and the consumer enqueues behind them.  The checks come in one order whatever the
+// consumer: its arguments and n; its early answer and the mode's own check (a MASH, EUCLIDEAN or JSD source); the
+// device; the pointer (a caller's device matrix, used where it is); the fit in HBM.
+static int square_run(dvs_ctx *ctx, const dvs_source *src, const dvs_square_consumer &c) {
+    const uint32_t n = src->n;
+    if (int rc = c.check()) return rc;
+    PooledBuf d_dist{ctx}, d_scratch{ctx};
+    double *dist = static_cast<double *>(src->handle);
+    const uint32_t *d_zerodiv = nullptr;
+    if (src->kind != DVS_SRC_GIVEN) {
+        if (c.early && c.early()) return DVS_OK;
+        const dvs_dist_stage st = source_stage(ctx, src);
+        if (int rc = st.check()) return rc;
+        DVS_HIP(ctx, hipSetDevice(ctx->device));
+        int rc = dvs_square_fits(ctx, c.name, n, true, c.extra_bytes(), c.extra_what);
+        if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
+        if (rc) return rc;
+        dist = d_dist.as<double>();
+        if (st.scratch_is_zerodiv) d_zerodiv = d_scratch.as<uint32_t>();
+    } else {
+        DVS_HIP(ctx, hipSetDevice(ctx->device));
+        int rc = src->on_device ? dvs_given_on_device(ctx, c.name, dist) : DVS_OK;
+        if (!rc) rc = dvs_square_fits(ctx, c.name, n, !src->on_device, c.extra_bytes(), c.extra_what);
+        if (!rc && !src->on_device) rc = dvs_given_upload(ctx, dist, n, &d_dist);
+        if (rc) return rc;
+        if (!src->on_device) dist = d_dist.as<double>();
+    }
+    const int rc = c.run(dist, d_zerodiv);
+    // (the one place that keeps PooledBuf's contract for the matrix: a run that failed may have left the kernels that
+    // write it, or its own that read it, queued)
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
 extern "C" int dvs_linkage(dvs_ctx *ctx, const dvs_source *src, int method, uint32_t *pairs, double *heights,
                            uint32_t *sizes) {
     if (int rc = dvs_source_check(ctx, src, src)) return rc;
     if (!pairs || !heights || !sizes) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     if (int rc = dvs_source_whole(ctx, "dvs_linkage", src)) return rc;
-    if (src->kind == DVS_SRC_GIVEN)
-        return dvs_linkage_given(ctx, static_cast<double *>(src->handle), src->on_device, src->n, method, pairs, heights, sizes);
-    return stage_to_tree(ctx, source_stage(ctx, src), method, pairs, heights, sizes);
+    return square_run(ctx, src, dvs_linkage_consumer(ctx, src->n, src->kind == DVS_SRC_GIVEN, method, pairs, heights, sizes));
 }
 
 extern "C" int dvs_nj(dvs_ctx *ctx, const dvs_source *src, uint32_t *joins, double *lengths) {
     if (int rc = dvs_source_check(ctx, src, src)) return rc;
     if (!joins || !lengths) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     if (int rc = dvs_source_whole(ctx, "dvs_nj", src)) return rc;
-    if (src->kind == DVS_SRC_GIVEN)
-        return dvs_nj_given(ctx, static_cast<double *>(src->handle), src->on_device, src->n, joins, lengths);
-    return stage_to_nj(ctx, source_stage(ctx, src), joins, lengths);
+    return square_run(ctx, src, dvs_nj_consumer(ctx, src->n, joins, lengths));
 }
 
 extern "C" int dvs_pcoa(dvs_ctx *ctx, const dvs_source *src, const dvs_pcoa_params *params, double *values, double *vectors,
@@ -383,10 +390,7 @@ extern "C" int dvs_pcoa(dvs_ctx *ctx, const dvs_source *src, const dvs_pcoa_para
     if (int rc = dvs_source_check(ctx, src, src)) return rc;
     if (!params || !values || !vectors || !residuals || !row_means || !info) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     if (int rc = dvs_source_whole(ctx, "dvs_pcoa", src)) return rc;
-    if (src->kind == DVS_SRC_GIVEN)
-        return dvs_pcoa_given(ctx, static_cast<const double *>(src->handle), src->on_device, src->n, params, values, vectors,
-                              residuals, row_means, info);
-    return stage_to_pcoa(ctx, source_stage(ctx, src), params, values, vectors, residuals, row_means, info);
+    return square_run(ctx, src, dvs_pcoa_consumer(ctx, src->n, params, values, vectors, residuals, row_means, info));
 }
 
 extern "C" int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src, const dvs_kmedoids_params *params, uint32_t *medoids,
@@ -396,7 +400,5 @@ extern "C" int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src, const dvs_kmedo
     if (!params || !medoids || !labels || !dist || !info) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_kmedoids: null argument");
     if (int rc = dvs_source_whole(ctx, "dvs_kmedoids", src)) return rc;
     const dvs_kmedoids_out out{medoids, labels, dist, second, swaps, td, info};
-    if (src->kind == DVS_SRC_GIVEN)
-        return dvs_kmedoids_given(ctx, static_cast<const double *>(src->handle), src->on_device, src->n, params, out);
-    return stage_to_kmedoids(ctx, source_stage(ctx, src), params, out);
+    return square_run(ctx, src, dvs_kmedoids_consumer(ctx, src->n, src->kind == DVS_SRC_GIVEN, params, out));
 }
