@@ -10,9 +10,9 @@ workgroup, csrc/linkage.hip, the same linkage matrix bit for bit); `tree="sklear
 reference's host path (`make_cluster_tree`, average linkage only).
 
 Beyond the reference: the flat clusters of a tree (`cut_tree`: scipy's fcluster partitions, on the host), the
-scores of a labelling (`cluster_scores`, csrc/crossdist.hip: sums within a cluster, the nearest other cluster,
+scores of a labelling (`cluster_scores`, csrc/clusters.hip: sums within a cluster, the nearest other cluster,
 silhouettes, medoids) and both behind one call (`ctree_clusters`); how well a tree represents its distances (`cophenet`:
-scipy's cophenet, the correlation reduced on the GPU by csrc/crossdist.hip's cophenet_kernel; `ctree_cophenet`,
+scipy's cophenet, the correlation reduced on the GPU by csrc/cophenet.hip's cophenet_kernel; `ctree_cophenet`,
 `compare_linkages`); and the tree of additive distances, neighbour joining (`neighbor_joining`, csrc/nj.hip: an unrooted
 tree with branch lengths and no molecular clock; `nj_to_newick`, `patristic`, `nj_tree`); and farthest-first selection
 of representatives over a caller's own distance matrix (`maxmin`, csrc/maxmin.hip); and the pairs of a caller's matrix

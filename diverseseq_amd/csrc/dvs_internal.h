@@ -384,6 +384,37 @@ struct dvs_cross_lists {
     }
 };
 
+// One consumer of an m x n f64 distance matrix that arrives strip by strip, as the strip driver of crossdist.hip
+// (dvs_strip_run) takes it.  An operation checks its own arguments, fills one of these in with lambdas that capture its
+// locals by reference, and calls the driver: the stage's check, the device, the strip height, the strip and the
+// stage's scratch, the stage's prepare, begin, strip behind each strip's distance kernels, the zero-division word, ONE
+// hipStreamSynchronize, then the errors (begin's; an enqueue's; the synchronisation's; DVS_ERR_ZERODIV).  THE DRAIN
+// IS THE DRIVER'S: whatever begin or strip return, the stream is waited for before the driver returns -- so an
+// operation never synchronises on account of an error, and its PooledBufs and the host memory its uploads read need
+// only be locals of the function that calls the driver.  The host work behind the drain follows the call.
+struct dvs_strip_consumer {
+    // optional: the blocks beside the strip (`rows`: the strip's height) and the uploads; DVS_OK, or the error it set
+    std::function<int(uint32_t rows)> begin;
+    std::function<hipError_t(uint32_t q0, uint32_t mq, double *d_strip)> strip;  // enqueued behind rows [q0, q0 + mq)
+    const bool *stop;  // optional: set by strip when no further strip is wanted
+};
+int dvs_strip_run(dvs_ctx *ctx, const dvs_cross_stage &st, const dvs_strip_consumer &c);  // crossdist.hip
+constexpr uint32_t DVS_NONE = 0xFFFFFFFFu;  // no row, no column, no cluster
+constexpr uint32_t DVS_TOPK_MAX = 64;       // the most nearest references, and axes of a projection, per query
+// the operations over a stage, called by the entries of crossdist.hip
+int dvs_nearest_strips(dvs_ctx *ctx, const dvs_cross_stage &st, uint32_t kk, uint32_t *idx, double *dist);  // nearest.hip
+int dvs_pcoa_project_strips(dvs_ctx *ctx, const dvs_cross_stage &st, uint32_t n_axes, const double *values,
+                            const double *vectors, const double *row_means, double *coords);  // pcoa.hip
+int dvs_cluster_scores_strips(dvs_ctx *ctx, const dvs_cross_stage &st, const uint32_t *labels, uint32_t n_clusters,
+                              double *within, double *a, double *b, uint32_t *neighbour, double *silhouette,
+                              uint32_t *medoids);  // clusters.hip
+int dvs_cophenet_strips(dvs_ctx *ctx, const dvs_cross_stage &st, const uint32_t *pairs, const double *heights, double *corr,
+                        double *row_sums, double *coph);  // cophenet.hip
+int dvs_within_strips(dvs_ctx *ctx, const dvs_cross_stage &st, double radius, uint32_t flags, uint64_t max_pairs,
+                      dvs_pairs **out);  // within.hip
+int dvs_threshold_clusters_strips(dvs_ctx *ctx, const dvs_cross_stage &st, double radius, uint32_t *labels,
+                                  uint32_t *n_clusters);  // within.hip
+
 // ---- an operation's source (include/dvs_hip.h dvs_source): the tag in front of the stages above
 uint32_t dvs_sketches_nseq(const dvs_sketches *sk);  // mash.hip, whose struct it is
 inline const dvs_matrix *dvs_src_matrix(const dvs_source *s) { return static_cast<const dvs_matrix *>(s->handle); }

@@ -16,6 +16,8 @@
 // The matrix is only READ.  Every reduction -- the row dot products, the column means, the Gram products, the norms --
 // adds its terms in an order that n and the block shape fix: a lane (thread) its strided terms in ascending order, the
 // lanes by the xor-shuffle tree, the waves in wave order.  No float atomics: the same bits on every run.
+//
+// Further rows are placed in a fitted ordination by pcoa_project_kernel, behind the strip driver (crossdist.hip dvs_strip_run).
 #include "dvs_internal.h"
 #include "pcoa_host.h"
 
@@ -245,6 +247,36 @@ __global__ __launch_bounds__(PCOA_THREADS) void pcoa_norm2_kernel(const double *
     for (uint32_t i = threadIdx.x; i < n; i += PCOA_THREADS) acc = fma(w[i], w[i], acc);
     acc = dvs_block_sum(acc, scratch);
     if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
+// Gower's add-a-point formula over the rows of a strip (mq x n): include/dvs_hip.h "principal coordinates".  Row r of the
+// strip holds a query's distances delta_j to the n fitted rows; out[r][a] = scale[a] * sum_j (delta_j^2 - mu_j) V[j][a],
+// scale[a] = -1/2 / sqrt(lambda_a) or 0 (the host's).  A workgroup per (row, eight axes): a thread adds its columns j =
+// tid, tid + 256, ... in ascending order, the 256 partials by the fixed tree of dvs_block_sum -- an order n alone fixes,
+// so the strip height and the run cannot change a bit.  A NaN cell makes every axis of its row NaN.
+constexpr int PROJ_THREADS = 256;
+constexpr uint32_t PROJ_AXES = 8;
+__global__ __launch_bounds__(PROJ_THREADS) void pcoa_project_kernel(const double *__restrict__ strip, uint32_t n, uint32_t m,
+                                                                    const double *__restrict__ V, const double *__restrict__ mu,
+                                                                    const double *__restrict__ scale, double *__restrict__ out) {
+    __shared__ double scratch[17];
+    const uint32_t a0 = blockIdx.y * PROJ_AXES;
+    const double *g = strip + uint64_t(blockIdx.x) * n;
+    double acc[PROJ_AXES];
+#pragma unroll
+    for (uint32_t a = 0; a < PROJ_AXES; a++) acc[a] = 0.0;
+    for (uint32_t j = threadIdx.x; j < n; j += PROJ_THREADS) {
+        const double d = g[j];
+        const double t = d * d - mu[j];
+#pragma unroll
+        for (uint32_t a = 0; a < PROJ_AXES; a++)
+            if (a0 + a < m) acc[a] = fma(t, V[size_t(j) * m + a0 + a], acc[a]);
+    }
+#pragma unroll
+    for (uint32_t a = 0; a < PROJ_AXES; a++) {
+        const double sum = dvs_block_sum(acc[a], scratch);
+        if (threadIdx.x == 0 && a0 + a < m) out[uint64_t(blockIdx.x) * m + a0 + a] = sum * scale[a0 + a];
+    }
 }
 
 size_t up8(size_t x) { return (x + 7) & ~size_t(7); }
@@ -496,4 +528,42 @@ dvs_square_consumer dvs_pcoa_consumer(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_p
         return pcoa_run(ctx, d_dist, n, d_zerodiv, p, values, vectors, residuals, row_means, info);
     };
     return c;
+}
+
+// the coordinates of every query in a fitted ordination (include/dvs_hip.h "principal coordinates") into the host array
+// coords (m x n_axes): the fit's tables uploaded once, pcoa_project_kernel behind each strip's distances
+int dvs_pcoa_project_strips(dvs_ctx *ctx, const dvs_cross_stage &st, uint32_t n_axes, const double *values,
+                            const double *vectors, const double *row_means, double *coords) {
+    if (n_axes == 0) return dvs_set_error(ctx, DVS_ERR_VALUE, "principal coordinates: one axis at least");
+    if (n_axes > DVS_TOPK_MAX)
+        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "%u axes: %u at most", n_axes, DVS_TOPK_MAX);
+    if (!values || !vectors || !row_means) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (st.n == 0) return dvs_set_error(ctx, DVS_ERR_VALUE, "a projection needs the fitted rows: no reference rows");
+    if (st.m == 0) return DVS_OK;
+    if (!coords) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    const size_t nv = size_t(st.n) * n_axes;
+    std::vector<double> scale(n_axes);
+    for (uint32_t a = 0; a < n_axes; a++) scale[a] = values[a] > 0.0 ? -0.5 / std::sqrt(values[a]) : 0.0;
+    PooledBuf d_fit{ctx}, d_out{ctx};  // d_fit: V [n x n_axes], mu [n], scale [n_axes]
+    double *d_v, *d_mu, *d_scale;
+    dvs_strip_consumer c{};
+    c.begin = [&](uint32_t rows) {
+        int rc = dvs_dev_alloc(ctx, &d_fit.p, (nv + st.n + n_axes) * 8, "fitted ordination");
+        if (!rc) rc = dvs_dev_alloc(ctx, &d_out.p, size_t(rows) * n_axes * 8, "projected coordinates");
+        if (rc) return rc;
+        d_v = d_fit.as<double>(), d_mu = d_v + nv, d_scale = d_mu + st.n;
+        hipError_t e = hipMemcpyAsync(d_v, vectors, nv * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_mu, row_means, size_t(st.n) * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_scale, scale.data(), size_t(n_axes) * 8, hipMemcpyHostToDevice, ctx->stream);
+        return e == hipSuccess ? DVS_OK : dvs_hip_fail(ctx, e, "fitted ordination upload");
+    };
+    c.strip = [&](uint32_t q0, uint32_t mq, double *d_strip) {
+        hipLaunchKernelGGL(pcoa_project_kernel, dim3(mq, (n_axes + PROJ_AXES - 1) / PROJ_AXES), dim3(PROJ_THREADS), 0, ctx->stream,
+                           d_strip, st.n, n_axes, d_v, d_mu, d_scale, d_out.as<double>());
+        hipError_t le = hipGetLastError();
+        if (le == hipSuccess)
+            le = hipMemcpyAsync(coords + size_t(q0) * n_axes, d_out.p, size_t(mq) * n_axes * 8, hipMemcpyDeviceToHost, ctx->stream);
+        return le;
+    };
+    return dvs_strip_run(ctx, st, c);
 }

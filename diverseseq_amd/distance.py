@@ -16,13 +16,14 @@ branch lengths, the matrix left in HBM as for the linkage trees; no counterpart 
 csrc/maxmin.hip, one row of distances per pick and never the matrix; no counterpart in the reference); and the sparse
 product over the same strips: the pairs within a radius (within, neighbours, matrix_within -> `Neighbours`) and the
 groups they make (threshold_clusters, matrix_threshold_clusters -> `ThresholdClusters`: connected components, the
-single-linkage clusters at that height), each strip compacted on the device (csrc/crossdist.hip) so that only the listed
+single-linkage clusters at that height), each strip compacted on the device (csrc/within.hip) so that only the listed
 pairs cross to the host; no counterpart in the reference; and the ordination of a collection's distances, principal
 coordinates (pcoa, matrix_pcoa, mash_pcoa / euclidean_pcoa / jsd_pcoa -> `PCoA`: csrc/pcoa.hip, the few largest eigenpairs
 of the double-centred matrix by an iteration that only reads the N x N matrix in HBM) with the projection of further
 rows into a fitted ordination (pcoa_project, matrix_pcoa_project: Gower's formula beside each strip of
-cross_distances, csrc/crossdist.hip); no counterpart in the reference; and the representatives that lie closest, in
-total, to everything else, k-medoids (kmedoids, matrix_kmedoids, mash_kmedoids / euclidean_kmedoids / jsd_kmedoids ->
+cross_distances, csrc/pcoa.hip behind the strip driver of csrc/crossdist.hip); no counterpart in the reference; and
+the representatives that lie closest, in total, to everything else, k-medoids (kmedoids, matrix_kmedoids,
+mash_kmedoids / euclidean_kmedoids / jsd_kmedoids ->
 `KMedoids`: csrc/kmedoids.hip, PAM's BUILD and FastPAM1's swaps over the N x N matrix in HBM); no counterpart in the
 reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the

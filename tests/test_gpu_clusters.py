@@ -1,5 +1,5 @@
 """Flat clusters and the scores of a labelling on the GPU (cluster_scores_kernel and its driver in
-csrc/crossdist.hip, the host cut in csrc/linkage.hip).  Every comparison is against something other than the code
+csrc/clusters.hip, the host cut in csrc/linkage.hip).  Every comparison is against something other than the code
 under test: the long-double yardstick of tests/test_clusters_host.py (which also pins that no neighbour or medoid of
 the random cases hangs on rounding), sklearn's silhouette_samples, scipy's fcluster, numpy on the distance matrices the
 earlier entries return."""

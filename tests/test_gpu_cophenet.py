@@ -1,4 +1,4 @@
-"""The cophenetic correlation on the GPU (cophenet_kernel and its driver in csrc/crossdist.hip, the in-order walk in
+"""The cophenetic correlation on the GPU (cophenet_kernel and its consumer in csrc/cophenet.hip, the in-order walk in
 csrc/linkage.hip).  Every comparison is against something other than the code under test: the long-double yardstick of
 tests/test_cophenet_host.py (which also pins that float64 raw moments miss the bound by more than 100 x on the saturated
 cases, so meeting it there takes the shift), scipy's cophenet for the cophenetic matrix bit for bit and for r, numpy on

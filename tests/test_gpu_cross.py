@@ -1,4 +1,4 @@
-"""Distances between two collections and the nearest references on the GPU (csrc/crossdist.hip, the cross
+"""Distances between two collections and the nearest references on the GPU (csrc/crossdist.hip, csrc/nearest.hip, the cross
 instantiation of csrc/mash.hip's pair kernel).  Every comparison is against something other than the code under test:
 the square entries (same bits for the same two rows), the long-double yardsticks of tests/test_distance_truth_host.py,
 the oracle's sketches and mash distances, the reference's own mash_distance vectors, numpy's stable argsort, the oracle's

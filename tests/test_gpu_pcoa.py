@@ -1,4 +1,4 @@
-"""Principal coordinates on the GPU (csrc/pcoa.hip, the projection kernel of csrc/crossdist.hip) against the yardstick
+"""Principal coordinates on the GPU (csrc/pcoa.hip, the projection kernel included) against the yardstick
 and the cases of test_pcoa_host.py.
 
 The bounds.  unit(n) = (n + 8) 2^-52 ||A||_F, A = -1/2 D o D: the rounding of one f64 pass over A.  The Frobenius norm,

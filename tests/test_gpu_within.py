@@ -1,5 +1,5 @@
 """Neighbours within a radius and threshold clusters on the GPU (the within_* kernels and their drivers in
-csrc/crossdist.hip).  The expected pairs always come from something other than the code under test: `expected_within`
+csrc/within.hip).  The expected pairs always come from something other than the code under test: `expected_within`
 (tests/test_within_host.py: numpy's nonzero of d <= radius) over the matrix that the existing cross_distances / distances
 entries return for the same handles, or over a caller's own seeded matrix; the expected labels from `expected_components`
 (pinned there against scipy twice) and from the project's own single linkage and cut.  tests/test_within_host.py pins

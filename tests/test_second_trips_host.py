@@ -4,8 +4,8 @@ one new yardstick they need, and CPU tests that tie both to the yardsticks the p
 The suites of neighbour joining, cophenet and nearest choose their sizes around the wave (64), the workgroup (256) and the
 32-row tile.  Each of these kernels also has a regime that begins at a larger size -- a loop takes its second trip, a row
 no longer fits in LDS, a grid is capped and the rows are dealt out in passes -- and the constants below say where.  They
-restate the kernels' own (csrc/nj.hip, csrc/crossdist.hip, csrc/mash.hip); a case asserts on the host that it lies beyond
-the one it is there for.
+restate the kernels' own (csrc/nj.hip, csrc/cophenet.hip, csrc/nearest.hip, csrc/crossdist.hip, csrc/mash.hip); a case
+asserts on the host that it lies beyond the one it is there for.
 
 `restated_prefix(d, steps)` is test_nj_host.restated for the first `steps` records only: `_nj`'s algorithm and order of
 operands in float64, but a retired slot stays where it is (its R is -inf, so every Q it takes part in is +inf) and nothing
