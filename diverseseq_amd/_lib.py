@@ -40,10 +40,8 @@ EXPORTS = (
     "dvs_sketches_from_device", "dvs_sketches_copy_to_device", "dvs_sketches_distances_device",
     "dvs_default_alphabet_lut", "dvs_seqbatch_from_fasta", "dvs_seqbatch_destroy", "dvs_seqbatch_info",
     "dvs_seqbatch_offsets", "dvs_seqbatch_header_positions", "dvs_seqbatch_dev_codes", "dvs_seqbatch_get_codes",
-    "dvs_matrix_build_from_seqbatch",
     "dvs_pack_sequences", "dvs_packed_destroy", "dvs_packed_info", "dvs_packed_dev_codes", "dvs_packed_dev_mask",
-    "dvs_packed_get", "dvs_matrix_build_packed", "dvs_sketches_build_packed", "dvs_seqbatch_pack",
-    "dvs_seqbatch_packed", "dvs_sketches_build_from_seqbatch",
+    "dvs_packed_get", "dvs_seqbatch_pack", "dvs_seqbatch_packed",
     "dvs_canonical_bins", "dvs_matrix_fold_canonical", "dvs_matrix_is_canonical",
     "dvs_linkage_cut", "dvs_linkage_cophenet", "dvs_nj_patristic", "dvs_pairs_destroy", "dvs_pairs_info", "dvs_pairs_get",
     # one entry per operation over the distances of a `Source`
@@ -52,12 +50,28 @@ EXPORTS = (
 )
 WITHIN_SKIP_SELF = 1
 SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
+SEQ_HOST, SEQ_DEVICE, SEQ_PACKED, SEQ_BATCH = range(4)
 
 
 class Source(C.Structure):
     """dvs_source: where an operation's distances come from"""
     _fields_ = [("kind", C.c_uint32), ("handle", C.c_void_p), ("rows", C.POINTER(C.c_uint32)), ("n", C.c_uint32),
                 ("k", C.c_uint32), ("sketch_size", C.c_uint32), ("on_device", C.c_int)]
+
+
+class Seqs(C.Structure):
+    """dvs_seqs: where a build's sequences come from"""
+    _fields_ = [("kind", C.c_uint32), ("handle", C.c_void_p), ("offsets", C.POINTER(C.c_uint64)), ("nseq", C.c_uint32)]
+
+
+def make_seqs(kind: int, handle, offsets: np.ndarray | None = None, keep=None) -> Seqs:
+    """the dvs_seqs of one build: `kind` (SEQ_*), the pointer or handle and, except for SEQ_BATCH, the nseq + 1 offsets
+    (made contiguous uint64 here).  The offsets array and `keep`, the owner of the bytes, live as long as the structure"""
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    seqs = Seqs(kind, handle, ptr(offsets, C.c_uint64), 0 if offsets is None else offsets.size - 1)
+    seqs._keep = (handle, offsets, keep)
+    return seqs
 
 
 class PcoaParams(C.Structure):
@@ -164,8 +178,7 @@ def load() -> C.CDLL:
         L.dvs_ctx_set_timing.argtypes = [vp, C.c_int]
         L.dvs_ctx_refresh_knobs.argtypes = [vp]
         L.dvs_ctx_device_info.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), u64p]
-        L.dvs_matrix_build.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                       C.POINTER(vp)]
+        L.dvs_matrix_build.argtypes = [vp, C.POINTER(Seqs), C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.dvs_matrix_from_freqs.argtypes = [vp, f64p, C.c_uint32, C.c_uint64, C.POINTER(vp)]
         L.dvs_matrix_from_device_freqs.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.POINTER(vp)]
         L.dvs_select_gather_members.argtypes = [vp, vp, vp, vp, C.c_uint32]
@@ -207,8 +220,7 @@ def load() -> C.CDLL:
                                       C.c_uint32, C.c_int, u32p, u32p]
         L.dvs_mash_distances.argtypes = [vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, f64p]
-        L.dvs_sketches_build.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                         C.c_int, C.POINTER(vp)]
+        L.dvs_sketches_build.argtypes = [vp, C.POINTER(Seqs), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(vp)]
         L.dvs_sketches_destroy.argtypes = [vp]
         L.dvs_sketches_destroy.restype = None
         L.dvs_sketches_get.argtypes = [vp, vp, u32p, u32p]
@@ -230,7 +242,6 @@ def load() -> C.CDLL:
         L.dvs_seqbatch_dev_codes.argtypes = [vp]
         L.dvs_seqbatch_dev_codes.restype = vp
         L.dvs_seqbatch_get_codes.argtypes = [vp, vp, u8p]
-        L.dvs_matrix_build_from_seqbatch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.dvs_pack_sequences.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(vp)]
         L.dvs_packed_destroy.argtypes = [vp]
         L.dvs_packed_destroy.restype = None
@@ -239,12 +250,7 @@ def load() -> C.CDLL:
             getattr(L, n).argtypes = [vp]
             getattr(L, n).restype = vp
         L.dvs_packed_get.argtypes = [vp, vp, u32p, C.POINTER(C.c_uint16)]
-        L.dvs_matrix_build_packed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.POINTER(vp)]
-        L.dvs_sketches_build_packed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
-                                                C.POINTER(vp)]
         L.dvs_seqbatch_pack.argtypes = [vp, vp]
-        L.dvs_sketches_build_from_seqbatch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
-                                                       C.POINTER(vp)]
         u32, srcp = C.c_uint32, C.POINTER(Source)
         L.dvs_linkage_cut.argtypes = [vp, u32, u32p, f64p, C.c_int, C.c_double, u32p, u32p]
         L.dvs_linkage_cophenet.argtypes = [vp, u32, u32p, f64p, f64p]
@@ -276,7 +282,7 @@ def load() -> C.CDLL:
         # params, medoids, labels, dist, second, swaps, td, info
         L.dvs_kmedoids.argtypes = [vp, srcp, C.POINTER(KmedoidsParams), u32p, u32p, f64p, f64p, u32p, f64p,
                                    C.POINTER(KmedoidsInfo)]
-        if L.dvs_abi_version() != 4:
+        if L.dvs_abi_version() != 5:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L
         return _lib

@@ -6,15 +6,6 @@
 #include <cstring>
 #include <mutex>
 
-uint64_t dvs_pow_u64(uint32_t base, uint32_t exp, bool *overflow);
-void dvs_matrix_free_fields(dvs_matrix *m);
-int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, const uint64_t *offsets, bool no_wait);
-int dvs_matrix_fill_freq_entropy(dvs_ctx *ctx, dvs_matrix *m);
-int dvs_hist_prepare(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint32_t k, uint64_t nbins, uint64_t nbytes, size_t *n_long_out);
-bool dvs_hist_rows_fit_u16(const dvs_ctx *ctx, uint64_t B, size_t n_long);
-int dvs_matrix_fill_freq_totals(dvs_ctx *ctx, dvs_matrix *m, const double *d_meta);
-int dvs_matrix_fill_compacted(dvs_ctx *ctx, dvs_matrix *m, const double *d_in, const double *d_meta);
-
 static std::string g_create_err;
 
 int dvs_set_error(dvs_ctx *ctx, int code, const char *fmt, ...) {
@@ -321,6 +312,8 @@ int dvs_ctx_device_info(dvs_ctx *ctx, char *name, size_t name_len, int *n_cu, ui
     return DVS_OK;
 }
 
+}  // extern "C"
+
 static int matrix_alloc(dvs_ctx *ctx, dvs_matrix *m) {
     const size_t cells = size_t(m->nrows) * m->nbins;
     const size_t bytes = cells * (m->kind == 0 ? 4 : m->kind == 2 ? 2 : 8);
@@ -341,6 +334,25 @@ static int matrix_alloc(dvs_ctx *ctx, dvs_matrix *m) {
     if (!rc) rc = dvs_dev_alloc(ctx, (void **)&m->d_totals, nr * 4, "matrix totals");
     if (!rc) rc = dvs_dev_alloc(ctx, (void **)&m->d_entropy, nr * 8, "matrix entropy");
     return rc;
+}
+
+// how every constructor ends: the matrix handed over, or released with the error that stopped it
+static int matrix_made(int rc, dvs_matrix *m, dvs_matrix **out) {
+    if (rc) dvs_matrix_destroy(m);
+    else *out = m;
+    return rc;
+}
+
+int dvs_matrix_new(dvs_ctx *ctx, int kind, uint32_t nrows, uint64_t nbins, uint32_t k, uint32_t num_states, dvs_matrix **out) {
+    *out = nullptr;
+    dvs_matrix *m = new dvs_matrix();
+    m->kind = kind;
+    m->nrows = nrows;
+    m->nbins = nbins;
+    m->k = k;
+    m->num_states = num_states;
+    m->device = ctx->device;
+    return matrix_made(matrix_alloc(ctx, m), m, out);
 }
 
 // k and num_states of a build: the reference's panics first, then what the device path cannot hold
@@ -372,95 +384,31 @@ static int matrix_build_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_
         const int prc = dvs_hist_prepare(ctx, offsets, nseq, k, B, sv.nbytes, &n_long);
         if (prc) return prc;
     }
-    dvs_matrix *m = new dvs_matrix();
-    m->kind = (nseq && dvs_hist_rows_fit_u16(ctx, B, n_long)) ? 2 : 0;
-    m->nrows = nseq;
-    m->nbins = B;
-    m->k = k;
-    m->num_states = num_states;
-    m->device = ctx->device;
-    int rc = matrix_alloc(ctx, m);
+    dvs_matrix *m = nullptr;
+    int rc = dvs_matrix_new(ctx, (nseq && dvs_hist_rows_fit_u16(ctx, B, n_long)) ? 2 : 0, nseq, B, k, num_states, &m);
+    if (rc) return rc;
     // (a device-resident input needs no host wait: the kernels' completion is an event the consumers
     // of the matrix wait on when they need host-side data, dvs_matrix_settle)
-    if (!rc && nseq) rc = dvs_matrix_fill_counts(ctx, m, sv, offsets, no_wait);
-    if (rc) {
-        dvs_matrix_free_fields(m);
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return DVS_OK;
+    if (nseq) rc = dvs_matrix_fill_counts(ctx, m, sv, offsets, no_wait);
+    return matrix_made(rc, m, out);
 }
 
-int dvs_matrix_build(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device, const uint64_t *offsets,
-                     uint32_t nseq, uint32_t k, uint32_t num_states, dvs_matrix **out) {
-    if (!ctx || !offsets || !out || (!seqs && nseq && offsets[nseq] > 0))
-        return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+extern "C" {
+
+int dvs_matrix_build(dvs_ctx *ctx, const dvs_seqs *src, uint32_t k, uint32_t num_states, dvs_matrix **out) {
+    if (!out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     *out = nullptr;
-    {
-        uint64_t B_ = 0;
-        const int arc = build_shape(ctx, k, num_states, &B_);
-        if (arc) return arc;
-    }
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t nbytes = nseq ? offsets[nseq] : 0;
-    dvs_seq_view sv;
-    if (seqs_on_device) {
-        if (reinterpret_cast<uintptr_t>(seqs) & 15)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "device sequence buffer must be 16-byte aligned");
-        sv.seqs = seqs;
-        sv.nbytes = nbytes;
-        return matrix_build_view(ctx, sv, offsets, nseq, k, num_states, !ctx->knobs.build_wait, out);
-    }
-    // Host memory.  Four-state sequences cross PCIe packed -- 3 bits per base, packed by host threads
-    // beside the copies -- and the histogram reads the packed words as they are (pack.hip); anything
-    // else is copied as it is.
-    if (nbytes && dvs_packed_upload_wanted(ctx, num_states, nbytes)) {
-        dvs_packed *p = nullptr;
-        int rc = dvs_packed_alloc(ctx, nbytes, &p);
-        if (!rc) rc = dvs_packed_fill_from_host(ctx, p, seqs);
-        if (!rc) {
-            sv.codes = p->d_codes;
-            sv.mask = p->d_mask;
-            sv.nbytes = nbytes;
-            rc = matrix_build_view(ctx, sv, offsets, nseq, k, num_states, false, out);
-        }
-        if (p) {
-            (void)hipStreamSynchronize(ctx->stream);  // (the planes go back to the cache: nothing may still read them)
-            dvs_packed_destroy(p);
-        }
-        return rc;
-    }
-    const uint64_t padded = ((nbytes + 15) & ~15ull) + 16;
-    uint8_t *d_tmp = nullptr;
-    int rc = dvs_dev_alloc(ctx, (void **)&d_tmp, padded, "sequence upload buffer");
+    int rc = dvs_seqs_check(ctx, src, num_states);
+    uint64_t B = 0;
+    if (!rc) rc = build_shape(ctx, k, num_states, &B);
     if (rc) return rc;
-    hipError_t ue = hipMemsetAsync(d_tmp + (nbytes & ~15ull), 0xFF, padded - (nbytes & ~15ull), ctx->stream);
-    if (ue == hipSuccess && nbytes) ue = hipMemcpyAsync(d_tmp, seqs, nbytes, hipMemcpyHostToDevice, ctx->stream);
-    if (ue != hipSuccess) {  // a failed upload must not become a silently wrong matrix
-        (void)hipStreamSynchronize(ctx->stream);
-        dvs_dev_free(ctx, d_tmp);
-        return dvs_hip_fail(ctx, ue, "sequence upload");
-    }
-    sv.seqs = d_tmp;
-    sv.nbytes = padded;
-    rc = matrix_build_view(ctx, sv, offsets, nseq, k, num_states, false, out);
-    (void)hipStreamSynchronize(ctx->stream);
-    dvs_dev_free(ctx, d_tmp);
-    return rc;
-}
-
-int dvs_matrix_build_packed(dvs_ctx *ctx, const dvs_packed *p, const uint64_t *offsets, uint32_t nseq, uint32_t k,
-                            dvs_matrix **out) {
-    if (!ctx || !p || !offsets || !out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    *out = nullptr;
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    dvs_seq_view sv;
-    sv.codes = p->d_codes;
-    sv.mask = p->d_mask;
-    sv.nbytes = p->nbases;
-    p->async_readers = true;  // (dvs_packed_destroy waits for the kernels enqueued here)
-    return matrix_build_view(ctx, sv, offsets, nseq, k, 4, !ctx->knobs.build_wait, out);
+    dvs_seqs_held held(ctx);
+    rc = dvs_seqs_bring(ctx, src, k, num_states, &held);
+    if (rc) return rc;
+    // (the histogram reads bytes in HBM sixteen at a time)
+    if (held.resident && (reinterpret_cast<uintptr_t>(held.view.seqs) & 15))
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "device sequence buffer must be 16-byte aligned");
+    return matrix_build_view(ctx, held.view, held.offsets, held.nseq, k, num_states, held.resident && !ctx->knobs.build_wait, out);
 }
 
 int dvs_matrix_from_freqs(dvs_ctx *ctx, const double *freqs, uint32_t nrows, uint64_t nbins,
@@ -482,13 +430,10 @@ int dvs_matrix_from_freqs(dvs_ctx *ctx, const double *freqs, uint32_t nrows, uin
                                  "cannot calculate entropy as frequency vector total %.17g!=1.0", tot);
     }
     DVS_HIP(ctx, hipSetDevice(ctx->device));
-    dvs_matrix *m = new dvs_matrix();
-    m->kind = 1;
-    m->nrows = nrows;
-    m->nbins = nbins;
-    m->device = ctx->device;
-    int rc = matrix_alloc(ctx, m);
-    if (!rc && nrows) {
+    dvs_matrix *m = nullptr;
+    int rc = dvs_matrix_new(ctx, 1, nrows, nbins, 0, 0, &m);
+    if (rc) return rc;
+    if (nrows) {
         std::vector<uint32_t> ones(nrows, 1u);
         hipError_t e = hipMemcpyAsync(m->d_freqs, freqs, size_t(nrows) * nbins * 8,
                                       hipMemcpyHostToDevice, ctx->stream);
@@ -500,13 +445,7 @@ int dvs_matrix_from_freqs(dvs_ctx *ctx, const double *freqs, uint32_t nrows, uin
         if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess)
             rc = dvs_set_error(ctx, DVS_ERR_RUNTIME, "stream sync failed");
     }
-    if (rc) {
-        dvs_matrix_free_fields(m);
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return DVS_OK;
+    return matrix_made(rc, m, out);
 }
 
 // Frequency rows already in HBM (e.g. the all-gathered winners of a chunked run).  meta may be
@@ -520,31 +459,22 @@ int dvs_matrix_from_device_freqs(dvs_ctx *ctx, const double *d_freqs, const doub
     if (nbins == 0)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "cannot calculate entropy as frequency vector empty");
     DVS_HIP(ctx, hipSetDevice(ctx->device));
-    dvs_matrix *m = new dvs_matrix();
-    m->kind = 1;
-    m->nrows = nrows;
-    m->nbins = nbins;
-    m->device = ctx->device;
-    int rc = matrix_alloc(ctx, m);
-    if (!rc && nrows && d_meta) {
+    dvs_matrix *m = nullptr;
+    int rc = dvs_matrix_new(ctx, 1, nrows, nbins, 0, 0, &m);
+    if (rc) return rc;
+    if (nrows && d_meta) {
         // flagged rows: real ones first (in input order), padding behind them, in one copy pass
         rc = dvs_dev_alloc(ctx, (void **)&m->d_src_row, size_t(nrows) * 4, "source rows");
         if (!rc) rc = dvs_matrix_fill_compacted(ctx, m, d_freqs, d_meta);
         if (!rc) rc = dvs_matrix_fill_freq_entropy(ctx, m);
-    } else if (!rc && nrows) {
+    } else if (nrows) {
         hipError_t e = hipMemcpyAsync(m->d_freqs, d_freqs, size_t(nrows) * nbins * 8, hipMemcpyDeviceToDevice,
                                       ctx->stream);
         if (e != hipSuccess) rc = dvs_hip_fail(ctx, e, "hipMemcpyAsync(freqs)");
         if (!rc) rc = dvs_matrix_fill_freq_totals(ctx, m, nullptr);
         if (!rc) rc = dvs_matrix_fill_freq_entropy(ctx, m);
     }
-    if (rc) {
-        dvs_matrix_free_fields(m);
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return DVS_OK;
+    return matrix_made(rc, m, out);
 }
 
 int dvs_matrix_get_source_rows(dvs_ctx *ctx, const dvs_matrix *m, uint32_t *out) {
@@ -615,8 +545,9 @@ int dvs_matrix_get_entropy(dvs_ctx *ctx, const dvs_matrix *m, double *out) {
 int dvs_kmer_counts(dvs_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint32_t nseq,
                     uint32_t k, uint32_t num_states, uint32_t *counts_out, uint32_t *totals_out,
                     double *entropy_out) {
+    const dvs_seqs src = {DVS_SEQ_HOST, seqs, offsets, nseq};
     dvs_matrix *m = nullptr;
-    int rc = dvs_matrix_build(ctx, seqs, 0, offsets, nseq, k, num_states, &m);
+    int rc = dvs_matrix_build(ctx, &src, k, num_states, &m);
     if (rc) return rc;
     if (counts_out) rc = dvs_matrix_get_counts(ctx, m, 0, nseq, counts_out);
     if (!rc && totals_out) rc = dvs_matrix_get_totals(ctx, m, totals_out);
@@ -626,6 +557,3 @@ int dvs_kmer_counts(dvs_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, 
 }
 
 }  // extern "C"
-
-// matrix_alloc for the other files that make a count matrix (canon.hip's folded one)
-int dvs_matrix_alloc_fields(dvs_ctx *ctx, dvs_matrix *m) { return matrix_alloc(ctx, m); }

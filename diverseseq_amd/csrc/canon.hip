@@ -8,9 +8,6 @@
 
 #include <algorithm>
 
-int dvs_matrix_alloc_fields(dvs_ctx *ctx, dvs_matrix *m);  // api.cpp
-void dvs_matrix_free_fields(dvs_matrix *m);                // kmer_hist.hip
-
 namespace {
 
 constexpr int CLOG_TBL = 256;            // c log2 c is looked up below this count, as in kmer_hist.hip
@@ -210,17 +207,12 @@ int dvs_matrix_fold_canonical(dvs_ctx *ctx, const dvs_matrix *m, dvs_matrix **ou
     const uint64_t C = dvs_canon_count(m->k);
     if (!C) return dvs_set_error(ctx, DVS_ERR_VALUE, "canonical bins are defined for k in 1..%u, not %u", DVS_CANON_MAX_K, m->k);
     DVS_HIP(ctx, hipSetDevice(ctx->device));
-    dvs_matrix *f = new dvs_matrix();
-    f->kind = m->kind;  // 16-bit rows stay 16-bit: a folded count is at most the row's total
-    f->nrows = m->nrows;
-    f->nbins = C;
-    f->k = m->k;
-    f->num_states = m->num_states;
+    dvs_matrix *f = nullptr;  // (16-bit rows stay 16-bit: a folded count is at most the row's total)
+    int rc = dvs_matrix_new(ctx, m->kind, m->nrows, C, m->k, m->num_states, &f);
+    if (rc) return rc;
     f->canonical = true;
-    f->device = ctx->device;
-    int rc = dvs_matrix_alloc_fields(ctx, f);
     const uint32_t *d_reps = nullptr;
-    if (!rc && m->nrows) rc = canon_reps_device(ctx, m->k, C, &d_reps);
+    if (m->nrows) rc = canon_reps_device(ctx, m->k, C, &d_reps);
     // enqueued on the context's stream, which holds the source's build (or the wait for the rest of a split one)
     if (!rc && m->nrows)
         rc = m->kind == 2 ? canon_launch<uint16_t>(ctx, m->d_counts16, f->d_counts16, d_reps, m, f)
@@ -233,17 +225,13 @@ int dvs_matrix_fold_canonical(dvs_ctx *ctx, const dvs_matrix *m, dvs_matrix **ou
         (void)hipGetLastError();
         f->h_head_totals.clear();
     }
-    if (f->ctx && m->nrows) {
+    if (m->nrows) {
         const hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess && !rc) rc = dvs_hip_fail(ctx, e, "canonical fold");
     }
-    if (rc) {
-        dvs_matrix_free_fields(f);
-        delete f;
-        return rc;
-    }
-    *out = f;
-    return DVS_OK;
+    if (rc) dvs_matrix_destroy(f);
+    else *out = f;
+    return rc;
 }
 
 }  // extern "C"

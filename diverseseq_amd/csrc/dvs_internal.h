@@ -218,6 +218,17 @@ struct dvs_matrix {
     int device = 0;
     dvs_ctx *ctx = nullptr;  // owner of the allocations
 };
+// api.cpp: a new matrix of that kind and shape (k, num_states: 0 for frequency rows) with its device blocks allocated
+// and nothing written; nothing is left behind on failure.  A constructor that fails later hands it to dvs_matrix_destroy.
+int dvs_matrix_new(dvs_ctx *ctx, int kind, uint32_t nrows, uint64_t nbins, uint32_t k, uint32_t num_states, dvs_matrix **out);
+// kmer_hist.hip: what the constructors of api.cpp enqueue, and the release of a matrix's blocks
+uint64_t dvs_pow_u64(uint32_t base, uint32_t exp, bool *overflow);
+void dvs_matrix_free_fields(dvs_matrix *m);
+int dvs_hist_prepare(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint32_t k, uint64_t nbins, uint64_t nbytes, size_t *n_long_out);
+bool dvs_hist_rows_fit_u16(const dvs_ctx *ctx, uint64_t B, size_t n_long);
+int dvs_matrix_fill_freq_entropy(dvs_ctx *ctx, dvs_matrix *m);
+int dvs_matrix_fill_freq_totals(dvs_ctx *ctx, dvs_matrix *m, const double *d_meta);
+int dvs_matrix_fill_compacted(dvs_ctx *ctx, dvs_matrix *m, const double *d_in, const double *d_meta);
 
 // Four-state sequences in HBM at 3 bits per base (pack.hip, pack_host.cpp): positions index the
 // concatenated buffer exactly as in the one-byte form, so a batch's offsets are the same in both.
@@ -230,10 +241,25 @@ struct dvs_packed {
     uint32_t *d_codes = nullptr;
     uint16_t *d_mask = nullptr;
     uint64_t nbases = 0, nwords = 0;
-    // kernels that read the planes were enqueued without being waited for (dvs_matrix_build_packed,
-    // dvs_sketches_build_packed -- on the context's stream or, for a split build, its stream_rest): the planes
-    // go back to the block cache, which orders reuse on the context's stream only, so dvs_packed_destroy drains
-    // those streams first
+    // kernels that read the planes were enqueued without being waited for (a build over the planes, dvs_seqs_bring
+    // -- on the context's stream or, for a split build, its stream_rest): the planes go back to the block cache,
+    // which orders reuse on the context's stream only, so dvs_packed_destroy drains those streams first
+    mutable bool async_readers = false;
+};
+// An ingested file (ingest.hip): the encoded bases of its sequences in HBM, in byte form or packed in place.
+struct dvs_seqbatch {
+    dvs_ctx *ctx = nullptr;
+    uint8_t *d_codes = nullptr;  // total + 16 bytes (the histogram kernel reads 16-byte chunks)
+    uint64_t total = 0;
+    uint32_t nseq = 0;
+    std::vector<uint64_t> offsets;     // nseq + 1
+    std::vector<uint64_t> header_pos;  // file offset of the '>' of every record of the file
+    dvs_packed *packed = nullptr;      // after dvs_seqbatch_pack: the bases at 3 bits each (d_codes released)
+    // the alphabet the batch was encoded with puts the four bases first (the library's own DNA / RNA table): only
+    // then is "symbol >= 4" the same as "not a base" and the batch may be re-stated in the packed form
+    bool four_state_alphabet = false;
+    // builds over d_codes that were not waited for (dvs_seqs_bring: the context's stream or, for a split build,
+    // its stream_rest): dvs_seqbatch_destroy drains those streams before the block goes back
     mutable bool async_readers = false;
 };
 // what the kernels take: either the byte form (seqs) or the packed planes
@@ -247,6 +273,36 @@ int dvs_packed_alloc(dvs_ctx *ctx, uint64_t nbases, dvs_packed **out);          
 int dvs_packed_fill_from_device(dvs_ctx *ctx, dvs_packed *p, const uint8_t *d_seqs);         // bytes in HBM -> planes
 int dvs_packed_fill_from_host(dvs_ctx *ctx, dvs_packed *p, const uint8_t *seqs);             // host threads pack, chunks cross PCIe packed
 bool dvs_packed_upload_wanted(const dvs_ctx *ctx, uint32_t num_states, uint64_t nbytes);
+extern "C" void dvs_pack_bases(const uint8_t *src, size_t n, uint32_t *codes, uint16_t *mask);  // pack_host.cpp
+unsigned dvs_host_threads();  // pack.hip: host cores this process may use (cgroup quota respected), at most 16
+
+// ---- a build's sequences (include/dvs_hip.h dvs_seqs) on the device, as the histogram and the sketcher take them
+// pack.hip.  What both build entries check before anything else, host work only: DVS_ERR_VALUE for a NULL context,
+// source, offsets or handle (bytes: unless the batch has no bases), an unknown kind, and num_states != 4 over packed
+// planes.
+int dvs_seqs_check(dvs_ctx *ctx, const dvs_seqs *src, uint32_t num_states);
+inline uint32_t dvs_seqs_count(const dvs_seqs *src) {  // of a checked source
+    return src->kind == DVS_SEQ_BATCH ? static_cast<const dvs_seqbatch *>(src->handle)->nseq : src->nseq;
+}
+// The view of a checked source, with whatever was made for the call: host bytes are uploaded -- packed (k <= 32 and
+// dvs_packed_upload_wanted) or as they are, in a buffer padded to a multiple of 16 bytes plus 16 whose tail is 0xFF --
+// and everything else is used where it lies.  When the object goes it waits for the context's stream and hands the
+// upload's blocks back to the cache: a consumer only enqueues.
+struct dvs_seqs_held {
+    dvs_seq_view view;
+    const uint64_t *offsets = nullptr;  // host, nseq + 1
+    uint32_t nseq = 0;
+    bool resident = false;  // the sequences were in HBM already: nothing here makes a build wait for its kernels
+    PooledBuf bytes;                // HOST: the upload buffer ...
+    dvs_packed *planes = nullptr;   // ... or the planes of the packed upload
+    explicit dvs_seqs_held(dvs_ctx *ctx) : bytes{ctx} {}
+    dvs_seqs_held(const dvs_seqs_held &) = delete;
+    ~dvs_seqs_held();
+};
+// pack.hip, the only maker of that view.  A PACKED or BATCH source is marked as read by kernels nobody waits for
+// (async_readers), so it is called only when something will be enqueued.
+int dvs_seqs_bring(dvs_ctx *ctx, const dvs_seqs *src, uint32_t k, uint32_t num_states, dvs_seqs_held *held);
+int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, const uint64_t *offsets, bool no_wait);  // kmer_hist.hip
 
 // linkage.hip's prepare pass on its own, enqueued on the context's stream: every entry of the n x n matrix checked and
 // the upper triangle copied over the lower one; the bits below are OR-ed into the device word *d_status (`sign`: a

@@ -21,8 +21,6 @@
 
 #include <cstddef>
 
-unsigned dvs_host_threads();  // pack.hip: host cores this process may use (cgroup quota respected), at most 16
-
 namespace {
 
 // A frequency row: written once when it is fetched, read-only afterwards -- copies (the reference's clone,

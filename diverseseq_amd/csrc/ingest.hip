@@ -269,22 +269,6 @@ __global__ __launch_bounds__(ING_THREADS) void ing_emit_kernel(const uint8_t *__
 
 }  // namespace
 
-struct dvs_seqbatch {
-    dvs_ctx *ctx = nullptr;
-    uint8_t *d_codes = nullptr;  // total + 16 bytes (the histogram kernel reads 16-byte chunks)
-    uint64_t total = 0;
-    uint32_t nseq = 0;
-    std::vector<uint64_t> offsets;     // nseq + 1
-    std::vector<uint64_t> header_pos;  // file offset of the '>' of every record of the file
-    dvs_packed *packed = nullptr;      // after dvs_seqbatch_pack: the bases at 3 bits each (d_codes released)
-    // the alphabet the batch was encoded with puts the four bases first (the library's own DNA / RNA table): only
-    // then is "symbol >= 4" the same as "not a base" and the batch may be re-stated in the packed form
-    bool four_state_alphabet = false;
-    // builds over d_codes that were not waited for (dvs_matrix_build_from_seqbatch: the context's stream or, for
-    // a split build, its stream_rest): dvs_seqbatch_destroy drains those streams before the block goes back
-    mutable bool async_readers = false;
-};
-
 extern "C" void dvs_seqbatch_destroy(dvs_seqbatch *b) {
     if (!b) return;
     if (b->packed) dvs_packed_destroy(b->packed);
@@ -547,25 +531,3 @@ extern "C" int dvs_seqbatch_pack(dvs_ctx *ctx, dvs_seqbatch *b) {
     return DVS_OK;
 }
 extern "C" const dvs_packed *dvs_seqbatch_packed(const dvs_seqbatch *b) { return b ? b->packed : nullptr; }
-extern "C" int dvs_matrix_build_from_seqbatch(dvs_ctx *ctx, const dvs_seqbatch *b, uint32_t k, uint32_t num_states,
-                                              dvs_matrix **out) {
-    if (!ctx || !b || !out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    if (b->packed) {
-        if (num_states != 4)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "a packed batch holds four-state sequences, not %u states", num_states);
-        return dvs_matrix_build_packed(ctx, b->packed, b->offsets.data(), b->nseq, k, out);
-    }
-    b->async_readers = true;  // (dvs_seqbatch_destroy waits for the kernels enqueued here)
-    return dvs_matrix_build(ctx, b->d_codes, 1, b->offsets.data(), b->nseq, k, num_states, out);
-}
-extern "C" int dvs_sketches_build_from_seqbatch(dvs_ctx *ctx, const dvs_seqbatch *b, uint32_t k, uint32_t sketch_size,
-                                                uint32_t num_states, int mash_canonical, dvs_sketches **out) {
-    if (!ctx || !b || !out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    if (b->packed) {
-        if (num_states != 4)
-            return dvs_set_error(ctx, DVS_ERR_VALUE, "a packed batch holds four-state sequences, not %u states", num_states);
-        return dvs_sketches_build_packed(ctx, b->packed, b->offsets.data(), b->nseq, k, sketch_size, mash_canonical, out);
-    }
-    b->async_readers = true;
-    return dvs_sketches_build(ctx, b->d_codes, 1, b->offsets.data(), b->nseq, k, sketch_size, num_states, mash_canonical, out);
-}

@@ -888,77 +888,6 @@ static int mash_sketch_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_t
     return DVS_OK;
 }
 
-// the byte form, from either side of PCIe.  Host memory: four-state sequences of k <= 32 cross packed
-// (pack.hip: 3/8 of the bytes) and are sketched from the packed words; anything else is copied as it is.
-static int mash_sketch_core(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device, const uint64_t *offsets,
-                            uint32_t nseq, uint32_t k, uint32_t sketch_size, uint32_t num_states,
-                            int mash_canonical, uint32_t **d_sk_out, uint32_t **d_lens_out) {
-    const uint64_t nbytes = offsets[nseq];
-    dvs_seq_view sv;
-    sv.nbytes = nbytes;
-    if (seqs_on_device) {
-        sv.seqs = seqs;
-        return mash_sketch_view(ctx, sv, offsets, nseq, k, sketch_size, num_states, mash_canonical, d_sk_out, d_lens_out);
-    }
-    DVS_HIP(ctx, hipSetDevice(ctx->device));
-    if (k <= 32 && dvs_packed_upload_wanted(ctx, num_states, nbytes)) {
-        dvs_packed *p = nullptr;
-        int rc = dvs_packed_alloc(ctx, nbytes, &p);
-        if (!rc) rc = dvs_packed_fill_from_host(ctx, p, seqs);
-        if (!rc) {
-            sv.codes = p->d_codes;
-            sv.mask = p->d_mask;
-            rc = mash_sketch_view(ctx, sv, offsets, nseq, k, sketch_size, num_states, mash_canonical, d_sk_out, d_lens_out);
-        }
-        if (p) {
-            (void)hipStreamSynchronize(ctx->stream);
-            dvs_packed_destroy(p);
-        }
-        return rc;
-    }
-    PooledBuf d_own{ctx};
-    int rc = dvs_dev_alloc(ctx, &d_own.p, nbytes ? nbytes : 16, "sequence upload buffer");
-    if (rc) return rc;
-    if (nbytes) DVS_HIP(ctx, hipMemcpyAsync(d_own.p, seqs, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    sv.seqs = d_own.as<uint8_t>();
-    rc = mash_sketch_view(ctx, sv, offsets, nseq, k, sketch_size, num_states, mash_canonical, d_sk_out, d_lens_out);
-    (void)hipStreamSynchronize(ctx->stream);  // (the upload buffer goes back to the cache)
-    return rc;
-}
-
-static int mash_check_args(dvs_ctx *ctx, const uint64_t *offsets, uint32_t k) {
-    if (!ctx || !offsets) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    if (k == 0 || k > MAX_K)
-        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "mash k = %u outside 1..%d", k, MAX_K);
-    return DVS_OK;
-}
-
-extern "C" int dvs_mash_sketch(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device,
-                               const uint64_t *offsets, uint32_t nseq, uint32_t k,
-                               uint32_t sketch_size, uint32_t num_states, int mash_canonical,
-                               uint32_t *sketches_out, uint32_t *lens_out) {
-    if (!sketches_out || !lens_out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    int rc = mash_check_args(ctx, offsets, k);
-    if (rc) return rc;
-    if (sketch_size == 0) {
-        for (uint32_t i = 0; i < nseq; i++) lens_out[i] = 0;
-        return DVS_OK;
-    }
-    if (nseq == 0) return DVS_OK;
-    uint32_t *d_sk = nullptr, *d_lens = nullptr;
-    rc = mash_sketch_core(ctx, seqs, seqs_on_device, offsets, nseq, k, sketch_size, num_states, mash_canonical,
-                          &d_sk, &d_lens);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(sketches_out, d_sk, size_t(nseq) * sketch_size * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(lens_out, d_lens, size_t(nseq) * 4, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t se = hipStreamSynchronize(ctx->stream);
-    dvs_dev_free(ctx, d_sk);
-    dvs_dev_free(ctx, d_lens);
-    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "sketch copy");
-    if (se != hipSuccess) return dvs_hip_fail(ctx, se, "sketch copy");
-    return DVS_OK;
-}
-
 // ---- sketches that stay in HBM between the two stages of ctree (sketch, then N x N distances)
 struct dvs_sketches {
     dvs_ctx *ctx = nullptr;
@@ -967,57 +896,44 @@ struct dvs_sketches {
     bool borrowed = false;  // dvs_sketches_from_device: the caller's buffers, not handed back to the cache
 };
 
-extern "C" int dvs_sketches_build(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device, const uint64_t *offsets,
-                                  uint32_t nseq, uint32_t k, uint32_t sketch_size, uint32_t num_states,
+extern "C" int dvs_sketches_build(dvs_ctx *ctx, const dvs_seqs *src, uint32_t k, uint32_t sketch_size, uint32_t num_states,
                                   int mash_canonical, dvs_sketches **out) {
     if (!out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     *out = nullptr;
-    int rc = mash_check_args(ctx, offsets, k);
+    int rc = dvs_seqs_check(ctx, src, num_states);
     if (rc) return rc;
+    if (k == 0 || k > MAX_K)
+        return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "mash k = %u outside 1..%d", k, MAX_K);
     dvs_sketches *sk = new dvs_sketches();
     sk->ctx = ctx;
-    sk->nseq = nseq;
+    sk->nseq = dvs_seqs_count(src);
     sk->stride = sketch_size;
     dvs_ctx_retain(ctx);
-    if (nseq && sketch_size) {
-        rc = mash_sketch_core(ctx, seqs, seqs_on_device, offsets, nseq, k, sketch_size, num_states, mash_canonical,
-                              &sk->d_sk, &sk->d_lens);
-        if (rc) {
-            dvs_ctx_release(ctx);
-            delete sk;
-            return rc;
-        }
+    if (sk->nseq && sketch_size) {
+        // (the sketcher waits for its own rounds: the held upload has nothing left to drain on the usual return)
+        dvs_seqs_held held(ctx);
+        rc = dvs_seqs_bring(ctx, src, k, num_states, &held);
+        if (!rc)
+            rc = mash_sketch_view(ctx, held.view, held.offsets, held.nseq, k, sketch_size, num_states, mash_canonical,
+                                  &sk->d_sk, &sk->d_lens);
     }
-    *out = sk;
-    return DVS_OK;
+    if (rc) dvs_sketches_destroy(sk);
+    else *out = sk;
+    return rc;
 }
 
-extern "C" int dvs_sketches_build_packed(dvs_ctx *ctx, const dvs_packed *p, const uint64_t *offsets, uint32_t nseq,
-                                         uint32_t k, uint32_t sketch_size, int mash_canonical, dvs_sketches **out) {
-    if (!out || !p) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
-    *out = nullptr;
-    int rc = mash_check_args(ctx, offsets, k);
-    if (rc) return rc;
-    dvs_sketches *sk = new dvs_sketches();
-    sk->ctx = ctx;
-    sk->nseq = nseq;
-    sk->stride = sketch_size;
-    dvs_ctx_retain(ctx);
-    if (nseq && sketch_size) {
-        dvs_seq_view sv;
-        sv.codes = p->d_codes;
-        sv.mask = p->d_mask;
-        sv.nbytes = p->nbases;
-        p->async_readers = true;  // (dvs_packed_destroy waits for the kernels enqueued here)
-        rc = mash_sketch_view(ctx, sv, offsets, nseq, k, sketch_size, 4, mash_canonical, &sk->d_sk, &sk->d_lens);
-        if (rc) {
-            dvs_ctx_release(ctx);
-            delete sk;
-            return rc;
-        }
-    }
-    *out = sk;
-    return DVS_OK;
+// the host one-shot: the build above, and its sketches copied out
+extern "C" int dvs_mash_sketch(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device,
+                               const uint64_t *offsets, uint32_t nseq, uint32_t k,
+                               uint32_t sketch_size, uint32_t num_states, int mash_canonical,
+                               uint32_t *sketches_out, uint32_t *lens_out) {
+    if (!sketches_out || !lens_out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    const dvs_seqs src = {uint32_t(seqs_on_device ? DVS_SEQ_DEVICE : DVS_SEQ_HOST), seqs, offsets, nseq};
+    dvs_sketches *sk = nullptr;
+    int rc = dvs_sketches_build(ctx, &src, k, sketch_size, num_states, mash_canonical, &sk);
+    if (!rc) rc = dvs_sketches_get(ctx, sk, sketches_out, lens_out);
+    dvs_sketches_destroy(sk);
+    return rc;
 }
 
 extern "C" void dvs_sketches_destroy(dvs_sketches *sk) {

@@ -21,8 +21,6 @@
 #include <thread>
 #include <vector>
 
-extern "C" void dvs_pack_bases(const uint8_t *src, size_t n, uint32_t *codes, uint16_t *mask);  // pack_host.cpp
-
 namespace {
 
 constexpr size_t PACK_CHUNK = size_t(1) << 20;  // bases per host-packed chunk (a multiple of 64)
@@ -197,6 +195,77 @@ int dvs_packed_fill_from_host(dvs_ctx *ctx, dvs_packed *p, const uint8_t *seqs) 
         return dvs_hip_fail(ctx, e, "packed sequence upload");
     }
     return DVS_OK;
+}
+
+// ---- a build's sequences (dvs_seqs), checked and brought to the device (dvs_internal.h)
+int dvs_seqs_check(dvs_ctx *ctx, const dvs_seqs *src, uint32_t num_states) {
+    if (!ctx || !src) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (src->kind > DVS_SEQ_BATCH) return dvs_set_error(ctx, DVS_ERR_VALUE, "unknown sequence source kind %u", src->kind);
+    const bool bytes = src->kind == DVS_SEQ_HOST || src->kind == DVS_SEQ_DEVICE;
+    if (src->kind != DVS_SEQ_BATCH && !src->offsets) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    if (!src->handle && !(bytes && !(src->nseq && src->offsets[src->nseq] > 0)))
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
+    const bool packed = src->kind == DVS_SEQ_PACKED ||
+                        (src->kind == DVS_SEQ_BATCH && static_cast<const dvs_seqbatch *>(src->handle)->packed);
+    if (packed && num_states != 4)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "a packed batch holds four-state sequences, not %u states", num_states);
+    return DVS_OK;
+}
+
+int dvs_seqs_bring(dvs_ctx *ctx, const dvs_seqs *src, uint32_t k, uint32_t num_states, dvs_seqs_held *held) {
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    const dvs_seqbatch *b = src->kind == DVS_SEQ_BATCH ? static_cast<const dvs_seqbatch *>(src->handle) : nullptr;
+    held->offsets = b ? b->offsets.data() : src->offsets;
+    held->nseq = b ? b->nseq : src->nseq;
+    held->resident = src->kind != DVS_SEQ_HOST;
+    const uint64_t nbytes = held->nseq ? held->offsets[held->nseq] : 0;
+    dvs_seq_view &sv = held->view;
+    sv.nbytes = nbytes;
+    if (src->kind == DVS_SEQ_DEVICE) {
+        sv.seqs = static_cast<const uint8_t *>(src->handle);
+        return DVS_OK;
+    }
+    if (src->kind != DVS_SEQ_HOST) {
+        const dvs_packed *p = b ? b->packed : static_cast<const dvs_packed *>(src->handle);
+        bool &async_readers = p ? p->async_readers : b->async_readers;  // (of whichever holds the bases)
+        async_readers = true;  // (its destroy waits for the kernels enqueued over this view)
+        if (p) {
+            sv.codes = p->d_codes;
+            sv.mask = p->d_mask;
+            sv.nbytes = p->nbases;
+        } else {
+            sv.seqs = b->d_codes;
+        }
+        return DVS_OK;
+    }
+    // Host memory.  Four-state sequences cross PCIe packed -- 3 bits per base, packed by host threads beside the
+    // copies -- and the kernels read the packed words as they are; anything else is copied as it is, with 16 .. 31
+    // invalid bytes behind it (the histogram's 16-byte reads end there).
+    const uint8_t *seqs = static_cast<const uint8_t *>(src->handle);
+    if (k <= 32 && dvs_packed_upload_wanted(ctx, num_states, nbytes)) {
+        int rc = dvs_packed_alloc(ctx, nbytes, &held->planes);
+        if (!rc) rc = dvs_packed_fill_from_host(ctx, held->planes, seqs);
+        if (rc) return rc;
+        sv.codes = held->planes->d_codes;
+        sv.mask = held->planes->d_mask;
+        return DVS_OK;
+    }
+    const uint64_t whole = nbytes & ~15ull, padded = ((nbytes + 15) & ~15ull) + 16;
+    const int rc = dvs_dev_alloc(ctx, &held->bytes.p, padded, "sequence upload buffer");
+    if (rc) return rc;
+    uint8_t *d_up = held->bytes.as<uint8_t>();
+    hipError_t e = hipMemsetAsync(d_up + whole, 0xFF, padded - whole, ctx->stream);
+    if (e == hipSuccess && nbytes) e = hipMemcpyAsync(d_up, seqs, nbytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "sequence upload");  // (never a silently wrong build)
+    sv.seqs = d_up;
+    sv.nbytes = padded;
+    return DVS_OK;
+}
+
+dvs_seqs_held::~dvs_seqs_held() {
+    if (!bytes.p && !planes) return;
+    (void)hipStreamSynchronize(bytes.ctx->stream);  // (the blocks go back to the cache: nothing may still read them)
+    if (planes) dvs_packed_destroy(planes);
 }
 
 // ---- C ABI (include/dvs_hip.h)

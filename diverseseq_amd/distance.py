@@ -181,31 +181,21 @@ class Sketches:
         (engine.Packed); or batch: an ingested engine.SeqBatch (packed or not)"""
         self.ctx = ctx or (batch.ctx if batch is not None else packed.ctx if packed is not None else engine.default_context())
         if batch is not None:
-            offsets = batch.offsets
-        elif packed is not None or dev_ptr is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            offsets, seqs = batch.offsets, _lib.make_seqs(_lib.SEQ_BATCH, batch._h)
+        elif packed is not None:
+            seqs = _lib.make_seqs(_lib.SEQ_PACKED, packed._h, offsets)
+        elif dev_ptr is not None:  # sequences already in HBM
+            seqs = _lib.make_seqs(_lib.SEQ_DEVICE, dev_ptr, offsets)
         else:
             data, offsets = engine.concat(seqs)
+            seqs = _lib.make_seqs(_lib.SEQ_HOST, data.ctypes.data, offsets, keep=data)
+        offsets = np.asarray(offsets)
         self.n = offsets.size - 1
         self.stride = _sketch_stride(offsets, k, sketch_size) if sketch_size else 0
         self.k, self.sketch_size = k, int(sketch_size)
         h = C.c_void_p()
-        L, flag = self.ctx._L, int(bool(mash_canonical))
-        if batch is not None:
-            self.ctx.check(L.dvs_sketches_build_from_seqbatch(self.ctx._h, batch._h, k, self.stride, num_states, flag,
-                                                             C.byref(h)))
-        elif packed is not None:
-            if num_states != 4:
-                raise ValueError("packed sequences have four states")
-            self.ctx.check(L.dvs_sketches_build_packed(self.ctx._h, packed._h, _lib.ptr(offsets, C.c_uint64), self.n, k,
-                                                      self.stride, flag, C.byref(h)))
-        else:
-            if dev_ptr is None:
-                src, on_dev = data.ctypes.data_as(C.c_void_p), 0
-            else:  # sequences already in HBM
-                src, on_dev = C.c_void_p(dev_ptr), 1
-            self.ctx.check(L.dvs_sketches_build(self.ctx._h, src, on_dev, _lib.ptr(offsets, C.c_uint64), self.n, k,
-                                               self.stride, num_states, flag, C.byref(h)))
+        self.ctx.check(self.ctx._L.dvs_sketches_build(self.ctx._h, seqs, k, self.stride, num_states,
+                                                      int(bool(mash_canonical)), C.byref(h)))
         self._h = h
         self._source = batch if batch is not None else packed  # (its planes must outlive the sketch kernels)
 

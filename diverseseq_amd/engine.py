@@ -151,26 +151,22 @@ class Context:
         data, offsets = concat(seqs)
         return self.build_matrix_concat(data, offsets, k, num_states, canonical=canonical)
 
+    def _build(self, seqs: "_lib.Seqs", k: int, num_states: int) -> "CountMatrix":
+        """dvs_matrix_build over one sequence source (_lib.make_seqs)"""
+        h = C.c_void_p()
+        self.check(self._L.dvs_matrix_build(self._h, seqs, k, num_states, C.byref(h)))
+        return CountMatrix(self, h, k, num_states)
+
     def build_matrix_concat(self, data: np.ndarray, offsets: np.ndarray, k: int,
                             num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
-        h = C.c_void_p()
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        self.check(self._L.dvs_matrix_build(self._h, data.ctypes.data_as(C.c_void_p), 0,
-                                            _lib.ptr(offsets, C.c_uint64), offsets.size - 1, k,
-                                            num_states, C.byref(h)))
-        return _folded(CountMatrix(self, h, k, num_states), canonical)
+        return _folded(self._build(_lib.make_seqs(_lib.SEQ_HOST, data.ctypes.data, offsets, keep=data), k, num_states), canonical)
 
     def build_matrix_device(self, dev_ptr: int, offsets: np.ndarray, k: int,
                             num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
         """sequences already resident in HBM (e.g. a torch uint8 tensor's data_ptr()).  The call
         does not wait for its kernels: keep the buffer alive and unmodified until the matrix is
         first used from the host side (a selection, counts(), ctx.sync(); a canonical build waits itself)"""
-        h = C.c_void_p()
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        self.check(self._L.dvs_matrix_build(self._h, C.c_void_p(dev_ptr), 1,
-                                            _lib.ptr(offsets, C.c_uint64), offsets.size - 1, k,
-                                            num_states, C.byref(h)))
-        return _folded(CountMatrix(self, h, k, num_states), canonical)
+        return _folded(self._build(_lib.make_seqs(_lib.SEQ_DEVICE, dev_ptr, offsets), k, num_states), canonical)
 
     # ---- packed sequences (3 bits per base in HBM: csrc/pack.hip) ------------------
     def pack_device(self, dev_ptr: int, nbases: int) -> "Packed":
@@ -191,11 +187,7 @@ class Context:
     def build_matrix_packed(self, packed: "Packed", offsets: np.ndarray, k: int, *,
                             canonical: bool = False) -> "CountMatrix":
         """k-mer count matrix of a packed batch (the histogram kernel reads the packed words as they are)"""
-        h = C.c_void_p()
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        self.check(self._L.dvs_matrix_build_packed(self._h, packed._h, _lib.ptr(offsets, C.c_uint64), offsets.size - 1,
-                                                   k, C.byref(h)))
-        m = CountMatrix(self, h, k, 4)
+        m = self._build(_lib.make_seqs(_lib.SEQ_PACKED, packed._h, offsets), k, 4)
         m._source = packed  # (the build is not waited for: the planes must outlive its kernels)
         return _folded(m, canonical)
 
@@ -360,9 +352,7 @@ class SeqBatch:
 
     def build_matrix(self, k: int, num_states: int = 4, *, canonical: bool = False) -> "CountMatrix":
         """k-mer count matrix straight from the encoded bases in HBM (no host round trip)"""
-        h = C.c_void_p()
-        self.ctx.check(self.ctx._L.dvs_matrix_build_from_seqbatch(self.ctx._h, self._h, k, num_states, C.byref(h)))
-        m = CountMatrix(self.ctx, h, k, num_states)
+        m = self.ctx._build(_lib.make_seqs(_lib.SEQ_BATCH, self._h), k, num_states)
         m._source = self  # (the build is not waited for: the batch must outlive its kernels)
         return _folded(m, canonical)
 

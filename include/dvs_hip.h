@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DVS_ABI_VERSION 4
+#define DVS_ABI_VERSION 5
 
 #define DVS_OK 0
 #define DVS_ERR_VALUE 1       /* the reference would panic -> python ValueError */
@@ -67,16 +67,34 @@ int dvs_ctx_device_info(dvs_ctx *ctx, char *name, size_t name_len, int *n_cu,
  *
  * Builds, on the device, row r = the k-mer histogram of sequence r (uint32),
  * plus per-row total (number of valid k-mers) and Shannon entropy (bits) of
- * the row's frequency vector.  `seqs` is a HOST pointer when seqs_on_device
- * is 0 (it is copied to HBM), else a 16-byte-aligned DEVICE pointer; `offsets` is always a
- * host array.  With a device pointer the call does NOT wait for its kernels: they are ordered on
- * the ctx stream in front of everything that uses the matrix, and the first call that needs
- * host-side data of it (a selection's seeds, dvs_matrix_get_*, dvs_ctx_sync) waits for them -- so
- * the device buffer must stay valid, and unmodified, until then (DVS_BUILD_WAIT=1 in the
- * environment restores a build that returns only when its kernels have finished). */
-int dvs_matrix_build(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device,
-                     const uint64_t *offsets, uint32_t nseq, uint32_t k,
-                     uint32_t num_states, dvs_matrix **out);
+ * the row's frequency vector.
+ *
+ * Where the sequences of a build come from: the counterpart, on the build side, of dvs_source below.  A plain value
+ * the caller fills per call; the library keeps no pointer to it once the call has returned.  `offsets` is always a
+ * HOST array of nseq + 1 entries (DVS_SEQ_BATCH: the batch's own, both fields ignored).  Who waits, and how long a
+ * buffer must live: a build from DVS_SEQ_HOST copies the bytes to HBM (four-state sequences of 32 MiB and more cross
+ * PCIe packed, 3/8 of the bytes) and returns when its kernels have finished, the caller's buffer free again.  A
+ * matrix build from a source that is in HBM already -- DEVICE, PACKED, BATCH -- does NOT wait for its kernels: they
+ * are ordered on the ctx stream in front of everything that uses the matrix, and the first call that needs host-side
+ * data of it (a selection's seeds, dvs_matrix_get_*, dvs_ctx_sync) waits for them -- so a DEVICE buffer must stay
+ * valid, and unmodified, until then, and a dvs_packed or dvs_seqbatch must outlive them (their destroy functions
+ * drain the streams such a build was enqueued on).  DVS_BUILD_WAIT=1 in the environment restores a build that
+ * returns only when its kernels have finished.  A DEVICE pointer must be 16-byte aligned for dvs_matrix_build;
+ * dvs_sketches_build takes any.  PACKED, and a BATCH after dvs_seqbatch_pack, hold four-state sequences:
+ * DVS_ERR_VALUE for another num_states; they are sketched with k <= 32.  Every build checks its source before
+ * anything else: DVS_ERR_VALUE for a NULL source, handle (unless the batch has no bases) or offsets, or an unknown
+ * kind. */
+#define DVS_SEQ_HOST 0   /* handle: const uint8_t *, host, one byte per base */
+#define DVS_SEQ_DEVICE 1 /* handle: const uint8_t *, device */
+#define DVS_SEQ_PACKED 2 /* handle: const dvs_packed * */
+#define DVS_SEQ_BATCH 3  /* handle: const dvs_seqbatch * (offsets, nseq: its own) */
+typedef struct dvs_seqs {
+    uint32_t kind;
+    const void *handle;
+    const uint64_t *offsets;
+    uint32_t nseq;
+} dvs_seqs;
+int dvs_matrix_build(dvs_ctx *ctx, const dvs_seqs *seqs, uint32_t k, uint32_t num_states, dvs_matrix **out);
 /* rows are frequency vectors (the members of SummedRecordsResult objects being
  * merged: get_kmerseqs_and_init_summed_records, src/records.rs:344-360).
  * DVS_ERR_VALUE if a row fails the reference's sum-to-one check
@@ -166,10 +184,6 @@ int dvs_packed_info(const dvs_packed *p, uint64_t *nbases, uint64_t *nwords); /*
 const void *dvs_packed_dev_codes(const dvs_packed *p); /* uint32 [nwords] in HBM */
 const void *dvs_packed_dev_mask(const dvs_packed *p);  /* uint16 [nwords] in HBM */
 int dvs_packed_get(dvs_ctx *ctx, const dvs_packed *p, uint32_t *codes_out, uint16_t *mask_out);
-/* dvs_matrix_build / dvs_sketches_build over a packed batch (num_states is 4 by construction).
- * Neither waits for its kernels; p must outlive them (until the next call that syncs). */
-int dvs_matrix_build_packed(dvs_ctx *ctx, const dvs_packed *p, const uint64_t *offsets, uint32_t nseq,
-                            uint32_t k, dvs_matrix **out);
 
 /* ---- ingest -------------------------------------- *
  * FASTA file bytes -> the data convention above, on the device: replaces, for the hot path's
@@ -179,7 +193,7 @@ int dvs_matrix_build_packed(dvs_ctx *ctx, const dvs_packed *p, const uint64_t *o
  * raw_on_device != 0); lut256 maps a file byte to its alphabet index (NULL: the cogent3 "dna"
  * table, dvs_default_alphabet_lut).  join_records != 0: one sequence per file, a gap symbol
  * between adjacent records (io.py:100); 0: one sequence per record.  The encoded bases stay in HBM
- * and feed dvs_matrix_build_from_seqbatch directly. */
+ * and feed dvs_matrix_build (a DVS_SEQ_BATCH source) directly. */
 typedef struct dvs_seqbatch dvs_seqbatch;
 void dvs_default_alphabet_lut(int rna, uint8_t lut[256]);
 int dvs_seqbatch_from_fasta(dvs_ctx *ctx, const uint8_t *raw, int raw_on_device, uint64_t nbytes,
@@ -191,11 +205,9 @@ int dvs_seqbatch_offsets(const dvs_seqbatch *b, uint64_t *offsets_out);        /
 int dvs_seqbatch_header_positions(const dvs_seqbatch *b, uint64_t *pos_out);   /* nrecords: offset of each '>' */
 const void *dvs_seqbatch_dev_codes(const dvs_seqbatch *b);                     /* uint8 [total] in HBM */
 int dvs_seqbatch_get_codes(dvs_ctx *ctx, const dvs_seqbatch *b, uint8_t *codes_out);
-int dvs_matrix_build_from_seqbatch(dvs_ctx *ctx, const dvs_seqbatch *b, uint32_t k, uint32_t num_states,
-                                   dvs_matrix **out);
 /* The batch's encoded bases re-stated in the packed form above and the byte form released: a genome
- * collection then sits in HBM at 3/8 of the bytes, and dvs_matrix_build_from_seqbatch /
- * dvs_sketches_build_from_seqbatch (num_states 4) read the packed words.  dvs_seqbatch_dev_codes returns
+ * collection then sits in HBM at 3/8 of the bytes, and dvs_matrix_build / dvs_sketches_build over the batch
+ * (num_states 4) read the packed words.  dvs_seqbatch_dev_codes returns
  * NULL afterwards, dvs_seqbatch_get_codes unpacks (invalid symbols come back as 255), and
  * dvs_seqbatch_packed hands out the planes (NULL before).  DVS_ERR_VALUE for a batch that was encoded
  * with a caller's alphabet table instead of the library's DNA / RNA one (its symbols >= 4 are states, not
@@ -364,16 +376,11 @@ int dvs_mash_distances(dvs_ctx *ctx, const uint32_t *sketches, uint32_t sketch_s
 /* The two stages of ctree (diverse_seq/cluster.py:241-297: sketches, then the N x N distances) with
  * the sketches left in HBM between them: dvs_sketches_build = dvs_mash_sketch without the copy to
  * the host, dvs_sketches_distances = dvs_mash_distances on that handle, dvs_sketches_get copies
- * sketches (may be NULL) and lengths out (what _dvs.mash_sketch returns). */
+ * sketches (may be NULL) and lengths out (what _dvs.mash_sketch returns).  dvs_sketches_build takes its sequences
+ * as dvs_matrix_build does (dvs_seqs, above) and returns with its sketches written, whatever the source. */
 typedef struct dvs_sketches dvs_sketches;
-int dvs_sketches_build(dvs_ctx *ctx, const uint8_t *seqs, int seqs_on_device, const uint64_t *offsets,
-                       uint32_t nseq, uint32_t k, uint32_t sketch_size, uint32_t num_states,
+int dvs_sketches_build(dvs_ctx *ctx, const dvs_seqs *seqs, uint32_t k, uint32_t sketch_size, uint32_t num_states,
                        int mash_canonical, dvs_sketches **out);
-/* the same from a packed batch (k <= 32) and from an ingested batch (packed or not) */
-int dvs_sketches_build_packed(dvs_ctx *ctx, const dvs_packed *p, const uint64_t *offsets, uint32_t nseq,
-                              uint32_t k, uint32_t sketch_size, int mash_canonical, dvs_sketches **out);
-int dvs_sketches_build_from_seqbatch(dvs_ctx *ctx, const dvs_seqbatch *b, uint32_t k, uint32_t sketch_size,
-                                     uint32_t num_states, int mash_canonical, dvs_sketches **out);
 void dvs_sketches_destroy(dvs_sketches *sk);
 int dvs_sketches_get(dvs_ctx *ctx, const dvs_sketches *sk, uint32_t *sketches_out, uint32_t *lens_out);
 const void *dvs_sketches_dev(const dvs_sketches *sk);      /* uint32 [nseq x sketch_size] in HBM */

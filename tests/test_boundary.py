@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(str(_lib.LIB_PATH))
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in dvs_hip.h but not exported"
-    assert _lib.load().dvs_abi_version() == 4
+    assert _lib.load().dvs_abi_version() == 5
 
 
 # the operations over "the distances of a collection": one C entry each, which takes a dvs_source
@@ -56,6 +56,37 @@ def test_one_entry_per_distance_operation():
     assert not re.search(r"\bdvs_\w*average_linkage\b", text)
     for name in ("dvs_average_linkage", "dvs_sketches_average_linkage", "dvs_matrix_euclidean_average_linkage"):
         assert not hasattr(lib, name), name
+
+
+def test_one_entry_per_build():
+    """the two consumers of a batch of sequences -- the k-mer histogram and the mash sketcher -- are declared exactly
+    once each, with a dvs_seqs behind the context, and no per-form spelling of either is left: neither declared, nor
+    listed in EXPORTS, nor exported by the library"""
+    header = (ROOT / "include" / "dvs_hip.h").read_text()
+    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for entry in ("dvs_matrix_build", "dvs_sketches_build"):
+        found = re.findall(rf"\bint\s+{entry}\s*\(([^)]*)\)\s*;", text)
+        assert len(found) == 1, (entry, found)
+        assert re.match(r"\s*dvs_ctx\s*\*\s*ctx\s*,\s*const\s+dvs_seqs\s*\*", found[0]), (entry, found[0])
+        assert entry in _lib.EXPORTS
+    per_form = r"dvs_(?:matrix|sketches)_build_\w+"
+    assert not re.findall(rf"\b{per_form}", text)
+    assert not [name for name in _lib.EXPORTS if re.fullmatch(per_form, name)]
+    # (every exported name lies in the library's dynamic string table; a C++ name carries a length in front of it)
+    assert not re.findall(rf"(?<![A-Za-z0-9_]){per_form}".encode(), _lib.LIB_PATH.read_bytes())
+    lib = ctypes.CDLL(str(_lib.LIB_PATH))
+    for name in ("dvs_matrix_build_packed", "dvs_matrix_build_from_seqbatch", "dvs_sketches_build_packed",
+                 "dvs_sketches_build_from_seqbatch"):
+        assert not hasattr(lib, name), name
+    assert (_lib.SEQ_HOST, _lib.SEQ_DEVICE, _lib.SEQ_PACKED, _lib.SEQ_BATCH) == (0, 1, 2, 3)
+    for value, name in enumerate(("HOST", "DEVICE", "PACKED", "BATCH")):
+        assert re.search(rf"#define\s+DVS_SEQ_{name}\s+{value}\b", header), name
+    # uint32 kind, 4 bytes of padding, two 8-byte pointers, uint32 nseq, 4 bytes of padding
+    assert ctypes.sizeof(_lib.Seqs) == 32
+    assert [(n, _lib.Seqs.__dict__[n].offset) for n, _ in _lib.Seqs._fields_] == [("kind", 0), ("handle", 8), ("offsets", 16),
+                                                                                ("nseq", 24)]
+    assert re.search(r"#define\s+DVS_ABI_VERSION\s+5\b", header)
+    assert _lib.load().dvs_abi_version() == 5
 
 
 def test_product_never_imports_oracle():

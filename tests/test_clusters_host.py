@@ -42,7 +42,7 @@ def test_public_names_exist():
     lib = _lib.load()
     for name in new:
         assert getattr(lib, name).argtypes is not None, name
-    assert lib.dvs_abi_version() == 4
+    assert lib.dvs_abi_version() == 5
 
 
 # ------------------------------------------------------------------ cut_tree against scipy

@@ -236,29 +236,45 @@ def test_ingested_batch_packed_in_place(ctx):
 
 
 def test_packed_batch_dropped_right_after_the_build(ctx):
-    """A build over packed planes is not waited for; the planes go back to the context's block cache when the
-    `Packed` goes.  Both guards: the C side (dvs_packed_destroy drains the streams its readers were enqueued on --
-    exercised by destroying the handle behind the Python object's back) and the Python side (the matrix keeps the
-    `Packed` it was built from), with an allocation of the same size filled right behind the destroy."""
+    """A build over packed planes, or over an ingested batch's bytes, is not waited for; the blocks go back to the
+    context's block cache when the `Packed` or the `SeqBatch` goes.  Both guards: the C side (dvs_packed_destroy and
+    dvs_seqbatch_destroy drain the streams their readers were enqueued on, which the one line of the library that marks
+    a source as read, in dvs_seqs_bring, tells them -- exercised by destroying the handle behind the Python object's
+    back) and the Python side (the matrix keeps the source it was built from), with an allocation of the same size
+    filled right behind the destroy."""
     from gpu_synth import synth_device
 
     seqs_t, offsets = synth_device(30_000, 1900, 2100, seed=5)
     host = seqs_t.cpu().numpy()
+    total = int(offsets[-1])
     exp = np.stack([oracle.count_kmers(host[int(offsets[i]): int(offsets[i + 1])], 4, 6) for i in (0, 1023, 1024, 17_000, 29_999)])
-    for via_c in (True, False):
-        p = ctx.pack_device(seqs_t.data_ptr(), int(offsets[-1]))
-        m = ctx.build_matrix_packed(p, offsets, 6)
+
+    def fasta(codes):  # one record per sequence: a file of the same size whatever the bases
+        letters = np.frombuffer(b"TCAG", dtype=np.uint8)[codes]
+        return b"".join(b">r\n" + letters[int(a): int(b)].tobytes() + b"\n" for a, b in zip(offsets[:-1], offsets[1:]))
+
+    raw, raw_other = fasta(host[:total]), fasta((host[:total] + 1) % 4)
+    for form, via_c in (("packed", True), ("packed", False), ("bytes", True)):
+        if form == "packed":
+            p = ctx.pack_device(seqs_t.data_ptr(), total)
+            m = ctx.build_matrix_packed(p, offsets, 6)
+            destroy = ctx._L.dvs_packed_destroy
+        else:  # an ingested batch in byte form
+            p = ctx.encode_fasta(raw)
+            assert (p.offsets == offsets).all() and p.packed is None
+            m = p.build_matrix(6)
+            destroy = ctx._L.dvs_seqbatch_destroy
         if via_c:  # the caller of the C ABI that destroys the batch right after the build call
-            ctx._L.dvs_packed_destroy(p._h)
+            destroy(p._h)
             p._h = None
             m._source = None
         del p
-        # the blocks the planes lived in are handed out again at once, for other content
+        # the blocks the planes or the bytes lived in are handed out again at once, for other content
         other = (seqs_t + 1) % 4
-        q = ctx.pack_device(other.data_ptr(), int(offsets[-1]))
+        q = ctx.pack_device(other.data_ptr(), total) if form == "packed" else ctx.encode_fasta(raw_other)
         got = m.counts()
         for j, i in enumerate((0, 1023, 1024, 17_000, 29_999)):
-            assert (got[i] == exp[j]).all(), (via_c, i)
+            assert (got[i] == exp[j]).all(), (form, via_c, i)
         assert (m.totals() == got.sum(axis=1)).all()
         q.close()
         m.close()

@@ -159,11 +159,11 @@ def test_the_names_exist():
     assert C.sizeof(_lib.KmedoidsParams) == 16 and C.sizeof(_lib.KmedoidsInfo) == 32
 
 
-def test_the_abi_version_stays_4():
+def test_the_abi_version_is_5():
     import pathlib
     import re
     header = (pathlib.Path(__file__).resolve().parent.parent / "include" / "dvs_hip.h").read_text()
-    assert re.search(r"#define\s+DVS_ABI_VERSION\s+4\b", header)
+    assert re.search(r"#define\s+DVS_ABI_VERSION\s+5\b", header)
     assert "int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src" in header
     assert re.search(r"#define\s+DVS_KMEDOIDS_INIT_BUILD\s+0", header) and re.search(r"#define\s+DVS_KMEDOIDS_INIT_GIVEN\s+1", header)
 

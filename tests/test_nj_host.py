@@ -435,7 +435,7 @@ def test_argument_errors_need_no_device():
 
 def test_c_boundary_without_a_device():
     L = _lib.load()
-    assert L.dvs_abi_version() == 4
+    assert L.dvs_abi_version() == 5
     names = ("dvs_nj", "dvs_nj_patristic")  # one entry for the tree: the mode, or the caller's matrix, travels in the dvs_source
     lib = C.CDLL(str(_lib.LIB_PATH))
     for name in names:

@@ -103,7 +103,7 @@ def test_public_names_and_exports():
     lib = _lib.load()
     for name in NEW_EXPORTS:
         assert getattr(lib, name).argtypes is not None, name
-    assert lib.dvs_abi_version() == 4
+    assert lib.dvs_abi_version() == 5
     assert _lib.WITHIN_SKIP_SELF == 1
     # no table of entries per mode any more: every operation, dense or sparse, is a method of DeviceSide over ONE entry,
     # which every mode reaches through the kind of its dvs_source
