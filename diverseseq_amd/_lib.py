@@ -47,6 +47,7 @@ EXPORTS = (
     # one entry per operation over the distances of a `Source`
     "dvs_distances", "dvs_linkage", "dvs_nj", "dvs_maxmin", "dvs_cross_distances", "dvs_nearest", "dvs_within",
     "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters", "dvs_pcoa", "dvs_pcoa_project", "dvs_kmedoids",
+    "dvs_mst", "dvs_linkage_from_mst",
 )
 WITHIN_SKIP_SELF = 1
 SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
@@ -282,6 +283,8 @@ def load() -> C.CDLL:
         # params, medoids, labels, dist, second, swaps, td, info
         L.dvs_kmedoids.argtypes = [vp, srcp, C.POINTER(KmedoidsParams), u32p, u32p, f64p, f64p, u32p, f64p,
                                    C.POINTER(KmedoidsInfo)]
+        L.dvs_mst.argtypes = [vp, srcp, f64p, u32p, f64p, u32p, u32p]  # core, edges, weights, n_edges, n_rounds
+        L.dvs_linkage_from_mst.argtypes = [vp, u32, u32p, f64p, u32p, f64p, u32p]  # edges, weights, pairs, heights, sizes
         if L.dvs_abi_version() != 5:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

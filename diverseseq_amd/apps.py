@@ -44,7 +44,7 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa", "dvs_kmedoids"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa", "dvs_kmedoids", "dvs_mst"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -570,3 +570,37 @@ class dvs_maxmin(_DistanceApp):
         return {"picks": picked, "radius": [float(v) for v in r.radius],
                 "representative": {name: picked[o] if o >= 0 else None for name, o in zip(names, r.owner.tolist())},
                 "distance": {name: float(d) for name, d in zip(names, r.dist)}, "cover": r.cover}
+
+
+@_define_app
+class dvs_mst(_DistanceApp):
+    """The minimum spanning tree of the sequences by any distance of `dvs_dist` (beyond the reference, which has no
+    such app): single linkage for collections whose N x N matrix could never exist -- the distances are recomputed strip
+    by strip, once per Boruvka round.  `main(seqs)` returns the edges, [(name, name, distance)] in ascending (distance,
+    position of the first name, position of the second) -- a minimum spanning network to draw --, or with tree=True the
+    Newick string of the single-linkage tree, the merge heights of `dvs_ctree(linkage="single")`.  min_samples: the
+    tree of the mutual-reachability distance max(d(a, b), core(a), core(b)) instead, core(a) the min_samples-th smallest
+    distance from a, its own included: robust single linkage, the first half of HDBSCAN.  A sequence without a valid
+    k-mer (jsd, euclidean) is joined by no edge; tree=True then raises ValueError."""
+
+    def __init__(self, distance_mode: str = "mash", *, tree: bool = False, min_samples: int | None = None, k: int = 12,
+                 sketch_size: int | None = 3_000, moltype: str = "dna", mash_canonical_kmers: bool | None = None,
+                 canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
+        if not isinstance(tree, (bool, np.bool_)):
+            raise ValueError(f"tree must be True or False, not {tree!r}")
+        if min_samples is not None and (isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer))
+                                        or not 1 <= min_samples <= _distance.MIN_SAMPLES_MAX):
+            raise ValueError(f"min_samples must be an integer between 1 and {_distance.MIN_SAMPLES_MAX}, not {min_samples!r}")
+        self._tree, self._min_samples = bool(tree), min_samples
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
+
+    def main(self, seqs):
+        names, arrays = _as_arrays(seqs, self._moltype)
+        if self._tree:
+            return _cluster.mst_ctree(dict(zip(names, arrays)), min_samples=self._min_samples, **self._mode_kwargs())
+        tree = _distance.mst(arrays, self._distance_mode, k=self._k, sketch_size=self._sketch_size,
+                             num_states=self._num_states, mash_canonical=self._mash_canonical, canonical=self._canonical,
+                             min_samples=self._min_samples)
+        return _cluster.mst_to_edges(names, tree)

@@ -23,7 +23,10 @@ collection's distances, principal coordinates (`pcoa` over a caller's matrix, `o
 it, for collections whose N x N matrix could never exist); and the representatives that lie closest, in total, to
 everything else, k-medoids (`kmedoids` over a caller's matrix, `representatives` over sequences, csrc/kmedoids.hip;
 `sampled_kmedoids`: k-medoids of farthest-first landmarks with every sequence assigned to its nearest medoid, for
-collections whose N x N matrix could never exist).
+collections whose N x N matrix could never exist); and the tree itself for such collections, the minimum spanning tree
+(`minimum_spanning_tree` over a caller's matrix, `mst_ctree` over sequences, csrc/mst.hip: Boruvka rounds over strips of
+distances; `mst_linkage`, `mst_to_edges`): single linkage, and with a core vector robust single linkage, in O(N) device
+memory beside one strip.
 """
 
 from __future__ import annotations
@@ -477,6 +480,111 @@ def threshold_clusters(dist, radius, *, ctx: engine.Context | None = None) -> "d
     if n:
         wait()
     return distance._run_threshold_clusters(ctx, n, src, radius)
+
+
+def _check_symmetric(dist, n: int) -> None:
+    """ValueError unless a caller's matrix equals its transpose, NaN cells in the same places: on the host for an array,
+    with torch for a device tensor (one n x n boolean beside it)"""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor):
+        same = bool(((dist == dist.T) | (torch.isnan(dist) & torch.isnan(dist.T))).all())
+    else:
+        d = np.asarray(dist, dtype=np.float64)
+        same = bool(((d == d.T) | (np.isnan(d) & np.isnan(d.T))).all())
+    if not same:
+        raise ValueError(f"the {n} x {n} distance matrix is not symmetric (check_symmetric=False skips this check)")
+
+
+def _kth_smallest(dist, m: int) -> np.ndarray:
+    """the m-th smallest cell of every row of a caller's matrix, the row's own cell included, NaN cells last: float64
+    [n] on the host (np.partition, or torch.kthvalue for a device tensor)"""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dist, torch.Tensor):
+        filled = torch.where(torch.isnan(dist), torch.full_like(dist, float("inf")), dist)
+        return torch.kthvalue(filled, m, dim=1).values.cpu().numpy()
+    d = np.asarray(dist, dtype=np.float64)
+    return np.partition(np.where(np.isnan(d), np.inf, d), m - 1, axis=1)[:, m - 1]
+
+
+def minimum_spanning_tree(dist, *, core=None, min_samples: int | None = None, check_symmetric: bool = True,
+                          ctx: engine.Context | None = None) -> "distance.MST":
+    """the minimum spanning tree (`distance.MST`: the edges in ascending (weight, lower row, higher row), unique under
+    that order) of a caller's symmetric n x n distance matrix, a strip of rows at a time: a host matrix larger than the
+    device's memory is served, where `linkage(dist, "single")` -- the faster route to the same heights when the matrix
+    fits -- is not.  A NaN entry is no edge (a spanning forest comes back where they disconnect the rows); the diagonal
+    is never taken.  core: one distance per row, the weights become max(dist[i, j], core[i], core[j]) (the
+    mutual-reachability distance of HDBSCAN); or min_samples = m: core[i] the m-th smallest entry of row i, the diagonal
+    included (sklearn's convention) -- ValueError for a row with fewer than m entries that are not NaN.
+    check_symmetric=False skips the symmetry check; for an asymmetric matrix some spanning tree is returned and nothing
+    more is promised.
+
+    `dist`: as `cluster_scores` takes it, only READ.  The arguments are checked before the tree's device work."""
+    if min_samples is not None and core is not None:
+        raise ValueError("minimum_spanning_tree takes at most one of min_samples and core")
+    src, n, wait = _caller_matrix(dist)
+    if min_samples is not None:
+        m = distance.check_min_samples(min_samples, n)
+    core = distance.check_core(core, n)
+    if n:
+        wait()
+    if check_symmetric and n:
+        _check_symmetric(dist, n)
+    if min_samples is not None:
+        core = _kth_smallest(dist, m)
+        if np.isinf(core).any():
+            raise ValueError(f"row {int(np.argmax(np.isinf(core)))} has fewer than min_samples = {m} distances that are not NaN")
+        core = distance.check_core(core, n)
+    return distance.run_mst(ctx or (engine.default_context() if n else None), n, src, core)
+
+
+def mst_linkage(mst) -> np.ndarray:
+    """a `distance.MST` -> scipy's linkage matrix Z of the single-linkage tree (host only, dvs_linkage_from_mst): the
+    heights are the sorted weights, bit for bit those of `linkage(dist, "single")`; where no two weights are equal Z is
+    scipy's, among equal weights the merges follow the edges' order (the same partitions at every cut).  ValueError for
+    a forest (`mst.connected` is False) and for fewer than two rows"""
+    n = int(mst.n)
+    if n < 2:
+        raise ValueError("need at least two sequences to build a tree")
+    edges = np.ascontiguousarray(np.asarray(mst.edges, dtype=np.int64).reshape(-1, 2))
+    weights = np.ascontiguousarray(np.asarray(mst.weights, dtype=np.float64))
+    if edges.shape[0] != weights.size:
+        raise ValueError(f"{edges.shape[0]} edges with {weights.size} weights")
+    if weights.size != n - 1:
+        raise ValueError(f"a spanning forest of {n - weights.size} trees ({weights.size} edges over {n} rows) has no linkage tree")
+    if edges.size and (edges.min() < 0 or edges.max() >= n):
+        raise ValueError(f"an edge names a row outside 0 .. {n - 1}")
+    pairs, heights, sizes = distance.tree_outputs(n)
+    e32 = np.ascontiguousarray(edges.astype(np.uint32).ravel())
+    _lib.raise_for(_lib.load().dvs_linkage_from_mst(None, n, _lib.ptr(e32, C.c_uint32), _lib.ptr(weights, C.c_double),
+                                                    _lib.ptr(pairs, C.c_uint32), _lib.ptr(heights, C.c_double),
+                                                    _lib.ptr(sizes, C.c_uint32)), None)
+    return distance.linkage_matrix(pairs, heights, sizes)
+
+
+def mst_to_edges(names: Sequence, mst) -> list:
+    """a `distance.MST` over the rows `names` -> [(name, name, weight)], in the tree's order"""
+    if len(names) != mst.n:
+        raise ValueError(f"{len(names)} names for a spanning tree over {mst.n} rows")
+    return [(names[int(a)], names[int(b)], float(w)) for (a, b), w in zip(mst.edges.tolist(), mst.weights.tolist())]
+
+
+def mst_ctree(seqs: dict, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
+              mash_canonical_kmers: bool | None = None, num_states: int = 4, canonical: bool = False,
+              min_samples: int | None = None) -> str:
+    """sequences {name: uint8 codes} -> the Newick string of `ctree(..., linkage="single")` without the N x N matrix: the
+    minimum spanning tree strip by strip (`distance.mst`), `mst_linkage`, `linkage_to_newick`.  The merge heights are
+    ctree's bit for bit; among merges of equal height the nesting may differ.  min_samples: the tree of the
+    mutual-reachability distance instead (robust single linkage).  Argument checks as `ctree`, before any device work;
+    ValueError where NaN distances (a sequence without a valid k-mer) leave a forest."""
+    if mash_canonical_kmers is None:
+        mash_canonical_kmers = False
+    distance.check_mode_args(distance_mode, sketch_size, mash_canonical_kmers, canonical)
+    names = list(seqs)
+    if len(names) < 2:
+        raise ValueError("need at least two sequences to build a tree")
+    tree = distance.mst([seqs[n] for n in names], distance_mode, k=k, sketch_size=sketch_size, num_states=num_states,
+                        mash_canonical=mash_canonical_kmers, canonical=canonical, min_samples=min_samples)
+    return linkage_to_newick(names, mst_linkage(tree))
 
 
 def dereplicate(seqs: dict, radius, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",

@@ -15,7 +15,7 @@
 // matrix (here), the kk nearest references per query (nearest.hip), the coordinates in a fitted ordination (pcoa.hip),
 // or (queries = references) the scores of a labelling of the rows (clusters.hip), the correlation of the distances
 // with a tree's cophenetic distances (cophenet.hip), the list of the cells within a radius and the connected
-// components they make (within.hip).  Every C entry of these operations is at the end of this file, as rowdist.hip
+// components they make (within.hip), the minimum spanning tree (mst.hip: one pass of the strips per Boruvka round).  Every C entry of these operations is at the end of this file, as rowdist.hip
 // keeps the square ones.  The strip is CROSS_STRIP_BYTES at most (and a tile row of 32 queries at least).
 #include "dvs_internal.h"
 #include "rowdist_dev.h"
@@ -450,4 +450,10 @@ extern "C" int dvs_threshold_clusters(dvs_ctx *ctx, const dvs_source *src, doubl
                                       uint32_t *n_clusters) {
     if (int rc = dvs_source_check(ctx, src, src)) return rc;
     return dvs_threshold_clusters_strips(ctx, source_cross_stage(ctx, src, src), radius, labels, n_clusters);
+}
+
+extern "C" int dvs_mst(dvs_ctx *ctx, const dvs_source *src, const double *core, uint32_t *edges, double *weights,
+                       uint32_t *n_edges, uint32_t *n_rounds) {
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    return dvs_mst_strips(ctx, source_cross_stage(ctx, src, src), core, edges, weights, n_edges, n_rounds);
 }

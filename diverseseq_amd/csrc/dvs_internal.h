@@ -470,6 +470,8 @@ int dvs_within_strips(dvs_ctx *ctx, const dvs_cross_stage &st, double radius, ui
                       dvs_pairs **out);  // within.hip
 int dvs_threshold_clusters_strips(dvs_ctx *ctx, const dvs_cross_stage &st, double radius, uint32_t *labels,
                                   uint32_t *n_clusters);  // within.hip
+int dvs_mst_strips(dvs_ctx *ctx, const dvs_cross_stage &st, const double *core, uint32_t *edges, double *weights,
+                   uint32_t *n_edges, uint32_t *n_rounds);  // mst.hip
 
 // ---- an operation's source (include/dvs_hip.h dvs_source): the tag in front of the stages above
 uint32_t dvs_sketches_nseq(const dvs_sketches *sk);  // mash.hip, whose struct it is

@@ -25,7 +25,9 @@ cross_distances, csrc/pcoa.hip behind the strip driver of csrc/crossdist.hip); n
 the representatives that lie closest, in total, to everything else, k-medoids (kmedoids, matrix_kmedoids,
 mash_kmedoids / euclidean_kmedoids / jsd_kmedoids ->
 `KMedoids`: csrc/kmedoids.hip, PAM's BUILD and FastPAM1's swaps over the N x N matrix in HBM); no counterpart in the
-reference.  `DeviceSide`
+reference; and the tree without the matrix, the minimum spanning tree (mst, matrix_mst, mash_mst / euclidean_mst /
+jsd_mst -> `MST`: csrc/mst.hip, a Boruvka round per pass over the strips of cross_distances; single linkage, and with a
+core vector the mutual-reachability tree of HDBSCAN); no counterpart in the reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
 matrix_* functions and the Sketches methods are a few lines over it.  Every operation has one C entry, which takes a
 `_lib.Source` (dvs_source: the mode and its handle, or a caller's matrix): `make_source` fills one per call."""
@@ -355,7 +357,88 @@ class MedoidOps:
         return run_kmedoids(self.ctx, self.n, self._source(), k, rows, max_swaps)
 
 
-class DeviceSide(OrdinationOps, MedoidOps):
+MIN_SAMPLES_MAX = 64  # N_NEAREST_MAX: the core distances come from `DeviceSide.nearest`
+
+
+class MST(NamedTuple):
+    """The minimum spanning tree of the distances of n rows (include/dvs_hip.h "minimum spanning tree"): edges int64
+    [n_edges, 2], edge e joining positions edges[e, 0] < edges[e, 1] at weights[e] (float64), in ascending (weight,
+    lower position, higher position) -- the order under which the tree is unique; n; n_rounds, the passes over the
+    distances that were made.  Where NaN distances disconnect the rows it is a spanning forest of n - n_edges trees:
+    `connected` tells.  The sorted weights are the heights of the single-linkage tree: `cluster.mst_linkage`."""
+    edges: np.ndarray
+    weights: np.ndarray
+    n: int
+    n_rounds: int
+
+    @property
+    def connected(self) -> bool:
+        return self.n > 0 and self.weights.size == self.n - 1
+
+
+def check_core(core, n: int) -> np.ndarray | None:
+    """a core vector as dvs_mst takes it (float64 [n], or None), checked before any device work: ValueError unless it
+    has one finite, non-negative entry per row"""
+    if core is None:
+        return None
+    c = np.ascontiguousarray(np.asarray(core, dtype=np.float64))
+    if c.shape != (n,):
+        raise ValueError(f"core must hold one distance per row ({n}), got shape {c.shape}")
+    bad = ~(np.isfinite(c) & (c >= 0))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"core distance {c[i]} of position {i}: finite and not negative")
+    return c
+
+
+def check_min_samples(min_samples, n: int) -> int:
+    """min_samples as `SpanningOps.mst` takes it: ValueError unless an integer in 1 .. min(MIN_SAMPLES_MAX, n)"""
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)):
+        raise ValueError(f"min_samples must be an integer, not {min_samples!r}")
+    if min_samples < 1 or min_samples > MIN_SAMPLES_MAX:
+        raise ValueError(f"min_samples = {min_samples}: between 1 and {MIN_SAMPLES_MAX}")
+    if min_samples > n:
+        raise ValueError(f"min_samples = {min_samples} of {n} rows: no row has that many cells")
+    return int(min_samples)
+
+
+def run_mst(ctx: engine.Context | None, n: int, src: _lib.Source | None, core: np.ndarray | None = None) -> MST:
+    """dvs_mst over the n rows of `src` (not looked at for n == 0) with the checked core vector -> MST"""
+    edges = np.zeros(2 * max(n - 1, 0), dtype=np.uint32)
+    weights = np.zeros(max(n - 1, 0), dtype=np.float64)
+    count, rounds = C.c_uint32(0), C.c_uint32(0)
+    if n:
+        ctx = ctx or engine.default_context()
+        ctx.check(ctx._L.dvs_mst(ctx._h, src, _lib.ptr(core, C.c_double), _lib.ptr(edges, C.c_uint32),
+                                 _lib.ptr(weights, C.c_double), C.byref(count), C.byref(rounds)))
+    m = int(count.value)
+    return MST(edges[:2 * m].astype(np.int64).reshape(m, 2), weights[:m].copy(), int(n), int(rounds.value))
+
+
+class SpanningOps:
+    """The minimum spanning tree as an operation of a `DeviceSide`, which inherits it: `DeviceSide.mst`.  In a base
+    class of its own for the reason `OrdinationOps` gives; its poisoned-block cases are in tests/test_gpu_mst.py."""
+
+    def mst(self, rows=None, *, min_samples: int | None = None, core=None) -> "MST":
+        """the minimum spanning tree (`MST`) of the distances of this side's `rows` (None: all), strip by strip: the
+        N x N matrix never exists.  core: one distance per row, the weights become max(d(i, j), core[i], core[j]) (mutual
+        reachability); or min_samples = m (1 .. MIN_SAMPLES_MAX): core[i] the m-th smallest cell of row i, its own cell
+        included (sklearn's HDBSCAN convention; `nearest` over the same rows) -- ValueError for a row with fewer
+        than m cells that are not NaN"""
+        if min_samples is not None and core is not None:
+            raise ValueError("mst takes at most one of min_samples and core")
+        listed = _row_list(rows, self.n)
+        if min_samples is not None:
+            m = check_min_samples(min_samples, listed[1])
+            idx, dist = self.nearest(self, m, rows, rows)
+            short = idx[:, m - 1] < 0
+            if short.any():
+                raise ValueError(f"row {int(np.argmax(short))} has fewer than min_samples = {m} distances that are not NaN")
+            core = dist[:, m - 1]
+        return run_mst(self.ctx, listed[1], self._source(listed), check_core(core, listed[1]))
+
+
+class DeviceSide(OrdinationOps, MedoidOps, SpanningOps):
     """What a distance mode keeps in HBM of one batch -- its `Sketches` (mash) or its count matrix (euclidean, jsd) --
     together with the mode: every operation over "the distances of a collection", whatever the mode.  `device_side`
     makes one that owns its handle; DeviceSide(handle, mode) wraps a handle of the caller's, which close() then leaves
@@ -1201,6 +1284,64 @@ def threshold_clusters(seqs, radius, distance_mode: str = "mash", *, k: int, ske
     with device_side(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical), ctx=ctx,
                      canonical=canonical) as dev:
         return dev.threshold_clusters(radius)
+
+
+# ---- the minimum spanning tree: single linkage without the matrix (`MST`, `SpanningOps`)
+
+def matrix_mst(m: "engine.CountMatrix", mode: str = "jsd", rows=None, *, min_samples: int | None = None, core=None) -> MST:
+    """the minimum spanning tree (`MST`) of the `mode` ("jsd", "euclidean") distances of rows `rows` of m (None: all),
+    a Boruvka round per pass over the strips: the n x n matrix never exists.  A row without a valid k-mer (NaN distances)
+    is a tree of its own.  min_samples, core: as `SpanningOps.mst` takes them (mutual reachability)."""
+    return _count_side(m, mode).mst(rows, min_samples=min_samples, core=core)
+
+
+def mash_mst(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *,
+             min_samples: int | None = None, core=None, ctx: engine.Context | None = None) -> MST:
+    """the minimum spanning tree of the sequences by their mash distances: sketches, then a pass over the strips per
+    round, everything in HBM.  ZeroDivisionError as `cluster_scores`."""
+    return _mst(seqs, "mash", k, sketch_size, num_states, mash_canonical, min_samples=min_samples, core=core, ctx=ctx)
+
+
+def euclidean_mst(seqs, k: int, num_states: int = 4, *, min_samples: int | None = None, core=None,
+                  ctx: engine.Context | None = None, canonical: bool = False) -> MST:
+    """the same by the euclidean distances of the k-mer frequencies"""
+    return _mst(seqs, "euclidean", k, num_states, min_samples=min_samples, core=core, ctx=ctx, canonical=canonical)
+
+
+def jsd_mst(seqs, k: int, num_states: int = 4, *, min_samples: int | None = None, core=None,
+            ctx: engine.Context | None = None, canonical: bool = False) -> MST:
+    """the same by the Jensen-Shannon divergences of `jsd_distances`"""
+    return _mst(seqs, "jsd", k, num_states, min_samples=min_samples, core=core, ctx=ctx, canonical=canonical)
+
+
+def _mst(seqs, distance_mode: str, *args, min_samples, core, ctx, canonical: bool = False) -> MST:
+    if min_samples is not None and core is not None:
+        raise ValueError("mst takes at most one of min_samples and core")
+    if min_samples is not None:
+        check_min_samples(min_samples, len(seqs))
+    check_core(core, len(seqs))
+    if not len(seqs):
+        return run_mst(ctx, 0, None)
+    with device_side(seqs, distance_mode, *args, ctx=ctx, canonical=canonical) as dev:
+        return dev.mst(min_samples=min_samples, core=core)
+
+
+# a distance mode -> its minimum spanning tree: takes (seqs, *mode_args(...)), and min_samples=, core=, ctx=
+MST_MODES = {"mash": mash_mst, "euclidean": euclidean_mst, "jsd": jsd_mst}
+
+
+def mst(seqs, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
+        mash_canonical: bool = False, canonical: bool = False, min_samples: int | None = None, core=None,
+        ctx: engine.Context | None = None) -> MST:
+    """the minimum spanning tree (`MST`) of the sequences by `distance_mode`: single linkage -- and, with min_samples or
+    core, robust single linkage over the mutual-reachability distance -- for collections whose N x N matrix could never
+    exist.  Every round recomputes all N x N cells strip by strip and there are at most ceil(log2 N) rounds; where the
+    matrix fits, `MODES[distance_mode]`'s linkage with method "single" is the faster route to the same heights.  Argument
+    checks as cluster.ctree, and those of `check_min_samples` and `check_core`, before any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    seqs = list(seqs)
+    return _mst(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                min_samples=min_samples, core=core, ctx=ctx, canonical=canonical)
 
 
 # ---- principal coordinates (PCoA, classical MDS) and the projection of further rows

@@ -590,6 +590,44 @@ int dvs_pairs_get(const dvs_pairs *p, uint64_t *row_start, uint32_t *col, double
  *   DVS_ERR_ZERODIV: (MASH) exactly as dvs_cluster_scores */
 int dvs_threshold_clusters(dvs_ctx *ctx, const dvs_source *src, double radius, uint32_t *labels, uint32_t *n_clusters);
 
+/* ---- minimum spanning tree: single linkage without the matrix -------------------------------------- *
+ * The minimum spanning tree of the n x n distances of a source (queries = references = its rows), computed strip by
+ * strip as above: the n x n matrix never exists, the device holds one strip and O(n) beside it.  Edges are ordered by
+ * (weight, lower position, higher position); under that order the tree is unique -- the one Kruskal's algorithm
+ * builds when it visits the upper triangle in that order -- and so are the outputs, on every run and for every strip
+ * height.  It is built by Boruvka rounds: in a round every position finds, on the device, its nearest position of
+ * another component (a tie to the lower position), every component takes the least of its positions' finds, and the
+ * picks are merged on the host; a round is one pass over all n x n cells, and there are ceil(log2 n) rounds at most.
+ * A NaN cell is no edge: where NaN cells disconnect the positions the result is a spanning FOREST.
+ * core (host, n, or NULL): with it the weight of cell (i, j) is max(D(i, j), core[i], core[j]), the mutual-reachability
+ * distance of HDBSCAN / robust single linkage, and the tree is the minimum spanning tree of those weights.
+ * edges[2 (n - 1)], weights[n - 1]: edge e joins positions edges[2 e] < edges[2 e + 1] at weights[e]; the edges come in
+ * ascending (weight, lower, higher).  *n_edges = n - the number of components: n - 1 for a tree; the slots behind are
+ * left as they were.  *n_rounds (may be NULL): the passes over the strips that were made.  The sorted weights are the
+ * heights of dvs_linkage's DVS_LINKAGE_SINGLE tree, bit for bit.
+ * A GIVEN matrix, host or device, is only read, rows [q0, q0 + mq) at a time, the diagonal included (position i is in
+ * its own component: the cell is never taken).  It must be symmetric, which is not checked: for an asymmetric matrix
+ * some spanning tree (forest) of the graph of its non-NaN cells is returned, and nothing more is promised.
+ * (No counterpart in the reference.)  Errors, all before any device work:
+ *   DVS_OK with nothing written: n == 0.  n == 1: no edge, no round
+ *   DVS_ERR_VALUE: a NULL output; a core entry that is NaN, infinite or negative (the message names the position); a
+ *                  row index beyond the handle, a device mismatch, a matrix that is not device memory where it is
+ *                  said to be
+ *   DVS_ERR_UNSUPPORTED: n beyond the row limit of the square entries
+ *   DVS_ERR_NOMEM: the host arrays of the merge do not fit
+ * and DVS_ERR_ZERODIV: (MASH) exactly as dvs_cluster_scores.
+ * dvs_linkage_from_mst turns the n - 1 edges of a spanning tree, in ascending weight, into the outputs of dvs_linkage
+ * for the single-linkage tree (pairs, heights, sizes: scipy's ids, merge j makes cluster n + j, the lower id first), on
+ * the host (no device work; ctx only takes the error text and may be NULL).  Where no two weights are equal that is
+ * scipy's linkage(..., "single") bit for bit; among equal weights the merges follow the order of the edges.
+ *   DVS_ERR_VALUE: a NULL argument, n < 2, a weight that is NaN or below the one before it, an edge that closes a
+ *                  cycle, an end that is no position -- a forest has fewer than n - 1 edges and no tree: a caller
+ *                  who passes one fills the slots behind *n_edges with 0xFFFFFFFF and gets this error */
+int dvs_mst(dvs_ctx *ctx, const dvs_source *src, const double *core, uint32_t *edges, double *weights, uint32_t *n_edges,
+            uint32_t *n_rounds);
+int dvs_linkage_from_mst(dvs_ctx *ctx, uint32_t n, const uint32_t *edges, const double *weights, uint32_t *pairs,
+                         double *heights, uint32_t *sizes);
+
 /* ---- cophenetic distances of a tree, and their correlation with the distances it was built from ---- *
  * scipy.cluster.hierarchy.cophenet.  The cophenetic distance coph(i, j) of two leaves is the height of the merge at
  * which they first share a cluster.  Over dvs_linkage's outputs (pairs[2 (n - 1)], heights[n - 1], scipy's ids: leaves
