@@ -47,7 +47,7 @@ EXPORTS = (
     # one entry per operation over the distances of a `Source`
     "dvs_distances", "dvs_linkage", "dvs_nj", "dvs_maxmin", "dvs_cross_distances", "dvs_nearest", "dvs_within",
     "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters", "dvs_pcoa", "dvs_pcoa_project", "dvs_kmedoids",
-    "dvs_mst", "dvs_linkage_from_mst",
+    "dvs_mst", "dvs_linkage_from_mst", "dvs_permanova",
 )
 WITHIN_SKIP_SELF = 1
 SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
@@ -98,6 +98,11 @@ class KmedoidsInfo(C.Structure):
 
 
 KMEDOIDS_INIT_BUILD, KMEDOIDS_INIT_GIVEN = 0, 1
+
+
+class PermanovaInfo(C.Structure):
+    """dvs_permanova_info"""
+    _fields_ = [("n_le", C.c_uint32), ("passes", C.c_uint32), ("batch", C.c_uint32)]
 
 
 class SelectParams(C.Structure):
@@ -285,6 +290,8 @@ def load() -> C.CDLL:
                                    C.POINTER(KmedoidsInfo)]
         L.dvs_mst.argtypes = [vp, srcp, f64p, u32p, f64p, u32p, u32p]  # core, edges, weights, n_edges, n_rounds
         L.dvs_linkage_from_mst.argtypes = [vp, u32, u32p, f64p, u32p, f64p, u32p]  # edges, weights, pairs, heights, sizes
+        # labels, n_groups, perm_labels, n_perm, ss_total, ss_within, group_ss, info
+        L.dvs_permanova.argtypes = [vp, srcp, u32p, u32, u32p, u32, f64p, f64p, f64p, C.POINTER(PermanovaInfo)]
         if L.dvs_abi_version() != 5:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

@@ -12,7 +12,8 @@ lengths (diverseseq_amd.cluster.nj_tree); and `dvs_maxmin`: farthest-first selec
 a diverse panel or a dereplication (diverseseq_amd.distance.maxmin); and `dvs_pcoa`: the principal coordinates of the
 same distances, the picture that goes with the trees and the clusters (diverseseq_amd.cluster.ordinate); and
 `dvs_kmedoids`: the n sequences that represent a collection best, k-medoids over the same distances
-(diverseseq_amd.cluster.representatives).
+(diverseseq_amd.cluster.representatives); and `dvs_permanova`: whether a grouping of the sequences explains those
+distances, PERMANOVA (diverseseq_amd.distance.permanova).
 
 Constructor arguments, defaults, seeding (`numpy.random.default_rng(seed).shuffle` of the unique
 ids) and error messages are the reference's.  cogent3 is OPTIONAL: when it is importable the classes
@@ -44,7 +45,8 @@ except Exception:  # noqa: BLE001
         return wrap if not (len(a) == 1 and isinstance(a[0], type)) else wrap(a[0])
 
 __all__ = ["dvs_nmost", "dvs_max", "dvs_delta_jsd", "dvs_ctree", "dvs_par_ctree", "dvs_dist", "dvs_nearest",
-           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa", "dvs_kmedoids", "dvs_mst"]
+           "dvs_clusters", "dvs_cophenet", "dvs_njtree", "dvs_maxmin", "dvs_dereplicate", "dvs_pcoa", "dvs_kmedoids", "dvs_mst",
+           "dvs_permanova"]
 
 # len(get_moltype(m).alphabet) of the reference (records.py:299, 415-416)
 _NUM_STATES = {"dna": 4, "rna": 4, "protein": 20, "text": 26, "bytes": 256}
@@ -348,6 +350,47 @@ class dvs_kmedoids(_DistanceApp):
                 "representative": {name: reps[l] for name, l in zip(names, labels.tolist())},
                 "distance": {name: float(d) for name, d in zip(names, fit.dist)},
                 "total_distance": float(fit.td[-1]), "converged": bool(fit.stop)}
+
+
+@_define_app
+class dvs_permanova(_DistanceApp):
+    """Does a grouping of the sequences explain their distances (beyond the reference, which has no such app)?
+    PERMANOVA, the test that goes with `dvs_pcoa`, by any distance of `dvs_dist`.  grouping: {name: group}, any
+    hashables, with an entry for every sequence the app is given; permutations, seed and strata ({name: block}) as
+    `diverseseq_amd.distance.permanova`; the mode arguments and their checks as `dvs_maxmin`.  `main(seqs)` returns {"f",
+    "p_value", "r2", "ss_total", "ss_within", "ss_among": floats, "groups": [the groups in the order of their first
+    sequence], "group_sizes": {group: int}, "group_ss": {group: float}, "permutations": int}."""
+
+    def __init__(self, grouping: dict, distance_mode: str = "mash", *, k: int = 12, sketch_size: int | None = 3_000,
+                 moltype: str = "dna", mash_canonical_kmers: bool | None = None, permutations: int = 999, seed=None,
+                 strata: dict | None = None, canonical: bool = False) -> None:
+        sketch_size, mash_canonical_kmers = self._check_mode(distance_mode, sketch_size, moltype, mash_canonical_kmers,
+                                                             canonical=canonical)
+        if not hasattr(grouping, "keys") or (strata is not None and not hasattr(strata, "keys")):
+            raise ValueError("grouping (and strata) must map the names of the sequences to their groups")
+        if isinstance(permutations, bool) or not isinstance(permutations, (int, np.integer)) or permutations < 0:
+            raise ValueError(f"permutations must be an integer >= 0, not {permutations!r}")
+        self._grouping = {str(n): g for n, g in grouping.items()}
+        self._strata = None if strata is None else {str(n): g for n, g in strata.items()}
+        self._permutations, self._seed = int(permutations), seed
+        self._keep_mode(distance_mode, k, sketch_size, moltype, mash_canonical_kmers, canonical)
+
+    def main(self, seqs):
+        names, arrays = _as_arrays(seqs, self._moltype)
+        missing = [n for n in names if n not in self._grouping or (self._strata is not None and n not in self._strata)]
+        if missing:
+            raise ValueError(f"no group for sequence {missing[0]!r}")
+        groups = [self._grouping[n] for n in names]
+        strata = None if self._strata is None else [self._strata[n] for n in names]
+        fit = _distance.permanova(arrays, groups, self._distance_mode, k=self._k, sketch_size=self._sketch_size,
+                                  num_states=self._num_states, mash_canonical=self._mash_canonical,
+                                  permutations=self._permutations, seed=self._seed, strata=strata,
+                                  canonical=self._canonical)
+        order = list(dict.fromkeys(groups))
+        return {"f": fit.f, "p_value": fit.p_value, "r2": fit.r2, "ss_total": fit.ss_total, "ss_within": fit.ss_within,
+                "ss_among": fit.ss_among, "groups": order,
+                "group_sizes": {g: int(v) for g, v in zip(order, fit.group_sizes)},
+                "group_ss": {g: float(v) for g, v in zip(order, fit.group_ss)}, "permutations": fit.permutations}
 
 
 @_define_app

@@ -23,7 +23,8 @@ collection's distances, principal coordinates (`pcoa` over a caller's matrix, `o
 it, for collections whose N x N matrix could never exist); and the representatives that lie closest, in total, to
 everything else, k-medoids (`kmedoids` over a caller's matrix, `representatives` over sequences, csrc/kmedoids.hip;
 `sampled_kmedoids`: k-medoids of farthest-first landmarks with every sequence assigned to its nearest medoid, for
-collections whose N x N matrix could never exist); and the tree itself for such collections, the minimum spanning tree
+collections whose N x N matrix could never exist); and whether a grouping of the rows explains the distances, PERMANOVA
+(`permanova` over a caller's matrix, csrc/permanova.hip); and the tree itself for such collections, the minimum spanning tree
 (`minimum_spanning_tree` over a caller's matrix, `mst_ctree` over sequences, csrc/mst.hip: Boruvka rounds over strips of
 distances; `mst_linkage`, `mst_to_edges`): single linkage, and with a core vector robust single linkage, in O(N) device
 memory beside one strip.
@@ -395,6 +396,23 @@ def kmedoids(dist, n_medoids: int, *, init="build", max_swaps: int = 300,
         if rows.size != k:
             raise ValueError(f"farthest-first selection found only {rows.size} of {k} initial medoids")
     return distance.run_kmedoids(ctx, n, src, k, rows, max_swaps)
+
+
+def permanova(dist, grouping, *, permutations: int = 999, seed=None, strata=None,
+              ctx: engine.Context | None = None) -> "distance.PERMANOVA":
+    """PERMANOVA (Anderson 2001; include/dvs_hip.h "PERMANOVA") of a grouping of the rows of a caller's n x n
+    dissimilarity matrix on the GPU -> `distance.PERMANOVA`: the pseudo-F statistic of the sums of squared distances
+    within the groups, and its p-value under permutations of the labels, a batch of permutations per pass over the
+    matrix.  Only dist[i, j] with i < j counts: the matrix need not be symmetric, the diagonal and the lower triangle are
+    never read; every entry above the diagonal must be finite and >= 0 (ValueError).  grouping, permutations, seed and
+    strata as `distance.permanova`.
+
+    `dist`: anything np.asarray(dist, float64) takes, or a square, contiguous float64 torch tensor on the GPU, handled
+    as `cluster_scores` handles it and only READ.  The arguments are checked before any device work."""
+    src, n, wait = _caller_matrix(dist)
+    checked = distance.check_permanova_args(n, grouping, permutations, seed, strata)
+    wait()
+    return distance.run_permanova(ctx, n, src, *checked)
 
 
 def representatives(seqs: dict, n: int, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",

@@ -44,6 +44,7 @@ struct dvs_knobs {
     // farthest-first selection (maxmin.hip)
     uint32_t maxmin_batch = 0;        // DVS_MAXMIN_BATCH: steps enqueued between two reads of the status word (0: 64)
     uint32_t kmedoids_batch = 0;      // DVS_KMEDOIDS_BATCH: swap rounds enqueued between two reads of the status word (0: 8)
+    uint32_t permanova_batch = 0;     // DVS_PERMANOVA_BATCH: label vectors (the observed one and permutations) a pass over the matrix serves (0: 16; 32 at most)
     bool maxmin_jsd_cross = false;    // DVS_MAXMIN_JSD_CROSS: the jsd traversal runs jsd_cross_kernel on one query row (the A/B of DESIGN.md 4.13)
     // ingest
     bool ingest_no_stream = false;    // DVS_INGEST_NO_STREAM: host files are uploaded whole before they are parsed
@@ -137,7 +138,7 @@ struct dvs_ctx {
         bool lists_in_flight = false;
     } off_cache;
     // packed upload of host sequences (pack.hip): the pinned staging block, kept between calls, and the
-    // event behind the last copy that read it
+    // event behind the last copy that read it; PERMANOVA's label vectors travel through the same block (dvs_pinned_stage)
     void *h_pack = nullptr;
     size_t h_pack_cap = 0;
     hipEvent_t pack_ev = nullptr;
@@ -167,6 +168,9 @@ struct PooledBuf {
     T *as() { return static_cast<T *>(p); }
 };
 int dvs_pinned_get(dvs_ctx *ctx, void **ptr);  // 4 KiB pinned block from the ctx cache
+// pack.hip: ctx->h_pack, the context's large pinned staging block, with room for `bytes` and read by nobody any more; a
+// user that does not wait for its last copy out of the block records ctx->pack_ev behind it
+int dvs_pinned_stage(dvs_ctx *ctx, size_t bytes, const char *what);
 void dvs_pinned_put(dvs_ctx *ctx, void *ptr);
 hipEvent_t dvs_event_get(dvs_ctx *ctx);
 void dvs_event_put(dvs_ctx *ctx, hipEvent_t e);
@@ -318,7 +322,7 @@ int dvs_cophenet_walk(dvs_ctx *ctx, uint32_t n, const uint32_t *pairs, const dou
                       uint32_t *pos, uint32_t *gap, double *c_bar);
 
 // One consumer of a whole n x n f64 distance matrix in HBM, as the square driver of rowdist.hip takes it: what differs
-// between the linkage tree, the neighbour-joining tree, the principal coordinates and k-medoids.  The driver brings the
+// between the linkage tree, the neighbour-joining tree, the principal coordinates, k-medoids and PERMANOVA.  The driver brings the
 // matrix -- a MASH, EUCLIDEAN or JSD source's kernels enqueued, a caller's host matrix uploaded, a caller's device
 // matrix where it is -- and calls run.  On entry to run: check has passed, the context's device is set, the matrix and
 // extra_bytes() beside it have been found to fit, and the matrix is resident or enqueued on the context's stream.  run
@@ -351,6 +355,15 @@ dvs_square_consumer dvs_pcoa_consumer(dvs_ctx *ctx, uint32_t n, const dvs_pcoa_p
                                       double *residuals, double *row_means, dvs_pcoa_info *info);              // pcoa.hip
 dvs_square_consumer dvs_kmedoids_consumer(dvs_ctx *ctx, uint32_t n, bool given, const dvs_kmedoids_params *p,
                                           const dvs_kmedoids_out &out);                                        // kmedoids.hip
+struct dvs_permanova_args {  // dvs_permanova's, behind the source
+    const uint32_t *labels;
+    uint32_t n_groups;
+    const uint32_t *perm_labels;
+    uint32_t n_perm;
+    double *ss_total, *ss_within, *group_ss;
+    dvs_permanova_info *info;
+};
+dvs_square_consumer dvs_permanova_consumer(dvs_ctx *ctx, uint32_t n, const dvs_permanova_args &a);           // permanova.hip
 // A run's status words: `bytes` of them zeroed on the context's stream, then the distance kernels' zero-division word
 // (d_zerodiv, may be NULL) copied into word `at`.
 inline hipError_t dvs_status_begin(dvs_ctx *ctx, uint32_t *d_status, size_t bytes, uint32_t at, const uint32_t *d_zerodiv) {

@@ -109,6 +109,26 @@ int dvs_packed_fill_from_device(dvs_ctx *ctx, dvs_packed *p, const uint8_t *d_se
     return DVS_OK;
 }
 
+// The context's pinned staging block, kept between calls, with room for `bytes` (grown by an eighth more when it is too
+// small): ctx->h_pack.  Nobody may still be reading it: the last copy out of it that was not waited for is behind
+// ctx->pack_ev, which is waited for here.
+int dvs_pinned_stage(dvs_ctx *ctx, size_t bytes, const char *what) {
+    if (ctx->pack_ev) (void)hipEventSynchronize(ctx->pack_ev);
+    if (ctx->h_pack_cap < bytes) {
+        if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
+        ctx->h_pack = nullptr;
+        ctx->h_pack_cap = 0;
+        const size_t cap = bytes + bytes / 8;
+        const hipError_t he = hipHostMalloc(&ctx->h_pack, cap, hipHostMallocDefault);
+        if (he != hipSuccess) {
+            ctx->h_pack = nullptr;
+            return dvs_hip_fail(ctx, he, what);
+        }
+        ctx->h_pack_cap = cap;
+    }
+    return DVS_OK;
+}
+
 // seqs[0, nbases) (host, one byte per base) -> the planes, enqueued on the context's stream; returns when the
 // last chunk's copy has been ENQUEUED (the staging block is protected by ctx->pack_ev).
 int dvs_packed_fill_from_host(dvs_ctx *ctx, dvs_packed *p, const uint8_t *seqs) {
@@ -116,20 +136,7 @@ int dvs_packed_fill_from_host(dvs_ctx *ctx, dvs_packed *p, const uint8_t *seqs) 
     if (!nbytes) return DVS_OK;
     const size_t nchunks = size_t((nbytes + PACK_CHUNK - 1) / PACK_CHUNK);
     const size_t stage_bytes = nchunks * (PACK_CODE_BYTES + PACK_MASK_BYTES);
-    // the staging block: nobody may still be reading it (the previous call's last copy)
-    if (ctx->pack_ev) (void)hipEventSynchronize(ctx->pack_ev);
-    if (ctx->h_pack_cap < stage_bytes) {
-        if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
-        ctx->h_pack = nullptr;
-        ctx->h_pack_cap = 0;
-        const size_t cap = stage_bytes + stage_bytes / 8;
-        const hipError_t he = hipHostMalloc(&ctx->h_pack, cap, hipHostMallocDefault);
-        if (he != hipSuccess) {
-            ctx->h_pack = nullptr;
-            return dvs_hip_fail(ctx, he, "pinned staging block of the packed upload");
-        }
-        ctx->h_pack_cap = cap;
-    }
+    if (int rc = dvs_pinned_stage(ctx, stage_bytes, "pinned staging block of the packed upload")) return rc;
     // staging layout: every chunk's codes, then every chunk's masks (the planes as they lie on the device)
     uint8_t *stage_codes = static_cast<uint8_t *>(ctx->h_pack);
     uint8_t *stage_mask = stage_codes + nchunks * PACK_CODE_BYTES;

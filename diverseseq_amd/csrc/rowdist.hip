@@ -402,3 +402,13 @@ extern "C" int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src, const dvs_kmedo
     const dvs_kmedoids_out out{medoids, labels, dist, second, swaps, td, info};
     return square_run(ctx, src, dvs_kmedoids_consumer(ctx, src->n, src->kind == DVS_SRC_GIVEN, params, out));
 }
+
+extern "C" int dvs_permanova(dvs_ctx *ctx, const dvs_source *src, const uint32_t *labels, uint32_t n_groups,
+                             const uint32_t *perm_labels, uint32_t n_perm, double *ss_total, double *ss_within, double *group_ss,
+                             dvs_permanova_info *info) {
+    if (!ctx || !src) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_permanova: null argument");
+    if (int rc = dvs_source_check(ctx, src, src)) return rc;
+    if (int rc = dvs_source_whole(ctx, "dvs_permanova", src)) return rc;
+    const dvs_permanova_args args{labels, n_groups, perm_labels, n_perm, ss_total, ss_within, group_ss, info};
+    return square_run(ctx, src, dvs_permanova_consumer(ctx, src->n, args));
+}

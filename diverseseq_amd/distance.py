@@ -27,7 +27,11 @@ mash_kmedoids / euclidean_kmedoids / jsd_kmedoids ->
 `KMedoids`: csrc/kmedoids.hip, PAM's BUILD and FastPAM1's swaps over the N x N matrix in HBM); no counterpart in the
 reference; and the tree without the matrix, the minimum spanning tree (mst, matrix_mst, mash_mst / euclidean_mst /
 jsd_mst -> `MST`: csrc/mst.hip, a Boruvka round per pass over the strips of cross_distances; single linkage, and with a
-core vector the mutual-reachability tree of HDBSCAN); no counterpart in the reference.  `DeviceSide`
+core vector the mutual-reachability tree of HDBSCAN); no counterpart in the reference; and the test that goes with
+the ordination, PERMANOVA (permanova, matrix_permanova, mash_permanova / euclidean_permanova / jsd_permanova ->
+`PERMANOVA`: csrc/permanova.hip, whether a grouping of the sequences explains their distances -- a pseudo-F statistic
+and its p-value under permutations of the labels, a batch of permutations per pass over the N x N matrix in HBM); no
+counterpart in the reference.  `DeviceSide`
 is what a mode keeps in HBM of one batch, with every one of these operations as a method; the per-mode functions, the
 matrix_* functions and the Sketches methods are a few lines over it.  Every operation has one C entry, which takes a
 `_lib.Source` (dvs_source: the mode and its handle, or a caller's matrix): `make_source` fills one per call."""
@@ -300,6 +304,11 @@ class Sketches:
         read in HBM (dvs_kmedoids); ZeroDivisionError as `distances`"""
         return DeviceSide(self, "mash").kmedoids(n_medoids, init=init, max_swaps=max_swaps)
 
+    def permanova(self, grouping, *, permutations: int = 999, seed=None, strata=None) -> "PERMANOVA":
+        """PERMANOVA (`PERMANOVA`) of a grouping of this set's sketches over their mash distances, the N x N matrix
+        written and only read in HBM (dvs_permanova); ZeroDivisionError as `distances`"""
+        return DeviceSide(self, "mash").permanova(grouping, permutations=permutations, seed=seed, strata=strata)
+
     def within(self, other: "Sketches", radius, rows=None, other_rows=None, *, skip_self: bool = False,
                max_pairs: int | None = None) -> "Neighbours":
         """for each of this set's sketches `rows` the sketches of `other` at a mash distance <= radius (`Neighbours`:
@@ -355,6 +364,17 @@ class MedoidOps:
             if rows.size != k:
                 raise ValueError(f"farthest-first selection found only {rows.size} of {k} initial medoids")
         return run_kmedoids(self.ctx, self.n, self._source(), k, rows, max_swaps)
+
+
+class GroupOps:
+    """PERMANOVA as an operation of a `DeviceSide`, which inherits it: `DeviceSide.permanova`.  In a base class of its
+    own for the reason `OrdinationOps` gives; its poisoned-block cases are in tests/test_gpu_permanova.py."""
+
+    def permanova(self, grouping, *, permutations: int = 999, seed=None, strata=None) -> "PERMANOVA":
+        """PERMANOVA of `grouping` over the distances (`PERMANOVA`), the N x N matrix written and only read in HBM; the
+        arguments as `permanova`"""
+        labels, n_groups, perms = check_permanova_args(self.n, grouping, permutations, seed, strata)
+        return run_permanova(self.ctx, self.n, self._source(), labels, n_groups, perms)
 
 
 MIN_SAMPLES_MAX = 64  # N_NEAREST_MAX: the core distances come from `DeviceSide.nearest`
@@ -438,7 +458,7 @@ class SpanningOps:
         return run_mst(self.ctx, listed[1], self._source(listed), check_core(core, listed[1]))
 
 
-class DeviceSide(OrdinationOps, MedoidOps, SpanningOps):
+class DeviceSide(OrdinationOps, MedoidOps, SpanningOps, GroupOps):
     """What a distance mode keeps in HBM of one batch -- its `Sketches` (mash) or its count matrix (euclidean, jsd) --
     together with the mode: every operation over "the distances of a collection", whatever the mode.  `device_side`
     makes one that owns its handle; DeviceSide(handle, mode) wraps a handle of the caller's, which close() then leaves
@@ -1639,3 +1659,180 @@ def kmedoids(seqs, n_medoids: int, distance_mode: str = "mash", *, k: int, sketc
     seqs = list(seqs)
     return _kmedoids(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
                      n_medoids=n_medoids, init=init, max_swaps=max_swaps, ctx=ctx, canonical=canonical)
+
+
+# ---- PERMANOVA: do the groups explain the distances?
+
+PERMANOVA_MAX_GROUPS = 65_535  # include/dvs_hip.h: a label travels in 8 or 16 bits
+
+
+class PERMANOVA(NamedTuple):
+    """A permutational multivariate analysis of variance (Anderson 2001; include/dvs_hip.h "PERMANOVA") of n items in a
+    groups.  f: the pseudo-F statistic (SS_A / (a - 1)) / (SS_W / (n - a)), inf where SS_W == 0 < SS_A, nan where
+    SS_T == 0; p_value: (1 + the permutations whose SS_W is <= the observed one, i.e. whose F is >= the observed F) /
+    (1 + permutations), nan for permutations = 0; r2: SS_A / SS_T; ss_total, ss_within, ss_among = ss_total -
+    ss_within; group_ss float64 [a]: each group's own term of ss_within, in the order of the groups' first appearance
+    in the grouping; group_sizes int64 [a]; perm_f float64 [permutations]: F under each permutation, in the order they
+    were drawn; permutations."""
+    f: float
+    p_value: float
+    r2: float
+    ss_total: float
+    ss_within: float
+    ss_among: float
+    group_ss: np.ndarray
+    group_sizes: np.ndarray
+    perm_f: np.ndarray
+    permutations: int
+
+
+def encode_grouping(grouping, n: int, what: str = "grouping") -> tuple:
+    """any sequence of n hashables -> (uint32 [n] codes 0 .. a - 1 in the order of first appearance, the a distinct
+    values in that order); ValueError unless it holds one value per row"""
+    if isinstance(grouping, (str, bytes)) or not hasattr(grouping, "__len__") or not hasattr(grouping, "__iter__"):
+        raise ValueError(f"{what}: a sequence with one value per row")
+    if len(grouping) != n:
+        raise ValueError(f"{len(grouping)} values of {what} for {n} rows")
+    codes, names = {}, []
+    out = np.zeros(n, dtype=np.uint32)
+    for i, g in enumerate(grouping.tolist() if isinstance(grouping, np.ndarray) else grouping):
+        try:
+            c = codes.get(g)
+        except TypeError:
+            raise ValueError(f"{what}: value {g!r} of row {i} is not hashable") from None
+        if c is None:
+            c = codes[g] = len(names)
+            names.append(g)
+        out[i] = c
+    return out, names
+
+
+def permuted_labels(labels: np.ndarray, permutations: int, seed=None, strata: np.ndarray | None = None) -> np.ndarray:
+    """the label vectors of a PERMANOVA run: uint32 [permutations, n].  THE RULE, which the tests restate: rng =
+    numpy.random.default_rng(seed); for each row, in order, ONE perm = rng.permutation(n); without strata the row is
+    labels[perm]; with strata (codes, one per item) the positions of every block, in ascending order, receive the
+    labels of that block's positions taken in ascending order of perm -- labels move inside their block only."""
+    n = labels.size
+    rng = np.random.default_rng(seed)
+    out = np.zeros((permutations, n), dtype=np.uint32)
+    blocks = None if strata is None else [np.flatnonzero(strata == s) for s in range(int(strata.max()) + 1)]
+    for p in range(permutations):
+        perm = rng.permutation(n)
+        if blocks is None:
+            out[p] = labels[perm]
+        else:
+            for idx in blocks:
+                out[p, idx] = labels[idx[np.argsort(perm[idx], kind="stable")]]
+    return out
+
+
+def check_permanova_args(n: int, grouping, permutations, seed, strata) -> tuple:
+    """the arguments of a PERMANOVA over n items, checked before any device work -> (labels uint32 [n], n_groups,
+    perm_labels uint32 [permutations, n]).  ValueError unless n >= 3, grouping (and strata, if given) holds one
+    hashable per row, there are between 2 and n - 1 groups and permutations is an integer >= 0; NotImplementedError
+    beyond PERMANOVA_MAX_GROUPS groups.  The permutations are drawn here: `permuted_labels`."""
+    if n < 3:
+        raise ValueError("need at least three rows for PERMANOVA")
+    labels, names = encode_grouping(grouping, n)
+    a = len(names)
+    if a < 2 or a >= n:
+        raise ValueError(f"{a} groups of {n} rows: between 2 and {n - 1} (a group of its own for every row leaves no "
+                         "distance within a group)")
+    if a > PERMANOVA_MAX_GROUPS:
+        raise NotImplementedError(f"{a} groups: {PERMANOVA_MAX_GROUPS} at most")
+    if isinstance(permutations, bool) or not isinstance(permutations, (int, np.integer)) or permutations < 0:
+        raise ValueError(f"permutations must be an integer >= 0, not {permutations!r}")
+    if permutations >= _U32_MAX:
+        raise ValueError(f"permutations = {permutations}: fewer than 2^32 - 1")
+    blocks = None if strata is None else encode_grouping(strata, n, "strata")[0]
+    return labels, a, permuted_labels(labels, int(permutations), seed, blocks)
+
+
+def permanova_statistics(n: int, n_groups: int, ss_total: float, ss_within: np.ndarray) -> tuple:
+    """(SS_A, F, R^2) from SS_T and SS_W (a scalar or one per label vector) in float64, as `PERMANOVA` states them:
+    SS_A = SS_T - SS_W; F = (SS_A / (a - 1)) / (SS_W / (n - a)), x / 0 = inf and 0 / 0 = nan as IEEE has them, nan
+    wherever SS_T == 0; R^2 = SS_A / SS_T"""
+    ssw = np.asarray(ss_within, dtype=np.float64)
+    sst = np.float64(ss_total)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ssa = sst - ssw
+        f = (ssa / np.float64(n_groups - 1)) / (ssw / np.float64(n - n_groups))
+        f = np.where(sst == 0, np.nan, f)
+        r2 = ssa / sst
+    return ssa, f, r2
+
+
+def run_permanova(ctx: engine.Context | None, n: int, src: _lib.Source, labels: np.ndarray, n_groups: int,
+                  perms: np.ndarray) -> PERMANOVA:
+    """dvs_permanova over `src` for n rows with the checked labels and label vectors -> PERMANOVA"""
+    ctx = ctx or engine.default_context()
+    n_perm = int(perms.shape[0])
+    perms = np.ascontiguousarray(perms, dtype=np.uint32)
+    ss_total = C.c_double(0.0)
+    ss_within = np.zeros(n_perm + 1, dtype=np.float64)
+    group_ss = np.zeros(n_groups, dtype=np.float64)
+    info = _lib.PermanovaInfo()
+    ctx.check(ctx._L.dvs_permanova(ctx._h, src, _lib.ptr(labels, C.c_uint32), n_groups,
+                                   _lib.ptr(perms, C.c_uint32) if n_perm else None, n_perm, C.byref(ss_total),
+                                   _lib.ptr(ss_within, C.c_double), _lib.ptr(group_ss, C.c_double), C.byref(info)))
+    ssa, f, r2 = permanova_statistics(n, n_groups, ss_total.value, ss_within)
+    p_value = (1.0 + int(info.n_le)) / (1.0 + n_perm) if n_perm else float("nan")
+    return PERMANOVA(float(f[0]), p_value, float(r2[0]), float(ss_total.value), float(ss_within[0]), float(ssa[0]), group_ss,
+                     np.bincount(labels, minlength=n_groups).astype(np.int64), f[1:].copy(), n_perm)
+
+
+def matrix_permanova(m: "engine.CountMatrix", grouping, *, mode: str = "jsd", permutations: int = 999, seed=None,
+                     strata=None) -> PERMANOVA:
+    """`permanova` over the rows of a matrix already in HBM, by `mode` ("jsd" or "euclidean")"""
+    return _count_side(m, mode).permanova(grouping, permutations=permutations, seed=seed, strata=strata)
+
+
+def mash_permanova(seqs, k: int, sketch_size: int, num_states: int = 4, mash_canonical: bool = False, *, grouping,
+                   permutations: int = 999, seed=None, strata=None, ctx: engine.Context | None = None) -> PERMANOVA:
+    """PERMANOVA of the mash distances on the device: sketches, the N x N distances and the sums under every
+    permutation, every stage in HBM.  ZeroDivisionError as `mash_distances`."""
+    return _permanova(seqs, "mash", k, sketch_size, num_states, mash_canonical, grouping=grouping, permutations=permutations,
+                      seed=seed, strata=strata, ctx=ctx)
+
+
+def euclidean_permanova(seqs, k: int, num_states: int = 4, *, grouping, permutations: int = 999, seed=None, strata=None,
+                        ctx: engine.Context | None = None, canonical: bool = False) -> PERMANOVA:
+    """the same for the euclidean distances (a sequence without valid k-mers: NaN distances, ValueError)"""
+    return _permanova(seqs, "euclidean", k, num_states, grouping=grouping, permutations=permutations, seed=seed,
+                      strata=strata, ctx=ctx, canonical=canonical)
+
+
+def jsd_permanova(seqs, k: int, num_states: int = 4, *, grouping, permutations: int = 999, seed=None, strata=None,
+                  ctx: engine.Context | None = None, canonical: bool = False) -> PERMANOVA:
+    """the same for the Jensen-Shannon divergences of `jsd_distances` (a sequence without valid k-mers: ValueError)"""
+    return _permanova(seqs, "jsd", k, num_states, grouping=grouping, permutations=permutations, seed=seed, strata=strata,
+                      ctx=ctx, canonical=canonical)
+
+
+def _permanova(seqs, distance_mode: str, *args, grouping, permutations, seed, strata, ctx, canonical: bool = False) -> PERMANOVA:
+    checked = check_permanova_args(len(seqs), grouping, permutations, seed, strata)
+    with device_side(seqs, distance_mode, *args, ctx=ctx, canonical=canonical) as dev:
+        return run_permanova(dev.ctx, dev.n, dev._source(), *checked)
+
+
+# a distance mode -> its PERMANOVA: takes (seqs, *mode_args(...)), and grouping=, permutations=, seed=, strata=, ctx=
+PERMANOVA_MODES = {"mash": mash_permanova, "euclidean": euclidean_permanova, "jsd": jsd_permanova}
+
+
+def permanova(seqs, grouping, distance_mode: str = "mash", *, k: int, sketch_size: int | None = None, num_states: int = 4,
+              mash_canonical: bool = False, permutations: int = 999, seed=None, strata=None,
+              ctx: engine.Context | None = None, canonical: bool = False) -> PERMANOVA:
+    """PERMANOVA (`PERMANOVA`) of a grouping of a collection of sequences by `distance_mode`: are the distances between
+    the groups larger than within them, beyond chance?  The test that goes with `pcoa`.  The distances are written into
+    HBM and stay there; one pass over them serves a batch of permutations.
+
+    grouping: any sequence of hashables, one per sequence (host species, sampling site, the labels of `cut_tree`,
+    `kmedoids` or `threshold_clusters`), encoded 0 .. a - 1 in the order of first appearance.  permutations: how many
+    label vectors are drawn (0: the statistic alone, p_value nan); seed: of numpy.random.default_rng, from which one
+    rng.permutation(n) is drawn per label vector, in order (`permuted_labels` has the rule); strata: a second sequence
+    of hashables, labels are then permuted inside its blocks only.  Argument checks as cluster.ctree and those of
+    `check_permanova_args`, before any device work."""
+    check_mode_args(distance_mode, sketch_size, mash_canonical, canonical)
+    seqs = list(seqs)
+    return _permanova(seqs, distance_mode, *mode_args(distance_mode, k, sketch_size, num_states, mash_canonical),
+                      grouping=grouping, permutations=permutations, seed=seed, strata=strata, ctx=ctx, canonical=canonical)

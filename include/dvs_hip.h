@@ -858,6 +858,65 @@ typedef struct dvs_kmedoids_info {
 int dvs_kmedoids(dvs_ctx *ctx, const dvs_source *src, const dvs_kmedoids_params *params, uint32_t *medoids,
                  uint32_t *labels, double *dist, double *second, uint32_t *swaps, double *td, dvs_kmedoids_info *info);
 
+/* ---- PERMANOVA (Anderson 2001): do the groups explain the distances? -------------------------------- *
+ * A pseudo-F statistic from the sums of squared distances within the groups of a labelling, and what the same sum
+ * is under permutations of the labels.  (No counterpart in the reference.)  Items are 0 .. n - 1 with labels g[i] in
+ * [0, a), a = n_groups, group sizes n_g; D is the n x n matrix of the source.  Only D[i][j] with i < j counts, as in
+ * dvs_linkage: the matrix need not be symmetric, and the diagonal and the lower triangle are never read.  Every entry
+ * above the diagonal must be finite and >= 0 (DVS_ERR_VALUE; for NaN or +-inf with the text the trees give).
+ *   q_ij    = D[i][j] * D[i][j]
+ *   SS_T    = (1/n) sum_{i<j} q_ij
+ *   SS_W(g) = sum_{i<j, g_i = g_j} q_ij / n_{g_i}
+ *   SS_A = SS_T - SS_W;  F = (SS_A / (a - 1)) / (SS_W / (n - a));  R^2 = SS_A / SS_T
+ *   p = (1 + #{pi : SS_W(g o pi) <= SS_W(g)}) / (1 + P)
+ * SS_T and the group sizes do not change under a permutation and F falls strictly as SS_W rises: the count is taken
+ * on SS_W, in float64, and the library returns the sums -- SS_T, SS_W of the observed labels and of every permutation,
+ * the observed term of each group -- from which a caller derives F, R^2 and p.  The caller makes the permutations
+ * (the library carries no random numbers; permuting inside strata is the caller's choice): perm_labels[p][i] is the
+ * label of item i after permutation p.
+ * The order of every sum (w[g] = 1.0 / n_g, rounded once; x (+) y: a float64 addition; no fused multiply-add):
+ *   a tile is 128 rows x 256 columns of the matrix, tile (rb, cb) holding rows 128 rb .. and columns 256 cb ..;
+ *   C_j(tile) = the q_ij of the tile's rows i < j with g_i = g_j, added in ascending i from +0.0 (a cell that does not
+ *       match adds +0.0 in its place);
+ *   S(tile)  = w[g_j] * C_j(tile) over the tile's columns: each of the four runs of 64 columns by the xor tree (lanes
+ *       l and l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1), the four runs added in ascending order;
+ *   SS_W     = S over all tiles (rb * ceil(n / 256) + cb = t): 256 strided chains t = k, k + 256, ... in ascending
+ *       order, chain k in lane k & 63 of run k >> 6, the lanes by the same tree, the runs in ascending order.
+ *   T_i = sum_{j>i} q_ij and, for the observed labels, R_i = sum_{j>i, g_j = g_i} q_ij: 64 strided chains over the
+ *       columns from 64 floor((i + 1) / 64) in ascending order (a column <= i adds +0.0), met by the same tree;
+ *   SS_T = (T_0 (+) T_1 (+) ... (+) T_{n-1}) / n;  group_ss[g] = w[g] * (the R_i of the group's items in ascending i).
+ * Every order depends on positions and n only, never on the label values, and there is no floating-point atomic.  So
+ * the same bits come back on every run, for every batch length (DVS_PERMANOVA_BATCH: the label vectors, the observed
+ * one among them, that one pass over the matrix serves: 16 by default, 32 at most), for a host matrix and the same
+ * matrix in device memory; and SS_W is a function of the PARTITION and its sizes alone: two label vectors that induce
+ * the same partition -- renamed groups, the identity permutation, a permutation that maps every group onto itself --
+ * give the same bits, and all of these count towards p.  Two DISTINCT partitions whose sums are equal in exact
+ * arithmetic (the quantised distances of mash) may still differ in the last bit.  Each of ss_total, ss_within[p] and
+ * group_ss[g] lies within (n + 8) 2^-52 of its exact value, relatively (two levels of sums of at most n terms).
+ *   labels[n]  the observed labels; perm_labels[n_perm][n] row-major, NULL exactly when n_perm == 0
+ *   ss_total[1]; ss_within[n_perm + 1], [0] the observed labels'; group_ss[n_groups] (optional: NULL), the observed
+ *       within-group term of each group: their sum is SS_W(g) up to rounding
+ *   info (optional: NULL): n_le, the count in p's numerator (without the 1); passes, the reads of the matrix's upper
+ *       triangle: the entry check and one per batch; batch, the batch length used
+ * The sources as for dvs_kmedoids: whole, no row list; MASH, EUCLIDEAN and JSD write their matrix into the context's
+ * scratch, where it stays; a GIVEN host matrix is uploaded and left as it is, a GIVEN device matrix only read.  The
+ * checks come in dvs_kmedoids's order: the arguments, n, the source's own, the device, the fit in HBM; the arguments
+ * and n before any device work.
+ *   DVS_ERR_VALUE: a NULL labels, ss_total or ss_within; perm_labels NULL with n_perm > 0 or not NULL with n_perm == 0;
+ *                  n < 3; n_groups < 2 or >= n; a label >= n_groups; an empty group; a row of perm_labels whose group
+ *                  sizes are not the observed ones (the message names the first); a non-finite or negative entry
+ *                  above the diagonal; a device matrix on another device
+ *   DVS_ERR_UNSUPPORTED: a row list, or n other than the handle's rows; n_groups > 65 535 (a label travels in 8 or 16
+ *                  bits)
+ *   DVS_ERR_ZERODIV: (MASH) as dvs_nj
+ *   DVS_ERR_NOMEM: the matrix and the sums' state do not fit in HBM */
+typedef struct dvs_permanova_info {
+    uint32_t n_le, passes, batch;
+} dvs_permanova_info;
+int dvs_permanova(dvs_ctx *ctx, const dvs_source *src, const uint32_t *labels, uint32_t n_groups,
+                  const uint32_t *perm_labels, uint32_t n_perm, double *ss_total, double *ss_within, double *group_ss,
+                  dvs_permanova_info *info);
+
 #ifdef __cplusplus
 }
 #endif
