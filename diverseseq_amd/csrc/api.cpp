@@ -34,7 +34,22 @@ static int dev_poison(dvs_ctx *ctx, void *p, size_t sz, const char *what) {
     return e == hipSuccess ? DVS_OK : dvs_hip_fail(ctx, e, what);
 }
 
+// Every request for memory passes here first: counted (dvs_ctx_block_stats), and with DVS_TEST_KNOBS=refuse_block_<i>
+// request number i since the knobs were read is refused -- the ordinary DVS_ERR_NOMEM return, taken on purpose, with
+// neither the runtime called nor a cache touched.  Requests before and after it behave as always.
+static bool gate_refuses(dvs_ctx *ctx, const char *what) {
+    const uint64_t nth = ++ctx->block_requests;
+    if (__builtin_expect(ctx->knobs.test_refuse_block == 0, 1) || nth != ctx->knobs.test_refuse_block) return false;
+    dvs_set_error(ctx, DVS_ERR_NOMEM, "%s: request %llu refused by the test knob refuse_block_%llu", what,
+                  (unsigned long long)nth, (unsigned long long)ctx->knobs.test_refuse_block);
+    return true;
+}
+
 int dvs_dev_alloc(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what) {
+    if (gate_refuses(ctx, what)) {
+        *ptr = nullptr;
+        return DVS_ERR_NOMEM;
+    }
     const size_t sz = ((bytes ? bytes : 1) + 4095) & ~size_t(4095);
     auto it = ctx->pool.find(sz);
     if (it != ctx->pool.end()) {
@@ -73,21 +88,44 @@ void dvs_dev_free(dvs_ctx *ctx, void *ptr) {
 }
 
 int dvs_pinned_get(dvs_ctx *ctx, void **ptr) {
+    if (gate_refuses(ctx, "pinned page")) {
+        *ptr = nullptr;
+        return DVS_ERR_NOMEM;
+    }
     if (!ctx->pinned_pool.empty()) {
         *ptr = ctx->pinned_pool.back();
         ctx->pinned_pool.pop_back();
+        ctx->pinned_out++;
         if (__builtin_expect(ctx->knobs.test_poison_blocks, 0)) memset(*ptr, 0xFF, 4096);
         return DVS_OK;
     }
     hipError_t e = hipHostMalloc(ptr, 4096, hipHostMallocDefault);
-    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "hipHostMalloc");
+    if (e != hipSuccess) {
+        *ptr = nullptr;
+        return dvs_hip_fail(ctx, e, "hipHostMalloc");
+    }
+    ctx->pinned_out++;
     if (__builtin_expect(ctx->knobs.test_poison_blocks, 0)) memset(*ptr, 0xFF, 4096);
     return DVS_OK;
 }
 void dvs_pinned_put(dvs_ctx *ctx, void *ptr) {
     if (!ptr) return;
-    if (ctx) ctx->pinned_pool.push_back(ptr);
-    else (void)hipHostFree(ptr);
+    if (ctx) {
+        ctx->pinned_pool.push_back(ptr);
+        ctx->pinned_out--;
+    } else {
+        (void)hipHostFree(ptr);
+    }
+}
+int dvs_pinned_grow(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what) {
+    *ptr = nullptr;
+    if (gate_refuses(ctx, what)) return DVS_ERR_NOMEM;
+    const hipError_t e = hipHostMalloc(ptr, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        *ptr = nullptr;
+        return dvs_hip_fail(ctx, e, what);
+    }
+    return DVS_OK;
 }
 hipEvent_t dvs_event_get(dvs_ctx *ctx) {
     if (!ctx->event_pool.empty()) {
@@ -144,6 +182,7 @@ void dvs_knobs_from_env(dvs_knobs *k) {
     k->test_rowlog_ring = 0;
     if (const char *rr = tk ? strstr(tk, "rowlog_ring_") : nullptr) k->test_rowlog_ring = uint32_t(strtoul(rr + 12, nullptr, 10));
     k->test_poison_blocks = tk && strstr(tk, "poison_blocks") != nullptr;
+    if (const char *rb = tk ? strstr(tk, "refuse_block_") : nullptr) k->test_refuse_block = strtoull(rb + 13, nullptr, 10);
     if (const char *ic = tk ? strstr(tk, "ingest_chunk_") : nullptr)
         k->test_ingest_chunk = uint32_t(std::min<unsigned long>(std::max<unsigned long>(strtoul(ic + 13, nullptr, 10), 1ul), 256ul));
     if (const char *rc = tk ? strstr(tk, "ingest_reccap_") : nullptr)
@@ -157,6 +196,7 @@ int dvs_abi_version(void) { return DVS_ABI_VERSION; }
 int dvs_ctx_refresh_knobs(dvs_ctx *ctx) {
     if (!ctx) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     dvs_knobs_from_env(&ctx->knobs);
+    ctx->block_requests = 0;
     ctx->off_cache.n_off = 0;  // (the tile lists of the last build were made under the old switches)
     return DVS_OK;
 }
@@ -289,6 +329,16 @@ int dvs_ctx_trim(dvs_ctx *ctx) {
     return DVS_OK;
 }
 
+int dvs_ctx_block_stats(const dvs_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return DVS_ERR_VALUE;
+    out[0] = ctx->block_requests;
+    out[1] = ctx->live.size();
+    out[2] = 0;
+    for (const auto &kv : ctx->live) out[2] += kv.second;
+    out[3] = ctx->pinned_out;
+    return DVS_OK;
+}
+
 int dvs_ctx_sync(dvs_ctx *ctx) {
     if (!ctx) return DVS_ERR_VALUE;
     DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -339,8 +389,14 @@ static int matrix_alloc(dvs_ctx *ctx, dvs_matrix *m) {
 
 // how every constructor ends: the matrix handed over, or released with the error that stopped it
 static int matrix_made(int rc, dvs_matrix *m, dvs_matrix **out) {
-    if (rc) dvs_matrix_destroy(m);
-    else *out = m;
+    if (rc) {
+        // (whatever the constructor enqueued before it failed may still write the blocks: waited for before they go back
+        // to the cache, whose next user may be on another stream)
+        if (m->ctx) (void)hipStreamSynchronize(m->ctx->stream);
+        dvs_matrix_destroy(m);
+    } else {
+        *out = m;
+    }
     return rc;
 }
 

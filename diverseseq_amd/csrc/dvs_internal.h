@@ -67,6 +67,11 @@ struct dvs_knobs {
     // test-only (DVS_TEST_KNOBS=ingest_reccap_<n>): the ingest's record arrays start with room for n >= 1 records
     // instead of nbytes / 256 + 2^20, so that a file of a few records overflows them and the last pass is repeated
     uint64_t test_ingest_reccap = 0;
+    // test-only (DVS_TEST_KNOBS=refuse_block_<i>, i >= 1): request number i that the context makes of dvs_dev_alloc,
+    // dvs_pinned_get or dvs_pinned_grow after it has read its knobs -- served from a cache or not -- is refused, once:
+    // NULL and DVS_ERR_NOMEM, the message naming the block and the knob, the runtime not called and no cache touched
+    // (0: nothing is refused).  tests/test_gpu_refused_blocks.py walks i over every request of every operation
+    uint64_t test_refuse_block = 0;
 };
 void dvs_knobs_from_env(dvs_knobs *k);
 
@@ -103,6 +108,11 @@ struct dvs_ctx {
     std::vector<hipEvent_t> event_pool;    // recycled HIP events
     std::map<void *, size_t> live;
     size_t pool_bytes = 0;
+    // what dvs_ctx_block_stats reports beside `live`: the requests made of dvs_dev_alloc, dvs_pinned_get and
+    // dvs_pinned_grow since the knobs were last read (refused ones too), and the 4 KiB pinned blocks handed out and not
+    // yet put back
+    uint64_t block_requests = 0;
+    uint64_t pinned_out = 0;
     // one reference for the owner (dropped by dvs_ctx_destroy) and one per matrix, selection and
     // sequence batch made from this context: their destroy functions hand blocks back to the caches
     // above, so the context outlives them whatever order the caller tears things down in
@@ -168,6 +178,9 @@ struct PooledBuf {
     T *as() { return static_cast<T *>(p); }
 };
 int dvs_pinned_get(dvs_ctx *ctx, void **ptr);  // 4 KiB pinned block from the ctx cache
+// a pinned block of `bytes` of its own, for the two staging blocks that grow (ctx->h_pack, the offsets cache's h_off):
+// counted and refusable like the others, not cached -- its owner keeps it and frees it with hipHostFree
+int dvs_pinned_grow(dvs_ctx *ctx, void **ptr, size_t bytes, const char *what);
 // pack.hip: ctx->h_pack, the context's large pinned staging block, with room for `bytes` and read by nobody any more; a
 // user that does not wait for its last copy out of the block records ctx->pack_ev behind it
 int dvs_pinned_stage(dvs_ctx *ctx, size_t bytes, const char *what);

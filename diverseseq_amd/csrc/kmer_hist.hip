@@ -541,11 +541,7 @@ int dvs_hist_prepare(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint3
             oc.h_off = nullptr;
             oc.h_cap = 0;
             const size_t cap = std::max<size_t>(n_off + n_off / 4, 1024);
-            const hipError_t he = hipHostMalloc((void **)&oc.h_off, cap * 8, hipHostMallocDefault);
-            if (he != hipSuccess) {
-                oc.h_off = nullptr;
-                return dvs_hip_fail(ctx, he, "pinned offsets block");
-            }
+            if (int rc = dvs_pinned_grow(ctx, (void **)&oc.h_off, cap * 8, "pinned offsets block")) return rc;
             oc.h_cap = cap;
         }
         oc.n_off = 0;  // (the block is being rewritten: no hit on a half-written copy after an error)

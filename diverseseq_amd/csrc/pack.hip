@@ -119,11 +119,7 @@ int dvs_pinned_stage(dvs_ctx *ctx, size_t bytes, const char *what) {
         ctx->h_pack = nullptr;
         ctx->h_pack_cap = 0;
         const size_t cap = bytes + bytes / 8;
-        const hipError_t he = hipHostMalloc(&ctx->h_pack, cap, hipHostMallocDefault);
-        if (he != hipSuccess) {
-            ctx->h_pack = nullptr;
-            return dvs_hip_fail(ctx, he, what);
-        }
+        if (int rc = dvs_pinned_grow(ctx, &ctx->h_pack, cap, what)) return rc;
         ctx->h_pack_cap = cap;
     }
     return DVS_OK;

@@ -1451,11 +1451,17 @@ extern "C" int dvs_select_run(dvs_ctx *ctx, const dvs_matrix *m, const uint32_t 
     s->dev.nlabels = a.nlabels;
     s->dev.totals = m->d_totals;
     s->dev.rowH = m->d_entropy;
+    // (a set-up that fails has uploads, fills and perhaps kernels queued on the context's stream over blocks that sel_free
+    // is about to hand back: the stream is waited for first; the side streams are sel_free's own, used_side_streams)
+    auto failed = [&](int code) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return code;
+    };
     if ((rc = sel_geometry(ctx, s.get(), order, labels)) || (rc = sel_alloc(ctx, s.get(), order, labels)) ||
         (rc = sel_prepare_engine(ctx, s.get(), order, labels)) || (rc = sel_read_seeds(ctx, s.get(), order)))
-        return rc;
+        return failed(rc);
     sel_init_ctl(ctx, s.get());
-    if ((rc = dvs_mat_dispatch(m, [&](auto *mp) { return sel_start(ctx, s.get(), mp); }))) return rc;
+    if ((rc = dvs_mat_dispatch(m, [&](auto *mp) { return sel_start(ctx, s.get(), mp); }))) return failed(rc);
     *out = s.release();
     return DVS_OK;
 }
@@ -1547,23 +1553,28 @@ extern "C" int dvs_select_delta_jsd(dvs_ctx *ctx, const dvs_select *s, const dvs
         }
         qlabels = qtrans.data();
     }
-    DVS_HIP(ctx, hipMalloc(&d_out, size_t(q->nrows) * 8));
-    if (qlabels) {
-        DVS_HIP(ctx, hipMalloc(&d_lab, size_t(q->nrows) * 4));
-        DVS_HIP(ctx, hipMemcpyAsync(d_lab, qlabels, size_t(q->nrows) * 4, hipMemcpyHostToDevice,
-                                    ctx->stream));
+    // (blocks of the context's cache; whatever fails once something is enqueued, the stream is waited for before they go back)
+    PooledBuf b_out{ctx}, b_lab{ctx};
+    if (int rc = dvs_dev_alloc(ctx, &b_out.p, size_t(q->nrows) * 8, "query scores")) return rc;
+    if (qlabels)
+        if (int rc = dvs_dev_alloc(ctx, &b_lab.p, size_t(q->nrows) * 4, "query labels")) return rc;
+    d_out = b_out.as<double>();
+    d_lab = b_lab.as<uint32_t>();
+    hipError_t e = hipSuccess;
+    if (qlabels) e = hipMemcpyAsync(d_lab, qlabels, size_t(q->nrows) * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        dvs_mat_dispatch(q, [&](auto *qp) {
+            using T = std::remove_cv_t<std::remove_pointer_t<decltype(qp)>>;
+            hipLaunchKernelGGL((score_kernel<T>), dim3(q->nrows), dim3(LOO_THREADS), 0, ctx->stream, s->dev, qp,
+                               q->d_totals, q->d_entropy, d_lab, d_out);
+            return 0;
+        });
+        e = hipGetLastError();
     }
-    dvs_mat_dispatch(q, [&](auto *qp) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(qp)>>;
-        hipLaunchKernelGGL((score_kernel<T>), dim3(q->nrows), dim3(LOO_THREADS), 0, ctx->stream, s->dev, qp,
-                           q->d_totals, q->d_entropy, d_lab, d_out);
-        return 0;
-    });
-    DVS_HIP(ctx, hipGetLastError());
-    DVS_HIP(ctx, hipMemcpyAsync(out, d_out, size_t(q->nrows) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_out);
-    if (d_lab) (void)hipFree(d_lab);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, size_t(q->nrows) * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "dvs_select_delta_jsd");
     return DVS_OK;
 }
 

@@ -96,14 +96,18 @@ static int selftest_run(dvs_ctx *ctx, void (*kernel)(W *), dim3 grid, R *out) {
     static_assert(sizeof(W) == 8 && sizeof(R) == 8, "one 8-byte word");
     if (!ctx || !out) return dvs_set_error(ctx, DVS_ERR_VALUE, "null argument");
     DVS_HIP(ctx, hipSetDevice(ctx->device));
-    W *d = nullptr;
-    DVS_HIP(ctx, hipMalloc(&d, 8));
-    DVS_HIP(ctx, hipMemsetAsync(d, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, d);
-    DVS_HIP(ctx, hipGetLastError());
-    DVS_HIP(ctx, hipMemcpyAsync(out, d, 8, hipMemcpyDeviceToHost, ctx->stream));
-    DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d);
+    PooledBuf word{ctx};  // (waited for on every path below before it goes back to the cache)
+    if (int rc = dvs_dev_alloc(ctx, &word.p, 8, "self-test word")) return rc;
+    W *d = word.as<W>();
+    hipError_t e = hipMemsetAsync(d, 0, 8, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return dvs_hip_fail(ctx, e, "self-test");
     return DVS_OK;
 }
 

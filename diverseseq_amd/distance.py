@@ -327,9 +327,9 @@ class Sketches:
 
 class OrdinationOps:
     """The ordination operations of a `DeviceSide` -- principal coordinates and the projection into a fitted ordination
-    -- which it inherits: `DeviceSide.pcoa`, `DeviceSide.pcoa_project`.  They stand in a base class of their own because
-    tests/test_blocks_host.py pins the operations `DeviceSide` itself defines to those with a poisoned-block case in
-    its table; the cases of these two are in tests/test_gpu_pcoa.py."""
+    -- which it inherits: `DeviceSide.pcoa`, `DeviceSide.pcoa_project`.  They stand in a base class of their own, as
+    every operation added after the first ten does; tests/test_blocks_host.py collects the operations of `DeviceSide`
+    through its base classes and demands a case of its table for each in every mode (more cases: tests/test_gpu_pcoa.py)."""
 
     def pcoa(self, n_axes: int = 3, *, tol: float = 1e-8, max_basis: int | None = None, strict: bool = True) -> "PCoA":
         """the principal coordinates of the distances (`PCoA`), the N x N matrix written and only read in HBM"""
@@ -352,7 +352,7 @@ class OrdinationOps:
 
 class MedoidOps:
     """k-medoids as an operation of a `DeviceSide`, which inherits it: `DeviceSide.kmedoids`.  In a base class of its
-    own for the reason `OrdinationOps` gives; its poisoned-block cases are in tests/test_gpu_kmedoids.py."""
+    own as `OrdinationOps` is; more poisoned-block cases are in tests/test_gpu_kmedoids.py."""
 
     def kmedoids(self, n_medoids: int, *, init="build", max_swaps: int = 300) -> "KMedoids":
         """k-medoids of the distances (`KMedoids`), the N x N matrix written and only read in HBM.  init: "build"
@@ -368,7 +368,7 @@ class MedoidOps:
 
 class GroupOps:
     """PERMANOVA as an operation of a `DeviceSide`, which inherits it: `DeviceSide.permanova`.  In a base class of its
-    own for the reason `OrdinationOps` gives; its poisoned-block cases are in tests/test_gpu_permanova.py."""
+    own as `OrdinationOps` is; more poisoned-block cases are in tests/test_gpu_permanova.py."""
 
     def permanova(self, grouping, *, permutations: int = 999, seed=None, strata=None) -> "PERMANOVA":
         """PERMANOVA of `grouping` over the distances (`PERMANOVA`), the N x N matrix written and only read in HBM; the
@@ -437,7 +437,7 @@ def run_mst(ctx: engine.Context | None, n: int, src: _lib.Source | None, core: n
 
 class SpanningOps:
     """The minimum spanning tree as an operation of a `DeviceSide`, which inherits it: `DeviceSide.mst`.  In a base
-    class of its own for the reason `OrdinationOps` gives; its poisoned-block cases are in tests/test_gpu_mst.py."""
+    class of its own as `OrdinationOps` is; more poisoned-block cases are in tests/test_gpu_mst.py."""
 
     def mst(self, rows=None, *, min_samples: int | None = None, core=None) -> "MST":
         """the minimum spanning tree (`MST`) of the distances of this side's `rows` (None: all), strip by strip: the

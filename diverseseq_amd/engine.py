@@ -135,6 +135,14 @@ class Context:
         """re-read the DVS_* environment switches (they are otherwise read once, when the context is made)"""
         self.check(self._L.dvs_ctx_refresh_knobs(self._h))
 
+    def block_stats(self) -> dict:
+        """what the context's memory gates have seen (dvs_ctx_block_stats; host only): `requests` for a device or pinned
+        block since the switches were last read, `live_blocks` and `live_bytes` of device memory handed out and not
+        yet given back, `pinned_out` 4 KiB pinned blocks likewise"""
+        out = (C.c_uint64 * 4)()
+        self.check(self._L.dvs_ctx_block_stats(self._h, out))
+        return {"requests": int(out[0]), "live_blocks": int(out[1]), "live_bytes": int(out[2]), "pinned_out": int(out[3])}
+
     def set_timing(self, on: bool):
         self.check(self._L.dvs_ctx_set_timing(self._h, int(on)))
 

@@ -330,6 +330,11 @@ int dvs_ctx_set_timing(dvs_ctx *ctx, int on);
  * read once, when a context is created; nothing on a per-call path looks at the environment.  This
  * re-reads them for an existing context (tests and A/B measurements that flip a switch in between). */
 int dvs_ctx_refresh_knobs(dvs_ctx *ctx);
+/* test aid: what the context's memory gates have seen.  out[0]: requests for a device block or a pinned host block
+ * since the switches were last read (dvs_ctx_create, dvs_ctx_refresh_knobs), served or not; out[1]: device blocks
+ * handed out and not yet given back; out[2]: their bytes; out[3]: 4 KiB pinned blocks handed out and not yet given
+ * back.  Host only.  (An addition to ABI 5.) */
+int dvs_ctx_block_stats(const dvs_ctx *ctx, uint64_t out[4]);
 /* measurement aid: average duration of ONE scan_kernel launch over every streamed row of
  * the selection's stream against its current state, with an unreachable threshold (no
  * events, state untouched): the steady-state streaming rate of the scan arithmetic */

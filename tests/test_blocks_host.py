@@ -31,6 +31,7 @@ from test_nj_host import (dyadic_tree, general_yardstick, length_tolerance, rest
                           truth)
 
 POISON = "poison_blocks"   # the word of DVS_TEST_KNOBS
+REFUSE = "refuse_block_"   # ... and the one tests/test_gpu_refused_blocks.py walks: refuse_block_<i>
 N = 257                    # rows of every square matrix: the N x N x 8-byte block (528 392 -> 528 384 + 4 096 bytes,
                            # rounded to 4 KiB: 532 480) passes between mash, jsd, euclidean, linkage, nj, cophenet, max-min
 MASH_RTOL = 1e-13          # a mash cell against the oracle (tests/test_gpu_cross.py, test_gpu_parity.py)
@@ -59,9 +60,11 @@ class ErrorCase(NamedTuple):
     raises: type
     follower: str       # the case that runs right behind it in schedule (c): it asks for blocks of the same sizes
     host: Callable      # host(): the same refusal from the reference's side, or None where it has none
+    setup: Callable = lambda ctx: None  # setup(ctx): what run makes before the refused call, made and closed again
 
 
-FAMILIES = ("distances", "trees", "cophenet_clusters", "maxmin", "sketches", "histograms", "ingest", "selections")
+FAMILIES = ("distances", "trees", "cophenet_clusters", "maxmin", "sketches", "histograms", "ingest", "selections", "neighbours",
+            "ordination", "medoids", "spanning", "groups")
 
 
 def _done(keep, *handles):
@@ -805,6 +808,10 @@ def _selection_out(ctx, sel, shape: int, extras: bool) -> dict:
     ctx.sync()
     out["gathered_rows"], out["gathered_meta"] = rows_t.cpu().numpy(), meta_t.cpu().numpy()
     if extras:
+        # (labels no member carries: the scores of the unlabelled call, through the call's second block)
+        q = ctx.build_matrix(list(query_seqs(shape)), k, 4)
+        out["query_delta_jsd_labelled"] = sel.delta_jsd(q, np.full(q.nrows, 0xFFFFFFFF, dtype=np.uint32))
+        q.close()
         out["assign_idx"], out["assign_val"] = sel.assign(2, "jsd")
         out["bench_scan_rows"] = np.array([sel.bench_scan(1)[1]])
     return out
@@ -840,6 +847,7 @@ def _check_selection_out(out, exp, shape, position_of=lambda p: p):
     assert out["gathered_totals"].tolist() == [1] * n + [0] * 3 and out["gathered_source_rows"].tolist() == list(range(n + 3))
     np.testing.assert_allclose(out["gathered_entropy"][:n], eent, rtol=RTOL)
     if "assign_idx" in out:
+        assert same_bits(out["query_delta_jsd_labelled"], out["query_delta_jsd"])
         members = out["positions"].astype(np.int64)
         assert (out["assign_idx"][members, 0] == np.arange(n)).all() and (out["assign_val"][members, 0] == 0).all()
         assert out["bench_scan_rows"][0] == SELECT_SHAPES[shape][0] - SELECT_SHAPES[shape][3]
@@ -853,6 +861,16 @@ def collision_seqs() -> tuple:
 @functools.lru_cache(maxsize=None)
 def collision_ref():
     return oracle.nmost(list(collision_seqs()), 10, 3, 4)
+
+
+@functools.lru_cache(maxsize=None)
+def head_phase_seqs() -> tuple:
+    return tuple(synth_seqs(17_600, 120, 17_603, ragged=True, invalid_frac=0.001))
+
+
+@functools.lru_cache(maxsize=None)
+def head_phase_ref():
+    return oracle.nmost(list(head_phase_seqs()), 10, 4, 4)
 
 
 def selection_cases():
@@ -930,8 +948,8 @@ def selection_cases():
         del ta, tb
         return out
 
-    def check_collision(out):
-        exp = collision_ref()
+    def check_collision(out, exp=None):
+        exp = exp or collision_ref()
         elab, edelta, eent, efreq = exp.members(with_freqs=True)
         assert out["positions"].tolist() == elab.tolist() and (out["kfreqs"] == efreq).all()
         np.testing.assert_allclose(out["delta_jsd"], edelta, rtol=RTOL, atol=1e-13)
@@ -943,6 +961,32 @@ def selection_cases():
     yield Case("select_behind_a_closed_unwaited_build", "selections", ("Context.build_matrix_device", "CountMatrix.select"),
                "oracle selection", run_collision, check_collision, collision_ref, {})
 
+    def run_head_phase(ctx, keep=None):
+        """a device-resident build of more than 17 408 rows is split -- the head rows first, the rest on the CU-masked
+        stream -- and the selection behind it starts its persistent engine on the head CUs meanwhile: its set-up and
+        the head phase's blocks go out on side streams (tests/test_gpu_configs.py test_head_phase_of_a_split_build_vs_oracle)"""
+        import torch
+
+        data, offs = oracle.concat(list(head_phase_seqs()))
+        t = torch.from_numpy(np.concatenate([data, np.zeros(16, np.uint8)])).to("cuda:0")
+        torch.cuda.synchronize()
+        m = ctx.build_matrix_device(t.data_ptr(), offs, 4, 4)
+        sel = m.nmost(10)
+        mem, s = sel.members(), sel.summary()
+        out = dict(positions=mem.positions, delta_jsd=mem.delta_jsd, entropy=mem.entropy, kfreqs=mem.kfreqs,
+                   summary=np.array([float(getattr(s, f)) for f in SUMMARY_FIELDS]), count_bytes=np.array([m.count_bytes]))
+        _done(keep, sel, m)
+        ctx.sync()
+        del t
+        return out
+
+    def check_head_phase(out):
+        assert out["count_bytes"][0] == 2 and len(head_phase_seqs()) - 1024 >= 16 * 1024  # (what makes the build split)
+        check_collision(out, head_phase_ref())
+
+    yield Case("select_head_phase", "selections", ("Context.build_matrix_device", "CountMatrix.select"), "oracle selection",
+               run_head_phase, check_head_phase, head_phase_ref, {})
+
     for shape in range(len(SELECT_SHAPES)):
         yield case(shape, "nmost", ops=("Selection.assign", "Selection.member_rows", "Selection.bench_scan", "Selection.diversify"))
         yield case(shape, "no_persist", env={"DVS_NO_PERSIST": "1"})
@@ -953,10 +997,361 @@ def selection_cases():
         yield case(shape, "resident", ops=("Context.build_matrix_device",))
 
 
+# ------------------------------------------------------------------ the operations added after the first table
+
+def _put(out, name, got):
+    """a NamedTuple result into the outputs, field by field (scalars as 0-d arrays)"""
+    for field, value in zip(got._fields, got):
+        out[f"{name}.{field}"] = np.asarray(value)
+
+
+def _get(out, name, cls):
+    """... and back: arrays as they are, scalars as Python's"""
+    return cls(*(out[f"{name}.{f}"] if out[f"{name}.{f}"].ndim else out[f"{name}.{f}"].item() for f in cls._fields))
+
+
+def _mode_side(ctx, mode, clean=True, mash=(12, 400)):
+    """the side of one distance mode over the 257 sequences (mash: always the clean rows, two empty sketches would
+    divide by zero)"""
+    if mode == "mash":
+        return distance.device_side(list(seqs257(True)), "mash", *mash, 4, False, ctx=ctx)
+    return distance.device_side(list(seqs257(clean)), mode, 3, 4, ctx=ctx)
+
+
+def _mode_ref(mode, clean=True, mash=(12, 400)) -> np.ndarray:
+    """the CPU reference's matrix of that side"""
+    if mode == "mash":
+        return sketch_ref("clean257", *mash, 4, False)[1]
+    return (euclid_ref if mode == "euclidean" else jsd_ref)(clean)
+
+
+def _per_mode(name, family, ops, reference, run, check, ref, env) -> list:
+    """one case per distance mode (a case over all three would make three times the requests, each run three times as
+    long): run(ctx, mode) -> outputs, check(out, mode), ref(mode)"""
+    return [Case(f"{name}_{mode}257", family, tuple(f"DeviceSide.{op}:{mode}" for op in ops[0]) + tuple(ops[1]), reference,
+                 functools.partial(lambda ctx, keep=None, *, mode: run(ctx, mode, keep), mode=mode),
+                 functools.partial(check, mode=mode), functools.partial(ref, mode), env)
+            for mode in distance.DeviceSide.MODE_NAMES]
+
+
+# radii between two cell values of the CPU references' matrices (about 2 % of the cells for the lists, about two edges a
+# row for the components); the lists are checked against the device's own matrix, so the exact place does not matter
+WITHIN_RADII = {"mash": (0.33, 0.30), "euclidean": (0.0428, 0.0407), "jsd": (0.0217, 0.0195), "matrix": (0.02, 0.008)}
+
+
+def neighbour_cases():
+    from test_within_host import expected_components, expected_within
+
+    env = {"DVS_CROSS_STRIP_ROWS": "7"}  # 37 strips reuse one strip block and grow one pair buffer
+
+    def check_lists(out, name, d, radii):
+        nb, tc = _get(out, name + "_within", distance.Neighbours), _get(out, name + "_clusters", distance.ThresholdClusters)
+        rs, idx, val = expected_within(d, radii[0], skip_self=True)
+        assert np.array_equal(nb.row_start, rs) and np.array_equal(nb.index, idx) and same_bits(nb.distance, val), name
+        assert N < idx.size < N * N // 4, (name, idx.size)
+        labels = expected_components(d, radii[1])
+        assert np.array_equal(tc.labels, labels) and tc.n_clusters == labels.max() + 1, name
+        assert np.array_equal(tc.sizes, np.bincount(labels)) and 1 < tc.n_clusters < N, (name, tc.n_clusters)
+
+    def run_matrix(ctx, keep=None):
+        out = {}
+        _put(out, "matrix_within", cluster.within(symmetric257(), WITHIN_RADII["matrix"][0], ctx=ctx))
+        _put(out, "matrix_clusters", cluster.threshold_clusters(symmetric257(), WITHIN_RADII["matrix"][1], ctx=ctx))
+        return out
+
+    yield Case("within_matrix257", "neighbours", ("cluster.within", "cluster.threshold_clusters"),
+               "expected_within, expected_components", run_matrix,
+               lambda out: check_lists(out, "matrix", symmetric257(), WITHIN_RADII["matrix"]),
+               lambda: (expected_within(symmetric257(), WITHIN_RADII["matrix"][0], True),
+                        expected_components(symmetric257(), WITHIN_RADII["matrix"][1])), env)
+
+    def run_mode(ctx, mode, keep=None):
+        side = _mode_side(ctx, mode, clean=False, mash=(8, 50))  # (row 7 of the count modes: NaN cells, never listed)
+        out = {"distances": side.distances()}
+        _put(out, "mode_within", side.within(side, WITHIN_RADII[mode][0], skip_self=True))
+        _put(out, "mode_clusters", side.threshold_clusters(WITHIN_RADII[mode][1]))
+        _done(keep, side)
+        return out
+
+    def check_mode(out, mode):
+        check_lists(out, "mode", out["distances"], WITHIN_RADII[mode])
+        if mode != "mash":
+            assert np.isnan(out["distances"][7, 8]) and 7 not in out["mode_within.index"]
+
+    def ref_mode(mode):  # (the check: over the device's own matrix; here: over the oracle's)
+        d = _mode_ref(mode, False, (8, 50))
+        return expected_within(d, WITHIN_RADII[mode][0], True), expected_components(d, WITHIN_RADII[mode][1])
+
+    yield from _per_mode("within", "neighbours", (("within", "threshold_clusters", "distances"), ()),
+                         "expected_within, expected_components over the mode's own matrix", run_mode, check_mode, ref_mode, env)
+
+
+def canonical_cases():
+    from test_canonical_host import ENTROPY_TOL, folded, ragged
+    from test_distance_truth_host import truth_euclid_rows, truth_jsd_rows
+
+    seqs, k = list(ragged(65)), 3
+
+    def run(ctx, keep=None):
+        f = ctx.build_matrix(seqs, k, canonical=True)
+        out = _matrix_out(f)
+        for mode in ("jsd", "euclidean"):
+            out[mode] = distance.DeviceSide(f, mode).distances()
+        plain = ctx.build_matrix(seqs, k)
+        again = plain.canonical()  # (the fold of a matrix that stays open)
+        out["again_counts"] = again.counts()
+        _done(keep, f, plain, again)
+        return out
+
+    def check(out):
+        """tests/test_gpu_canonical.py test_fold_against_the_yardstick, test_distances_of_the_folded_matrix_against_the_truth"""
+        counts, totals, ent = folded(seqs, k)
+        assert out["count_bytes"][0] == 2
+        assert np.array_equal(out["counts"], counts) and np.array_equal(out["again_counts"], counts)
+        assert np.array_equal(out["totals"], totals)
+        live = np.flatnonzero(totals > 0)
+        assert (np.abs(out["entropy"][live] - ent[live]) <= ENTROPY_TOL * np.maximum(1.0, np.abs(ent[live]))).all()
+        pairs = np.array([(i, j) for a, i in enumerate(live) for j in live[a + 1:]])
+        err = np.abs(out["jsd"][pairs[:, 0], pairs[:, 1]].astype(np.longdouble) - truth_jsd_rows(counts, pairs))
+        assert float(err.max()) <= tol_derived(counts.shape[1])
+        truth = truth_euclid_rows(counts, pairs)
+        rel = np.abs(out["euclidean"][pairs[:, 0], pairs[:, 1]].astype(np.longdouble) - truth) / truth
+        assert (truth > 0).all() and float(rel.max()) <= EUCLID_RTOL
+        dead = np.flatnonzero(totals == 0)
+        assert dead.size == 3 and np.isnan(out["jsd"][dead][:, live]).all() and (np.diag(out["jsd"]) == 0).all()
+
+    yield Case("canonical_k3", "histograms", ("Context.build_matrix", "CountMatrix.canonical", "DeviceSide.distances:jsd",
+                                              "DeviceSide.distances:euclidean"),
+               "test_canonical_host.folded; truth_jsd_rows (tol_derived), truth_euclid_rows (EUCLID_RTOL)", run, check,
+               lambda: folded(seqs, k), {})
+
+
+def _pcoa_holds(fit, d, label, n_axes):
+    """tests/test_gpu_pcoa.py check_contract over a yardstick of the matrix d itself: the sign rule, honest residuals,
+    orthonormal vectors orthogonal to 1, eigenvalues within Weyl's bound, the definitions"""
+    from test_pcoa_host import EPS, Yardstick, sign_rule
+
+    y, n, m = Yardstick(d), d.shape[0], n_axes
+    unit = y.unit(n)
+    assert fit.converged and fit.vectors.shape == fit.coordinates.shape == (n, m) and (np.diff(fit.values) <= 0).all(), label
+    assert same_bits(sign_rule(fit.vectors), fit.vectors), label
+    true_res = np.linalg.norm(y.B @ fit.vectors - fit.vectors * fit.values, axis=0)
+    basis = max(fit.basis, 1)
+    assert np.abs(true_res - fit.residuals).max() <= unit, label
+    assert np.abs(fit.vectors.T @ fit.vectors - np.eye(m)).max() <= (n + 8) * EPS * basis, label
+    assert np.abs(fit.vectors.sum(axis=0)).max() <= (n + 8) * EPS * basis * np.sqrt(n), label
+    assert (np.abs(fit.values - y.values[:m]) <= fit.residuals + y.residuals[:m] + np.finfo(float).tiny).all(), label
+    pos = fit.values > 0
+    assert same_bits(fit.coordinates, np.where(pos, fit.vectors * np.sqrt(np.where(pos, fit.values, 0.0)), 0.0)), label
+    assert same_bits(fit.proportion, fit.values / fit.trace) and abs(fit.trace - y.trace) <= 4 * n * EPS * y.trace, label
+    assert np.abs(fit.row_means - y.mu).max() <= 4 * n * EPS * np.abs(y.mu).max(), label
+
+
+def ordination_cases():
+    import test_pcoa_host as ph
+
+    shapes = (("cloud6", 9), ("jsd", 3))  # nine axes: one past a chunk of the Ritz kernel; a non-Euclidean matrix
+
+    def run_matrix(ctx, keep=None):
+        out = {}
+        for kind, m in shapes:
+            _put(out, kind, cluster.pcoa(ph.case(kind, N), m, ctx=ctx))
+        return out
+
+    def check_matrix(out):
+        for kind, m in shapes:
+            _pcoa_holds(_get(out, kind, distance.PCoA), ph.case(kind, N), kind, m)
+
+    yield Case("pcoa_matrix257", "ordination", ("cluster.pcoa",), "test_pcoa_host.Yardstick, check_contract's bounds",
+               run_matrix, check_matrix, lambda: [ph.yardstick(kind, N) for kind, _ in shapes], {})
+
+    marks = np.arange(0, N, 2)  # the fitted rows of the projection: 129 of the 257
+
+    def run_mode(ctx, mode, keep=None):
+        side = _mode_side(ctx, mode)
+        out = {"distances": side.distances()}
+        _put(out, "fused", side.pcoa(3))
+        _put(out, "route", cluster.pcoa(out["distances"], 3, ctx=ctx))
+        fit = cluster.pcoa(side.cross_distances(side, marks, marks), 3, ctx=ctx)
+        _put(out, "marks", fit)
+        out["projected"] = side.pcoa_project(fit, side, None, marks)
+        _done(keep, side)
+        return out
+
+    def check_mode(out, mode):
+        """tests/test_gpu_pcoa.py: the fused route is the matrix route bit for bit; a projection against Gower's formula
+        in numpy over the same cells (test_projection_row_lists_nan_rows_and_many_axes' bound)"""
+        d, fused = out["distances"], _get(out, "fused", distance.PCoA)
+        assert all(same_bits(a, b) for a, b in zip(fused, _get(out, "route", distance.PCoA))), mode
+        _pcoa_holds(fused, d, mode, 3)
+        fit = _get(out, "marks", distance.PCoA)
+        _pcoa_holds(fit, d[np.ix_(marks, marks)], mode + " marks", 3)
+        ref = ph.project(d[:, marks], fit.values, fit.vectors, fit.row_means)
+        unit = marks.size * ph.EPS * np.abs(fit.coordinates).max() / np.sqrt(fit.values[fit.values > 0].min() / fit.values[0])
+        assert np.abs(out["projected"] - ref).max() <= 8 * unit, mode
+        assert np.abs(out["projected"][marks] - fit.coordinates).max() <= 1e-9 * np.abs(fit.coordinates).max(), mode
+
+    yield from _per_mode("pcoa", "ordination", (("pcoa", "pcoa_project", "cross_distances", "distances"), ("cluster.pcoa",)),
+                         "the yardstick over the mode's own matrix; test_pcoa_host.project", run_mode, check_mode,
+                         lambda mode: ph.Yardstick(_mode_ref(mode)), {})
+
+
+def medoid_cases():
+    import kmedoids_cases as kc
+
+    exact = tuple(kc.Case("clustered", N, k, init, 300, 2) for k in (7, 17) for init in ("build", "given"))
+    assert all(c in kc.EXACT_CASES for c in exact)
+
+    def run_matrix(ctx, keep=None):
+        out = {}
+        for c in exact:
+            init = "build" if c.init == "build" else kc.given_medoids(c)
+            _put(out, c.id, cluster.kmedoids(kc.case_matrix(c), c.k, init=init, max_swaps=c.max_swaps, ctx=ctx))
+        return out
+
+    def check_matrix(out):
+        """tests/test_gpu_kmedoids.py assert_is_ref"""
+        for c in exact:
+            got, ref = _get(out, c.id, distance.KMedoids), kc.case_ref(c)
+            for f in ("medoids", "swaps", "td", "labels", "dist", "second"):
+                assert np.array_equal(getattr(got, f), getattr(ref, f)), (c.id, f)
+            assert (got.stop, got.passes) == (ref.stop, ref.passes), c.id
+
+    yield Case("kmedoids_matrix257", "medoids", ("cluster.kmedoids",), "kmedoids_cases.kmedoids_ref, as arrays", run_matrix,
+               check_matrix, lambda: [kc.case_ref(c) for c in exact], {"DVS_KMEDOIDS_BATCH": "3"})
+
+    def run_mode(ctx, mode, keep=None):
+        side = _mode_side(ctx, mode)
+        out = {"distances": side.distances()}
+        _put(out, "fused", side.kmedoids(7))
+        _put(out, "route", cluster.kmedoids(out["distances"], 7, ctx=ctx))
+        _put(out, "maxmin", side.kmedoids(17, init="maxmin"))
+        _done(keep, side)
+        return out
+
+    def check_mode(out, mode):
+        """tests/test_gpu_kmedoids.py test_brca1_fused_equals_the_matrix_route"""
+        fused = _get(out, "fused", distance.KMedoids)
+        assert all(same_bits(a, b) for a, b in zip(fused, _get(out, "route", distance.KMedoids))), mode
+        for got in (fused, _get(out, "maxmin", distance.KMedoids)):
+            assert got.stop == 1 and (np.diff(got.td) < 0).all(), mode
+            near, dn, ds = kc.state_of(kc.zero_diagonal(out["distances"]), got.medoids)
+            assert np.array_equal(got.labels, near) and np.array_equal(got.dist, dn) and np.array_equal(got.second, ds), mode
+
+    yield from _per_mode("kmedoids", "medoids", (("kmedoids", "maxmin", "distances"), ("cluster.kmedoids",)),
+                         "kmedoids_cases.state_of over the mode's own matrix", run_mode, check_mode,
+                         lambda mode: kc.kmedoids_ref(_mode_ref(mode), 7), {})
+
+
+def spanning_cases():
+    import mst_cases as mc
+
+    env = {"DVS_CROSS_STRIP_ROWS": "64"}  # five strips of the 257 rows, the last of one row
+    given = (("euclid", "none"), ("euclid", "given"), ("hamming", "none"), ("nan_blocks", "none"))
+
+    def tree_out(out, name, got):
+        out[name + "_edges"], out[name + "_weights"] = got.edges, got.weights
+        out[name + "_rounds"] = np.array([got.n, got.n_rounds])
+
+    def tree_check(out, name, want, n=N):
+        """tests/test_gpu_mst.py assert_tree"""
+        edges, weights, rounds = want
+        assert np.array_equal(out[name + "_edges"], edges) and same_bits(out[name + "_weights"], weights), name
+        assert out[name + "_rounds"].tolist() == [n, rounds], name
+
+    def run_matrix(ctx, keep=None):
+        out = {}
+        for family, core in given:
+            tree_out(out, f"{family}_{core}", cluster.minimum_spanning_tree(
+                mc.FAMILIES[family](N), core=mc.core_of(N) if core == "given" else None, ctx=ctx))
+        return out
+
+    def check_matrix(out):
+        for family, core in given:
+            tree_check(out, f"{family}_{core}", mc.expected(family, N, core))
+
+    yield Case("mst_matrix257", "spanning", ("cluster.minimum_spanning_tree",), "mst_cases.boruvka", run_matrix, check_matrix,
+               lambda: [mc.expected(family, N, core) for family, core in given], env)
+
+    def run_mode(ctx, mode, keep=None):
+        side = _mode_side(ctx, mode)
+        out = {"distances": side.distances()}
+        tree_out(out, "plain", side.mst())
+        tree_out(out, "m5", side.mst(min_samples=5))  # (the core distances: `nearest` over the same rows)
+        tree_out(out, "rows", side.mst(Q_ROWS))
+        _done(keep, side)
+        return out
+
+    def check_mode(out, mode):
+        """tests/test_gpu_mst.py test_modes_against_their_own_distances"""
+        d = out["distances"]
+        tree_check(out, "plain", mc.boruvka(d))
+        tree_check(out, "m5", mc.boruvka(d, mc.kth_smallest(d, 5)))
+        tree_check(out, "rows", mc.boruvka(d[np.ix_(Q_ROWS, Q_ROWS)]), Q_ROWS.size)
+
+    yield from _per_mode("mst", "spanning", (("mst", "nearest", "distances"), ()), "mst_cases.boruvka over the mode's own matrix",
+                         run_mode, check_mode, lambda mode: mc.boruvka(_mode_ref(mode)), env)
+
+
+PERMUTATIONS = 40  # with the observed labels 41 vectors: two batches of 16 and one of 9
+
+
+def group_cases():
+    import permanova_cases as pc
+
+    exact = pc.Case("integer", N, 6, PERMUTATIONS, 4242)
+
+    def run_matrix(ctx, keep=None):
+        out = {}
+        _put(out, "exact", cluster.permanova(pc.case_matrix(exact), pc.case_labels(exact).tolist(), permutations=exact.P,
+                                             seed=exact.seed + 2, ctx=ctx))
+        return out
+
+    def check_matrix(out):
+        """tests/test_gpu_permanova.py test_exact_families_as_arrays, through the Python layer"""
+        got, ref = _get(out, "exact", distance.PERMANOVA), pc.case_ref(exact)
+        assert got.ss_total == ref.ss_total and got.ss_within == ref.ss_within[0] and np.array_equal(got.group_ss, ref.group_ss)
+        assert same_bits(np.float64(got.f), ref.f[0]) and same_bits(np.float64(got.r2), np.float64(ref.r2))
+        assert same_bits(got.perm_f, ref.f[1:]) and got.p_value == ref.p_value and got.permutations == exact.P
+        assert np.array_equal(got.group_sizes, np.bincount(pc.case_labels(exact)))
+
+    yield Case("permanova_matrix257", "groups", ("cluster.permanova",), "permanova_cases.permanova_ref, as arrays", run_matrix,
+               check_matrix, lambda: pc.case_ref(exact), {})
+
+    def run_mode(ctx, mode, keep=None):
+        side = _mode_side(ctx, mode)
+        out = {"distances": side.distances()}
+        _put(out, "fused", side.permanova(labels257(), permutations=PERMUTATIONS, seed=5))
+        _put(out, "route", cluster.permanova(out["distances"], labels257(), permutations=PERMUTATIONS, seed=5, ctx=ctx))
+        _done(keep, side)
+        return out
+
+    def labels_and_perms():
+        lab = pc.encode(labels257().tolist())
+        return lab, pc.documented_permutations(lab, PERMUTATIONS, 5)
+
+    def check_mode(out, mode):
+        """the fused route is the matrix route bit for bit; the sums within permanova_cases.band of the long-double
+        truth over the mode's own matrix (tests/test_gpu_permanova.py test_real_valued_input_within_the_band)"""
+        lab, perms = labels_and_perms()
+        d, got = out["distances"], _get(out, "fused", distance.PERMANOVA)
+        assert all(same_bits(np.asarray(a), np.asarray(b)) for a, b in zip(got, _get(out, "route", distance.PERMANOVA))), mode
+        t_total, t_within, t_group = pc.sums(d, lab, 6, perms, np.longdouble)
+        band = pc.band(N)
+        assert abs(np.longdouble(got.ss_total) - t_total) <= band * t_total, mode
+        assert abs(np.longdouble(got.ss_within) - t_within[0]) <= band * t_within[0], mode
+        assert (np.abs(got.group_ss.astype(np.longdouble) - t_group) <= band * t_group).all(), mode
+        assert got.p_value == pc.permanova_ref(d, lab, 6, perms).p_value and got.perm_f.size == PERMUTATIONS, mode
+
+    yield from _per_mode("permanova", "groups", (("permanova", "distances"), ("cluster.permanova",)),
+                         "permanova_cases.sums in long double over the mode's own matrix", run_mode, check_mode,
+                         lambda mode: pc.permanova_ref(_mode_ref(mode), *(lambda lp: (lp[0], 6, lp[1]))(labels_and_perms())), {})
+
+
 def all_cases() -> dict:
     cases = {}
     for gen in (distance_cases, tree_cases, cophenet_cluster_cases, maxmin_cases, sketch_cases, histogram_cases, ingest_cases,
-                selection_cases):
+                selection_cases, neighbour_cases, canonical_cases, ordination_cases, medoid_cases, spanning_cases, group_cases):
         for c in gen():
             assert c.name not in cases and c.family in FAMILIES
             cases[c.name] = c
@@ -1001,6 +1396,28 @@ def error_cases() -> dict:
             m.close()
             ctx.sync()
 
+    def setup_side(ctx):
+        mash_side(ctx).close()
+
+    def setup_bad_seeds(ctx):
+        import torch
+
+        seqs = list(select_seqs(0))
+        for r in range(SELECT_SHAPES[0][3]):
+            seqs[r] = np.full(40, 4, dtype=np.uint8)
+        data, offs = oracle.concat(seqs)
+        t = torch.from_numpy(np.concatenate([data, np.zeros(16, np.uint8)])).to("cuda:0")
+        torch.cuda.synchronize()
+        ctx.build_matrix_device(t.data_ptr(), offs, SELECT_SHAPES[0][2], 4).close()
+        ctx.sync()
+
+    def setup_delta_jsd(ctx):
+        m = ctx.build_matrix(list(select_seqs(0)), 3, 4)
+        q = ctx.build_matrix(list(query_seqs(0)), 4, 4)
+        sel = m.nmost(10)
+        for h in (sel, q, m):
+            h.close()
+
     def host_bad_seeds():
         seqs = list(select_seqs(0))
         for r in range(SELECT_SHAPES[0][3]):
@@ -1037,13 +1454,15 @@ def error_cases() -> dict:
         ErrorCase("ward_negative", "trees", lambda ctx: cluster.linkage(negative, "ward", ctx=ctx), ValueError,
                   "linkage_random257", None),
         ErrorCase("mash_distances_two_empty", "distances", lambda ctx: with_side(ctx, lambda s: s.distances()), ZeroDivisionError,
-                  "distances_mash", host_mash),
+                  "distances_mash", host_mash, setup_side),
         ErrorCase("mash_cluster_scores_two_empty", "cophenet_clusters",
-                  lambda ctx: with_side(ctx, lambda s: s.cluster_scores(labels257())), ZeroDivisionError, "scores_modes257", host_mash),
+                  lambda ctx: with_side(ctx, lambda s: s.cluster_scores(labels257())), ZeroDivisionError, "scores_modes257", host_mash,
+                  setup_side),
         ErrorCase("mash_maxmin_two_empty", "maxmin", lambda ctx: with_side(ctx, lambda s: s.maxmin(N, seeds=(3,))), ZeroDivisionError,
-                  "maxmin_mash", host_mash),
-        ErrorCase("bad_seeds_behind_resident_build", "selections", bad_seeds, ValueError, "select0_resident", host_bad_seeds),
-        ErrorCase("delta_jsd_bins_mismatch", "selections", refused_delta_jsd, ValueError, "select0_nmost", None),
+                  "maxmin_mash", host_mash, setup_side),
+        ErrorCase("bad_seeds_behind_resident_build", "selections", bad_seeds, ValueError, "select0_resident", host_bad_seeds,
+                  setup_bad_seeds),
+        ErrorCase("delta_jsd_bins_mismatch", "selections", refused_delta_jsd, ValueError, "select0_nmost", None, setup_delta_jsd),
     ]
     return {e.name: e for e in cases}
 
@@ -1094,18 +1513,26 @@ ENQUEUES = {
     "Selection": ("members", "gather_members", "bench_scan", "delta_jsd", "member_rows", "assign", "diversify"),
 }
 HOST_ONLY = {
-    "Context": ("close", "check", "sync", "refresh_knobs", "set_timing", "device_info"),
+    "Context": ("close", "check", "sync", "refresh_knobs", "set_timing", "device_info", "block_stats"),
     "Selection": ("close", "summary", "global_ids"),
 }
 
 
-# the operations of a DeviceSide whose result is dense (the written list), and the two whose result is sparse
+# the operations of a DeviceSide whose result is dense (the written list), the two whose result is sparse, and those it
+# inherits from its mixins (distance.OrdinationOps, MedoidOps, SpanningOps, GroupOps); every one serves every mode
 DENSE_OPS = ("distances", "linkage", "nj", "cross_distances", "nearest", "cluster_scores", "cophenet", "maxmin")
 SPARSE_OPS = ("within", "threshold_clusters")
+MIXIN_OPS = ("pcoa", "pcoa_project", "kmedoids", "mst", "permanova")
+
+
+def device_side_operations() -> set:
+    """the public methods of DeviceSide and of every class it inherits from"""
+    return {n for klass in distance.DeviceSide.__mro__ if klass is not object
+            for n, v in vars(klass).items() if callable(v) and not n.startswith("_")} - {"close"}
 
 
 def required_ops() -> set:
-    ops = {f"DeviceSide.{op}:{mode}" for op in DENSE_OPS for mode in distance.DeviceSide.MODE_NAMES}
+    ops = {f"DeviceSide.{op}:{mode}" for op in DENSE_OPS + SPARSE_OPS + MIXIN_OPS for mode in distance.DeviceSide.MODE_NAMES}
     ops |= {f"{cls}.{m}" for cls, methods in ENQUEUES.items() for m in methods}
     return ops
 
@@ -1122,6 +1549,25 @@ def test_the_knob_is_a_word_of_the_test_knobs_variable():
     assert any(POISON in line and "test_gpu_poisoned_blocks.py" in line for line in table)
 
 
+def test_the_refusing_knob_is_a_word_of_the_test_knobs_variable():
+    """... and one more: parsed in api.cpp, described where the others are, listed with the test that walks it; the
+    runtime's allocation calls stand in api.cpp alone, behind the counted gates"""
+    import pathlib
+    import re
+
+    root = pathlib.Path(__file__).resolve().parent.parent
+    csrc = root / "diverseseq_amd" / "csrc"
+    assert f'"{REFUSE}"' in (csrc / "api.cpp").read_text() and REFUSE + "<i>" in (csrc / "dvs_internal.h").read_text()
+    table = [line for line in (root / "INTEGRATION.md").read_text().splitlines() if "DVS_TEST_KNOBS" in line]
+    assert any(REFUSE in line and "test_gpu_refused_blocks.py" in line for line in table)
+    assert REFUSE in (root / "DESIGN.md").read_text()
+    assert "int dvs_ctx_block_stats(const dvs_ctx *ctx, uint64_t out[4]);" in (root / "include" / "dvs_hip.h").read_text()
+    assert "dvs_ctx_block_stats" in _lib.EXPORTS
+    calls = re.compile(r"\bhip(Malloc|HostMalloc|MallocAsync|HostAlloc|MallocManaged|ExtMallocWithFlags|MallocPitch)\s*\(")
+    found = sorted(f.name for f in csrc.iterdir() if f.suffix in (".hip", ".cpp", ".h") and calls.search(f.read_text()))
+    assert found == ["api.cpp"], found
+
+
 def test_every_public_method_is_sorted_and_every_operation_named():
     for cls in (engine.Context, engine.Selection):
         public = {n for n in vars(cls) if not n.startswith("_")}
@@ -1129,8 +1575,13 @@ def test_every_public_method_is_sorted_and_every_operation_named():
         assert public == listed, (cls.__name__, public ^ listed)  # a method added later is sorted here, and gets a case
     named = {op for c in CASES.values() for op in c.ops}
     assert required_ops() <= named, sorted(required_ops() - named)
-    operations = {n for n, v in vars(distance.DeviceSide).items() if callable(v) and not n.startswith("_")} - {"close"}
-    assert operations == set(DENSE_OPS) | set(SPARSE_OPS), operations  # (an operation added later is sorted here)
+    own = {n for n, v in vars(distance.DeviceSide).items() if callable(v) and not n.startswith("_")} - {"close"}
+    assert own == set(DENSE_OPS) | set(SPARSE_OPS), own  # (an operation added later is sorted here)
+    # ... wherever it is defined: the mixins' operations too, each with a case in every mode
+    assert device_side_operations() == set(DENSE_OPS) | set(SPARSE_OPS) | set(MIXIN_OPS), device_side_operations()
+    assert {f"DeviceSide.{op}:{mode}" for op in device_side_operations() for mode in distance.DeviceSide.MODE_NAMES} <= named
+    mixins = [klass.__name__ for klass in distance.DeviceSide.__mro__[1:-1]]
+    assert sorted(mixins) == ["GroupOps", "MedoidOps", "OrdinationOps", "SpanningOps"], mixins
 
 
 def test_the_table_has_every_family_and_its_shapes():

@@ -73,6 +73,31 @@ def test_selections(monkeypatch, name):
     _case_under_poison(monkeypatch, name)
 
 
+@pytest.mark.parametrize("name", cases_of("neighbours"))
+def test_neighbours(monkeypatch, name):
+    _case_under_poison(monkeypatch, name)
+
+
+@pytest.mark.parametrize("name", cases_of("ordination"))
+def test_ordination(monkeypatch, name):
+    _case_under_poison(monkeypatch, name)
+
+
+@pytest.mark.parametrize("name", cases_of("medoids"))
+def test_medoids(monkeypatch, name):
+    _case_under_poison(monkeypatch, name)
+
+
+@pytest.mark.parametrize("name", cases_of("spanning"))
+def test_spanning(monkeypatch, name):
+    _case_under_poison(monkeypatch, name)
+
+
+@pytest.mark.parametrize("name", cases_of("groups"))
+def test_groups(monkeypatch, name):
+    _case_under_poison(monkeypatch, name)
+
+
 @pytest.mark.parametrize("name", list(ERROR_CASES))
 def test_error_cases_raise_the_same(monkeypatch, name):
     """... and the case that asks for blocks of the same sizes right behind the failing call gives its clean bits"""
