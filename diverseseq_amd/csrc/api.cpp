@@ -446,7 +446,7 @@ static int matrix_build_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_
     if (rc) return rc;
     // (a device-resident input needs no host wait: the kernels' completion is an event the consumers
     // of the matrix wait on when they need host-side data, dvs_matrix_settle)
-    if (nseq) rc = dvs_matrix_fill_counts(ctx, m, sv, offsets, no_wait);
+    if (nseq) rc = dvs_matrix_fill_counts(ctx, m, sv, no_wait);
     return matrix_made(rc, m, out);
 }
 

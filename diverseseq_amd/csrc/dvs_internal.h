@@ -319,7 +319,7 @@ struct dvs_seqs_held {
 // pack.hip, the only maker of that view.  A PACKED or BATCH source is marked as read by kernels nobody waits for
 // (async_readers), so it is called only when something will be enqueued.
 int dvs_seqs_bring(dvs_ctx *ctx, const dvs_seqs *src, uint32_t k, uint32_t num_states, dvs_seqs_held *held);
-int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, const uint64_t *offsets, bool no_wait);  // kmer_hist.hip
+int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, bool no_wait);  // kmer_hist.hip
 
 // linkage.hip's prepare pass on its own, enqueued on the context's stream: every entry of the n x n matrix checked and
 // the upper triangle copied over the lower one; the bits below are OR-ed into the device word *d_status (`sign`: a

@@ -30,6 +30,7 @@
 #include <cstring>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -444,6 +445,58 @@ int set_dyn_lds(dvs_ctx *ctx, K kernel, size_t bytes) {
     return dvs_raise_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), bytes);
 }
 
+// What every histogram launch of one build shares (its shape is the matrix's; packed: `d_seqs` carries the code
+// words, `d_pmask` the mask words; d_off NULL: sequences of one length, the cache entry's uni_base + r * uni_stride).
+struct HistBuild {
+    dvs_ctx *ctx;
+    dvs_matrix *m;
+    const uint8_t *d_seqs;
+    const uint16_t *d_pmask;
+    uint64_t nbytes;
+    const uint64_t *d_off;
+    bool packed, lds_hist;  // lds_hist: the histogram fits the LDS (else the row itself takes the atomics)
+    uint32_t hot_rows;
+};
+
+// one launch of one instantiation
+template <bool NS4, bool LDS_HIST, bool PK16, bool OUT16, bool PACKED>
+int hist_launch(const HistBuild &b, uint32_t grid, int threads, size_t lds, hipStream_t stream, const KTile *tiles, uint32_t *out,
+                uint32_t hot_end, uint32_t row0) {
+    const auto kernel = kmer_hist_kernel<NS4, LDS_HIST, PK16, OUT16, PACKED>;
+    if (int rc = set_dyn_lds(b.ctx, kernel, lds)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, b.d_seqs, b.d_pmask, b.nbytes, b.d_off, tiles, out,
+                       b.m->d_totals, b.m->d_entropy, b.ctx->d_clog_tbl, b.m->k, b.m->num_states, b.m->nbins, hot_end, row0,
+                       b.ctx->off_cache.uni_base, b.ctx->off_cache.uni_stride);
+    return DVS_OK;
+}
+
+// The run-time flags of a launch as compile-time ones (as dvs_mat_dispatch does for the row type): f(NS4, LDS_HIST, PK16,
+// OUT16, PACKED), each a std::true_type or std::false_type.  Three input forms -- packed words, four-state bytes, another
+// alphabet -- times four placements -- 16-bit rows (matrix kind 2); 32-bit whole rows from packed LDS counters; neither
+// (tiles of long rows, whole rows where B % 4 != 0 or 4 B > 64 KiB), histogram in the LDS or not: twelve kernels, no other.
+template <typename F>
+int hist_dispatch(const HistBuild &b, bool pk16, bool out16, F &&f) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    auto placed = [&](auto ns4, auto packed) {
+        if (out16) return f(ns4, Y{}, Y{}, Y{}, packed);
+        if (pk16) return f(ns4, Y{}, Y{}, N{}, packed);
+        return b.lds_hist ? f(ns4, Y{}, N{}, N{}, packed) : f(ns4, N{}, N{}, N{}, packed);
+    };
+    if (b.packed) return placed(Y{}, Y{});
+    return b.m->num_states == 4 ? placed(Y{}, N{}) : placed(N{}, N{});
+}
+
+// a launch of the instantiation that serves this build (LDS: the histogram if it is there, the table, the scratch)
+int hist_launch_any(const HistBuild &b, bool pk16, bool out16, uint32_t grid, int threads, hipStream_t stream,
+                    const KTile *tiles, uint32_t *out, uint32_t hot_end, uint32_t row0) {
+    const uint64_t hist = pk16 ? b.m->nbins * 2 : b.lds_hist ? b.m->nbins * 4 : 0;
+    const size_t lds = ((hist + 15) & ~15ull) + (CLOG_TBL + 32) * sizeof(double);
+    return hist_dispatch(b, pk16, out16, [&](auto... flag) {
+        return hist_launch<decltype(flag)::value...>(b, grid, threads, lds, stream, tiles, out, hot_end, row0);
+    });
+}
+
 }  // namespace
 
 uint64_t dvs_pow_u64(uint32_t base, uint32_t exp, bool *overflow) {
@@ -494,6 +547,151 @@ void dvs_matrix_free_fields(dvs_matrix *m) {
     m->ctx = nullptr;
 }
 
+// Sequences of ONE length laid end to end (fixed-length reads, amplicons, synthetic sets) need no
+// offsets on the device at all: the kernel derives row r's span from (base, stride).  One read-only
+// pass decides (it stops at the first span of another length), nothing is copied or uploaded.
+static bool hist_offsets_uniform(dvs_ctx::OffsetsCache &oc, const uint64_t *offsets, uint32_t nseq, uint32_t k, uint64_t nbytes) {
+    const uint64_t base = offsets[0], stride = offsets[1] - offsets[0];
+    bool uni = offsets[1] >= offsets[0] && stride < uint64_t(TILE_LEN) + k;
+    uint64_t diff = 0;
+    for (uint32_t r = 0; r < nseq && uni; r += 4096) {  // (blocks: vectorised, with an early way out)
+        const uint32_t e = std::min<uint32_t>(nseq, r + 4096);
+        for (uint32_t q = r; q < e; q++) diff |= (offsets[q + 1] - offsets[q]) ^ stride;
+        uni = diff == 0;
+    }
+    if (!uni || base + uint64_t(nseq) * stride > nbytes) return false;
+    oc.uni_base = base;
+    oc.uni_stride = stride;
+    return true;
+}
+
+// The cache entry's row and tile lists go back to the block cache: behind a build that was not waited for the stream
+// is drained first -- the cache's next user may write the block on another stream.  (`offsets_block_too`: the offsets
+// block is about to go as well; it is kept while it is large enough.)
+static void hist_release_lists(dvs_ctx *ctx, bool offsets_block_too) {
+    dvs_ctx::OffsetsCache &oc = ctx->off_cache;
+    if (oc.lists_in_flight && (oc.d_rows || oc.d_tiles || offsets_block_too)) {
+        (void)hipStreamSynchronize(ctx->stream);
+        oc.lists_in_flight = false;
+    }
+    dvs_dev_free(ctx, oc.d_rows);
+    dvs_dev_free(ctx, oc.d_tiles);
+    oc.d_rows = oc.d_tiles = nullptr;
+    oc.n_long = oc.n_tiles = 0;
+}
+
+// The offsets copied into the cache entry's pinned block and checked: every pair in order and in range.
+// *longest_out = the longest sequence.
+static int hist_validate_offsets(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint64_t nbytes, uint64_t *longest_out) {
+    dvs_ctx::OffsetsCache &oc = ctx->off_cache;
+    const size_t n_off = size_t(nseq) + 1;
+    // the pinned block: no upload may still be reading it, and it must be large enough
+    if (oc.ev_up) (void)hipEventSynchronize(oc.ev_up);
+    if (oc.h_cap < n_off) {
+        if (oc.h_off) (void)hipHostFree(oc.h_off);
+        oc.h_off = nullptr;
+        oc.h_cap = 0;
+        const size_t cap = std::max<size_t>(n_off + n_off / 4, 1024);
+        if (int rc = dvs_pinned_grow(ctx, (void **)&oc.h_off, cap * 8, "pinned offsets block")) return rc;
+        oc.h_cap = cap;
+    }
+    oc.n_off = 0;  // (the block is being rewritten: no hit on a half-written copy after an error)
+    uint64_t *dst = oc.h_off;
+    // one pass, branch-free (it vectorises): the pinned copy, whether any pair is out of order or out of range, and
+    // the longest sequence; rows are looked at one by one only when something is wrong
+    uint64_t bad = 0, longest = 0;
+    dst[0] = offsets[0];
+    for (uint32_t r = 0; r < nseq; r++) {
+        const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
+        dst[r + 1] = s1;
+        bad |= uint64_t(s1 < s0) | uint64_t(s1 > nbytes);
+        const uint64_t len = s1 - s0;
+        longest = len > longest ? len : longest;
+    }
+    for (uint32_t r = 0; bad && r < nseq; r++) {
+        const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
+        if (s1 < s0 || s1 > nbytes)
+            return dvs_set_error(ctx, DVS_ERR_VALUE, "offsets[%u..%u] = %llu..%llu out of range", r, r + 1,
+                                 (unsigned long long)s0, (unsigned long long)s1);
+    }
+    *longest_out = longest;
+    return DVS_OK;
+}
+
+// The rows that need more than one tile, and their tiles (valid offsets with some such row).
+static void hist_tile_plan(const dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint32_t k, uint64_t nbins,
+                           std::vector<uint32_t> &long_rows, std::vector<KTile> &tiles) {
+    uint64_t long_windows = 0;
+    for (uint32_t r = 0; r < nseq; r++) {
+        const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
+        if (s1 - s0 >= k && s1 - (s0 + k - 1) > TILE_LEN) long_windows += s1 - (s0 + k - 1);
+    }
+    // A tile of a long row ends in one global atomic per non-empty bin, so it should hold many more windows
+    // than there are bins (at 4^7 bins a 32768-window tile spent as long merging as counting: 4.35 ms for
+    // 1050 genomes of 3 Mb) -- 16 windows a bin, while that still leaves >= 2048 tiles for the grid.
+    // (The tiles of a long row count in 32-bit LDS words: no limit from the packed 16-bit counters.)
+    uint64_t tile_long = TILE_LEN;
+    const uint64_t B_ = nbins ? nbins : 1;  // (num_states^k of this build; any tile length counts correctly)
+    while (tile_long < 262144 && tile_long < 16 * B_ && long_windows / (2 * tile_long) >= 2048) tile_long *= 2;
+    // (tests: small inputs, long tiles -- at most 2^20 windows, far below what a 32-bit counter holds)
+    if (ctx->knobs.test_long_tile >= TILE_LEN) tile_long = std::min<uint64_t>(ctx->knobs.test_long_tile, uint64_t(1) << 20);
+    for (uint32_t r = 0; r < nseq; r++) {
+        const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
+        if (s1 - s0 < k) continue;
+        const uint64_t first = s0 + k - 1;
+        if (s1 - first <= TILE_LEN) continue;
+        long_rows.push_back(r);
+        for (uint64_t b = first; b < s1; b += tile_long)  // {begin, end, seq_begin, row, single}
+            tiles.push_back(KTile{b, std::min<uint64_t>(b + tile_long, s1), s0, r, 0u});
+    }
+}
+
+// The new cache entry: the blocks, the uploads from the entry's own copies, and -- only once every upload was
+// enqueued -- the key (n_off, nbytes, k) under which the next build finds it.
+static int hist_commit_offsets(dvs_ctx *ctx, uint32_t nseq, uint32_t k, uint64_t nbytes, const std::vector<uint32_t> &long_rows,
+                               const std::vector<KTile> &tiles) {
+    dvs_ctx::OffsetsCache &oc = ctx->off_cache;
+    const size_t n_off = size_t(nseq) + 1;
+    hist_release_lists(ctx, oc.d_off_cap < n_off);
+    int arc = DVS_OK;
+    if (oc.d_off_cap < n_off) {
+        dvs_dev_free(ctx, oc.d_off);
+        oc.d_off = nullptr;
+        oc.d_off_cap = 0;
+        arc = dvs_dev_alloc(ctx, &oc.d_off, (n_off + n_off / 4) * 8, "offsets");
+        if (!arc) oc.d_off_cap = n_off + n_off / 4;
+    }
+    if (!arc && !long_rows.empty()) arc = dvs_dev_alloc(ctx, &oc.d_rows, long_rows.size() * 4, "row list");
+    if (!arc && !tiles.empty()) arc = dvs_dev_alloc(ctx, &oc.d_tiles, tiles.size() * sizeof(KTile), "tile list");
+    hipError_t ue = hipSuccess;
+    // (the other uploads read from the cache entry's own copies, which outlive the call)
+    oc.h_tiles.assign(reinterpret_cast<const unsigned char *>(tiles.data()),
+                      reinterpret_cast<const unsigned char *>(tiles.data()) + tiles.size() * sizeof(KTile));
+    oc.h_long_rows = long_rows;
+    if (!arc) ue = hipMemcpyAsync(oc.d_off, oc.h_off, n_off * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (!arc && ue == hipSuccess) {
+        if (!oc.ev_up) oc.ev_up = dvs_event_get(ctx);
+        if (oc.ev_up) ue = hipEventRecord(oc.ev_up, ctx->stream);
+    }
+    if (!arc && ue == hipSuccess && !long_rows.empty()) {
+        ue = hipMemcpyAsync(oc.d_rows, oc.h_long_rows.data(), long_rows.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (ue == hipSuccess)
+            ue = hipMemcpyAsync(oc.d_tiles, oc.h_tiles.data(), oc.h_tiles.size(), hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (arc || ue != hipSuccess) {
+        dvs_dev_free(ctx, oc.d_rows);
+        dvs_dev_free(ctx, oc.d_tiles);
+        oc.d_rows = oc.d_tiles = nullptr;
+        return arc ? arc : dvs_hip_fail(ctx, ue, "histogram setup");
+    }
+    oc.n_off = n_off;
+    oc.nbytes = nbytes;
+    oc.k = k;
+    oc.n_long = long_rows.size();
+    oc.n_tiles = tiles.size();
+    return DVS_OK;
+}
+
 // The offsets of a build: validated, the tile lists of genome-length sequences derived, everything
 // uploaded -- or found unchanged in the context's cache.  *n_long = sequences needing more than one
 // tile (none: every row's counts fit 16 bits and the matrix may be built as kind 2).
@@ -501,150 +699,23 @@ int dvs_hist_prepare(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint3
                      size_t *n_long_out) {
     dvs_ctx::OffsetsCache &oc = ctx->off_cache;
     const size_t n_off = size_t(nseq) + 1;
-    // Sequences of ONE length laid end to end (fixed-length reads, amplicons, synthetic sets) need no
-    // offsets on the device at all: the kernel derives row r's span from (base, stride).  One read-only
-    // pass decides (it stops at the first span of another length), nothing is copied or uploaded.
     oc.uniform = false;
-    if (nseq >= 1 && !ctx->knobs.no_uniform_offsets) {
-        const uint64_t base = offsets[0], stride = offsets[1] - offsets[0];
-        bool uni = offsets[1] >= offsets[0] && stride < uint64_t(TILE_LEN) + k;
-        uint64_t diff = 0;
-        for (uint32_t r = 0; r < nseq && uni; r += 4096) {  // (blocks: vectorised, with an early way out)
-            const uint32_t e = std::min<uint32_t>(nseq, r + 4096);
-            for (uint32_t q = r; q < e; q++) diff |= (offsets[q + 1] - offsets[q]) ^ stride;
-            uni = diff == 0;
-        }
-        if (uni && base + uint64_t(nseq) * stride <= nbytes) {
-            if (oc.lists_in_flight && (oc.d_rows || oc.d_tiles)) {
-                (void)hipStreamSynchronize(ctx->stream);
-                oc.lists_in_flight = false;
-            }
-            dvs_dev_free(ctx, oc.d_rows);
-            dvs_dev_free(ctx, oc.d_tiles);
-            oc.d_rows = oc.d_tiles = nullptr;
-            oc.n_long = oc.n_tiles = 0;
-            oc.n_off = 0;  // (no entry of the content cache: the next non-uniform build starts afresh)
-            oc.uniform = true;
-            oc.uni_base = base;
-            oc.uni_stride = stride;
-            *n_long_out = 0;
-            return DVS_OK;
-        }
+    if (nseq >= 1 && !ctx->knobs.no_uniform_offsets && hist_offsets_uniform(oc, offsets, nseq, k, nbytes)) {
+        hist_release_lists(ctx, false);
+        oc.n_off = 0;  // (no entry of the content cache: the next non-uniform build starts afresh)
+        oc.uniform = true;
+        *n_long_out = 0;
+        return DVS_OK;
     }
     const bool hit = oc.d_off && oc.h_off && oc.k == k && oc.nbytes == nbytes && oc.n_off == n_off &&
                      !ctx->knobs.no_offsets_cache && std::memcmp(oc.h_off, offsets, n_off * 8) == 0;
     if (!hit) {
-        // the pinned block: no upload may still be reading it, and it must be large enough
-        if (oc.ev_up) (void)hipEventSynchronize(oc.ev_up);
-        if (oc.h_cap < n_off) {
-            if (oc.h_off) (void)hipHostFree(oc.h_off);
-            oc.h_off = nullptr;
-            oc.h_cap = 0;
-            const size_t cap = std::max<size_t>(n_off + n_off / 4, 1024);
-            if (int rc = dvs_pinned_grow(ctx, (void **)&oc.h_off, cap * 8, "pinned offsets block")) return rc;
-            oc.h_cap = cap;
-        }
-        oc.n_off = 0;  // (the block is being rewritten: no hit on a half-written copy after an error)
+        uint64_t longest = 0;
+        if (int rc = hist_validate_offsets(ctx, offsets, nseq, nbytes, &longest)) return rc;
         std::vector<KTile> tiles;
         std::vector<uint32_t> long_rows;
-        uint64_t *dst = oc.h_off;
-        // first pass, branch-free (it vectorises): the pinned copy, whether any pair is out of order or
-        // out of range, and the longest sequence; rows are looked at one by one only when something is
-        // wrong or some sequence needs more than one tile
-        uint64_t bad = 0, longest = 0;
-        dst[0] = offsets[0];
-        for (uint32_t r = 0; r < nseq; r++) {
-            const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
-            dst[r + 1] = s1;
-            bad |= uint64_t(s1 < s0) | uint64_t(s1 > nbytes);
-            const uint64_t len = s1 - s0;
-            longest = len > longest ? len : longest;
-        }
-        if (bad || longest >= uint64_t(TILE_LEN) + k) {
-            uint64_t long_windows = 0;
-            for (uint32_t r = 0; r < nseq; r++) {
-                const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
-                if (s1 < s0 || s1 > nbytes)
-                    return dvs_set_error(ctx, DVS_ERR_VALUE, "offsets[%u..%u] = %llu..%llu out of range", r,
-                                         r + 1, (unsigned long long)s0, (unsigned long long)s1);
-                if (s1 - s0 >= k && s1 - (s0 + k - 1) > TILE_LEN) long_windows += s1 - (s0 + k - 1);
-            }
-            // A tile of a long row ends in one global atomic per non-empty bin, so it should hold many more windows
-            // than there are bins (at 4^7 bins a 32768-window tile spent as long merging as counting: 4.35 ms for
-            // 1050 genomes of 3 Mb) -- 16 windows a bin, while that still leaves >= 2048 tiles for the grid.
-            // (The tiles of a long row count in 32-bit LDS words: no limit from the packed 16-bit counters.)
-            uint64_t tile_long = TILE_LEN;
-            {
-                const uint64_t B_ = nbins ? nbins : 1;  // (num_states^k of this build; any tile length counts correctly)
-                while (tile_long < 262144 && tile_long < 16 * B_ && long_windows / (2 * tile_long) >= 2048) tile_long *= 2;
-                // (tests: small inputs, long tiles -- at most 2^20 windows, far below what a 32-bit counter holds)
-                if (ctx->knobs.test_long_tile >= TILE_LEN) tile_long = std::min<uint64_t>(ctx->knobs.test_long_tile, uint64_t(1) << 20);
-            }
-            for (uint32_t r = 0; r < nseq; r++) {
-                const uint64_t s0 = offsets[r], s1 = offsets[r + 1];
-                if (s1 - s0 < k) continue;
-                const uint64_t first = s0 + k - 1;
-                if (s1 - first <= TILE_LEN) continue;
-                long_rows.push_back(r);
-                for (uint64_t b = first; b < s1; b += tile_long) {
-                    KTile t;
-                    t.begin = b;
-                    t.end = std::min<uint64_t>(b + tile_long, s1);
-                    t.seq_begin = s0;
-                    t.row = r;
-                    t.single = 0;
-                    tiles.push_back(t);
-                }
-            }
-        }
-        // (the previous lists go back to the block cache: behind a build that was not waited for the stream is
-        // drained first -- the cache's next user may write the block on another stream; the offsets block is kept
-        // while it is large enough)
-        if (oc.lists_in_flight && (oc.d_rows || oc.d_tiles || oc.d_off_cap < n_off)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            oc.lists_in_flight = false;
-        }
-        dvs_dev_free(ctx, oc.d_rows);
-        dvs_dev_free(ctx, oc.d_tiles);
-        oc.d_rows = oc.d_tiles = nullptr;
-        oc.n_long = oc.n_tiles = 0;
-        int arc = DVS_OK;
-        if (oc.d_off_cap < n_off) {
-            dvs_dev_free(ctx, oc.d_off);
-            oc.d_off = nullptr;
-            oc.d_off_cap = 0;
-            arc = dvs_dev_alloc(ctx, &oc.d_off, (n_off + n_off / 4) * 8, "offsets");
-            if (!arc) oc.d_off_cap = n_off + n_off / 4;
-        }
-        if (!arc && !long_rows.empty()) arc = dvs_dev_alloc(ctx, &oc.d_rows, long_rows.size() * 4, "row list");
-        if (!arc && !tiles.empty()) arc = dvs_dev_alloc(ctx, &oc.d_tiles, tiles.size() * sizeof(KTile), "tile list");
-        hipError_t ue = hipSuccess;
-        // (the other uploads read from the cache entry's own copies, which outlive the call)
-        oc.h_tiles.assign(reinterpret_cast<const unsigned char *>(tiles.data()),
-                          reinterpret_cast<const unsigned char *>(tiles.data()) + tiles.size() * sizeof(KTile));
-        oc.h_long_rows = long_rows;
-        if (!arc) ue = hipMemcpyAsync(oc.d_off, oc.h_off, n_off * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (!arc && ue == hipSuccess) {
-            if (!oc.ev_up) oc.ev_up = dvs_event_get(ctx);
-            if (oc.ev_up) ue = hipEventRecord(oc.ev_up, ctx->stream);
-        }
-        if (!arc && ue == hipSuccess && !long_rows.empty()) {
-            ue = hipMemcpyAsync(oc.d_rows, oc.h_long_rows.data(), long_rows.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (ue == hipSuccess)
-                ue = hipMemcpyAsync(oc.d_tiles, oc.h_tiles.data(), oc.h_tiles.size(), hipMemcpyHostToDevice,
-                                    ctx->stream);
-        }
-        if (arc || ue != hipSuccess) {
-            dvs_dev_free(ctx, oc.d_rows);
-            dvs_dev_free(ctx, oc.d_tiles);
-            oc.d_rows = oc.d_tiles = nullptr;
-            return arc ? arc : dvs_hip_fail(ctx, ue, "histogram setup");
-        }
-        oc.n_off = n_off;
-        oc.nbytes = nbytes;
-        oc.k = k;
-        oc.n_long = long_rows.size();
-        oc.n_tiles = tiles.size();
+        if (longest >= uint64_t(TILE_LEN) + k) hist_tile_plan(ctx, offsets, nseq, k, nbins, long_rows, tiles);
+        if (int rc = hist_commit_offsets(ctx, nseq, k, nbytes, long_rows, tiles)) return rc;
     }
     *n_long_out = oc.n_long;
     return DVS_OK;
@@ -659,222 +730,150 @@ bool dvs_hist_rows_fit_u16(const dvs_ctx *ctx, uint64_t B, size_t n_long) {
     return n_long == 0 && B <= 4096 && (B & 3) == 0 && !ctx->knobs.counts_u32;
 }
 
-// Launches the histogram build for sequences already in HBM (d_seqs, nbytes
-// readable) into an allocated matrix, after dvs_hist_prepare for the same offsets.  One launch gives
-// every sequence that fits a single tile its own workgroup (tile derived from the offsets on the
-// device); genome-length sequences get an explicit tile list and a second launch.
-int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, const uint64_t *offsets,
-                           bool no_wait) {
-    // (packed: the kernel's `seqs` argument carries the code words, `pmask` the mask words)
-    const bool packed = sv.codes != nullptr;
-    const uint8_t *d_seqs = packed ? reinterpret_cast<const uint8_t *>(sv.codes) : sv.seqs;
-    const uint16_t *d_pmask = sv.mask;
-    const uint64_t nbytes = sv.nbytes;
-    const uint32_t nseq = m->nrows, k = m->k, ns = m->num_states;
-    if (packed && ns != 4) return dvs_set_error(ctx, DVS_ERR_VALUE, "packed sequences have four states, not %u", ns);
-    const uint64_t B = m->nbins;
-    const bool lds_hist = B * 4 <= 64 * 1024;
-    const bool ns4 = ns == 4;
-    (void)offsets;
-    dvs_ctx::OffsetsCache &oc = ctx->off_cache;
-    uint64_t *d_off = oc.uniform ? nullptr : static_cast<uint64_t *>(oc.d_off);
-    const uint64_t uni_base = oc.uni_base, uni_stride = oc.uni_stride;
-    uint32_t *d_rows = static_cast<uint32_t *>(oc.d_rows);
-    KTile *d_tiles = static_cast<KTile *>(oc.d_tiles);
-    const size_t n_long = oc.n_long, n_tiles = oc.n_tiles;
-    auto cleanup = [&]() {};  // (the lists belong to the context's cache now)
-    int rc = DVS_OK;
+// Zeroing: rows that take global atomics start at zero; the c log2 c table is made on first use.
+static int hist_zero(const HistBuild &b) {
+    dvs_ctx *ctx = b.ctx;
+    const dvs_ctx::OffsetsCache &oc = ctx->off_cache;
+    const uint64_t B = b.m->nbins;
     hipError_t e = hipSuccess;
-    if (!lds_hist)  // the rows take the atomics directly: all start at zero
-        e = hipMemsetAsync(m->d_counts, 0, size_t(nseq) * B * 4, ctx->stream);
-    if (e == hipSuccess && n_long && lds_hist)
-        hipLaunchKernelGGL(zero_rows_kernel, dim3(uint32_t(n_long)), dim3(HIST_THREADS), 0, ctx->stream,
-                           m->d_counts, d_rows, B);
+    if (!b.lds_hist)  // the rows take the atomics directly: all start at zero
+        e = hipMemsetAsync(b.m->d_counts, 0, size_t(b.m->nrows) * B * 4, ctx->stream);
+    if (e == hipSuccess && oc.n_long && b.lds_hist)
+        hipLaunchKernelGGL(zero_rows_kernel, dim3(uint32_t(oc.n_long)), dim3(HIST_THREADS), 0, ctx->stream, b.m->d_counts,
+                           static_cast<const uint32_t *>(oc.d_rows), B);
     if (e != hipSuccess) return dvs_hip_fail(ctx, e, "histogram setup");
     if (!ctx->d_clog_tbl) {
-        rc = dvs_dev_alloc(ctx, (void **)&ctx->d_clog_tbl, CLOG_TBL * sizeof(double), "c log2 c table");
-        if (rc) {
-            cleanup();
-            return rc;
-        }
+        if (int rc = dvs_dev_alloc(ctx, (void **)&ctx->d_clog_tbl, CLOG_TBL * sizeof(double), "c log2 c table")) return rc;
         hipLaunchKernelGGL(clog_tbl_kernel, dim3(1), dim3(CLOG_TBL), 0, ctx->stream, ctx->d_clog_tbl);
     }
-    // 256 threads for whole sequences: with 16-18 KB of LDS each, 8 workgroups (32 waves) fill a CU;
-    // measured on 100k x 5 kb: 0.67 ms at 256 threads, 0.78 at 320, 0.86 at 384 and 512
-    // (genome tiles: 256 and 512 measure the same at 4^6 bins; a 64 KB histogram -- 4^7 bins -- leaves room for two
-    // workgroups a CU, and 512 threads each put sixteen waves on it instead of eight)
-    int nthreads = HIST_THREADS;
-    const int tile_threads = (lds_hist && B * 4 > 32768) ? HIST_MAX_THREADS : HIST_THREADS;
-    const size_t lds = (lds_hist ? ((B * 4 + 15) & ~15ull) : 0) + (CLOG_TBL + 32) * sizeof(double);
-#define DVS_LAUNCH_HIST(NS4, LH, PKD, GRID, TILES, NTHR, HOT)                                             \
-    do {                                                                                         \
-        rc = set_dyn_lds(ctx, kmer_hist_kernel<NS4, LH, false, false, PKD>, lds);                \
-        if (!rc)                                                                                 \
-            hipLaunchKernelGGL((kmer_hist_kernel<NS4, LH, false, false, PKD>), dim3(GRID), dim3(NTHR), lds,  \
-                               ctx->stream, d_seqs, d_pmask, nbytes, d_off, TILES, m->d_counts,  \
-                               m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, HOT, 0u, uni_base, uni_stride);   \
-    } while (0)
-#define DVS_LAUNCH_HIST_ANY(GRID, TILES, NTHR, HOT)                            \
-    do {                                                                  \
-        if (packed && lds_hist) DVS_LAUNCH_HIST(true, true, true, GRID, TILES, NTHR, HOT);   \
-        else if (packed) DVS_LAUNCH_HIST(true, false, true, GRID, TILES, NTHR, HOT);         \
-        else if (ns4 && lds_hist) DVS_LAUNCH_HIST(true, true, false, GRID, TILES, NTHR, HOT);   \
-        else if (ns4) DVS_LAUNCH_HIST(true, false, false, GRID, TILES, NTHR, HOT);         \
-        else if (lds_hist) DVS_LAUNCH_HIST(false, true, false, GRID, TILES, NTHR, HOT);    \
-        else DVS_LAUNCH_HIST(false, false, false, GRID, TILES, NTHR, HOT);                 \
-    } while (0)
-    // The rows a selection reads first (its event-dense head is bound by fetch latency) are built
-    // last and with ordinary stores, so that they are what the 256 MB memory-side cache still holds
-    // when the selection starts; every other row is a streaming store.  Measured on 100k x 4^6:
-    // streaming stores -0.04 ms per build + selection, the hot head another -0.01 ms.
-    uint32_t hot_rows = uint32_t(std::min<uint64_t>(nseq, (192ull << 20) / (B * (m->kind == 2 ? 2 : 4))));
-    // whole sequences: the packed histogram at 128 threads when the row layout allows it
-    const bool pk16 = lds_hist && (B & 3) == 0;
-    // A build that does not wait for its kernels is cut in two launches: the head of the matrix first
-    // (what a selection reads first: its seeds), the totals of those rows on their way to the host right
-    // behind it, then everything else.  The selection's set-up kernels run on the context's second
-    // stream beside the second launch (select.hip sel_start).
-    uint32_t head_rows = 0;
-    if (m->kind == 2 && no_wait) {
-        uint32_t want = DVS_HEAD_ROWS;
-        head_rows = std::min<uint32_t>(nseq, want);
+    return DVS_OK;
+}
+
+// The totals of the first `rows` rows (a pinned page of them at most) set out for the host behind what the context's
+// stream holds, and ev_built marks their arrival: whoever needs them (the selection's seeds) waits on that event --
+// after doing the rest of its set-up while the histogram kernel runs (dvs_matrix_settle).  The page, the copy and the
+// event: all three undone if any step fails (false: the caller waits for the build instead).
+static bool hist_send_head_totals(dvs_ctx *ctx, dvs_matrix *m, uint32_t rows) {
+    void *pin = nullptr;
+    if (dvs_pinned_get(ctx, &pin) != DVS_OK) return false;
+    m->head_count = uint32_t(std::min<size_t>(rows, 4096 / sizeof(uint32_t)));
+    m->h_head_pinned = static_cast<uint32_t *>(pin);
+    m->ev_built = dvs_event_get(ctx);
+    if (m->ev_built &&
+        hipMemcpyAsync(m->h_head_pinned, m->d_totals, size_t(m->head_count) * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+        hipEventRecord(m->ev_built, ctx->stream) == hipSuccess)
+        return true;
+    if (m->ev_built) dvs_event_put(ctx, m->ev_built);
+    dvs_pinned_put(ctx, pin);
+    m->ev_built = nullptr;
+    m->h_head_pinned = nullptr;
+    return false;
+}
+
+// 16-bit rows row0 .. row0 + count - 1 on `on` (128 threads: the packed histogram)
+static int hist_rows16(const HistBuild &b, uint32_t row0, uint32_t count, uint32_t hot_end, hipStream_t on) {
+    return hist_launch_any(b, true, true, count, 128, on, nullptr, reinterpret_cast<uint32_t *>(b.m->d_counts16), hot_end, row0);
+}
+
+// A build of 16-bit rows that does not wait for its kernels is cut in two launches: the head of the matrix first (what a
+// selection reads first: its seeds), the totals of those rows on their way to the host right behind it (*head_sent), then
+// everything else.  The selection's set-up kernels run on the context's second stream beside the second launch (sel_start).
+static int hist_rows16_split(const HistBuild &b, uint32_t head_rows, bool *head_sent) {
+    dvs_ctx *ctx = b.ctx;
+    dvs_matrix *m = b.m;
+    const uint32_t nseq = m->nrows;
+    // With a CU split (dvs_ctx_cu_split) the rest of the matrix is built on the stream that leaves the head CUs alone --
+    // forked here, so that it is ordered behind everything the context's stream holds so far (the sequences' producer,
+    // the offsets' upload) and runs beside the head launch; the context's stream joins it again below.
+    const bool split = nseq - head_rows >= 16u * head_rows && dvs_ctx_cu_split(ctx);
+    hipEvent_t ev_fork = split ? dvs_event_get(ctx) : nullptr;
+    bool forked = ev_fork && hipEventRecord(ev_fork, ctx->stream) == hipSuccess &&
+                  hipStreamWaitEvent(ctx->stream_rest, ev_fork, 0) == hipSuccess;
+    int rc = hist_rows16(b, 0, head_rows, head_rows, ctx->stream);
+    if (!rc && hist_send_head_totals(ctx, m, head_rows)) {
+        *head_sent = true;
+        m->head_rows_built = head_rows;
     }
-    if (head_rows == nseq) head_rows = 0;  // (nothing left to run beside)
-    bool head_event_done = false;
-    if (m->kind == 2) {  // 16-bit rows (dvs_hist_rows_fit_u16 held when the matrix was allocated)
-        const size_t lds16 = ((B * 2 + 15) & ~15ull) + (CLOG_TBL + 32) * sizeof(double);
-        uint32_t *out16 = reinterpret_cast<uint32_t *>(m->d_counts16);
-        auto launch16 = [&](uint32_t row0, uint32_t count, uint32_t hot_end, hipStream_t on) {
-            if (packed) {
-                rc = set_dyn_lds(ctx, kmer_hist_kernel<true, true, true, true, true>, lds16);
-                if (!rc)
-                    hipLaunchKernelGGL((kmer_hist_kernel<true, true, true, true, true>), dim3(count), dim3(128), lds16, on,
-                                       d_seqs, d_pmask, nbytes, d_off, static_cast<const KTile *>(nullptr), out16,
-                                       m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, hot_end, row0, uni_base, uni_stride);
-            } else if (ns4) {
-                rc = set_dyn_lds(ctx, kmer_hist_kernel<true, true, true, true>, lds16);
-                if (!rc)
-                    hipLaunchKernelGGL((kmer_hist_kernel<true, true, true, true>), dim3(count), dim3(128), lds16, on,
-                                       d_seqs, d_pmask, nbytes, d_off, static_cast<const KTile *>(nullptr), out16,
-                                       m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, hot_end, row0, uni_base, uni_stride);
+    if (!rc) {
+        const uint32_t hot_end = uint32_t(std::min<uint64_t>(nseq, uint64_t(head_rows) + b.hot_rows));
+        forked = forked && *head_sent;
+        rc = hist_rows16(b, head_rows, nseq - head_rows, hot_end, forked ? ctx->stream_rest : ctx->stream);
+        if (forked) {
+            hipEvent_t ev_join = dvs_event_get(ctx);
+            if (!ev_join || hipEventRecord(ev_join, ctx->stream_rest) != hipSuccess ||
+                hipStreamWaitEvent(ctx->stream, ev_join, 0) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(ctx->stream_rest);  // (no event: the host orders the two streams)
             } else {
-                rc = set_dyn_lds(ctx, kmer_hist_kernel<false, true, true, true>, lds16);
-                if (!rc)
-                    hipLaunchKernelGGL((kmer_hist_kernel<false, true, true, true>), dim3(count), dim3(128), lds16, on,
-                                       d_seqs, d_pmask, nbytes, d_off, static_cast<const KTile *>(nullptr), out16,
-                                       m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, hot_end, row0, uni_base, uni_stride);
+                m->rest_beside_head = true;
             }
-        };
-        if (head_rows) {
-            // With a CU split (dvs_ctx_cu_split) the rest of the matrix is built on the stream that
-            // leaves the head CUs alone -- forked here, so that it is ordered behind everything the
-            // context's stream holds so far (the sequences' producer, the offsets' upload) and runs
-            // beside the head launch; the context's stream joins it again below.
-            const bool split = nseq - head_rows >= 16u * head_rows && dvs_ctx_cu_split(ctx);
-            hipEvent_t ev_fork = split ? dvs_event_get(ctx) : nullptr;
-            bool forked = ev_fork && hipEventRecord(ev_fork, ctx->stream) == hipSuccess &&
-                          hipStreamWaitEvent(ctx->stream_rest, ev_fork, 0) == hipSuccess;
-            launch16(0, head_rows, head_rows, ctx->stream);
-            void *pin = nullptr;
-            if (!rc && dvs_pinned_get(ctx, &pin) == DVS_OK) {
-                m->head_count = uint32_t(std::min<size_t>(head_rows, 4096 / sizeof(uint32_t)));
-                m->h_head_pinned = static_cast<uint32_t *>(pin);
-                m->ev_built = dvs_event_get(ctx);
-                if (m->ev_built &&
-                    hipMemcpyAsync(m->h_head_pinned, m->d_totals, size_t(m->head_count) * 4, hipMemcpyDeviceToHost,
-                                   ctx->stream) == hipSuccess &&
-                    hipEventRecord(m->ev_built, ctx->stream) == hipSuccess) {
-                    head_event_done = true;
-                    m->head_rows_built = head_rows;
-                } else {
-                    if (m->ev_built) dvs_event_put(ctx, m->ev_built);
-                    dvs_pinned_put(ctx, pin);
-                    m->ev_built = nullptr;
-                    m->h_head_pinned = nullptr;
-                }
-            }
-            if (!rc) {
-                const uint32_t hot_end = uint32_t(std::min<uint64_t>(nseq, uint64_t(head_rows) + hot_rows));
-                forked = forked && head_event_done;
-                launch16(head_rows, nseq - head_rows, hot_end, forked ? ctx->stream_rest : ctx->stream);
-                if (forked) {
-                    hipEvent_t ev_join = dvs_event_get(ctx);
-                    if (!ev_join || hipEventRecord(ev_join, ctx->stream_rest) != hipSuccess ||
-                        hipStreamWaitEvent(ctx->stream, ev_join, 0) != hipSuccess) {
-                        (void)hipGetLastError();
-                        (void)hipStreamSynchronize(ctx->stream_rest);  // (no event: the host orders the two streams)
-                    } else {
-                        m->rest_beside_head = true;
-                    }
-                    // (kept with the matrix until it goes, for the reason ev_fork is kept below: the
-                    // context's stream may not have performed its wait yet when this call returns)
-                    m->ev_join = ev_join;
-                }
-            }
-            // (back to the pool only now: an event handed out again and re-recorded while the wait on
-            // its first record is still queued would move that wait to the later record)
-            if (ev_fork) dvs_event_put(ctx, ev_fork);
-        } else {
-            launch16(0, nseq, hot_rows, ctx->stream);
+            // (kept with the matrix until it goes, for the reason ev_fork is kept below: the
+            // context's stream may not have performed its wait yet when this call returns)
+            m->ev_join = ev_join;
         }
-    } else if (pk16) {
-        const size_t lds16 = ((B * 2 + 15) & ~15ull) + (CLOG_TBL + 32) * sizeof(double);
-        if (packed) {
-            rc = set_dyn_lds(ctx, kmer_hist_kernel<true, true, true, false, true>, lds16);
-            if (!rc)
-                hipLaunchKernelGGL((kmer_hist_kernel<true, true, true, false, true>), dim3(nseq), dim3(128), lds16, ctx->stream,
-                                   d_seqs, d_pmask, nbytes, d_off, static_cast<const KTile *>(nullptr), m->d_counts,
-                                   m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, hot_rows, 0u, uni_base, uni_stride);
-        } else if (ns4) {
-            rc = set_dyn_lds(ctx, kmer_hist_kernel<true, true, true>, lds16);
-            if (!rc)
-                hipLaunchKernelGGL((kmer_hist_kernel<true, true, true>), dim3(nseq), dim3(128), lds16, ctx->stream,
-                                   d_seqs, d_pmask, nbytes, d_off, static_cast<const KTile *>(nullptr), m->d_counts,
-                                   m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, hot_rows, 0u, uni_base, uni_stride);
-        } else {
-            rc = set_dyn_lds(ctx, kmer_hist_kernel<false, true, true>, lds16);
-            if (!rc)
-                hipLaunchKernelGGL((kmer_hist_kernel<false, true, true>), dim3(nseq), dim3(128), lds16, ctx->stream,
-                                   d_seqs, d_pmask, nbytes, d_off, static_cast<const KTile *>(nullptr), m->d_counts,
-                                   m->d_totals, m->d_entropy, ctx->d_clog_tbl, k, ns, B, hot_rows, 0u, uni_base, uni_stride);
-        }
-    } else
-        DVS_LAUNCH_HIST_ANY(nseq, static_cast<const KTile *>(nullptr), nthreads, hot_rows);
-    if (!rc && n_tiles) {
-        DVS_LAUNCH_HIST_ANY(uint32_t(n_tiles), d_tiles, tile_threads, 0u);
-        if (!rc)
-            hipLaunchKernelGGL(row_stats_kernel, dim3(uint32_t(n_long)), dim3(HIST_THREADS), 0,
-                               ctx->stream, m->d_counts, d_rows, m->d_totals, m->d_entropy, B);
     }
-#undef DVS_LAUNCH_HIST_ANY
-#undef DVS_LAUNCH_HIST
-    if (!rc && (e = hipGetLastError()) != hipSuccess) rc = dvs_hip_fail(ctx, e, "histogram launch");
-    if (!rc && no_wait && head_event_done) {  // (the head's totals are already on their way)
+    // (back to the pool only now: an event handed out again and re-recorded while the wait on
+    // its first record is still queued would move that wait to the later record)
+    if (ev_fork) dvs_event_put(ctx, ev_fork);
+    return rc;
+}
+
+// Whole-row launch: every sequence that fits a single tile, one workgroup each (a longer one's leaves at once).
+static int hist_whole_rows(const HistBuild &b, bool no_wait, bool *head_sent) {
+    dvs_matrix *m = b.m;
+    const uint32_t nseq = m->nrows;
+    if (m->kind == 2) {  // 16-bit rows (dvs_hist_rows_fit_u16 held when the matrix was allocated)
+        uint32_t head_rows = no_wait ? std::min<uint32_t>(nseq, DVS_HEAD_ROWS) : 0;
+        if (head_rows == nseq) head_rows = 0;  // (nothing left to run beside)
+        return head_rows ? hist_rows16_split(b, head_rows, head_sent) : hist_rows16(b, 0, nseq, b.hot_rows, b.ctx->stream);
+    }
+    // the packed histogram at 128 threads when the row layout allows it; else 256 threads: with 16-18 KB of LDS each,
+    // 8 workgroups (32 waves) fill a CU; measured on 100k x 5 kb: 0.67 ms at 256 threads, 0.78 at 320, 0.86 at 384 and 512
+    const bool pk16 = b.lds_hist && (m->nbins & 3) == 0;
+    return hist_launch_any(b, pk16, false, nseq, pk16 ? 128 : HIST_THREADS, b.ctx->stream, nullptr, m->d_counts, b.hot_rows, 0u);
+}
+
+// Tile launch: the explicit tile list of the genome-length sequences, then the totals and entropies of their rows.
+static int hist_tiles(const HistBuild &b) {
+    const dvs_ctx::OffsetsCache &oc = b.ctx->off_cache;
+    // (256 and 512 threads measure the same at 4^6 bins; a 64 KB histogram -- 4^7 bins -- leaves room for two
+    // workgroups a CU, and 512 threads each put sixteen waves on it instead of eight)
+    const int tile_threads = (b.lds_hist && b.m->nbins * 4 > 32768) ? HIST_MAX_THREADS : HIST_THREADS;
+    if (int rc = hist_launch_any(b, false, false, uint32_t(oc.n_tiles), tile_threads, b.ctx->stream,
+                                 static_cast<const KTile *>(oc.d_tiles), b.m->d_counts, 0u, 0u))
+        return rc;
+    hipLaunchKernelGGL(row_stats_kernel, dim3(uint32_t(oc.n_long)), dim3(HIST_THREADS), 0, b.ctx->stream, b.m->d_counts,
+                       static_cast<const uint32_t *>(oc.d_rows), b.m->d_totals, b.m->d_entropy, b.m->nbins);
+    return DVS_OK;
+}
+
+// Launches the histogram build for sequences already in HBM (sv, nbytes readable) into an allocated matrix, after
+// dvs_hist_prepare for the same offsets.  One launch gives every sequence that fits a single tile its own workgroup (tile
+// derived from the offsets on the device); genome-length sequences get an explicit tile list and a second launch.
+int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, bool no_wait) {
+    dvs_ctx::OffsetsCache &oc = ctx->off_cache;
+    const bool packed = sv.codes != nullptr;
+    const uint32_t nseq = m->nrows;
+    if (packed && m->num_states != 4)
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "packed sequences have four states, not %u", m->num_states);
+    // The rows a selection reads first (its event-dense head is bound by fetch latency) are built last and with ordinary
+    // stores, so that they are what the 256 MB memory-side cache still holds when the selection starts; every other row is
+    // a streaming store.  Measured on 100k x 4^6: streaming stores -0.04 ms per build + selection, the hot head another -0.01.
+    const uint32_t hot_rows = uint32_t(std::min<uint64_t>(nseq, (192ull << 20) / (m->nbins * (m->kind == 2 ? 2 : 4))));
+    const HistBuild b = {ctx, m, packed ? reinterpret_cast<const uint8_t *>(sv.codes) : sv.seqs, sv.mask, sv.nbytes,
+                         oc.uniform ? nullptr : static_cast<const uint64_t *>(oc.d_off), packed, m->nbins * 4 <= 64 * 1024,
+                         hot_rows};
+    int rc = hist_zero(b);
+    if (rc) return rc;
+    bool head_sent = false;
+    rc = hist_whole_rows(b, no_wait, &head_sent);
+    if (!rc && oc.n_tiles) rc = hist_tiles(b);
+    if (hipError_t e = rc ? hipSuccess : hipGetLastError()) rc = dvs_hip_fail(ctx, e, "histogram launch");
+    // Completion.  Device-resident input: nothing here needs the host to wait (a split build's head totals are
+    // already on their way; otherwise the first rows' totals follow the kernels).
+    if (!rc && no_wait && (head_sent || hist_send_head_totals(ctx, m, nseq))) {
         m->in_flight = oc.lists_in_flight = true;
         return DVS_OK;
-    }
-    if (!rc && no_wait) {
-        // Device-resident input: nothing here needs the host to wait.  The first rows' totals are
-        // copied to a pinned block behind the kernels and an event marks their arrival; whoever
-        // needs them (the selection's seeds) waits on that event -- after doing the rest of its
-        // set-up while the histogram kernel runs.
-        void *pin = nullptr;
-        if (dvs_pinned_get(ctx, &pin) == DVS_OK) {
-            m->head_count = uint32_t(std::min<size_t>(nseq, 4096 / sizeof(uint32_t)));
-            m->h_head_pinned = static_cast<uint32_t *>(pin);
-            m->ev_built = dvs_event_get(ctx);
-            if (m->ev_built &&
-                hipMemcpyAsync(m->h_head_pinned, m->d_totals, size_t(m->head_count) * 4, hipMemcpyDeviceToHost,
-                               ctx->stream) == hipSuccess &&
-                hipEventRecord(m->ev_built, ctx->stream) == hipSuccess) {
-                m->in_flight = oc.lists_in_flight = true;
-                return DVS_OK;
-            }
-            if (m->ev_built) dvs_event_put(ctx, m->ev_built);
-            dvs_pinned_put(ctx, pin);
-            m->ev_built = nullptr;
-            m->h_head_pinned = nullptr;
-        }
     }
     // the totals of the first rows travel back in the same synchronisation (seed rows of a selection)
     m->h_head_totals.assign(std::min<size_t>(nseq, 4096), 0u);
@@ -882,10 +881,8 @@ int dvs_matrix_fill_counts(dvs_ctx *ctx, dvs_matrix *m, const dvs_seq_view &sv, 
         hipMemcpyAsync(m->h_head_totals.data(), m->d_totals, m->h_head_totals.size() * 4, hipMemcpyDeviceToHost,
                        ctx->stream) != hipSuccess)
         m->h_head_totals.clear();
-    // the lists go back to the cache; stream order protects them until the kernels ran
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc)
         rc = dvs_set_error(ctx, DVS_ERR_RUNTIME, "histogram kernels failed");
-    cleanup();
     return rc;
 }
 

@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -669,6 +670,254 @@ __global__ __launch_bounds__(256) void mash_tiles_kernel(const uint64_t *__restr
 
 }  // namespace
 
+// ---- the sketch build: plan, blocks, set-up, then rounds of filter + sort until every sequence's range search ends
+
+// Everything on the host that an asynchronous copy reads or writes: it outlives the StreamDrain of the call.
+struct SketchHost {
+    // the plan over the offsets
+    std::vector<uint32_t> nwin, cap;  // windows; candidates one round may hold
+    std::vector<uint64_t> coff, tpre; // prefix sums of cap and of the tile counts
+    uint64_t n_tiles = 0;
+    // the range search: hashes in (lo, hi] are wanted this round
+    std::vector<long long> lo;
+    std::vector<uint32_t> hi, status, lens, lens_before, list, idle;  // (idle: unproductive rounds in a row)
+    std::vector<uint8_t> active;
+};
+
+// (every block comes from the context's cache: a sketch call used to hipMalloc and hipFree a dozen buffers)
+struct SketchBlocks {
+    PooledBuf tiles, lo, hi, cap, coff, cnt, active, cand, list, status, off, tpre;
+    PooledBuf sk, lens;  // (the two results; released with the rest unless handed over)
+    explicit SketchBlocks(dvs_ctx *c)
+        : tiles{c}, lo{c}, hi{c}, cap{c}, coff{c}, cnt{c}, active{c}, cand{c}, list{c}, status{c}, off{c}, tpre{c}, sk{c}, lens{c} {}
+};
+
+// Whenever work is pending on the stream, a return (an error, the batch whose every sequence is shorter than k) drains
+// it before host memory or blocks go away.  (Every round of the search ends with a synchronisation, so the usual
+// return has nothing left to wait for.)
+struct StreamDrain {
+    hipStream_t st;
+    bool pending = true;
+    ~StreamDrain() {
+        if (pending) (void)hipStreamSynchronize(st);
+    }
+};
+
+// tiles and the first hash range (lo, hi] per sequence: hashes are ~uniform, so
+// hi = 2^32 * (1.5 s + 256) / n_windows holds ~1.5 s candidates; a sequence of
+// at most SORT_CAP windows takes the whole range at once
+static int sketch_plan(dvs_ctx *ctx, const uint64_t *offsets, uint32_t nseq, uint32_t k, uint32_t s, SketchHost &h) {
+    h.lo.assign(nseq, -1);
+    h.hi.resize(nseq);
+    h.cap.resize(nseq);
+    h.nwin.resize(nseq);
+    h.coff.assign(nseq + 1, 0);
+    h.tpre.assign(nseq + 1, 0);
+    const uint64_t want = uint64_t(s) + s / 2 + 256;
+    for (uint32_t q = 0; q < nseq; q++) {
+        const uint64_t len = offsets[q + 1] - offsets[q];
+        const uint64_t w = len >= k ? len - k + 1 : 0;
+        if (w > 0xFFFFFFFFull)
+            return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "sequence %u longer than 2^32", q);
+        h.nwin[q] = uint32_t(w);
+        h.cap[q] = uint32_t(std::min<uint64_t>(std::max<uint64_t>(w, 1), SORT_CAP));
+        if (w <= SORT_CAP) {
+            h.hi[q] = 0xFFFFFFFFu;
+        } else {
+            const long double tv = (long double)std::min<uint64_t>(want, SORT_CAP / 2) / (long double)w * 4294967296.0L;
+            h.hi[q] = tv >= 4294967295.0L ? 0xFFFFFFFFu : uint32_t(tv);
+        }
+        h.coff[q + 1] = h.coff[q] + h.cap[q];
+        // tiles of this sequence (mash_tiles_kernel lays them out): a first one up to the next packed word
+        // boundary + MASH_TILE windows, then whole tiles
+        uint64_t nt = 0;
+        if (w) {
+            const uint64_t first = std::min<uint64_t>(uint64_t(MASH_TILE) - (offsets[q] & 15), w);
+            nt = 1 + (w - first + MASH_TILE - 1) / MASH_TILE;
+        }
+        h.tpre[q + 1] = h.tpre[q] + nt;
+    }
+    h.n_tiles = h.tpre[nseq];
+    if (h.n_tiles > 0xFFFFFFFFull) return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "more than 2^32 - 1 tiles in one batch");
+    return DVS_OK;
+}
+
+static int sketch_alloc(dvs_ctx *ctx, SketchBlocks &d, const SketchHost &h, uint32_t nseq, uint32_t s) {
+    const size_t ntile = std::max<size_t>(size_t(h.n_tiles), 1);
+    int arc = dvs_dev_alloc(ctx, &d.tiles.p, ntile * sizeof(MTile), "sketch tiles");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.lo.p, size_t(nseq) * 8, "hash range (lo)");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.hi.p, size_t(nseq) * 4, "hash range (hi)");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.cap.p, size_t(nseq) * 4, "candidate caps");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.coff.p, (size_t(nseq) + 1) * 8, "candidate offsets");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.cnt.p, size_t(nseq) * 4, "candidate counts");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.active.p, size_t(nseq), "active flags");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.cand.p, std::max<uint64_t>(h.coff[nseq], 1) * 4, "candidates");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.list.p, size_t(nseq) * 4, "active list");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.status.p, size_t(nseq) * 4, "sort status");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.off.p, (size_t(nseq) + 1) * 8, "sequence offsets");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.tpre.p, (size_t(nseq) + 1) * 8, "tile prefix");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.sk.p, size_t(nseq) * s * 4, "sketches");
+    if (!arc) arc = dvs_dev_alloc(ctx, &d.lens.p, size_t(nseq) * 4, "sketch lengths");
+    return arc;
+}
+
+// what does not change between rounds: uploads, the zeroed results, the tile list written on the device
+static hipError_t sketch_setup(dvs_ctx *ctx, SketchBlocks &d, const SketchHost &h, const uint64_t *offsets, uint32_t nseq,
+                               uint32_t k, uint32_t s) {
+    hipError_t ue = hipMemcpyAsync(d.off.p, offsets, (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (ue == hipSuccess) ue = hipMemcpyAsync(d.tpre.p, h.tpre.data(), (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (ue == hipSuccess) ue = hipMemcpyAsync(d.cap.p, h.cap.data(), size_t(nseq) * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (ue == hipSuccess) ue = hipMemcpyAsync(d.coff.p, h.coff.data(), (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (ue == hipSuccess) ue = hipMemsetAsync(d.lens.p, 0, size_t(nseq) * 4, ctx->stream);
+    if (ue == hipSuccess) ue = hipMemsetAsync(d.sk.p, 0, size_t(nseq) * s * 4, ctx->stream);
+    if (ue == hipSuccess && h.n_tiles) {
+        hipLaunchKernelGGL(mash_tiles_kernel, dim3(uint32_t((h.n_tiles + 255) / 256)), dim3(256), 0, ctx->stream, d.off.as<uint64_t>(),
+                           d.tpre.as<uint64_t>(), nseq, k, h.n_tiles, d.tiles.as<MTile>());
+        ue = hipGetLastError();
+    }
+    return ue;
+}
+
+// The run-time choice among the DNA filter's instantiations as compile-time values: f(K16, TBLW, PACKED) -- windows
+// of at most 32 bits or of up to 64, the small hash set or the full one, bytes or packed words: eight kernels.
+template <typename F>
+static void dna_filter_dispatch(bool k16, bool small, bool packed, F &&f) {
+    using Small = std::integral_constant<uint32_t, 2048>;
+    using Full = std::integral_constant<uint32_t, 2 * MASH_TILE>;
+    auto sized = [&](auto k16_c, auto packed_c) {
+        if (small) f(k16_c, Small{}, packed_c);
+        else f(k16_c, Full{}, packed_c);
+    };
+    auto formed = [&](auto k16_c) {
+        if (packed) sized(k16_c, std::true_type{});
+        else sized(k16_c, std::false_type{});
+    };
+    if (k16) formed(std::true_type{});
+    else formed(std::false_type{});
+}
+
+// one round's hash pass over the tiles of the active sequences
+static void sketch_filter_launch(dvs_ctx *ctx, const dvs_seq_view &sv, SketchBlocks &d, const SketchHost &h, uint64_t nbytes,
+                                 uint32_t k, uint32_t num_states, int mash_canonical) {
+    const bool packed = sv.codes != nullptr;
+    const uint8_t *d_seqs = packed ? reinterpret_cast<const uint8_t *>(sv.codes) : sv.seqs;
+    if (num_states != 4 || k > 32) {
+        hipLaunchKernelGGL(hash_filter_kernel, dim3(uint32_t(h.n_tiles)), dim3(MASH_THREADS), 0, ctx->stream, d_seqs,
+                           d.tiles.as<MTile>(), k, num_states, mash_canonical, d.lo.as<long long>(), d.hi.as<uint32_t>(),
+                           d.active.as<uint8_t>(), d.cand.as<uint32_t>(), d.coff.as<uint64_t>(), d.cap.as<uint32_t>(),
+                           d.cnt.as<uint32_t>());
+        return;
+    }
+    // 2-bit packed windows; the small hash set when no active sequence lets more than ~512 windows of a tile through
+    bool small = true;
+    for (uint32_t q : h.list) {
+        const long double frac = ((long double)h.hi[q] - (long double)h.lo[q]) / 4294967296.0L;
+        if (frac * MASH_TILE > 512.0L) small = false;
+    }
+    // (sixteen workgroups' worth of tiles per CU at most: every workgroup loops over its share)
+    const uint32_t dna_grid = uint32_t(std::min<size_t>(size_t(h.n_tiles), size_t(ctx->n_cu) * 16));
+    dna_filter_dispatch(k <= 16, small, packed, [&](auto k16, auto tblw, auto pk) {
+        hipLaunchKernelGGL((hash_filter_dna_kernel<decltype(k16)::value, decltype(tblw)::value, decltype(pk)::value>),
+                           dim3(dna_grid), dim3(MASH_THREADS), 0, ctx->stream, d_seqs, sv.mask, nbytes, d.tiles.as<MTile>(),
+                           uint32_t(h.n_tiles), k, mash_canonical, d.lo.as<long long>(), d.hi.as<uint32_t>(),
+                           d.active.as<uint8_t>(), d.cand.as<uint32_t>(), d.coff.as<uint64_t>(), d.cap.as<uint32_t>(),
+                           d.cnt.as<uint32_t>());
+    });
+}
+
+constexpr size_t SORT_LDS = SORT_CAP * 4;
+
+// one workgroup per active sequence: its candidates sorted, made unique and appended to its sketch
+static void sketch_sort_launch(dvs_ctx *ctx, SketchBlocks &d, uint32_t nlist, uint32_t s) {
+    hipLaunchKernelGGL(sort_select_kernel, dim3(nlist), dim3(1024), SORT_LDS, ctx->stream, d.list.as<uint32_t>(),
+                       d.cand.as<uint32_t>(), d.coff.as<uint64_t>(), d.cap.as<uint32_t>(), d.cnt.as<uint32_t>(),
+                       d.hi.as<uint32_t>(), s, d.sk.as<uint32_t>(), d.lens.as<uint32_t>(), d.status.as<uint32_t>());
+}
+
+// The next range (lo, hi] of one sequence after a round of status 1 or 2; false: the range cannot be halved any more.
+// Status 1 -- everything in (lo, hi] is final; continue above it with a range sized by the density seen so far:
+// wide enough for what is still needed (1.5 x) but at most what holds ~SORT_CAP / 2 candidates --
+// for a large s the estimate reaches the top of the hash space, and shrinking such a range back to
+// SORT_CAP candidates took a halving round (a hash pass over the sequence) per factor of two.  A range
+// that held nothing new says nothing about the density: the next one is at least twice as wide.
+// Status 2 -- more than SORT_CAP (tile-distinct) candidates in the range: halve it.
+static bool sketch_next_range(long long &lo, uint32_t &hi, uint32_t status, uint32_t len, uint32_t len_before, uint32_t s) {
+    const uint64_t width = uint64_t((long long)hi - lo);
+    if (status == 1) {
+        const long double per_hash = (long double)(uint64_t(hi) + 1) / std::max<uint32_t>(len, 1);
+        const uint64_t need = s - len;
+        const uint64_t est = uint64_t(std::min<long double>(per_hash * need * 1.5L, 8589934592.0L));
+        const uint64_t cap_w = uint64_t(std::min<long double>(per_hash * (SORT_CAP / 2), 8589934592.0L));
+        const uint64_t next = len == len_before ? std::max<uint64_t>(2 * width, std::min(est, cap_w))
+                                                : std::min(std::max<uint64_t>(2 * width, est), cap_w);
+        lo = hi;
+        const uint64_t nh = uint64_t(hi) + std::max<uint64_t>(next, 1);
+        hi = nh >= 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(nh);
+        return true;
+    }
+    if (width <= 1) return false;
+    hi = uint32_t(lo + (long long)(width / 2));
+    return true;
+}
+
+// The rounds of the range search of one sequence are bounded.  A round either halves its range (status 2: only
+// ranges at least 2 wide are halved, so at most 32 halvings come in a row) or advances past it (status 1), and the
+// search of a sequence ends in a round of status 0.  Call an advance PRODUCTIVE when its range held a hash not in
+// the sketch yet: each one lengthens the sketch, so a sequence of w windows has at most min(s, w) of them, and
+// one final round.  Between two productive rounds, let h* be the least hash above lo and d = h* - lo: an
+// unproductive advance moves lo by the width it covered, which is < d, and (sketch_next_range) at least doubles the
+// next width; a halving needs width >= d (its range held h*).  So first come at most 33 doubling advances; after
+// a run of halvings the range is narrower than d but half the last one was not, and the advance past it at least
+// halves d -- at most 33 such runs of at most 32 halvings, each followed by one advance.  That is at most
+// 33 + 33 * 33 unproductive rounds between productive ones: a sequence that goes on longer without one is refused
+// at once (a bug, not a hard input), and the batch as a whole within (min(s, w) + 1) * (STRETCH + 1) rounds.
+static int sketch_rounds(dvs_ctx *ctx, const dvs_seq_view &sv, SketchBlocks &d, SketchHost &h, StreamDrain &drain, uint64_t nbytes,
+                         uint32_t nseq, uint32_t k, uint32_t s, uint32_t num_states, int mash_canonical) {
+    constexpr uint32_t STRETCH = 33 + 33 * 33;
+    uint64_t max_productive = 0;
+    for (uint32_t q = 0; q < nseq; q++) {
+        if (h.nwin[q] == 0) h.active[q] = 0;  // L < k: empty sketch (distance.rs:102-104)
+        max_productive = std::max<uint64_t>(max_productive, std::min<uint64_t>(s, h.nwin[q]) + 1);
+    }
+    const uint64_t max_rounds = max_productive * (STRETCH + 1);
+    if (int lrc = dvs_raise_dyn_lds(ctx, reinterpret_cast<const void *>(sort_select_kernel), SORT_LDS)) return lrc;
+
+    for (uint64_t round = 0;; round++) {
+        h.list.clear();
+        for (uint32_t q = 0; q < nseq; q++)
+            if (h.active[q]) h.list.push_back(q);
+        if (h.list.empty()) return DVS_OK;
+        if (round >= max_rounds)
+            return dvs_set_error(ctx, DVS_ERR_RUNTIME, "mash sketch range search did not converge in %llu rounds",
+                                 (unsigned long long)max_rounds);
+        h.lens_before = h.lens;
+        drain.pending = true;
+        DVS_HIP(ctx, hipMemcpyAsync(d.lo.p, h.lo.data(), nseq * 8, hipMemcpyHostToDevice, ctx->stream));
+        DVS_HIP(ctx, hipMemcpyAsync(d.hi.p, h.hi.data(), nseq * 4, hipMemcpyHostToDevice, ctx->stream));
+        DVS_HIP(ctx, hipMemcpyAsync(d.active.p, h.active.data(), nseq, hipMemcpyHostToDevice, ctx->stream));
+        DVS_HIP(ctx, hipMemcpyAsync(d.list.p, h.list.data(), h.list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        DVS_HIP(ctx, hipMemsetAsync(d.cnt.p, 0, nseq * 4, ctx->stream));
+        sketch_filter_launch(ctx, sv, d, h, nbytes, k, num_states, mash_canonical);
+        sketch_sort_launch(ctx, d, uint32_t(h.list.size()), s);
+        DVS_HIP(ctx, hipGetLastError());
+        DVS_HIP(ctx, hipMemcpyAsync(h.status.data(), d.status.p, nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        DVS_HIP(ctx, hipMemcpyAsync(h.lens.data(), d.lens.p, nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        drain.pending = false;
+        for (uint32_t q : h.list) {
+            h.idle[q] = h.status[q] == 1 && h.lens[q] != h.lens_before[q] ? 0u : h.idle[q] + 1u;
+            if (h.status[q] != 0 && h.idle[q] > STRETCH)
+                return dvs_set_error(ctx, DVS_ERR_RUNTIME,
+                                     "mash sketch range search: sequence %u found no new hash in %u rounds", q, STRETCH);
+            if (h.status[q] == 0)
+                h.active[q] = 0;
+            else if (!sketch_next_range(h.lo[q], h.hi[q], h.status[q], h.lens[q], h.lens_before[q], s))
+                return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "sequence %u: one hash value occurs in more than %u tiles",
+                                     q, SORT_CAP);
+        }
+    }
+}
+
 // sketches of a batch, left in HBM: nseq x sketch_size uint32 (ascending, first d_lens[i] valid) in
 // blocks of the context's cache (the caller hands them back with dvs_dev_free)
 static int mash_sketch_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_t *offsets,
@@ -679,212 +928,27 @@ static int mash_sketch_view(dvs_ctx *ctx, const dvs_seq_view &sv, const uint64_t
     DVS_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t s = sketch_size;
     const uint64_t nbytes = offsets[nseq];
-    const bool packed = sv.codes != nullptr;
     if (nbytes > sv.nbytes)
         return dvs_set_error(ctx, DVS_ERR_VALUE, "offsets[%u] = %llu beyond the %llu bases of the batch", nseq,
                              (unsigned long long)nbytes, (unsigned long long)sv.nbytes);
-    if (packed && (num_states != 4 || k > 32))
+    if (sv.codes != nullptr && (num_states != 4 || k > 32))
         return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "packed sequences are sketched with four states and k <= 32 (k = %u, %u states)",
                              k, num_states);
-    const uint8_t *d_seqs = packed ? reinterpret_cast<const uint8_t *>(sv.codes) : sv.seqs;
-    const uint16_t *d_pmask = sv.mask;
-
-    // tiles and the first hash range (lo, hi] per sequence: hashes are ~uniform, so
-    // hi = 2^32 * (1.5 s + 256) / n_windows holds ~1.5 s candidates; a sequence of
-    // at most SORT_CAP windows takes the whole range at once
-    std::vector<long long> lo(nseq, -1);
-    std::vector<uint32_t> hi(nseq), cap(nseq), nwin(nseq);
-    std::vector<uint64_t> coff(nseq + 1, 0), tpre(nseq + 1, 0);
-    const uint64_t want = uint64_t(s) + s / 2 + 256;
-    for (uint32_t q = 0; q < nseq; q++) {
-        const uint64_t len = offsets[q + 1] - offsets[q];
-        const uint64_t w = len >= k ? len - k + 1 : 0;
-        if (w > 0xFFFFFFFFull)
-            return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "sequence %u longer than 2^32", q);
-        nwin[q] = uint32_t(w);
-        cap[q] = uint32_t(std::min<uint64_t>(std::max<uint64_t>(w, 1), SORT_CAP));
-        if (w <= SORT_CAP) {
-            hi[q] = 0xFFFFFFFFu;
-        } else {
-            const long double tv = (long double)std::min<uint64_t>(want, SORT_CAP / 2) / (long double)w * 4294967296.0L;
-            hi[q] = tv >= 4294967295.0L ? 0xFFFFFFFFu : uint32_t(tv);
-        }
-        coff[q + 1] = coff[q] + cap[q];
-        // tiles of this sequence (mash_tiles_kernel lays them out): a first one up to the next packed word
-        // boundary + MASH_TILE windows, then whole tiles
-        uint64_t nt = 0;
-        if (w) {
-            const uint64_t first = std::min<uint64_t>(uint64_t(MASH_TILE) - (offsets[q] & 15), w);
-            nt = 1 + (w - first + MASH_TILE - 1) / MASH_TILE;
-        }
-        tpre[q + 1] = tpre[q] + nt;
-    }
-    const uint64_t n_tiles = tpre[nseq];
-    if (n_tiles > 0xFFFFFFFFull) return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED, "more than 2^32 - 1 tiles in one batch");
-    // (every block comes from the context's cache: a sketch call used to hipMalloc and hipFree a dozen buffers)
-    PooledBuf d_tiles{ctx}, d_lo{ctx}, d_hi{ctx}, d_cap{ctx}, d_coff{ctx}, d_cnt{ctx}, d_active{ctx}, d_cand{ctx}, d_list{ctx},
-        d_status{ctx}, d_off{ctx}, d_tpre{ctx};
-    PooledBuf d_sk{ctx}, d_lens{ctx};  // (the two results; released here unless handed over)
-    {
-        const size_t ntile = std::max<size_t>(size_t(n_tiles), 1);
-        int arc = dvs_dev_alloc(ctx, &d_tiles.p, ntile * sizeof(MTile), "sketch tiles");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_lo.p, size_t(nseq) * 8, "hash range (lo)");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_hi.p, size_t(nseq) * 4, "hash range (hi)");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_cap.p, size_t(nseq) * 4, "candidate caps");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_coff.p, (size_t(nseq) + 1) * 8, "candidate offsets");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_cnt.p, size_t(nseq) * 4, "candidate counts");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_active.p, size_t(nseq), "active flags");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_cand.p, std::max<uint64_t>(coff[nseq], 1) * 4, "candidates");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_list.p, size_t(nseq) * 4, "active list");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_status.p, size_t(nseq) * 4, "sort status");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_off.p, (size_t(nseq) + 1) * 8, "sequence offsets");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_tpre.p, (size_t(nseq) + 1) * 8, "tile prefix");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_sk.p, size_t(nseq) * s * 4, "sketches");
-        if (!arc) arc = dvs_dev_alloc(ctx, &d_lens.p, size_t(nseq) * 4, "sketch lengths");
-        if (arc) return arc;
-    }
-    // Host memory -- tpre, cap, coff, lo, hi, active, list, the caller's offsets -- is the source of asynchronous
-    // copies, and a kernel may still be reading the blocks above: whenever work is pending on the stream, a return
-    // from here on (an error, the batch whose every sequence is shorter than k) drains it before either goes away.
-    // (Every round of the search ends with a synchronisation, so the usual return has nothing left to wait for.)
-    std::vector<uint8_t> active(nseq, 1);
-    std::vector<uint32_t> status(nseq, 0), lens(nseq, 0), lens_before(nseq, 0), list;
-    struct StreamDrain {
-        hipStream_t st;
-        bool pending = true;
-        ~StreamDrain() {
-            if (pending) (void)hipStreamSynchronize(st);
-        }
-    } drain{ctx->stream};
-    hipError_t ue = hipMemcpyAsync(d_off.p, offsets, (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (ue == hipSuccess) ue = hipMemcpyAsync(d_tpre.p, tpre.data(), (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (ue == hipSuccess) ue = hipMemcpyAsync(d_cap.p, cap.data(), size_t(nseq) * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (ue == hipSuccess) ue = hipMemcpyAsync(d_coff.p, coff.data(), (size_t(nseq) + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (ue == hipSuccess) ue = hipMemsetAsync(d_lens.p, 0, size_t(nseq) * 4, ctx->stream);
-    if (ue == hipSuccess) ue = hipMemsetAsync(d_sk.p, 0, size_t(nseq) * s * 4, ctx->stream);
-    if (ue == hipSuccess && n_tiles) {
-        hipLaunchKernelGGL(mash_tiles_kernel, dim3(uint32_t((n_tiles + 255) / 256)), dim3(256), 0, ctx->stream, d_off.as<uint64_t>(),
-                           d_tpre.as<uint64_t>(), nseq, k, n_tiles, d_tiles.as<MTile>());
-        ue = hipGetLastError();
-    }
+    SketchHost h;
+    if (int rc = sketch_plan(ctx, offsets, nseq, k, s, h)) return rc;
+    SketchBlocks d(ctx);
+    if (int rc = sketch_alloc(ctx, d, h, nseq, s)) return rc;
+    // Host memory -- h, the caller's offsets -- is the source of asynchronous copies, and a kernel may still be
+    // reading the blocks above: from here on a return with work pending drains the stream before either goes away.
+    h.active.assign(nseq, 1);
+    for (auto *v : {&h.status, &h.lens, &h.lens_before, &h.idle}) v->assign(nseq, 0);
+    StreamDrain drain{ctx->stream};
+    const hipError_t ue = sketch_setup(ctx, d, h, offsets, nseq, k, s);
     if (ue != hipSuccess) return dvs_hip_fail(ctx, ue, "sketch set-up");
-
-    // The rounds of the range search of one sequence are bounded.  A round either halves its range (status 2: only
-    // ranges at least 2 wide are halved, so at most 32 halvings come in a row) or advances past it (status 1), and the
-    // search of a sequence ends in a round of status 0.  Call an advance PRODUCTIVE when its range held a hash not in
-    // the sketch yet: each one lengthens the sketch, so a sequence of w windows has at most min(s, w) of them, and
-    // one final round.  Between two productive rounds, let h* be the least hash above lo and d = h* - lo: an
-    // unproductive advance moves lo by the width it covered, which is < d, and (the rule below) at least doubles the
-    // next width; a halving needs width >= d (its range held h*).  So first come at most 33 doubling advances; after
-    // a run of halvings the range is narrower than d but half the last one was not, and the advance past it at least
-    // halves d -- at most 33 such runs of at most 32 halvings, each followed by one advance.  That is at most
-    // 33 + 33 * 33 unproductive rounds between productive ones: a sequence that goes on longer without one is refused
-    // at once (a bug, not a hard input), and the batch as a whole within (min(s, w) + 1) * (STRETCH + 1) rounds.
-    constexpr uint32_t STRETCH = 33 + 33 * 33;
-    std::vector<uint32_t> idle(nseq, 0);  // unproductive rounds in a row, per sequence
-    uint64_t max_productive = 0;
-    for (uint32_t q = 0; q < nseq; q++) {
-        if (nwin[q] == 0) active[q] = 0;  // L < k: empty sketch (distance.rs:102-104)
-        max_productive = std::max<uint64_t>(max_productive, std::min<uint64_t>(s, nwin[q]) + 1);
-    }
-    const uint64_t max_rounds = max_productive * (STRETCH + 1);
-    const size_t sort_lds = SORT_CAP * 4;
-    {
-        const int lrc = dvs_raise_dyn_lds(ctx, reinterpret_cast<const void *>(sort_select_kernel), sort_lds);
-        if (lrc) return lrc;
-    }
-
-    for (uint64_t round = 0;; round++) {
-        list.clear();
-        for (uint32_t q = 0; q < nseq; q++)
-            if (active[q]) list.push_back(q);
-        if (list.empty()) break;
-        if (round >= max_rounds)
-            return dvs_set_error(ctx, DVS_ERR_RUNTIME, "mash sketch range search did not converge in %llu rounds",
-                                 (unsigned long long)max_rounds);
-        lens_before = lens;
-        drain.pending = true;
-        DVS_HIP(ctx, hipMemcpyAsync(d_lo.p, lo.data(), nseq * 8, hipMemcpyHostToDevice, ctx->stream));
-        DVS_HIP(ctx, hipMemcpyAsync(d_hi.p, hi.data(), nseq * 4, hipMemcpyHostToDevice, ctx->stream));
-        DVS_HIP(ctx, hipMemcpyAsync(d_active.p, active.data(), nseq, hipMemcpyHostToDevice, ctx->stream));
-        DVS_HIP(ctx, hipMemcpyAsync(d_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        DVS_HIP(ctx, hipMemsetAsync(d_cnt.p, 0, nseq * 4, ctx->stream));
-        if (num_states == 4 && k <= 32 && true) {  // 2-bit packed windows
-            // the small hash set when no active sequence lets more than ~512 windows of a tile through
-            bool small = true;
-            for (uint32_t q : list) {
-                const long double frac = ((long double)hi[q] - (long double)lo[q]) / 4294967296.0L;
-                if (frac * MASH_TILE > 512.0L) small = false;
-            }
-            // (sixteen workgroups' worth of tiles per CU at most: every workgroup loops over its share)
-            const uint32_t dna_grid = uint32_t(std::min<size_t>(size_t(n_tiles), size_t(ctx->n_cu) * 16));
-#define DVS_LAUNCH_DNA(K16, TBLW, PKD)                                                                         \
-    hipLaunchKernelGGL((hash_filter_dna_kernel<K16, TBLW, PKD>), dim3(dna_grid), dim3(MASH_THREADS), 0, \
-                       ctx->stream, d_seqs, d_pmask, nbytes, d_tiles.as<MTile>(), uint32_t(n_tiles), k, mash_canonical, d_lo.as<long long>(), \
-                       d_hi.as<uint32_t>(), d_active.as<uint8_t>(), d_cand.as<uint32_t>(), d_coff.as<uint64_t>(), \
-                       d_cap.as<uint32_t>(), d_cnt.as<uint32_t>())
-#define DVS_LAUNCH_DNA_ANY(PKD)                                  \
-    do {                                                         \
-        if (k <= 16 && small) DVS_LAUNCH_DNA(true, 2048, PKD);   \
-        else if (k <= 16) DVS_LAUNCH_DNA(true, 2 * MASH_TILE, PKD); \
-        else if (small) DVS_LAUNCH_DNA(false, 2048, PKD);        \
-        else DVS_LAUNCH_DNA(false, 2 * MASH_TILE, PKD);          \
-    } while (0)
-            if (packed) DVS_LAUNCH_DNA_ANY(true);
-            else DVS_LAUNCH_DNA_ANY(false);
-#undef DVS_LAUNCH_DNA_ANY
-#undef DVS_LAUNCH_DNA
-        } else
-            hipLaunchKernelGGL(hash_filter_kernel, dim3(uint32_t(n_tiles)), dim3(MASH_THREADS), 0,
-                               ctx->stream, d_seqs, d_tiles.as<MTile>(), k, num_states, mash_canonical,
-                               d_lo.as<long long>(), d_hi.as<uint32_t>(), d_active.as<uint8_t>(),
-                               d_cand.as<uint32_t>(), d_coff.as<uint64_t>(), d_cap.as<uint32_t>(),
-                               d_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(sort_select_kernel, dim3(uint32_t(list.size())), dim3(1024), sort_lds,
-                           ctx->stream, d_list.as<uint32_t>(), d_cand.as<uint32_t>(),
-                           d_coff.as<uint64_t>(), d_cap.as<uint32_t>(), d_cnt.as<uint32_t>(),
-                           d_hi.as<uint32_t>(), s, d_sk.as<uint32_t>(), d_lens.as<uint32_t>(),
-                           d_status.as<uint32_t>());
-        DVS_HIP(ctx, hipGetLastError());
-        DVS_HIP(ctx, hipMemcpyAsync(status.data(), d_status.p, nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        DVS_HIP(ctx, hipMemcpyAsync(lens.data(), d_lens.p, nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        DVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        drain.pending = false;
-        for (uint32_t q : list) {
-            const uint64_t width = uint64_t((long long)hi[q] - lo[q]);
-            idle[q] = status[q] == 1 && lens[q] != lens_before[q] ? 0u : idle[q] + 1u;
-            if (status[q] != 0 && idle[q] > STRETCH)
-                return dvs_set_error(ctx, DVS_ERR_RUNTIME,
-                                     "mash sketch range search: sequence %u found no new hash in %u rounds", q, STRETCH);
-            if (status[q] == 0) {
-                active[q] = 0;
-            } else if (status[q] == 1) {
-                // everything in (lo, hi] is final; continue above it with a range sized by the density seen so far:
-                // wide enough for what is still needed (1.5 x) but at most what holds ~SORT_CAP / 2 candidates --
-                // for a large s the estimate reaches the top of the hash space, and shrinking such a range back to
-                // SORT_CAP candidates took a halving round (a hash pass over the sequence) per factor of two.  A range
-                // that held nothing new says nothing about the density: the next one is at least twice as wide.
-                const long double per_hash = (long double)(uint64_t(hi[q]) + 1) / std::max<uint32_t>(lens[q], 1);
-                const uint64_t need = s - lens[q];
-                const uint64_t est = uint64_t(std::min<long double>(per_hash * need * 1.5L, 8589934592.0L));
-                const uint64_t cap_w = uint64_t(std::min<long double>(per_hash * (SORT_CAP / 2), 8589934592.0L));
-                const uint64_t next = lens[q] == lens_before[q] ? std::max<uint64_t>(2 * width, std::min(est, cap_w))
-                                                                : std::min(std::max<uint64_t>(2 * width, est), cap_w);
-                lo[q] = hi[q];
-                const uint64_t nh = uint64_t(hi[q]) + std::max<uint64_t>(next, 1);
-                hi[q] = nh >= 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(nh);
-            } else {
-                // more than SORT_CAP (tile-distinct) candidates in the range: halve it
-                if (width <= 1)
-                    return dvs_set_error(ctx, DVS_ERR_UNSUPPORTED,
-                                         "sequence %u: one hash value occurs in more than %u tiles", q, SORT_CAP);
-                hi[q] = uint32_t(lo[q] + (long long)(width / 2));
-            }
-        }
-    }
-    *d_sk_out = d_sk.as<uint32_t>();
-    *d_lens_out = d_lens.as<uint32_t>();
-    d_sk.p = d_lens.p = nullptr;  // handed over
+    if (int rc = sketch_rounds(ctx, sv, d, h, drain, nbytes, nseq, k, s, num_states, mash_canonical)) return rc;
+    *d_sk_out = d.sk.as<uint32_t>();
+    *d_lens_out = d.lens.as<uint32_t>();
+    d.sk.p = d.lens.p = nullptr;  // handed over
     return DVS_OK;
 }
 
