@@ -94,8 +94,7 @@ def linkage(dist, method: str = "average", *, ctx: engine.Context | None = None)
     code = distance.linkage_method_code(method)
     src, n, wait = _caller_matrix(dist)
     wait()
-    return distance.run_linkage(ctx, n, src, code,
-                                too_few=f"Found array with {n} sample(s) while a minimum of 2 is required")
+    return distance.run_linkage(ctx, src, code, too_few=f"Found array with {n} sample(s) while a minimum of 2 is required")
 
 
 def average_linkage(dist, *, ctx: engine.Context | None = None) -> np.ndarray:
@@ -180,7 +179,7 @@ def neighbor_joining(dist, *, ctx: engine.Context | None = None) -> "distance.NJ
     if n < 3:
         raise ValueError(f"Found array with {n} sample(s) while a minimum of 3 is required for a neighbour-joining tree")
     wait()
-    return distance.run_nj(ctx, n, src)
+    return distance.run_nj(ctx, src)
 
 
 def nj_to_newick(names: Sequence, tree, *, lengths: bool = True) -> str:
@@ -267,7 +266,7 @@ def pcoa(dist, n_axes: int = 3, *, tol: float = 1e-8, max_basis: int | None = No
     src, n, wait = _caller_matrix(dist)
     args = distance.check_pcoa_args(n, n_axes, tol, max_basis)
     wait()
-    return distance.run_pcoa(ctx, n, src, *args, strict)
+    return distance.run_pcoa(ctx, src, *args, strict)
 
 
 def ordinate(seqs: dict, n_axes: int = 3, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
@@ -359,7 +358,7 @@ def cluster_scores(dist, labels, *, ctx: engine.Context | None = None) -> "dista
     lab = distance.check_labels(labels, n)
     if n:
         wait()
-    return distance._run_cluster_scores(ctx or (engine.default_context() if n else None), lab, src)
+    return distance.run_cluster_scores(ctx, src, lab)
 
 
 def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float | None = None,
@@ -374,7 +373,7 @@ def maxmin(dist, n_select: int | None = None, *, seeds=(0,), min_distance: float
     src, n, wait = _caller_matrix(dist)
     args = distance.check_maxmin_args(n, n_select, seeds, min_distance)
     wait()
-    return distance._run_maxmin(ctx, n, *args, src)
+    return distance.run_maxmin(ctx, src, *args)
 
 
 def kmedoids(dist, n_medoids: int, *, init="build", max_swaps: int = 300,
@@ -392,10 +391,10 @@ def kmedoids(dist, n_medoids: int, *, init="build", max_swaps: int = 300,
     k, kind, rows, max_swaps = distance.check_kmedoids_args(n, n_medoids, init, max_swaps)
     wait()
     if kind == "maxmin":
-        rows = distance._run_maxmin(ctx, n, *distance.check_maxmin_args(n, k, (0,), None), src).picks.astype(np.uint32)
+        rows = distance.run_maxmin(ctx, src, *distance.check_maxmin_args(n, k, (0,), None)).picks.astype(np.uint32)
         if rows.size != k:
             raise ValueError(f"farthest-first selection found only {rows.size} of {k} initial medoids")
-    return distance.run_kmedoids(ctx, n, src, k, rows, max_swaps)
+    return distance.run_kmedoids(ctx, src, k, rows, max_swaps)
 
 
 def permanova(dist, grouping, *, permutations: int = 999, seed=None, strata=None,
@@ -412,7 +411,7 @@ def permanova(dist, grouping, *, permutations: int = 999, seed=None, strata=None
     src, n, wait = _caller_matrix(dist)
     checked = distance.check_permanova_args(n, grouping, permutations, seed, strata)
     wait()
-    return distance.run_permanova(ctx, n, src, *checked)
+    return distance.run_permanova(ctx, src, *checked)
 
 
 def representatives(seqs: dict, n: int, *, k: int = 12, sketch_size: int | None = 3000, distance_mode: str = "mash",
@@ -481,10 +480,9 @@ def within(dist, radius, *, skip_self: bool = True, max_pairs: int | None = None
     radius = distance.check_radius(radius)
     limit = distance.check_max_pairs(max_pairs)
     src, n, wait = _caller_matrix(dist)
-    if not n:
-        return distance._no_neighbours(0)
-    wait()
-    return distance._run_within(ctx, src, None, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
+    if n:
+        wait()
+    return distance.run_within(ctx, src, None, radius, _lib.WITHIN_SKIP_SELF if skip_self else 0, limit)
 
 
 def threshold_clusters(dist, radius, *, ctx: engine.Context | None = None) -> "distance.ThresholdClusters":
@@ -497,7 +495,7 @@ def threshold_clusters(dist, radius, *, ctx: engine.Context | None = None) -> "d
     src, n, wait = _caller_matrix(dist)
     if n:
         wait()
-    return distance._run_threshold_clusters(ctx, n, src, radius)
+    return distance.run_threshold_clusters(ctx, src, radius)
 
 
 def _check_symmetric(dist, n: int) -> None:
@@ -552,7 +550,7 @@ def minimum_spanning_tree(dist, *, core=None, min_samples: int | None = None, ch
         if np.isinf(core).any():
             raise ValueError(f"row {int(np.argmax(np.isinf(core)))} has fewer than min_samples = {m} distances that are not NaN")
         core = distance.check_core(core, n)
-    return distance.run_mst(ctx or (engine.default_context() if n else None), n, src, core)
+    return distance.run_mst(ctx, src, core)
 
 
 def mst_linkage(mst) -> np.ndarray:
@@ -680,7 +678,7 @@ def cophenet(Z, dist=None, *, matrix: bool = False, ctx: engine.Context | None =
         return distance.CopheneticScores(float("nan"), np.zeros((5, 0)), np.zeros((0, 0)) if matrix else None)
     pairs, heights = distance.check_linkage_matrix(Z, n)
     wait()
-    return distance._run_cophenet(ctx or engine.default_context(), n, pairs, heights, matrix, src)
+    return distance.run_cophenet(ctx, src, pairs, heights, matrix)
 
 
 def ctree_cophenet(seqs: dict, *, linkage: str = "average", k: int = 12, sketch_size: int | None = 3000,

@@ -99,8 +99,8 @@ def main():
         base_ms = None
         for P in ints(args.perms):
             draw_ms, checked = timed(lambda: distance.check_permanova_args(n, grouping, P, 1, None))
-            call_ms, fit = timed(lambda: distance.run_permanova(ctx, n, tensor_src, *checked))
-            fused_ms, fused = timed(lambda: distance.run_permanova(ctx, n, side._source(), *checked))
+            call_ms, fit = timed(lambda: distance.run_permanova(ctx, tensor_src, *checked))
+            fused_ms, fused = timed(lambda: distance.run_permanova(ctx, side._source(), *checked))
             labels, a, perms = checked
             vectors = [labels] + [perms[p] for p in range(min(P, args.host_perms - 1))]
             per = []
@@ -127,7 +127,7 @@ def main():
                 for b in ints(args.batches):
                     os.environ["DVS_PERMANOVA_BATCH"] = str(b)
                     ctx.refresh_knobs()
-                    batch_ms[str(b)] = round(timed(lambda: distance.run_permanova(ctx, n, tensor_src, *checked))[0], 3)
+                    batch_ms[str(b)] = round(timed(lambda: distance.run_permanova(ctx, tensor_src, *checked))[0], 3)
                 del os.environ["DVS_PERMANOVA_BATCH"]
                 ctx.refresh_knobs()
                 line["batch_ms"] = batch_ms

@@ -1518,21 +1518,19 @@ HOST_ONLY = {
 }
 
 
-# the operations of a DeviceSide whose result is dense (the written list), the two whose result is sparse, and those it
-# inherits from its mixins (distance.OrdinationOps, MedoidOps, SpanningOps, GroupOps); every one serves every mode
-DENSE_OPS = ("distances", "linkage", "nj", "cross_distances", "nearest", "cluster_scores", "cophenet", "maxmin")
-SPARSE_OPS = ("within", "threshold_clusters")
-MIXIN_OPS = ("pcoa", "pcoa_project", "kmedoids", "mst", "permanova")
+# the operations of a DeviceSide (the written list), which defines every one of them itself; every one serves every mode
+DEVICE_SIDE_OPS = ("distances", "linkage", "nj", "cross_distances", "nearest", "cluster_scores", "cophenet", "maxmin", "within",
+                   "threshold_clusters", "pcoa", "pcoa_project", "kmedoids", "mst", "permanova")
 
 
 def device_side_operations() -> set:
-    """the public methods of DeviceSide and of every class it inherits from"""
+    """the public methods of DeviceSide, and of any class it might come to inherit from"""
     return {n for klass in distance.DeviceSide.__mro__ if klass is not object
             for n, v in vars(klass).items() if callable(v) and not n.startswith("_")} - {"close"}
 
 
 def required_ops() -> set:
-    ops = {f"DeviceSide.{op}:{mode}" for op in DENSE_OPS + SPARSE_OPS + MIXIN_OPS for mode in distance.DeviceSide.MODE_NAMES}
+    ops = {f"DeviceSide.{op}:{mode}" for op in DEVICE_SIDE_OPS for mode in distance.DeviceSide.MODE_NAMES}
     ops |= {f"{cls}.{m}" for cls, methods in ENQUEUES.items() for m in methods}
     return ops
 
@@ -1576,12 +1574,12 @@ def test_every_public_method_is_sorted_and_every_operation_named():
     named = {op for c in CASES.values() for op in c.ops}
     assert required_ops() <= named, sorted(required_ops() - named)
     own = {n for n, v in vars(distance.DeviceSide).items() if callable(v) and not n.startswith("_")} - {"close"}
-    assert own == set(DENSE_OPS) | set(SPARSE_OPS), own  # (an operation added later is sorted here)
-    # ... wherever it is defined: the mixins' operations too, each with a case in every mode
-    assert device_side_operations() == set(DENSE_OPS) | set(SPARSE_OPS) | set(MIXIN_OPS), device_side_operations()
+    assert len(set(DEVICE_SIDE_OPS)) == len(DEVICE_SIDE_OPS) == 15
+    assert own == set(DEVICE_SIDE_OPS), own ^ set(DEVICE_SIDE_OPS)  # (an operation added later is listed here)
+    # ... and nowhere but in the class itself, each with a case in every mode
+    assert distance.DeviceSide.__bases__ == (object,)
+    assert device_side_operations() == own
     assert {f"DeviceSide.{op}:{mode}" for op in device_side_operations() for mode in distance.DeviceSide.MODE_NAMES} <= named
-    mixins = [klass.__name__ for klass in distance.DeviceSide.__mro__[1:-1]]
-    assert sorted(mixins) == ["GroupOps", "MedoidOps", "OrdinationOps", "SpanningOps"], mixins
 
 
 def test_the_table_has_every_family_and_its_shapes():

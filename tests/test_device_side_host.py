@@ -71,7 +71,7 @@ def test_device_side_owns_what_it_builds(monkeypatch):
             made.append((_Handle(), args, self))
             return made[-1][0]
 
-    monkeypatch.setattr(distance, "Sketches", _Sketches)
+    monkeypatch.setattr(distance._sides, "Sketches", _Sketches)  # (where device_side looks it up)
     ctx = _Context()
     for mode, args in (("mash", (3, 10, 4, False)), ("euclidean", (3, 4)), ("jsd", (3, 4))):
         with distance.device_side(SEQS, mode, *args, ctx=ctx) as dev:
@@ -91,7 +91,7 @@ def test_a_failure_building_the_second_side_closes_the_first(monkeypatch):
             super().__init__()
             made.append(self)
 
-    monkeypatch.setattr(distance, "Sketches", _Sketches)
+    monkeypatch.setattr(distance._sides, "Sketches", _Sketches)  # (where device_side looks it up)
     for fn, extra in ((distance.mash_cross_distances, ()), (distance.mash_nearest, (1,))):
         made.clear()
         with pytest.raises(RuntimeError, match="the second side") as info:

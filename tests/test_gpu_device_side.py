@@ -1,6 +1,7 @@
-"""One distance.DeviceSide serving every operation over the distances of a batch, one after another, on the GPU: each
-result the bits of the public function of the mode for the same sequences, for a side that owns its handle and for one
-that wraps a count matrix of the caller's.  The batch is 35 ragged sequences: two 32-row tiles with a ragged edge."""
+"""One distance.DeviceSide serving every one of its fifteen operations over the distances of a batch, one after another,
+on the GPU: each result the bits of the public function of the mode for the same sequences, for a side that owns its
+handle and for one that wraps a count matrix or the sketches of the caller's -- whose own methods, where `Sketches` has
+one, give the same bits again.  The batch is 35 ragged sequences: two 32-row tiles with a ragged edge."""
 import numpy as np
 import pytest
 
@@ -39,26 +40,64 @@ def same_bits(got, want, what):
         assert g.tobytes() == w.tobytes(), (what, i)
 
 
-def serve_everything(dev, seqs, mode, ctx, what):
+def serve_everything(dev, seqs, mode, ctx, what, sketches=None):
+    """all fifteen operations of `dev`, each against the function over sequences of the mode; sketches: the
+    `distance.Sketches` that `dev` wraps, whose own methods must give the same bits"""
     args = distance.mode_args(mode, K, KW[mode].get("sketch_size"), 4, False)
+
+    def also(name, got, *a, **kw):
+        if sketches is not None:
+            same_bits(got, getattr(sketches, name)(*a, **kw), f"{what} Sketches.{name}")
+
     assert dev.mode == mode and dev.n == N and dev.ctx is ctx
     d = dev.distances()
     same_bits(d, distance.MODES[mode][0](seqs, *args, ctx=ctx), f"{what} distances")
+    also("distances", d)
     Z = dev.linkage("average")
     same_bits(Z, distance.MODES[mode][1](seqs, *args, method="average", ctx=ctx), f"{what} linkage")
+    also("linkage", Z, "average")
     labels = cluster.cut_tree(Z, n_clusters=3)
     assert labels.max() >= 1  # (a cut never separates merges of equal height: two clusters at least here)
-    same_bits(dev.cluster_scores(labels), distance.cluster_scores(seqs, labels, mode, ctx=ctx, **KW[mode]),
-              f"{what} cluster_scores")
-    same_bits(dev.cophenet(Z), distance.cophenet(seqs, Z, mode, ctx=ctx, **KW[mode]), f"{what} cophenet")
+    scores = dev.cluster_scores(labels)
+    same_bits(scores, distance.cluster_scores(seqs, labels, mode, ctx=ctx, **KW[mode]), f"{what} cluster_scores")
+    also("cluster_scores", scores, labels)
+    coph = dev.cophenet(Z)
+    same_bits(coph, distance.cophenet(seqs, Z, mode, ctx=ctx, **KW[mode]), f"{what} cophenet")
+    also("cophenet", coph, Z)
     same_bits(dev.nj(), distance.NJ_MODES[mode](seqs, *args, ctx=ctx), f"{what} nj")
-    same_bits(dev.maxmin(5), distance.MAXMIN_MODES[mode](seqs, *args, n_select=5, ctx=ctx), f"{what} maxmin")
+    picks = dev.maxmin(5)
+    same_bits(picks, distance.MAXMIN_MODES[mode](seqs, *args, n_select=5, ctx=ctx), f"{what} maxmin")
+    also("maxmin", picks, 5)
     cross = dev.cross_distances(dev)
     same_bits(cross, distance.CROSS_MODES[mode][0](seqs, seqs, *args, ctx=ctx), f"{what} cross_distances")
+    also("cross_distances", cross, sketches)
     off = ~np.eye(N, dtype=bool)
     assert not np.isnan(d).any()
     same_bits(cross[off], d[off], f"{what} cross_distances against distances")
-    same_bits(dev.nearest(dev, 2), distance.CROSS_MODES[mode][1](seqs, seqs, 2, *args, ctx=ctx), f"{what} nearest")
+    near = dev.nearest(dev, 2)
+    same_bits(near, distance.CROSS_MODES[mode][1](seqs, seqs, 2, *args, ctx=ctx), f"{what} nearest")
+    also("nearest", near, sketches, 2)
+    radius = float(np.median(d[off]))
+    close = dev.within(dev, radius, skip_self=True)
+    assert 0 < close.index.size < N * (N - 1)  # (the median: about half of the pairs, from both of their ends)
+    same_bits(close, distance.neighbours(seqs, radius, mode, ctx=ctx, **KW[mode]), f"{what} within")
+    also("within", close, sketches, radius, skip_self=True)
+    groups = dev.threshold_clusters(radius)
+    same_bits(groups, distance.threshold_clusters(seqs, radius, mode, ctx=ctx, **KW[mode]), f"{what} threshold_clusters")
+    also("threshold_clusters", groups, radius)
+    fit = dev.pcoa(2)
+    same_bits(fit, distance.PCOA_MODES[mode](seqs, *args, n_axes=2, ctx=ctx), f"{what} pcoa")
+    same_bits(dev.pcoa_project(fit, dev), distance.pcoa_project(fit, seqs, seqs, mode, ctx=ctx, **KW[mode]),
+              f"{what} pcoa_project")
+    medoids = dev.kmedoids(3)
+    same_bits(medoids, distance.KMEDOIDS_MODES[mode](seqs, *args, n_medoids=3, ctx=ctx), f"{what} kmedoids")
+    also("kmedoids", medoids, 3)
+    same_bits(dev.mst(), distance.MST_MODES[mode](seqs, *args, ctx=ctx), f"{what} mst")
+    grouping = [i % 3 for i in range(N)]
+    test = dev.permanova(grouping, permutations=19, seed=1)
+    same_bits(test, distance.PERMANOVA_MODES[mode](seqs, *args, grouping=grouping, permutations=19, seed=1, ctx=ctx),
+              f"{what} permanova")
+    also("permanova", test, grouping, permutations=19, seed=1)
     same_bits(dev.distances(), d, f"{what} distances, again")  # (the handle is as it was)
 
 
@@ -90,7 +129,7 @@ def test_a_wrapping_side_leaves_the_sketches_to_their_owner(ctx, seqs):
     try:
         before = sk.to_host()
         with distance.DeviceSide(sk, "mash") as dev:
-            serve_everything(dev, seqs, "mash", ctx, "mash wrapping")
+            serve_everything(dev, seqs, "mash", ctx, "mash wrapping", sketches=sk)
         assert sk._h
         same_bits(sk.to_host(), before, "the sketches after the wrapper is closed")
     finally:

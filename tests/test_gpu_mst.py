@@ -254,7 +254,7 @@ def test_c_entry_refuses_bad_arguments_and_writes_nothing(ctx):
     want = mc.expected("euclid", 40)
     assert np.array_equal(edges.reshape(39, 2), want[0]) and np.array_equal(weights, want[1])
     with pytest.raises(NotImplementedError):
-        distance.run_mst(ctx, big, given(big))
+        distance.run_mst(ctx, given(big))
 
 
 # ------------------------------------------------------------------ 7. trees and the app

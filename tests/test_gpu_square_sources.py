@@ -71,12 +71,12 @@ def given(ctx, consumer, d) -> dict:
 def raw_given(ctx, consumer, src, n):
     """the same calls over a dvs_source of the test's making"""
     if consumer == "linkage":
-        return distance.run_linkage(ctx, n, src, distance.linkage_method_code("average"))
+        return distance.run_linkage(ctx, src, distance.linkage_method_code("average"))
     if consumer == "nj":
-        return distance.run_nj(ctx, n, src)
+        return distance.run_nj(ctx, src)
     if consumer == "pcoa":
-        return distance.run_pcoa(ctx, n, src, 2, 1e-8, 0, False)
-    return distance.run_kmedoids(ctx, n, src, 3, None, 300)
+        return distance.run_pcoa(ctx, src, 2, 1e-8, 0, False)
+    return distance.run_kmedoids(ctx, src, 3, None, 300)
 
 
 @pytest.fixture(scope="module")

@@ -72,12 +72,12 @@ def call(ctx, entry, q, r, radius, *, kk=5, max_pairs=0) -> dict:
                                      _lib.ptr(t.row_means, f64), _lib.ptr(coords, f64)))
         return {"coords": coords}
     if entry == "cluster_scores":
-        return distance._run_cluster_scores(ctx, t.labels, q)._asdict()
+        return distance.run_cluster_scores(ctx, q, t.labels)._asdict()
     if entry == "cophenet":
-        return distance._run_cophenet(ctx, n, t.pairs, t.heights, True, q)._asdict()
+        return distance.run_cophenet(ctx, q, t.pairs, t.heights, True)._asdict()
     if entry == "within":
-        return distance._run_within(ctx, q, r, radius, 0, max_pairs)._asdict()
-    return distance._run_threshold_clusters(ctx, n, q, radius)._asdict()
+        return distance.run_within(ctx, q, r, radius, 0, max_pairs)._asdict()
+    return distance.run_threshold_clusters(ctx, q, radius)._asdict()
 
 
 def given(d, on_device: int = 0) -> _lib.Source:

@@ -577,9 +577,9 @@ def test_c_entries_refuse_bad_arguments_and_leave_the_context_usable(ctx):
     assert L.dvs_threshold_clusters(ctx._h, given(40), 0.1, _lib.ptr(lab, C.c_uint32), None) == _lib.ERR_VALUE
     assert (lab == 7).all() and cnt.value == 99
     with pytest.raises(NotImplementedError):  # the same through the Python layer: a matrix of `big` rows is never made,
-        distance._run_within(ctx, given(big), None, 0.1, 0, 0)                  # the entry refuses the number
+        distance.run_within(ctx, given(big), None, 0.1, 0, 0)                   # the entry refuses the number
     with pytest.raises(NotImplementedError):
-        distance._run_threshold_clusters(ctx, big, given(big), 0.1)
+        distance.run_threshold_clusters(ctx, given(big), 0.1)
     assert L.dvs_threshold_clusters(ctx._h, given(0), 0.1, None, None) == _lib.OK  # n == 0: nothing written
     assert L.dvs_threshold_clusters(ctx._h, given(1), 0.1, _lib.ptr(lab, C.c_uint32), C.byref(cnt)) == _lib.OK
     assert lab[0] == 0 and cnt.value == 1
