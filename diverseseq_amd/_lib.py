@@ -47,7 +47,7 @@ EXPORTS = (
     # one entry per operation over the distances of a `Source`
     "dvs_distances", "dvs_linkage", "dvs_nj", "dvs_maxmin", "dvs_cross_distances", "dvs_nearest", "dvs_within",
     "dvs_cluster_scores", "dvs_cophenet", "dvs_threshold_clusters", "dvs_pcoa", "dvs_pcoa_project", "dvs_kmedoids",
-    "dvs_mst", "dvs_linkage_from_mst", "dvs_permanova",
+    "dvs_mst", "dvs_linkage_from_mst", "dvs_permanova", "dvs_mantel",
 )
 WITHIN_SKIP_SELF = 1
 SRC_MASH, SRC_EUCLIDEAN, SRC_JSD, SRC_GIVEN = range(4)
@@ -103,6 +103,12 @@ KMEDOIDS_INIT_BUILD, KMEDOIDS_INIT_GIVEN = 0, 1
 class PermanovaInfo(C.Structure):
     """dvs_permanova_info"""
     _fields_ = [("n_le", C.c_uint32), ("passes", C.c_uint32), ("batch", C.c_uint32)]
+
+
+class MantelInfo(C.Structure):
+    """dvs_mantel_info"""
+    _fields_ = [("n_ge", C.c_uint32), ("n_le", C.c_uint32), ("n_abs_ge", C.c_uint32), ("passes", C.c_uint32),
+                ("batch", C.c_uint32)]
 
 
 class SelectParams(C.Structure):
@@ -293,6 +299,8 @@ def load() -> C.CDLL:
         L.dvs_linkage_from_mst.argtypes = [vp, u32, u32p, f64p, u32p, f64p, u32p]  # edges, weights, pairs, heights, sizes
         # labels, n_groups, perm_labels, n_perm, ss_total, ss_within, group_ss, info
         L.dvs_permanova.argtypes = [vp, srcp, u32p, u32, u32p, u32, f64p, f64p, f64p, C.POINTER(PermanovaInfo)]
+        # the two sources, perms, n_perm, moments, z, info
+        L.dvs_mantel.argtypes = [vp, srcp, srcp, u32p, u32, f64p, f64p, C.POINTER(MantelInfo)]
         if L.dvs_abi_version() != 5:
             raise RuntimeError("libdvs_hip.so ABI version mismatch")
         _lib = L

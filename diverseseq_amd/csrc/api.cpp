@@ -175,6 +175,7 @@ void dvs_knobs_from_env(dvs_knobs *k) {
     if (const char *mb = getenv("DVS_MAXMIN_BATCH")) k->maxmin_batch = uint32_t(strtoul(mb, nullptr, 10));
     if (const char *kb = getenv("DVS_KMEDOIDS_BATCH")) k->kmedoids_batch = uint32_t(strtoul(kb, nullptr, 10));
     if (const char *pb = getenv("DVS_PERMANOVA_BATCH")) k->permanova_batch = uint32_t(strtoul(pb, nullptr, 10));
+    if (const char *mb = getenv("DVS_MANTEL_BATCH")) k->mantel_batch = uint32_t(strtoul(mb, nullptr, 10));
     k->maxmin_jsd_cross = on("DVS_MAXMIN_JSD_CROSS");
     const char *tk = getenv("DVS_TEST_KNOBS");
     k->test_persist_fake_error = tk && strstr(tk, "fake_persist_error") != nullptr;

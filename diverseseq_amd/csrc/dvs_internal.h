@@ -45,6 +45,7 @@ struct dvs_knobs {
     uint32_t maxmin_batch = 0;        // DVS_MAXMIN_BATCH: steps enqueued between two reads of the status word (0: 64)
     uint32_t kmedoids_batch = 0;      // DVS_KMEDOIDS_BATCH: swap rounds enqueued between two reads of the status word (0: 8)
     uint32_t permanova_batch = 0;     // DVS_PERMANOVA_BATCH: label vectors (the observed one and permutations) a pass over the matrix serves (0: 16; 32 at most)
+    uint32_t mantel_batch = 0;        // DVS_MANTEL_BATCH: permutations (the identity among them) a scoring pass of the Mantel test serves (0: 32, which is also the most)
     bool maxmin_jsd_cross = false;    // DVS_MAXMIN_JSD_CROSS: the jsd traversal runs jsd_cross_kernel on one query row (the A/B of DESIGN.md 4.13)
     // ingest
     bool ingest_no_stream = false;    // DVS_INGEST_NO_STREAM: host files are uploaded whole before they are parsed
@@ -377,6 +378,17 @@ struct dvs_permanova_args {  // dvs_permanova's, behind the source
     dvs_permanova_info *info;
 };
 dvs_square_consumer dvs_permanova_consumer(dvs_ctx *ctx, uint32_t n, const dvs_permanova_args &a);           // permanova.hip
+// mantel.hip: dvs_mantel's arguments behind the two sources, the bytes of a run's state, and the run itself over the two
+// matrices in HBM (rowdist.hip's entry brings them)
+struct dvs_mantel_args {
+    const uint32_t *perms;
+    uint32_t n_perm;
+    double *moments, *z;
+    dvs_mantel_info *info;
+};
+size_t dvs_mantel_state_bytes(const dvs_ctx *ctx, uint32_t n, uint32_t n_perm);
+int dvs_mantel_run(dvs_ctx *ctx, uint32_t n, const double *d_x, double *d_y, bool y_owned, const uint32_t *d_zerodiv_x,
+                   const uint32_t *d_zerodiv_y, const dvs_mantel_args &a);
 // A run's status words: `bytes` of them zeroed on the context's stream, then the distance kernels' zero-division word
 // (d_zerodiv, may be NULL) copied into word `at`.
 inline hipError_t dvs_status_begin(dvs_ctx *ctx, uint32_t *d_status, size_t bytes, uint32_t at, const uint32_t *d_zerodiv) {

@@ -339,31 +339,50 @@ extern "C" int dvs_distances(dvs_ctx *ctx, const dvs_source *src, double *dist) 
 // into a block of the cache and the consumer enqueues behind them.  The checks come in one order whatever the
 // consumer: its arguments and n; its early answer and the mode's own check (a MASH, EUCLIDEAN or JSD source); the
 // device; the pointer (a caller's device matrix, used where it is); the fit in HBM.
-static int square_run(dvs_ctx *ctx, const dvs_source *src, const dvs_square_consumer &c) {
-    const uint32_t n = src->n;
-    if (int rc = c.check()) return rc;
-    PooledBuf d_dist{ctx}, d_scratch{ctx};
-    double *dist = static_cast<double *>(src->handle);
+//
+// The bringing half, which dvs_mantel goes through twice: a whole source as an n x n matrix in HBM.  The steps in
+// front of the fit -- the mode's own check (a MASH, EUCLIDEAN or JSD source), the pointer (a caller's device matrix)
+// -- and source_bring behind it, which gives the device pointer, the block it owns (none: a caller's device matrix,
+// used where it is) and the zero-division word.
+struct SquareBrought {
+    dvs_dist_stage st{};  // of a MASH, EUCLIDEAN or JSD source
+    PooledBuf d_dist, d_scratch;
+    double *dist = nullptr;
     const uint32_t *d_zerodiv = nullptr;
+    explicit SquareBrought(dvs_ctx *ctx) : d_dist{ctx}, d_scratch{ctx} {}
+    bool owned() const { return d_dist.p != nullptr; }
+};
+static bool source_needs_block(const dvs_source *src) { return !(src->kind == DVS_SRC_GIVEN && src->on_device); }
+static int source_own_check(dvs_ctx *ctx, const dvs_source *src, SquareBrought *b) {
+    if (src->kind == DVS_SRC_GIVEN) return DVS_OK;
+    b->st = source_stage(ctx, src);
+    return b->st.check();
+}
+static int source_pointer_check(dvs_ctx *ctx, const char *op, const dvs_source *src) {
+    return src->kind == DVS_SRC_GIVEN && src->on_device ? dvs_given_on_device(ctx, op, src->handle) : DVS_OK;
+}
+static int source_bring(dvs_ctx *ctx, const dvs_source *src, SquareBrought *b) {
+    b->dist = static_cast<double *>(src->handle);
     if (src->kind != DVS_SRC_GIVEN) {
-        if (c.early && c.early()) return DVS_OK;
-        const dvs_dist_stage st = source_stage(ctx, src);
-        if (int rc = st.check()) return rc;
-        DVS_HIP(ctx, hipSetDevice(ctx->device));
-        int rc = dvs_square_fits(ctx, c.name, n, true, c.extra_bytes(), c.extra_what);
-        if (!rc) rc = stage_enqueue(ctx, st, &d_dist, &d_scratch);
-        if (rc) return rc;
-        dist = d_dist.as<double>();
-        if (st.scratch_is_zerodiv) d_zerodiv = d_scratch.as<uint32_t>();
-    } else {
-        DVS_HIP(ctx, hipSetDevice(ctx->device));
-        int rc = src->on_device ? dvs_given_on_device(ctx, c.name, dist) : DVS_OK;
-        if (!rc) rc = dvs_square_fits(ctx, c.name, n, !src->on_device, c.extra_bytes(), c.extra_what);
-        if (!rc && !src->on_device) rc = dvs_given_upload(ctx, dist, n, &d_dist);
-        if (rc) return rc;
-        if (!src->on_device) dist = d_dist.as<double>();
+        if (int rc = stage_enqueue(ctx, b->st, &b->d_dist, &b->d_scratch)) return rc;
+        if (b->st.scratch_is_zerodiv) b->d_zerodiv = b->d_scratch.as<uint32_t>();
+    } else if (!src->on_device) {
+        if (int rc = dvs_given_upload(ctx, b->dist, src->n, &b->d_dist)) return rc;
     }
-    const int rc = c.run(dist, d_zerodiv);
+    if (b->owned()) b->dist = b->d_dist.as<double>();
+    return DVS_OK;
+}
+
+static int square_run(dvs_ctx *ctx, const dvs_source *src, const dvs_square_consumer &c) {
+    if (int rc = c.check()) return rc;
+    SquareBrought b(ctx);
+    if (src->kind != DVS_SRC_GIVEN && c.early && c.early()) return DVS_OK;
+    if (int rc = source_own_check(ctx, src, &b)) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = source_pointer_check(ctx, c.name, src)) return rc;
+    if (int rc = dvs_square_fits(ctx, c.name, src->n, source_needs_block(src), c.extra_bytes(), c.extra_what)) return rc;
+    if (int rc = source_bring(ctx, src, &b)) return rc;
+    const int rc = c.run(b.dist, b.d_zerodiv);
     // (the one place that keeps PooledBuf's contract for the matrix: a run that failed may have left the kernels that
     // write it, or its own that read it, queued)
     if (rc) (void)hipStreamSynchronize(ctx->stream);
@@ -411,4 +430,40 @@ extern "C" int dvs_permanova(dvs_ctx *ctx, const dvs_source *src, const uint32_t
     if (int rc = dvs_source_whole(ctx, "dvs_permanova", src)) return rc;
     const dvs_permanova_args args{labels, n_groups, perm_labels, n_perm, ss_total, ss_within, group_ss, info};
     return square_run(ctx, src, dvs_permanova_consumer(ctx, src->n, args));
+}
+
+// Two whole sources, of any two kinds, brought side by side (include/dvs_hip.h "Mantel"): the arguments and n, x's own
+// check, y's own check, the device, the pointers, ONE fit for both matrices, y's working copy and the state, then x, y
+// and the run (mantel.hip).
+extern "C" int dvs_mantel(dvs_ctx *ctx, const dvs_source *x, const dvs_source *y, const uint32_t *perms, uint32_t n_perm,
+                          double *moments, double *z, dvs_mantel_info *info) {
+    const char *op = "dvs_mantel";
+    if (!ctx || !x || !y) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_mantel: null argument");
+    if (int rc = dvs_source_check(ctx, x, x)) return rc;
+    if (int rc = dvs_source_check(ctx, y, y)) return rc;
+    if (!moments || !z || (n_perm != 0) != (perms != nullptr))
+        return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_mantel: null argument (perms is NULL exactly when n_perm is 0)");
+    if (x->n != y->n) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_mantel: %u rows against %u rows", x->n, y->n);
+    const uint32_t n = x->n;
+    if (n < 3) return dvs_set_error(ctx, DVS_ERR_VALUE, "dvs_mantel: %u rows: three at least", n);
+    if (int rc = dvs_source_whole(ctx, op, x)) return rc;
+    if (int rc = dvs_source_whole(ctx, op, y)) return rc;
+    SquareBrought bx(ctx), by(ctx);
+    if (int rc = source_own_check(ctx, x, &bx)) return rc;
+    if (int rc = source_own_check(ctx, y, &by)) return rc;
+    DVS_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = source_pointer_check(ctx, op, x)) return rc;
+    if (int rc = source_pointer_check(ctx, op, y)) return rc;
+    char what[64];
+    snprintf(what, sizeof what, "the second matrix and the sums of %u permutations", n_perm);
+    const uint64_t n2 = uint64_t(n) * n;
+    if (n2 > (uint64_t(1) << 58)) return dvs_square_fits(ctx, op, n, true, 0, what);  // (its own message)
+    if (int rc = dvs_square_fits(ctx, op, n, source_needs_block(x), size_t(n2) * 8 + dvs_mantel_state_bytes(ctx, n, n_perm), what))
+        return rc;
+    int rc = source_bring(ctx, x, &bx);
+    if (!rc) rc = source_bring(ctx, y, &by);
+    if (!rc) rc = dvs_mantel_run(ctx, n, bx.dist, by.dist, by.owned(), bx.d_zerodiv, by.d_zerodiv, dvs_mantel_args{perms, n_perm, moments, z, info});
+    // (as square_run: a step that failed may have left the kernels that write a matrix, or the run's own, queued)
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
 }

@@ -922,6 +922,68 @@ int dvs_permanova(dvs_ctx *ctx, const dvs_source *src, const uint32_t *labels, u
                   const uint32_t *perm_labels, uint32_t n_perm, double *ss_total, double *ss_within, double *group_ss,
                   dvs_permanova_info *info);
 
+/* ---- the Mantel test: do two distance matrices agree? -------------------------------------------------- *
+ * The Pearson correlation of the cells of two n x n distance matrices, and what the same correlation is after the
+ * items of one of them are permuted.  (No counterpart in the reference.)  Items are 0 .. n - 1, n >= 3, and
+ * m = n (n - 1) / 2.  X and Y are the matrices of the two sources, which may be of different kinds.
+ * What is read: only the cells above the diagonal, in both: x_ij = X[i][j] for i < j, and y(a, b) = Y[min(a, b)][max(a,
+ * b)].  The diagonal and the lower triangle of either matrix are never read.  Every counted cell must be finite and
+ * >= 0 (DVS_ERR_VALUE; for NaN or +-inf with the text the trees give, for a negative cell a message that says which
+ * matrix).
+ * Both variables are shifted, as dvs_cophenet shifts its own, which keeps the moments free of cancellation where
+ * the distances crowd near one value (fl: rounded to float64 once; r does not depend on the shifts):
+ *   s_x = fl(S_x / m), S_x the sum of the counted cells of X in the order below; s_y likewise
+ *   u_ij = fl(x_ij - s_x);  v(a, b) = fl(y(a, b) - s_y)
+ *   A = sum u,  B = sum v,  S_uu = sum fl(u * u),  S_vv = sum fl(v * v)            (the same under every permutation)
+ *   Z(pi) = sum_{i<j} fl(u_ij * v(pi[i], pi[j]))        pi[i]: the item of Y that stands at position i; Z(id) observed
+ *   r(pi) = (Z(pi) - A B / m) / sqrt((S_uu - A^2 / m) (S_vv - B^2 / m)),  NaN when either factor is <= 0 (a constant
+ *           matrix)
+ * r rises strictly with Z, so every count is taken on Z, in float64:
+ *   n_ge = #{pi : Z(pi) >= Z(id)},  n_le = #{pi : Z(pi) <= Z(id)},
+ *   n_abs_ge = #{pi : |fl(Z(pi) - c0)| >= |fl(Z(id) - c0)|},  c0 = fl(fl(A * B) / m);   p = (1 + count) / (1 + P)
+ * The library returns the sums and the counts; r and p are derived by the caller, who also makes the permutations
+ * (the library carries no random numbers).
+ * The order of every sum (x (+) y: a float64 addition; every product is rounded before it is added, no fused
+ * multiply-add; a chain starts from +0.0):
+ *   the row sums of X, Y, u, fl(u * u), v, fl(v * v): row i's cells j > i in 64 strided chains over the columns from
+ *       64 floor((i + 1) / 64) in ascending order (a column <= i adds +0.0), chain k in lane k, the lanes met by the xor
+ *       tree (lanes l and l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1);
+ *   S_x, S_y, A, B, S_uu, S_vv: the n row sums, row_0 (+) row_1 (+) ... (+) row_{n-1};
+ *   zpart(pi, i) = row i's products fl(u_ij * v(pi[i], pi[j])), j > i, in 256 strided chains over the columns from
+ *       256 floor((i + 1) / 256) in ascending order, chain k in lane k & 63 of run k >> 6, each run by the same tree,
+ *       the four runs added in ascending order; zpart(pi, n - 1) = +0.0;
+ *   Z(pi) = the n zpart(pi, i): 256 strided chains i = k, k + 256, ... in ascending order, met as above.
+ * Every order is a function of n and of positions only, never of pi or of the values, and there is no floating-point
+ * atomic.  So the same bits come back on every run, for every batch length (DVS_MANTEL_BATCH: the permutations, the
+ * identity among them, that one scoring pass serves: 32 by default and at most), wherever a permutation sits in its
+ * batch, and for a host matrix and the same matrix in device memory.  The identity permutation gives z[0]'s bits and counts towards p.
+ * Each of A, B, S_uu, S_vv and Z(pi) lies within band(n) = (n + 8) 2^-52 of its exact value over the u and v,
+ * relative to the sum of its terms' magnitudes (two levels of sums of at most n terms); r within 2 band(n) (1 + |r|) of
+ * Pearson's r of the original cells.
+ *   perms[n_perm][n] row-major, NULL exactly when n_perm == 0;  moments[6]: s_x, s_y, A, B, S_uu, S_vv
+ *   z[n_perm + 1], [0] the observed;  info (optional: NULL): the three counts (without the 1); passes, the reads of a
+ *       matrix's upper triangle by the longest chain: the entry pass, the centre pass and one per batch; batch, the
+ *       batch length used
+ * The sources: each whole, no row list, checked against itself; both of the same n.  MASH, EUCLIDEAN and JSD write
+ * their matrices into the context's blocks; a GIVEN host matrix is uploaded; a GIVEN device X is only read.  Y is
+ * always worked on in a block the library owns -- v is written over both [a][b] and [b][a] -- so a GIVEN device Y is
+ * copied first and the caller's matrix stays as it was.  The checks come in this order: the arguments and n (before
+ * any device work), x's own, y's own, the device, the pointers, the fit in HBM (asked once for both matrices, Y's copy
+ * and the state); the rows of perms are checked batch by batch while the device works on the batch before.
+ *   DVS_ERR_VALUE: a NULL argument; perms NULL with n_perm > 0 or not NULL with n_perm == 0; n < 3; x->n != y->n; a
+ *                  row of perms that is not a permutation of 0 .. n - 1 (the message names the first); a non-finite
+ *                  or negative counted cell; a device matrix on another device
+ *   DVS_ERR_UNSUPPORTED: a row list, or n other than the handle's rows
+ *   DVS_ERR_ZERODIV: (either MASH source) as dvs_nj
+ *   DVS_ERR_NOMEM: the matrices, Y's copy and the state do not fit in HBM */
+typedef struct dvs_mantel_info {
+    uint32_t n_ge, n_le, n_abs_ge, passes, batch;
+} dvs_mantel_info;
+int dvs_mantel(dvs_ctx *ctx, const dvs_source *x, const dvs_source *y,
+               const uint32_t *perms /* [n_perm][n], NULL exactly when n_perm == 0 */, uint32_t n_perm,
+               double moments[6] /* s_x, s_y, A, B, S_uu, S_vv */,
+               double *z /* [n_perm + 1], [0] the observed */, dvs_mantel_info *info /* optional */);
+
 #ifdef __cplusplus
 }
 #endif
